@@ -8,6 +8,7 @@ train-mode forward (dropout 0.3 active) + BCE-with-logits loss + backward into a
 buffer, plus -- for N > 1 -- one RCCL all-reduce of that buffer.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C2|C3|C4|C5] [--scaling weak|strong]
+                  [--dump-outputs DIR]
   N > 1 runs one process per GPU over RCCL: either launched by the driver as
   `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`, or -- when WORLD_SIZE is
   not set -- by this script itself: the parent (which never touches the GPU) starts that very command
@@ -17,6 +18,10 @@ buffer, plus -- for N > 1 -- one RCCL all-reduce of that buffer.
 workload's GLOBAL batch (C4: 8192 x 1000 bp x 50 tasks) is split over the N ranks.
 
 Prints ONE JSON line on rank 0 (see DESIGN.md section 6 for every field).
+
+--dump-outputs DIR: rank 0 also writes what the last timed step handed its caller -- logits, loss
+and the flat gradient buffer -- as DIR/<name>.npy (float32), so that two builds run with the same
+arguments (hence the same seeded model and batch) can be compared output for output.
 """
 import argparse
 import hashlib
@@ -95,6 +100,35 @@ def self_launch(argv, gpus):
         sys.stderr.write("bench.py: the ranks exited without a result line\n")
         rc = 1
     return rc
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 22             # elements kept of an output too large for the budget (16 MB of fp32)
+
+
+def dump_outputs(out_dir, arrays, max_bytes=DUMP_MAX_BYTES, sample=DUMP_SAMPLE, seed=0):
+    """Write each {name: array} as out_dir/<name>.npy, float32 (float64 stays float64).  When the
+    arrays exceed max_bytes in all, each one larger than `sample` elements is cut to the same
+    `sample` elements on every run: flat indices drawn by numpy's default_rng(seed), sorted.
+    Returns {name: note} for the arrays so cut."""
+    import numpy as np
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: v if v.dtype == np.float64 else v.astype(np.float32) for k, v in arrays.items()}
+    notes = {}
+    if sum(a.nbytes for a in arrays.values()) > max_bytes:
+        for name, a in arrays.items():
+            if a.size > sample:
+                idx = np.sort(np.random.default_rng(seed).choice(a.size, sample, replace=False))
+                arrays[name] = a.reshape(-1)[idx]
+                notes[name] = "%d of %d elements, flat indices from numpy default_rng(%d), sorted" % (
+                    sample, a.size, seed)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > max_bytes:
+        raise ValueError("outputs to dump take %d bytes, over the %d-byte budget" % (total, max_bytes))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return notes
 
 
 def algorithmic_bytes_per_step(B, L, T, P):
@@ -251,7 +285,12 @@ def main():
                     help="skip the secondary fwd+bwd+Adam timing (profiling runs: one leg only)")
     ap.add_argument("--skip-stage-times", action="store_true",
                     help="skip the per-kernel HIP-event leg (profiling runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's logits, loss and flat gradient as DIR/<name>.npy "
+                         "(float32, at most 64 MB: a seeded sample of a larger gradient)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher (before torch is even imported)
         raise SystemExit(self_launch(sys.argv[1:], args.gpus))
@@ -352,6 +391,11 @@ def main():
         eng.ctx.stage_timing(False)
         stage_us = {k_: round(v / reps, 2) for k_, v in acc.items()}
     wall, gpu_ms = timed_region(overlap)
+    # what the last timed step handed its caller, copied before a later leg overwrites it
+    outputs = None
+    if args.dump_outputs and rank == 0:
+        outputs = {"logits": eng.logits[:B].cpu().numpy(), "loss": eng.loss.cpu().numpy(),
+                   "flat_grad": eng.flat_grad.cpu().numpy()}
     # N > 1: the other all-reduce schedule is timed as well (same K steps, after the headline
     # region) so that the choice between them rests on data from the node that ran this
     wall_alt = 0.0
@@ -493,6 +537,10 @@ def main():
                 "rccl_debug": "run with NCCL_DEBUG=INFO to see the algorithm / protocol RCCL picked"}
         if args.n_frac > 0:
             out["data"] = "synthetic, %.3g N bases" % args.n_frac
+        if outputs is not None:
+            sampled = dump_outputs(args.dump_outputs, outputs)
+            sys.stderr.write("bench.py: outputs of the last timed step written to %s%s\n" % (
+                args.dump_outputs, "".join("; %s: %s" % kv for kv in sampled.items())))
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()
