@@ -8,7 +8,7 @@ train-mode forward (dropout 0.3 active) + BCE-with-logits loss + backward into a
 buffer, plus -- for N > 1 -- one RCCL all-reduce of that buffer.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C2|C3|C4|C5] [--scaling weak|strong]
-                  [--dump-outputs DIR]
+                  [--dump-outputs DIR] [--full]
   N > 1 runs one process per GPU over RCCL: either launched by the driver as
   `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`, or -- when WORLD_SIZE is
   not set -- by this script itself: the parent (which never touches the GPU) starts that very command
@@ -18,6 +18,12 @@ buffer, plus -- for N > 1 -- one RCCL all-reduce of that buffer.
 workload's GLOBAL batch (C4: 8192 x 1000 bp x 50 tasks) is split over the N ranks.
 
 Prints ONE JSON line on rank 0 (see DESIGN.md section 6 for every field).
+
+A plain run measures the headline alone: set-up, the per-kernel leg on one GPU (30 untimed steps
+that leave the device in the state `value` is measured from), W warm-up steps, the K timed steps,
+the result line.  --full adds every secondary figure: the per-kernel leg's HIP-event times, and in
+legs of their own the step with the Adam update, the other all-reduce schedule (N > 1), the device
+copy rate and the CPU baseline (about 25 s of host time).  A field a run did not measure is null.
 
 --dump-outputs DIR: rank 0 also writes what the last timed step handed its caller -- logits, loss
 and the flat gradient buffer -- as DIR/<name>.npy (float32), so that two builds run with the same
@@ -269,28 +275,37 @@ def kernel_model(w, B):
     }
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="C2")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the secondary figures (per-kernel times, with optimizer, the "
+                         "other all-reduce schedule, copy rate, CPU baseline); a plain run times the "
+                         "headline alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=24.0)
     ap.add_argument("--n-frac", type=float, default=0.0,
                     help="fraction of N bases in the synthetic batch (robustness variant; the "
                          "headline is 0)")
     ap.add_argument("--skip-optimizer", action="store_true",
-                    help="skip the secondary fwd+bwd+Adam timing (profiling runs: one leg only)")
+                    help="with --full: skip the secondary fwd+bwd+Adam timing (profiling runs: one leg only)")
     ap.add_argument("--skip-stage-times", action="store_true",
-                    help="skip the per-kernel HIP-event leg (profiling runs)")
+                    help="skip the per-kernel leg, its 30 steps included (profiling runs)")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="write the last timed step's logits, loss and flat gradient as DIR/<name>.npy "
                          "(float32, at most 64 MB: a seeded sample of a larger gradient)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    return args
+
+
+def main():
+    args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher (before torch is even imported)
         raise SystemExit(self_launch(sys.argv[1:], args.gpus))
@@ -377,7 +392,10 @@ def main():
     # every stage of the step (explainn_stage_timing), averaged over a few steps.  A separate leg (the
     # events themselves cost time), run BEFORE the headline region: the device then enters the W
     # warm-up steps with its clocks and caches already up (with `--steps 20 --warmup 5` straight
-    # after start-up the same step measured 0.2166 ms against 0.2024 after 200 warm-up steps)
+    # after start-up the same step measured 0.2166 ms against 0.2024 after 200 warm-up steps).
+    # A plain run takes the leg as well and drops its figures: `value` is measured from the state
+    # the leg leaves, and the same 30 steps WITHOUT the events measured 2.7 % slower at
+    # `--steps 20 --warmup 5` (with a device synchronize per step: 2 %)
     stage_us = None
     if not args.skip_stage_times and rank == 0 and world == 1:
         eng.ctx.stage_timing(True)
@@ -399,12 +417,13 @@ def main():
     # N > 1: the other all-reduce schedule is timed as well (same K steps, after the headline
     # region) so that the choice between them rests on data from the node that ran this
     wall_alt = 0.0
-    if sync is not None:
+    if sync is not None and args.full:
         wall_alt, _ = timed_region(not overlap)
     # secondary figure ("report with and without the optimiser step"): the same step
     # followed by the fused Adam update, timed the same way; not part of `value`
     wall_opt = 0.0
-    if not args.skip_optimizer:
+    with_opt = args.full and not args.skip_optimizer
+    if with_opt:
         from explainn_amd import get_optimizer
         opt = get_optimizer(model.parameters(), lr=0.003)
         eng.attach_grads()
@@ -435,14 +454,14 @@ def main():
         achieved = alg / step_gpu_s / 1e9
         counters = committed_counters(args.workload) if (world == 1 and B == w["B"]) else None
         traffic = counters["traffic_bytes_per_step"] if counters else None
-        copy_peak = measured_copy_peak(dev) if world == 1 else None
+        copy_peak = measured_copy_peak(dev) if world == 1 and args.full else None
         if args.workload == "C2":
             metric = "sequences/sec (fwd+bwd), 200bp one-hot, 300 units, batch 1024"
         else:
             metric = "sequences/sec (fwd+bwd), %d bp one-hot, %d units, %d tasks" % (L, U, T)
         kernels = None
         dominant = None
-        if stage_us:
+        if stage_us and args.full:
             model_k = kernel_model(w, B)
             kernels = {}
             for name, us in sorted(stage_us.items(), key=lambda kv: -kv[1]):
@@ -477,12 +496,21 @@ def main():
                         ent["hbm_frac"] = round(pc["hbm_bytes"] / (us * 1e-6) / 1e9 / HBM_PEAK_GBPS, 4)
                 kernels[name] = ent
             dominant = max(stage_us, key=stage_us.get)
+        legs = []
+        if stage_us is not None:
+            legs.append("per-kernel stage times (30 steps, the last 10 averaged%s)"
+                        % ("" if args.full else "; reported with --full"))
+        legs.append("W warm-up + K timed steps")
+        if sync is not None and args.full:
+            legs.append("the other all-reduce schedule (K steps)")
+        if with_opt:
+            legs.append("the optimizer leg")
         out = {
             "metric": metric,
             "value": round(seqs / wall, 1), "unit": "sequences/s", "n_gpus": world,
             "n_ranks_seen": n_ranks_seen,
             "steps": args.steps, "warmup": args.warmup,
-            "legs": "per-kernel stage times (30 steps, the last 10 averaged), then W warm-up + K timed steps, then the optimizer leg",
+            "legs": ", then ".join(legs),
             "ms_per_step": round(wall / args.steps * 1e3, 4), "higher_is_better": True,
             "scaling": args.scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": w["text"] + ", train fwd + BCE + bwd (dropout 0.3)"
@@ -515,13 +543,13 @@ def main():
                                        "the shader clock measured here is %.1f-%.1f GHz (tools/mfma_probe.hip)"
                                        % (CLOCK_HZ / 1e9, MFMA_SUSTAINED_CLOCK_GHZ[0], MFMA_SUSTAINED_CLOCK_GHZ[1]),
                          "kernels": kernels,
-                         "kernel_sum_us": round(sum(stage_us.values()), 1) if stage_us else None},
+                         "kernel_sum_us": round(sum(stage_us.values()), 1) if kernels else None},
         }
-        out["with_optimizer"] = None if args.skip_optimizer else {
+        out["with_optimizer"] = None if not with_opt else {
             "ms_per_step": round(wall_opt / args.steps * 1e3, 4),
             "value": round(seqs / wall_opt, 1), "unit": "sequences/s",
             "optimizer": "Adam(lr=0.003), one fused launch (csrc/adam.hip)"}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(w, args.cpu_seconds)
         else:
             out["cpu_baseline"] = None
@@ -532,7 +560,7 @@ def main():
                 "backend": "nccl (RCCL)", "bytes": 4 * P,
                 "schedule": names[1 if overlap else 0], "ms_per_step": round(wall / args.steps * 1e3, 4),
                 "other_schedule": names[0 if overlap else 1],
-                "other_ms_per_step": round(wall_alt / args.steps * 1e3, 4),
+                "other_ms_per_step": round(wall_alt / args.steps * 1e3, 4) if args.full else None,
                 "select": "EXPLAINN_BENCH_OVERLAP=0|1",
                 "rccl_debug": "run with NCCL_DEBUG=INFO to see the algorithm / protocol RCCL picked"}
         if args.n_frac > 0:

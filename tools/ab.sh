@@ -4,7 +4,7 @@
 for v in "$@"; do
   if [ "$v" = base ]; then unset EXPLAINN_HIP_LIB; else export EXPLAINN_HIP_LIB="$PWD/$v"; fi
   echo -n "$v : "
-  python3 bench.py --no-cpu-baseline --skip-optimizer --steps 400 --warmup 30 2>&1 | grep "^{" | python3 -c "
+  python3 bench.py --full --no-cpu-baseline --skip-optimizer --steps 400 --warmup 30 2>&1 | grep "^{" | python3 -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=d['roofline'].get('kernels') or {}

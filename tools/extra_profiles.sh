@@ -6,7 +6,7 @@
 TAG=${1:-r03_final}
 OUT=gpurun_out/${TAG}_extra
 mkdir -p "$OUT"
-B="python3 bench.py --no-cpu-baseline"
+B="python3 bench.py --full --no-cpu-baseline"
 for wl in C3 C4 C5; do timeout -k 10 300 $B --workload $wl --steps 100 --warmup 10 2> /dev/null | tail -1 > "$OUT/bench_$wl.json"; echo "$wl done"; done
 timeout -k 10 300 $B --workload C4 --scaling strong --steps 30 --warmup 5 2> /dev/null | tail -1 > "$OUT/bench_C4_strong.json"; echo strong done
 timeout -k 10 300 $B --n-frac 0.02 2> /dev/null | tail -1 > "$OUT/bench_nfrac.json"; echo nfrac done

@@ -25,7 +25,7 @@ python3 tools/pmc.py "$OUT/sq1" "$OUT/sq2" > "$OUT/pmc_sq_summary.txt" || true
 python3 tools/traffic.py "$OUT" "$OUT/counters.json" "$TAG" "$WL"
 # the bench line last, with the counters of THIS build in place so that roofline.traffic is filled in
 mkdir -p "$ROOT/profiles" && cp "$OUT/counters.json" "$ROOT/profiles/${TAG}_counters.json"
-timeout -k 10 400 python3 bench.py --workload $WL > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 400 python3 bench.py --full --workload $WL > "$OUT/bench.json" 2> "$OUT/bench.err"
 tail -1 "$OUT/bench.json" | cut -c1-300
 python3 tools/kstats.py "$OUT/stats" 220 "$OUT/bench.json" > "$OUT/kernel_summary.txt"
 tail -3 "$OUT/kernel_summary.txt"
