@@ -122,6 +122,7 @@ void explainn_set_error(const char* fmt, ...);
         if (e_ != hipSuccess) {                                                    \
             explainn_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
                                __FILE__, __LINE__);                                \
+            (void)hipGetLastError();  /* reported here: not left for the next launch check */ \
             return EXPLAINN_E_HIP;                                                 \
         }                                                                          \
     } while (0)

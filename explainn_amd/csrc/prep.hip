@@ -737,9 +737,14 @@ int prep_configure(explainn_ctx* c) {
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&prep1_stats_kernel<true>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)((size_t)c->K4 * c->K4 * sizeof(double))));
+    // (C and V1 of one unit: past n = 157 they outgrow the 160 KiB of LDS a workgroup can have)
     const size_t sm = prep2_lds(c->n, c->NS);
-    if (sm > 48 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&prep2_kernel<true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
+    if (sm > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(&prep2_kernel<true>),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm) != hipSuccess) {
+        (void)hipGetLastError();
+        explainn_set_error("pooled length n=%d: the train-mode BatchNorm2 fold needs %zu bytes of LDS, more than "
+                           "the device allows", c->n, sm);
+        return EXPLAINN_E_UNSUPPORTED;
+    }
     return EXPLAINN_OK;
 }

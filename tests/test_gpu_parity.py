@@ -13,59 +13,13 @@ import pytest
 torch = pytest.importorskip("torch")
 
 from conftest import Golden, record_margin  # noqa: E402
+from dispatch_model import ORACLE_STEP_SHAPES  # noqa: E402
 from oracle import explainn_oracle as orc  # noqa: E402
-from parity_util import compare_grads, reference_fp32_error  # noqa: E402
+from parity_util import (GRAD_ABS_FLOOR, GRAD_TOL_GOLDEN, GRAD_TOL_ORACLE, TOL,  # noqa: E402,F401
+                         check_grads as _check_grads, close as _close, close_rel as _close_rel,
+                         compare_grads, model as _model, oracle_step as _oracle_step, to_np as _np)
 
 pytestmark = pytest.mark.gpu
-
-TOL = 1e-4
-ZERO_GRAD = ("linears.0.bias", "linears.6.bias", "linears.10.bias")
-
-
-GRAD_TOL_GOLDEN = 2e-5     # gradients / BatchNorm buffers vs the reference's own numbers, relative to max|ref|
-# Absolute floor under the relative bounds: a tensor whose TRUE value is zero holds only rounding
-# noise on both sides (fixture tiny_u1_k5 has B = 2: a train-mode BatchNorm over two samples outputs
-# +-1 whatever its input, so every gradient in front of it is exactly zero and the reference's own
-# numbers there are ~1e-9 noise).  Real gradient tensors of the fixtures peak at 1e-3 ... 1e-2, six
-# orders above it.
-GRAD_ABS_FLOOR = 2e-9
-GRAD_TOL_ORACLE = 5e-5     # the same vs the fp64 numpy oracle on random cases
-
-
-def _close(a, b, tol=TOL, what=""):
-    """Absolute bound (logits, losses, predictions: north_star's "within 1e-4 fp32")."""
-    a = np.asarray(a, dtype=np.float64); b = np.asarray(b, dtype=np.float64)
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    assert np.isfinite(a).all(), what + ": non-finite values"
-    err = np.abs(a - b).max() if a.size else 0.0
-    scale = max(1.0, np.abs(b).max() if b.size else 1.0)
-    record_margin("abs " + what, err / scale, tol)
-    assert err <= tol * scale, "%s: max|d|=%.3e (scale %.3g)" % (what, err, scale)
-
-
-def _close_rel(a, b, tol=GRAD_TOL_GOLDEN, what=""):
-    """Relative to max|ref| of the tensor itself (gradients and buffers: a tensor whose entries
-    are all of order 1e-3 must agree to tol of THAT, not of 1.0)."""
-    a = np.asarray(a, dtype=np.float64); b = np.asarray(b, dtype=np.float64)
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    assert np.isfinite(a).all(), what + ": non-finite values"
-    err = np.abs(a - b).max() if a.size else 0.0
-    scale = max(1e-12, np.abs(b).max() if b.size else 1.0)
-    bound = tol * scale + GRAD_ABS_FLOOR
-    record_margin("rel " + what, err / bound * tol, tol)
-    assert err <= bound, "%s: max|d|=%.3e = %.3e of max|ref| %.3g (bound %.1e relative + %.0e)" % (
-        what, err, err / scale, scale, tol, GRAD_ABS_FLOOR)
-
-
-def _model(sd, U, k, L, T):
-    from explainn_amd import ExplaiNN
-    m = ExplaiNN(U, k, L, T)
-    m.load_state_dict({key: torch.from_numpy(np.array(v)) for key, v in sd.items()})
-    return m.cuda()
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
 
 
 def test_library_loaded_is_in_tree():
@@ -226,44 +180,8 @@ def test_adam_trajectory_golden(golden):
     assert followed >= min(n_steps, 3), "trajectory left the reference after %d steps" % followed
 
 
-@pytest.mark.parametrize("U,k,L,T,B,nfrac", [
-    (5, 19, 61, 3, 24, 0.05),       # tail = 1, N bases, B < 64
-    (7, 19, 200, 1, 130, 0.0),      # B not a multiple of 64, U not a multiple of 4
-    (4, 7, 75, 2, 64, 0.1),
-    (9, 26, 300, 4, 200, 0.01),     # n = 39 -> bucket 40 (zero-padded weights)
-    (3, 19, 1000, 2, 70, 0.0),      # n = 140 (config C4's pooled length)
-    (2, 19, 600, 5, 66, 0.02),      # n = 83  -> bucket 84 (config C5's pooled length)
-    (37, 19, 61, 50, 70, 0.02),     # T = 50 (C3/C4): combiner forward/backward as MFMA GEMMs
-    (70, 9, 40, 164, 131, 0.0),     # T = 164 (C5), ragged tiles in every GEMM dimension
-    (3, 5, 33, 9, 5, 0.0),          # smallest GEMM case: one partly filled tile
-    (6, 32, 120, 1, 40, 0.03),      # largest instantiated kernel size (two code words per window)
-    (5, 2, 40, 2, 33, 0.05),        # smallest kernel size
-    (4, 31, 260, 1, 20, 0.02),      # odd kernel size next to the maximum, two staging chunks (n = 32+)
-    # large-n kernels over SEVERAL batch chunks (QCH / ACH > 1, ragged last chunk): qmom_big,
-    # mid_big, passB<140>/<84>, fc_fwd<NQ > 32> -- the code paths configs C4 / C5 run
-    (3, 19, 1000, 2, 300, 0.01),    # n = 140, 3 chunks of 128 (last one 44 sequences)
-    (2, 19, 600, 5, 700, 0.02),     # n = 83, 6 chunks (last one 60)
-    (3, 19, 450, 1, 90, 0.0),       # n = 61 -> bucket 64: two 32-wide k-steps of the bf16 fc_fwd
-    (4, 19, 61, 2, 600, 0.0),       # few tasks, batch > 512: the per-unit head backward kernel (smaller
-                                    # batches run it inside passA)
-    (1100, 5, 40, 2, 70, 0.0),      # more units than threads in the combiner block that finishes BatchNorm3
-    # the lower edge of a pooled-length bucket (n = previous bucket + 1): passA and qmom decide at
-    # compile time which rows always / never exist inside the bucket (csrc/common.h: nq_lower)
-    (3, 19, 109, 1, 70, 0.0),       # n = 13 -> bucket 16
-    (3, 19, 165, 1, 70, 0.02),      # n = 21 -> bucket 24
-    (3, 19, 186, 2, 70, 0.0),       # n = 24 = bucket 24's upper edge
-    (3, 19, 193, 1, 70, 0.0),       # n = 25 -> bucket 26 (C2's kernels, one row short)
-    (3, 19, 207, 1, 70, 0.0),       # n = 27 -> bucket 28
-    (3, 19, 249, 1, 70, 0.0),       # n = 33 -> bucket 40 (first size with two row groups in passA)
-    (3, 19, 305, 1, 70, 0.0),       # n = 41 -> bucket 48
-    (2, 19, 529, 1, 70, 0.0),       # n = 73 -> bucket 84: the first n of the large-n kernels
-    # the filter-bank GEMM's edges: one pooling window (a wave's first window is its last), the
-    # widest kernel with one window, unit counts that leave a 32-unit tile / a two-tile group partly empty
-    (3, 19, 25, 1, 9, 0.0),         # n = 1, Lo = 7
-    (2, 32, 38, 1, 7, 0.0),         # k = 32, n = 1
-    (33, 19, 32, 1, 31, 0.0),       # 33 units: tile 1 holds one unit
-    (65, 4, 200, 1, 100, 0.02),     # 65 units: three tiles, the second group half empty; k = 4 is one k-step
-])
+# the shapes live in tests/dispatch_model.py, which builds the dispatch sweep around them
+@pytest.mark.parametrize("U,k,L,T,B,nfrac", ORACLE_STEP_SHAPES)
 def test_train_step_vs_oracle(U, k, L, T, B, nfrac):
     sd = orc.random_state_dict(U, k, L, T, seed=U + L)
     sd["linears.1.weight"][::2] *= -1
@@ -289,29 +207,6 @@ def test_train_step_vs_oracle(U, k, L, T, B, nfrac):
     sd2 = dict(sd); sd2.update(nb)
     with torch.no_grad():
         _close(_np(m(torch.from_numpy(x).cuda())), orc.forward(sd2, x), what="eval logits")
-
-
-_ORACLE_CACHES = {}       # id(reference gradient dict) -> (oracle cache, U): the knife-edge masks of that step
-
-
-def _oracle_step(sd, x, y, freeze=0, keep=None, kind="binary"):
-    """Logits, loss and BatchNorm buffers from the fp32 oracle (compared with absolute bounds);
-    gradients from the oracle in FP64 -- the truth -- together with the error the reference's own
-    fp32 arithmetic makes on this case (parity_util.reference_fp32_error), which sets the bar."""
-    ref_logits, _, nb = orc.forward(sd, x, training=True, dropout_mask=keep, return_cache=True)
-    lg64, cache, _ = orc.forward(sd, x, training=True, dropout_mask=keep, return_cache=True, dtype=np.float64)
-    loss_fn = orc.bce_with_logits if kind == "binary" else orc.mse
-    ref_loss, _ = loss_fn(ref_logits, y)
-    _, dl = loss_fn(lg64, y.astype(np.float64))
-    grads = orc.backward(cache, dl, freeze_top_n_filters=freeze)
-    ref_err = reference_fp32_error(sd, x, y, grads, kind, keep, freeze=freeze, cache=cache)
-    _ORACLE_CACHES[id(grads)] = (cache, sd["linears.0.weight"].shape[0], ref_err, grads)
-    return ref_logits, ref_loss, grads, nb
-
-
-def _check_grads(named, ref_grads, what=""):
-    cache, U, ref_err, _ = _ORACLE_CACHES[id(ref_grads)]
-    compare_grads([(key, _np(got)) for key, got in named], ref_grads, GRAD_TOL_ORACLE, cache, U, what, ref_err)
 
 
 @pytest.mark.parametrize("freeze", [1, 3, 5])

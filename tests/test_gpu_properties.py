@@ -5,6 +5,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 from oracle import explainn_oracle as orc  # noqa: E402
+from parity_util import compare_masked as _compare_masked  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 U, K, L, T, B = 300, 19, 200, 1, 1024
@@ -29,62 +30,6 @@ def _c2_model(seed=0, T_=T):
 
 def _batch(seed=1, n_frac=0.002):
     return torch.from_numpy(orc.random_onehot(B, L, seed=seed, n_frac=n_frac)).cuda()
-
-
-KNIFE = 5e-6     # |pre-activation| below this: fp32 and fp64 may legitimately disagree on its sign
-
-
-def _knife_masks(cache, U_):
-    """Which gradient entries a ReLU sign disagreement between two correct implementations could
-    move.  A flip of y2[b,u,r] changes d2 there, i.e. rows (u,r) of linears.{6,7}.* by one sample's
-    share (~1/B of the row) and unit u's filter / BatchNorm1 gradients by ~1/(100 B); a flip of
-    y3[b,u] changes d3 there, i.e. everything of unit u by ~1/B.  Returns (channel mask (U,100),
-    unit mask (U,)) of the entries that may NOT be compared tightly."""
-    Bc = cache["y2"].shape[0]
-    ch = np.abs(cache["y2"].reshape(Bc, U_, 100)).min(axis=0) < KNIFE
-    un = (np.abs(cache["y3"]).min(axis=0) < KNIFE) | ch.any(axis=1)
-    return ch, un
-
-
-def _compare_masked(named_grads, ref, cache, U_, tight=5e-5, loose=5e-2):
-    """Every gradient against the oracle: `tight` x max|ref| everywhere except the knife-edge
-    channels / units of _knife_masks, which only have to stay within `loose` (a flipped branch moves
-    a row by one sample's share, which can be a percent of a small tensor's max: 1.1e-2 seen at
-    T = 164).  Measured on MI355X: clean entries agree to 1e-6 .. 3e-6 of the tensor's max."""
-    ch, un = _knife_masks(cache, U_)
-    # the masks must stay a small exception: under 2 % of the channels, and enough clean units left
-    # for the tight comparison to mean something (an indexing bug hits every unit alike)
-    assert ch.mean() < 0.02 and (~un).sum() >= max(2, U_ // 8), (ch.mean(), un.mean())
-    report = {}
-    for name, g in named_grads:
-        r = ref[name].reshape(tuple(g.shape))
-        got = g.detach().cpu().numpy()
-        if name in ("linears.0.bias", "linears.6.bias", "linears.10.bias"):
-            assert np.abs(got).max() < 1e-6, name           # identically zero (SURVEY.md 7.2)
-            continue
-        if name == "linears.1.bias":
-            continue                                       # near-null direction (SURVEY.md 7.2)
-        scale = np.abs(r).max()
-        err = np.abs(got - r)
-        if name.startswith(("linears.6.", "linears.7.")):
-            rows = ch.reshape(-1)                           # channel index u*100 + r
-        elif name.startswith(("linears.0.", "linears.1.", "linears.10.", "linears.11.")):
-            rows = un
-        else:
-            rows = np.zeros(err.shape[0] if name != "final.weight" else 0, dtype=bool)
-        if name == "final.weight":                          # (T, U): columns are units; o ~ 0 at a knife-edge
-            masked, clean = err[:, un], err[:, ~un]
-        elif rows.size:
-            masked, clean = err[rows], err[~rows]
-        else:
-            masked, clean = err[:0], err
-        report[name] = (clean.max() / scale if clean.size else 0.0, masked.max() / scale if masked.size else 0.0)
-        assert clean.size == 0 or clean.max() <= tight * scale, (name, "clean", report[name])
-        assert masked.size == 0 or masked.max() <= loose * scale, (name, "knife-edge", report[name])
-    print("masked comparison: %.2f%% channels, %d/%d units masked; worst clean %.2e, worst masked %.2e" % (
-        100 * ch.mean(), int(un.sum()), U_, max(v[0] for v in report.values()),
-        max(v[1] for v in report.values())))
-    return report
 
 
 def _grads(m, x, y, scale=1.0):
@@ -217,7 +162,7 @@ def test_empty_batch_follows_torch():
 def test_c2_full_size_against_fp64_oracle():
     """Train-mode logits and all gradients at the full C2 size against the numpy oracle in fp64
     (a few seconds of host time).  Logits within 1e-4; every gradient within 2e-4 of the tensor's
-    max, except the rows the oracle itself marks as ReLU knife-edges (_knife_masks)."""
+    max, except the rows the oracle itself marks as ReLU knife-edges (parity_util.knife_masks)."""
     m = _c2_model(seed=3)
     x = _batch(seed=11)
     y = (torch.rand(B, T, generator=torch.Generator().manual_seed(12)) > 0.5).float().cuda()
