@@ -83,6 +83,7 @@ void carve(explainn_ctx* c, Carver& cv) {
     cv.take(&c->Dspp, U * (Bs / 4) * K4);
     cv.take(&c->dlogits, (int64_t)c->maxB * c->T);
     cv.take(&c->flags, 64);
+    cv.take(&c->bn1_ticket, 64);
     cv.take(&c->dlT, (int64_t)c->T * Bs);
     cv.take(&c->gWp, c->T > HEAD_GEMM_MIN_T ? (int64_t)head_gw_chunks(c->maxB) * c->T * (c->U + 1) : 0);
     cv.take(&c->lossp, 256);
@@ -355,13 +356,18 @@ extern "C" int explainn_forward_train(explainn_ctx* c, const float* x, int B,
         TRY(launch_pack(c, x, B, false, s));
         STAGE(ST_PACK, launch_prep1_tables(c, p, s));
     }
-    // input moments (bit masks -> Gram -> BatchNorm1 fold), then the filter bank.  (Round 1 forked the
-    // moment chain onto a side stream beside the filter bank; the filter bank fills every wave slot
-    // of the chip, the two stretched each other, and in series -- now that the chain takes 5 + 4 us
-    // -- the step is 4 us shorter.)
-    STAGE(ST_MOMENTS, launch_moments(c, B, s));
-    STAGE(ST_PREP1, launch_prep1(c, p, B, true, s));
-    STAGE(ST_CONV_POOL, launch_conv_pool(c, p, B, true, s));
+    // input moments (bit masks -> Gram -> BatchNorm1 fold) and the filter bank.  The filter bank reads
+    // none of the statistics, and at one wave per SIMD it leaves SIMDs idle: the moment chain runs
+    // inside its launch, on workgroups of its own (convpool.hip, cpm_bn1).  (Round 1 forked the chain
+    // onto a side stream instead; the filter bank of that time filled every wave slot and the two
+    // stretched each other.)  Grids too small to hide the chain keep the separate launches.
+    if (const int naux = conv_pool_bn1_workgroups(c, B)) {
+        STAGE(ST_CONV_POOL, launch_conv_pool_train(c, p, B, naux, s));
+    } else {
+        STAGE(ST_MOMENTS, launch_moments(c, B, s));
+        STAGE(ST_PREP1, launch_prep1(c, p, B, true, s));
+        STAGE(ST_CONV_POOL, launch_conv_pool(c, p, B, true, s));
+    }
     }
     STAGE(ST_QMOM, launch_qmoments(c, B, s));
     STAGE(ST_PREP2, launch_prep2(c, p, B, true, s));

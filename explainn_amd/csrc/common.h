@@ -105,6 +105,8 @@ struct explainn_ctx {
     bool dense;
     const float* dense_x;  // x of the train forward in flight (its backward reads it again)
     int* flags;           // [1]
+    int* bn1_ticket;      // [1]  arrivals of the filter bank's BatchNorm1 workgroups (convpool.hip),
+                          //      zeroed by the launch in front of it (pack_tables / prep1_tables)
     int* site_cnt;        // [U4][Bs]  sites per (unit, sequence) of the current batch (filter->PWM export)
     int* site_off;        // [U4][Bs]  their exclusive scan in sequence order, plus the running total
 };
@@ -134,6 +136,11 @@ int launch_prep1(explainn_ctx* c, const explainn_params* p, int B, bool train, h
 int launch_moments(explainn_ctx* c, int B, hipStream_t s);
 int launch_prep1_tables(explainn_ctx* c, const explainn_params* p, hipStream_t s);
 int launch_conv_pool(explainn_ctx* c, const explainn_params* p, int B, bool want_idx, hipStream_t s);
+// train forward, one-hot input: > 0 when the filter-bank launch also computes the input moments and
+// the BatchNorm1 fold, on that many workgroups of its own (launch_conv_pool_train) -- no moments /
+// prep1_stats launches in front of it; 0: the separate launches
+int conv_pool_bn1_workgroups(const explainn_ctx* c, int B);
+int launch_conv_pool_train(explainn_ctx* c, const explainn_params* p, int B, int naux, hipStream_t s);
 int launch_pack_tables(explainn_ctx* c, const float* x, const explainn_params* p, int B, hipStream_t s);
 int launch_pack_codes(explainn_ctx* c, const uint8_t* codes, int B, int rc, hipStream_t s);
 int launch_conv_act(explainn_ctx* c, int B, float* acts, hipStream_t s);
@@ -278,6 +285,29 @@ __device__ __forceinline__ bool unit_chunk_of_block(int U, int& u, int& chunk) {
     return u < U;
 }
 __host__ inline int units_grid(int U) { return (U + 7) & ~7; }
+
+// The end of the train-mode BatchNorm1 fold of unit u, from mu = w.m and wGw = w'Gw (both fp64):
+// alpha, shift, the saved mean / sigma for the backward and the running statistics.  One copy for
+// prep1_stats_kernel and the filter bank's BatchNorm1 workgroups (convpool.hip), so that the two
+// give the same bits.
+__device__ __forceinline__ void bn1_fold_finish(double mu, double wGw, int u, float g1u, float b1u,
+                                                float cbu, float rmu, float rvu, int B, int Lo,
+                                                float* __restrict__ alpha, float* __restrict__ shift,
+                                                double* __restrict__ mug, double* __restrict__ sig1,
+                                                float* __restrict__ rm, float* __restrict__ rv, int64_t* nbt) {
+    double var = wGw - mu * mu;
+    var = var > 0 ? var : 0;
+    const double sg = sqrt(var + BN_EPS_D);
+    const double a = (double)g1u / sg;
+    alpha[u] = (float)a;
+    shift[u] = (float)((double)b1u - a * mu);
+    mug[u] = mu;
+    sig1[u] = sg;
+    const double N1 = (double)B * (double)Lo;
+    rm[u] = (float)((1 - BN_MOM_D) * (double)rmu + BN_MOM_D * ((double)cbu + mu));
+    rv[u] = (float)((1 - BN_MOM_D) * (double)rvu + BN_MOM_D * var * N1 / (N1 - 1));
+    if (u == 0 && nbt) *nbt += 1;
+}
 
 // q = exp(alpha*ext + shift): every consumer must evaluate it identically
 __device__ __forceinline__ float qval(float alpha, float ext, float shift) {

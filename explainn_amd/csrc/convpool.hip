@@ -282,14 +282,236 @@ __device__ __forceinline__ void cpm_load_fragments(cpm_state<KS, UT>& S, const c
     });
 }
 
+// ---------------------------------------------------------------------------------------------
+// BatchNorm1's batch statistics inside the filter-bank launch (train forward, one-hot input).
+// The filter bank needs none of them (the sign of gamma1 is folded into Wf / Wsg by the tables), and
+// at one wave per SIMD its grid leaves SIMDs idle: so the launch carries `naux` more one-wave
+// workgroups (the leading z slices of the grid; ids past naux return at once) that do the work of
+// moments_kernel and prep1_stats_kernel<true> beside it, off the step's critical path:
+//   phase 1  input moments from the bit masks bm: job (d, a) = the four base pairs (a, a') at gap d,
+//            exact integer pair counts per position, window sums from their prefix sums -> G, m
+//            (every entry an exact count / (B Lo): any split of the jobs gives the same bits);
+//   hand-off G and m stored write-through (agent-scope relaxed atomic stores), drained, then one
+//            relaxed ticket add per workgroup; every workgroup polls the ticket relaxed with s_sleep
+//            until all naux have arrived and then makes ONE agent-scope acquire;
+//   phase 2  the BatchNorm1 fold of units id, id + naux, ... (up to BN1_NU of them per pass over G):
+//            prep1_stats_kernel<true>'s fp64 arithmetic in its order -- lane l plays that kernel's
+//            threads l and l + 64, and the two 64-lane sums are added as its red[0] + red[1].
+// Progress does not depend on dispatch order or XCD placement: only these workgroups wait, they wait
+// only for each other, and the filter-bank waves never wait for anything.  naux is far below the
+// waves the chip holds at once (>= 1024), so the filter-bank waves in front of a waiting workgroup
+// finish and every auxiliary workgroup is eventually dispatched, whatever the order.  The wait is
+// bounded all the same (BN1_SPIN_TICKS, far above any launch of this kernel): past it the workgroup
+// sets EXPLAINN_FLAG_BN1_TIMEOUT in the context's flags word and skips phase 2.
+// ---------------------------------------------------------------------------------------------
+struct cpm_bn1_args {
+    const unsigned long long* bm; double* G; double* m;
+    const float* conv_w; const float* conv_b; const float* g1; const float* b1;
+    float* rm; float* rv; int64_t* nbt;
+    float* alpha; float* shift; double* mug; double* sig1; double* Gw;
+    int* ticket; int* flags;
+    int naux, nz;                // auxiliary workgroups, the leading z slices that hold them (0: none)
+    int U, U4, k, B, L, Lp;
+};
+typedef __attribute__((address_space(1))) unsigned long long bn1_gu64;
+typedef __attribute__((address_space(1))) int bn1_gi32;
+// Register budget: the chain is dependent round trips (~1 us each beside the matrix load), so it
+// holds as many loads in flight as the form's registers allow without raising its arch VGPR count
+// past what its occupancy leaves (VGPRs and AccVGPRs share one file).  The forms with one wave per
+// SIMD anyway (UT = 2, KS >= 2: 196..203 arch VGPRs + 68..172 AccVGPRs of 512) take whole passes:
+// all tiles of a 64-position pass and 40 rows of G per round trip; the others stay under the ~110
+// arch VGPRs of the UT = 1 forms (4 tiles, 12 rows), or a form loses a wave per SIMD.
+template <int KS, int UT> struct bn1_cfg {
+    static constexpr bool big = UT == 2 && KS >= 2;
+    static constexpr int TQ = big ? 16 : 4;   // phase 1: 64-sequence tiles per round trip (5 loads each)
+    static constexpr int CH = big ? 40 : 12;  // phase 2: rows of G per round trip
+};
+#define BN1_NU 2                 // phase 2: units per pass over G
+#define BN1_SPIN_TICKS 10000000ull   // 100 ms of the 100 MHz wall clock
+
+__device__ __forceinline__ void bn1_store(double* p, double v) {
+    __hip_atomic_store((bn1_gu64*)p, (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// phase 1, job (d, a): lane = position q of a 64-position pass; P = inclusive prefix sums of the pair
+// counts over q (exact integers), G[(a,j),(a',j+d)] = (P(j+Lo-1) - P(j-1)) / (B Lo), kept by lane j
+template <int BN1_TQ>
+__device__ __forceinline__ void bn1_moments_job(const cpm_bn1_args& X, int job, int lane) {
+    const int d = job >> 2, a = job & 3;
+    const int NT = (X.B + 63) / 64, Lo = X.L - X.k + 1, K4 = 4 * X.k;
+    const size_t plane = (size_t)NT * X.Lp;
+    const unsigned long long* __restrict__ m0 = X.bm + (size_t)a * plane;
+    long long carry[4] = {0, 0, 0, 0}, plo[4] = {0, 0, 0, 0}, phi[4] = {0, 0, 0, 0};
+    const int jlo = lane - 1, jhi = lane + Lo - 1;
+    for (int qb = 0; qb < X.L; qb += 64) {
+        const int q = qb + lane;
+        int c[4] = {0, 0, 0, 0};
+        if (q + d < X.L) {
+            for (int t0 = 0; t0 < NT; t0 += BN1_TQ) {      // 5 BN1_TQ loads in flight
+                unsigned long long x0[BN1_TQ], x1[4][BN1_TQ];
+#pragma unroll
+                for (int i = 0; i < BN1_TQ; ++i) {
+                    const size_t o = (size_t)min(t0 + i, NT - 1) * X.Lp + q;
+                    x0[i] = m0[o];
+#pragma unroll
+                    for (int a2 = 0; a2 < 4; ++a2) x1[a2][i] = X.bm[a2 * plane + d + o];
+                }
+#pragma unroll
+                for (int i = 0; i < BN1_TQ; ++i)
+#pragma unroll
+                    for (int a2 = 0; a2 < 4; ++a2) c[a2] += (t0 + i < NT) ? __popcll(x0[i] & x1[a2][i]) : 0;
+            }
+        }
+#pragma unroll
+        for (int a2 = 0; a2 < 4; ++a2) {
+            int v = c[a2];
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const int y = __shfl_up(v, off, 64);
+                if (lane >= off) v += y;
+            }
+            const int vlo = __shfl(v, jlo & 63, 64), vhi = __shfl(v, jhi & 63, 64);
+            if (jlo >= qb && jlo < qb + 64) plo[a2] = carry[a2] + vlo;
+            if (jhi >= qb && jhi < qb + 64) phi[a2] = carry[a2] + vhi;
+            carry[a2] += __shfl(v, 63, 64);
+        }
+    }
+    const int j = lane;
+    if (j < X.k - d) {
+#pragma unroll
+        for (int a2 = 0; a2 < 4; ++a2) {
+            const long long sj = phi[a2] - plo[a2];
+            const double v = (double)sj / ((double)X.B * (double)Lo);
+            const int row = a * X.k + j, col = a2 * X.k + j + d;
+            bn1_store(X.G + (size_t)row * K4 + col, v);
+            bn1_store(X.G + (size_t)col * K4 + row, v);
+            if (row == col) bn1_store(X.m + row, v);
+        }
+    }
+}
+
+// phase 2: the BatchNorm1 fold of up to BN1_NU units (us[0..nu)) in one pass over G
+template <int CH>
+__device__ __forceinline__ void bn1_fold_units(const cpm_bn1_args& X, const int (&us)[BN1_NU], int nu, int lane) {
+    const int K4 = 4 * X.k, Lo = X.L - X.k + 1;
+    const int i0 = lane, i1 = lane + 64;                   // the two columns of this lane
+    const int c0i = min(i0, K4 - 1), c1i = min(i1, K4 - 1);
+    float wl[BN1_NU][2];
+#pragma unroll
+    for (int uu = 0; uu < BN1_NU; ++uu) {
+        const int u = min(us[uu], X.U - 1);
+        wl[uu][0] = X.conv_w[(size_t)u * K4 + c0i];
+        wl[uu][1] = X.conv_w[(size_t)u * K4 + c1i];
+    }
+    const double m0 = X.m[c0i], m1 = X.m[c1i];
+    // (G w)[i] = sum_c G[c][i] w[c]: even c into ge, odd c into go, in prep1_stats_kernel's order
+    double ge[BN1_NU][2], go[BN1_NU][2];
+#pragma unroll
+    for (int uu = 0; uu < BN1_NU; ++uu) ge[uu][0] = ge[uu][1] = go[uu][0] = go[uu][1] = 0;
+    for (int cb = 0; cb < K4; cb += CH) {
+        double gv[CH][2];
+#pragma unroll
+        for (int cc = 0; cc < CH; ++cc) {
+            const int c = min(cb + cc, K4 - 1);
+            gv[cc][0] = X.G[(size_t)c * K4 + c0i];
+            gv[cc][1] = X.G[(size_t)c * K4 + c1i];
+        }
+#pragma unroll
+        for (int cc = 0; cc < CH; cc += 2) {
+            const int c = cb + cc;
+            if (c < K4) {                                  // (K4 = 4k is even: rows come in pairs)
+#pragma unroll
+                for (int uu = 0; uu < BN1_NU; ++uu) {
+                    const float we = __int_as_float(__builtin_amdgcn_readlane(
+                        __float_as_int(c < 64 ? wl[uu][0] : wl[uu][1]), c & 63));
+                    const float wo = __int_as_float(__builtin_amdgcn_readlane(
+                        __float_as_int(c + 1 < 64 ? wl[uu][0] : wl[uu][1]), (c + 1) & 63));
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        ge[uu][h] = fma(gv[cc][h], (double)we, ge[uu][h]);
+                        go[uu][h] = fma(gv[cc + 1][h], (double)wo, go[uu][h]);
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int uu = 0; uu < BN1_NU; ++uu) {
+        if (uu >= nu) break;
+        const int u = us[uu];
+        if (u >= X.U) {
+            if (lane == 0) { X.alpha[u] = 0.f; X.shift[u] = 0.f; }
+            continue;
+        }
+        // prep1_stats_kernel's thread i (i < K4) holds mu_p = w_i m_i and q_p = w_i (G w)_i; its block
+        // sum is wave 0's sum (threads 0..63) + wave 1's (64..127)
+        double mu_p[2] = {0, 0}, q_p[2] = {0, 0};
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int i = h ? i1 : i0;
+            const double gw = ge[uu][h] + go[uu][h];
+            if (i < K4) {
+                X.Gw[(size_t)u * K4 + i] = gw;
+                mu_p[h] = fma((double)wl[uu][h], h ? m1 : m0, mu_p[h]);
+                q_p[h] = fma((double)wl[uu][h], gw, q_p[h]);
+            }
+        }
+        const double mu = wave_sum_d(mu_p[0]) + wave_sum_d(mu_p[1]);
+        const double wGw = wave_sum_d(q_p[0]) + wave_sum_d(q_p[1]);
+        if (lane == 0)
+            bn1_fold_finish(mu, wGw, u, X.g1[u], X.b1[u], X.conv_b[u], X.rm[u], X.rv[u], X.B, Lo, X.alpha,
+                            X.shift, X.mug, X.sig1, X.rm, X.rv, X.nbt);
+    }
+}
+
+// one auxiliary workgroup (id < naux): phase 1, the hand-off, phase 2
+template <int KS, int UT>
+__device__ __forceinline__ void cpm_bn1(const cpm_bn1_args& X, int id, int lane) {
+    for (int job = id; job < 4 * X.k; job += X.naux) bn1_moments_job<bn1_cfg<KS, UT>::TQ>(X, job, lane);
+    // publish: the write-through stores of G / m drained, then this workgroup's ticket
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (lane == 0) __hip_atomic_fetch_add((bn1_gi32*)X.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // wait for every auxiliary workgroup: relaxed polls, bounded, then ONE agent-scope acquire
+    const unsigned long long t0 = wall_clock64();
+    while (__builtin_amdgcn_readfirstlane(
+               __hip_atomic_load((bn1_gi32*)X.ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) < X.naux) {
+        if (wall_clock64() - t0 > BN1_SPIN_TICKS) {
+            if (lane == 0)
+                __hip_atomic_fetch_or((bn1_gi32*)X.flags, EXPLAINN_FLAG_BN1_TIMEOUT, __ATOMIC_RELAXED,
+                                      __HIP_MEMORY_SCOPE_AGENT);
+            return;
+        }
+        __builtin_amdgcn_s_sleep(2);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    for (int u0 = id; u0 < X.U4; u0 += BN1_NU * X.naux) {
+        int us[BN1_NU], nu = 0;
+#pragma unroll
+        for (int uu = 0; uu < BN1_NU; ++uu) {
+            us[uu] = u0 + uu * X.naux;
+            if (us[uu] < X.U4) nu = uu + 1;
+        }
+        bn1_fold_units<bn1_cfg<KS, UT>::CH>(X, us, nu, lane);
+    }
+}
+
 template <int KS, int UT, bool IDX>
 __global__ __launch_bounds__(64, (UT == 1 && KS <= 5) ? 2 : 1) void conv_pool_mm_kernel(
     const uint32_t* __restrict__ pk2, const uint32_t* __restrict__ nmask,
     const cu32x4* __restrict__ Wf, const cu32x4* __restrict__ Wsg,
-    float* __restrict__ ext, uint8_t* __restrict__ idx, int n, int Bs, int PW, int NW, int wper) {
+    float* __restrict__ ext, uint8_t* __restrict__ idx, int n, int Bs, int PW, int NW, int wper,
+    const cpm_bn1_args bn1) {
     __shared__ __attribute__((aligned(1024))) cu32x4 oh[64];      // [N bits of the two taps][code pair]
     typedef __attribute__((address_space(3))) char lds_char;
     const int lane = threadIdx.x;
+    if constexpr (IDX) {      // (train forward) the leading bn1.nz z slices: BatchNorm1's workgroups
+        if ((int)blockIdx.z < bn1.nz) {
+            const int id = ((int)blockIdx.z * (int)gridDim.y + (int)blockIdx.y) * (int)gridDim.x + (int)blockIdx.x;
+            if (id < bn1.naux) cpm_bn1<KS, UT>(bn1, id, lane);
+            return;
+        }
+    }
     STAMP(0);
     {
         const int c4 = lane & 15, nb = lane >> 4;
@@ -323,7 +545,7 @@ __global__ __launch_bounds__(64, (UT == 1 && KS <= 5) ? 2 : 1) void conv_pool_mm
         A.rext = __builtin_amdgcn_make_buffer_rsrc(uniform(ext + row0), 0, 4 * span, 0x00020000);
         A.ridx = __builtin_amdgcn_make_buffer_rsrc(uniform(idx + row0), 0, span, 0x00020000);
     }
-    const int wbeg = blockIdx.z * wper, wend = min(n, wbeg + wper);
+    const int wbeg = (IDX ? (int)blockIdx.z - bn1.nz : (int)blockIdx.z) * wper, wend = min(n, wbeg + wper);
     if (wbeg >= wend) return;
     cpm_load_fragments(S, Wf + (size_t)A.t0 * KS * 3 * 64 + lane);
     cpm_fetch(S, A, wbeg);
@@ -400,13 +622,44 @@ static int conv_pool_mm_parts(const explainn_ctx* c, int B, int ut) {
     return best;
 }
 
-int launch_conv_pool_mm(explainn_ctx* c, const explainn_params* p, int B, bool want_idx, hipStream_t s) {
+// BatchNorm1's workgroups in the filter-bank launch (cpm_bn1): two per moments job (d, a); the
+// second half only joins phase 2.  EXPLAINN_BN1_AUX (experiments; read per step, so that a test can
+// run both paths in one process): 0 = the separate launches, N > 0 = N workgroups whatever the shape
+// -- at most 256, a quarter of the waves the chip holds at once even at one wave per SIMD, so that
+// the progress argument of cpm_bn1 stands.
+// Where it pays, measured on MI355X (profiles/r04_bn1_ab.txt): the chain takes ~30 us on these
+// workgroups, so it leaves the critical path only beside a one-round filter bank about that long.
+// C2 (960 workgroups, 200 bp): 0.2029 -> 0.1972 ms per step.  Forced on, the other shapes lose: the
+// small grids (100 units x 64 sequences 0.0982 -> 0.1006, 300 x 128 0.1306 -> 0.1390; 104 and 520
+// workgroups), multi-round C3 0.550 -> 0.557 and C5 3.45 -> 3.49 (the workgroups take slots from a
+// filter bank that has no idle SIMDs), and C4's 1000 bp 1.197 -> 1.213 (phase 1 grows with L).
+int conv_pool_bn1_workgroups(const explainn_ctx* c, int B) {
+    if (const char* e = getenv("EXPLAINN_BN1_AUX")) return min(max(atoi(e), 0), 256);
     const int ut = conv_pool_mm_ut(c);
     const int parts = conv_pool_mm_parts(c, B, ut);
     const int wper = (c->n + parts - 1) / parts;
-    const dim3 grid((B + 31) / 32, ut == 1 ? (c->U + 31) / 32 : conv_tiles_padded(c->U, c->k) / ut, (c->n + wper - 1) / wper);
+    const long blocks = (long)((B + 31) / 32) * (ut == 1 ? (c->U + 31) / 32 : conv_tiles_padded(c->U, c->k) / ut) *
+                        ((c->n + wper - 1) / wper);
+    const int slots = (ut == 1 && conv_ksteps(c->k) <= 5) ? 2048 : 1024;
+    return blocks >= 768 && blocks <= slots && c->L <= 256 ? 8 * c->k : 0;
+}
+
+// bn1 != nullptr: the launch also carries BatchNorm1's workgroups (train forward, want_idx)
+static int launch_conv_pool_mm(explainn_ctx* c, const explainn_params* p, int B, bool want_idx,
+                               cpm_bn1_args* bn1, hipStream_t s) {
+    const int ut = conv_pool_mm_ut(c);
+    const int parts = conv_pool_mm_parts(c, B, ut);
+    const int wper = (c->n + parts - 1) / parts;
+    dim3 grid((B + 31) / 32, ut == 1 ? (c->U + 31) / 32 : conv_tiles_padded(c->U, c->k) / ut, (c->n + wper - 1) / wper);
+    cpm_bn1_args none = {};
+    if (bn1) {
+        const int slice = (int)(grid.x * grid.y);
+        bn1->nz = (bn1->naux + slice - 1) / slice;
+        grid.z += bn1->nz;
+    }
+    const cpm_bn1_args& bn1v = bn1 ? *bn1 : none;
 #define ARGS grid, dim3(64), 0, s, c->pk2, c->nmask, reinterpret_cast<const cu32x4*>(c->Wf), \
-             reinterpret_cast<const cu32x4*>(c->Wsg), c->ext, c->idx, c->n, c->Bs, c->PW, c->NW, wper
+             reinterpret_cast<const cu32x4*>(c->Wsg), c->ext, c->idx, c->n, c->Bs, c->PW, c->NW, wper, bn1v
 #define CALLKS(KSv, UTv)                                                                        \
     if (want_idx) hipLaunchKernelGGL((conv_pool_mm_kernel<KSv, UTv, true>), ARGS);              \
     else hipLaunchKernelGGL((conv_pool_mm_kernel<KSv, UTv, false>), ARGS);
@@ -432,7 +685,16 @@ int launch_conv_pool_mm(explainn_ctx* c, const explainn_params* p, int B, bool w
 }
 
 int launch_conv_pool(explainn_ctx* c, const explainn_params* p, int B, bool want_idx, hipStream_t s) {
-    return launch_conv_pool_mm(c, p, B, want_idx, s);
+    return launch_conv_pool_mm(c, p, B, want_idx, nullptr, s);
+}
+
+// train forward on one-hot input with the input moments and the BatchNorm1 fold inside the launch
+// (naux = conv_pool_bn1_workgroups(c, B) > 0): bm must hold the batch's bit masks and bn1_ticket must be 0
+int launch_conv_pool_train(explainn_ctx* c, const explainn_params* p, int B, int naux, hipStream_t s) {
+    cpm_bn1_args a = {c->bm, c->G, c->m, p->conv_w, p->conv_b, p->bn1_w, p->bn1_b, p->bn1_rm, p->bn1_rv,
+                      p->bn1_nbt, c->alpha, c->shift, c->mug, c->sig1, c->Gw, c->bn1_ticket, c->flags,
+                      naux, 0, c->U, c->U4, c->k, B, c->L, c->Lp};
+    return launch_conv_pool_mm(c, p, B, true, &a, s);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -159,9 +159,11 @@ __global__ __launch_bounds__(64 * PACK_WAVES) void pack_tables_kernel(const floa
                                                           float* __restrict__ Wt,
                                                           uint16_t* __restrict__ Wf,
                                                           uint32_t* __restrict__ Wsg, int U, int k,
-                                                          unsigned long long* __restrict__ bm, int Lp) {
+                                                          unsigned long long* __restrict__ bm, int Lp,
+                                                          int* __restrict__ bn1_ticket) {
     __shared__ float wsh[4 * MAX_K];
     const int blk = blockIdx.x;                        // block-uniform role
+    if (blk == 0 && threadIdx.x == 0) *bn1_ticket = 0;   // (for the filter-bank launch behind this one)
     if (blk < gx * gy)
         pack_tile<false>(x, nullptr, 0, codesT, pk2, nmask, B, L, Bs, PW, NW, flags, blk % gx, blk / gx,
                          bm, Lp);
@@ -246,7 +248,7 @@ int launch_pack_tables(explainn_ctx* c, const float* x, const explainn_params* p
     c->staged_B = 0;
     hipLaunchKernelGGL(pack_tables_kernel, dim3(gx * gy + c->U4), dim3(64 * PACK_WAVES), 0, s, x, c->codesT,
                        c->pk2, c->nmask, B, c->L, c->Bs, c->PW, c->NW, c->flags, gx, gy, p->conv_w,
-                       p->bn1_w, c->Wt, c->Wf, c->Wsg, c->U, c->k, c->bm, c->Lp);
+                       p->bn1_w, c->Wt, c->Wf, c->Wsg, c->U, c->k, c->bm, c->Lp, c->bn1_ticket);
     LAUNCH_CHECK();
     return EXPLAINN_OK;
 }

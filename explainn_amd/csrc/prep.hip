@@ -27,8 +27,10 @@ __global__ __launch_bounds__(128) void prep1_tables_kernel(const float* __restri
                                                            const float* __restrict__ gamma1,
                                                            float* __restrict__ Wt,
                                                            uint16_t* __restrict__ Wf,
-                                                           uint32_t* __restrict__ Wsg, int U, int k) {
+                                                           uint32_t* __restrict__ Wsg, int U, int k,
+                                                           int* __restrict__ bn1_ticket) {
     __shared__ float wsh[4 * MAX_K];
+    if (blockIdx.x == 0 && threadIdx.x == 0) *bn1_ticket = 0;   // (for a filter-bank launch behind this one)
     filter_tables_unit(conv_w, gamma1, Wt, Wf, Wsg, U, k, blockIdx.x, threadIdx.x, 128, wsh);
 }
 
@@ -97,25 +99,12 @@ __global__ __launch_bounds__(128) void prep1_stats_kernel(
     }
     const double mu = block_sum_128(mu_p, red);
     const double wGw = block_sum_128(q_p, red);
-    if (tid == 0) {
-        double var = wGw - mu * mu;
-        var = var > 0 ? var : 0;
-        const double sg = sqrt(var + BN_EPS_D);
-        const double a = (double)g1u / sg;
-        alpha[u] = (float)a;
-        shift[u] = (float)((double)b1u - a * mu);
-        mug[u] = mu;
-        sig1[u] = sg;
-        const double N1 = (double)B * (double)Lo;
-        rm[u] = (float)((1 - BN_MOM_D) * (double)rmu + BN_MOM_D * ((double)cbu + mu));
-        rv[u] = (float)((1 - BN_MOM_D) * (double)rvu + BN_MOM_D * var * N1 / (N1 - 1));
-        if (u == 0 && nbt) *nbt += 1;
-    }
+    if (tid == 0) bn1_fold_finish(mu, wGw, u, g1u, b1u, cbu, rmu, rvu, B, Lo, alpha, shift, mug, sig1, rm, rv, nbt);
 }
 
 int launch_prep1_tables(explainn_ctx* c, const explainn_params* p, hipStream_t s) {
     hipLaunchKernelGGL(prep1_tables_kernel, dim3(c->U4), dim3(128), 0, s, p->conv_w, p->bn1_w, c->Wt,
-                       c->Wf, c->Wsg, c->U, c->k);
+                       c->Wf, c->Wsg, c->U, c->k, c->bn1_ticket);
     LAUNCH_CHECK();
     return EXPLAINN_OK;
 }

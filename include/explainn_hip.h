@@ -215,8 +215,11 @@ int explainn_adam_step(int n_tensors, float* const* params, const float* const* 
                        int64_t step, double lr, double beta1, double beta2, double eps, void* stream);
 
 /* Input validation result of every pack since the last call: bit 0 set = some column of x was
- * neither one-hot nor all-zero (such columns were treated as N).  Synchronises `stream`,
- * writes the flags to *flags_host and clears them. */
+ * neither one-hot nor all-zero (such columns were treated as N); bit 1 (EXPLAINN_FLAG_BN1_TIMEOUT)
+ * set = a train forward's BatchNorm1 statistics, computed inside the filter-bank launch, gave up
+ * waiting for the input moments (bounded wait: that step's BatchNorm1 fold was skipped and its
+ * results are invalid).  Synchronises `stream`, writes the flags to *flags_host and clears them. */
+#define EXPLAINN_FLAG_BN1_TIMEOUT 2
 int explainn_input_flags(explainn_ctx* ctx, int* flags_host, void* stream);
 
 /* Measurement aid (bench.py's per-kernel roofline; the reference only logs steps per second,

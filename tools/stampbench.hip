@@ -159,7 +159,7 @@ int main() {
         for (int rep = 0; rep < 2; ++rep) {
             clear_stamps();
             CK(hipEventRecord(e0));
-            hipLaunchKernelGGL((conv_pool_mm_kernel<5, 2, true>), dim3(B / 32, tiles / 2, 6), dim3(64), 0, 0, pk2, nmask, Wf, Wsg, extp, idxp, n, Bs, PW, NW, 5);
+            hipLaunchKernelGGL((conv_pool_mm_kernel<5, 2, true>), dim3(B / 32, tiles / 2, 6), dim3(64), 0, 0, pk2, nmask, Wf, Wsg, extp, idxp, n, Bs, PW, NW, 5, cpm_bn1_args{});
             CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1)); CK(hipEventElapsedTime(&ms, e0, e1));
             if (rep) report("conv_pool", (B / 32) * (tiles / 2) * 6, 6, ms);
             {   // the matrix-core filter gradient: (32-sequence block, 16-unit tile, window half), two waves

@@ -19,6 +19,8 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# (at C2 the input moments and the BatchNorm1 fold run inside conv_pool_mm_kernel: the moments and
+# prep1_stats stages appear only for the grids that keep them as launches of their own)
 STAGE = {"pack_tables_kernel": "pack_tables", "moments_kernel": "moments", "prep1_stats_kernel": "prep1_stats",
          "conv_pool_mm_kernel": "conv_pool", "qmom_kernel": "qmom", "qmom_big_kernel": "qmom",
          "prep2_kernel": "prep2", "fc_fwd_kernel": "fc_fwd", "fc_fwd_bf_kernel": "fc_fwd",
