@@ -50,6 +50,7 @@ EXPORTS = (
     "explainn_stage_onehot", "explainn_dense_input",
     "explainn_stage_timing", "explainn_stage_count", "explainn_stage_name", "explainn_stage_times",
     "explainn_debug_keep_bits",
+    "explainn_forward_eval_keep", "explainn_input_grad", "explainn_backward_input",
 )
 
 
@@ -134,6 +135,12 @@ def load():
     lib.explainn_stage_times.restype = C.c_int
     lib.explainn_debug_keep_bits.argtypes = [ctx, C.c_int, _fp, _fp]
     lib.explainn_debug_keep_bits.restype = C.c_int
+    lib.explainn_forward_eval_keep.argtypes = [ctx, _fp, C.c_int, pp, _fp, _fp]
+    lib.explainn_forward_eval_keep.restype = C.c_int
+    lib.explainn_input_grad.argtypes = [ctx, _fp, C.c_int, pp, _fp, _fp]
+    lib.explainn_input_grad.restype = C.c_int
+    lib.explainn_backward_input.argtypes = [ctx, _fp, C.c_int, pp, gp, C.c_int, _fp, _fp]
+    lib.explainn_backward_input.restype = C.c_int
     lib.explainn_input_flags.argtypes = [ctx, C.POINTER(C.c_int), _fp]
     lib.explainn_input_flags.restype = C.c_int
     _lib = lib

@@ -169,13 +169,38 @@ class _TrainStep(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, x, *params):
         ctx.model = model
-        logits, ctx.token = model._launch_train(x)
+        ctx.x_dtype = x.dtype if torch.is_tensor(x) else None
+        # x.grad wanted: validate this batch before computing, so that soft input takes the dense
+        # kernels (and its gradient is the gradient at that x)
+        want_dx = torch.is_tensor(x) and x.requires_grad
+        logits, ctx.token = model._launch_train(x, validate=True if want_dx else None)
         return logits
 
     @staticmethod
     def backward(ctx, dlogits):
+        if ctx.needs_input_grad[1]:
+            grads, dx = ctx.model._launch_backward(dlogits, ctx.token, want_dx=True)
+            return (None, dx.to(ctx.x_dtype)) + tuple(grads)
         grads = ctx.model._launch_backward(dlogits, ctx.token)
         return (None, None) + tuple(grads)
+
+
+class _EvalInputGrad(torch.autograd.Function):
+    """Eval-mode forward whose logits carry a grad_fn back to x (saliency, gradient x input,
+    Integrated Gradients): the gradient flows to x only -- an eval forward gives no parameter
+    gradients, as before."""
+
+    @staticmethod
+    def forward(ctx, model, x):
+        ctx.model = model
+        ctx.x_dtype = x.dtype
+        logits, ctx.token = model._launch_eval_keep(x)
+        return logits
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dlogits):
+        return None, ctx.model._launch_input_grad(dlogits, ctx.token).to(ctx.x_dtype)
 
 
 class _Model(nn.Module):
@@ -538,6 +563,8 @@ class ExplaiNN(_Model):
             if torch.is_grad_enabled():
                 return _TrainStep.apply(self, x, *self.parameters())
             return self._launch_train(x)[0]
+        if torch.is_grad_enabled() and torch.is_tensor(x) and x.requires_grad and x.shape[0] > 0:
+            return _EvalInputGrad.apply(self, x)
         x = self._prep_input(x, dev)
         B = x.shape[0]
         if B == 0:                                   # torch returns an empty (0, T) tensor in eval
@@ -552,7 +579,53 @@ class ExplaiNN(_Model):
             self._check_flags(ctx, dev, x)
         return logits
 
-    def _launch_train(self, x, keep_mask=None):
+    def _launch_eval_keep(self, x):
+        """Eval forward that keeps what _launch_input_grad needs (explainn_forward_eval_keep: the
+        same logits as forward()).  The batch is validated first, so soft input takes the dense
+        kernels.  Returns (logits, token)."""
+        dev = self._device()
+        x = self._prep_input(x, dev)
+        B = x.shape[0]
+        self._rt.token += 1
+        ctx = self._context(B, dev)
+        ps, keep = self._params_struct(dev)
+        logits = torch.empty(B, self._options["n_features"], device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            xp = self._x_ptr(ctx, x, dev, validate=not isinstance(x, BaseCodes))
+            self._rt.x_keep = x                # a dense batch is read again by the input gradient
+            _lib.check(ctx.lib.explainn_forward_eval_keep(ctx.handle, xp, B, C.byref(ps),
+                                                          logits.data_ptr(), self._stream(dev)))
+            if isinstance(x, BaseCodes):
+                self._check_flags(ctx, dev, x)
+        return logits, self._rt.token
+
+    def _launch_input_grad(self, dlogits, token):
+        """dx (B,4,L) of the last _launch_eval_keep for d loss / d logits = dlogits."""
+        if token != self._rt.token:
+            raise RuntimeError("input gradient of a stale forward: the fused kernels keep one forward "
+                               "per model (call backward before the next forward)")
+        dev = self._device()
+        ctx = self._rt.ctx
+        ps, keep = self._params_struct(dev)
+        dl = dlogits.to(device=dev, dtype=torch.float32).contiguous()
+        B = dl.shape[0]
+        dx = torch.empty(B, 4, self._options["sequence_length"], device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            _lib.check(ctx.lib.explainn_input_grad(ctx.handle, dl.data_ptr(), B, C.byref(ps),
+                                                   dx.data_ptr(), self._stream(dev)))
+        return dx
+
+    def input_gradient(self, x, dlogits):
+        """d(sum(dlogits * model(x))) / dx in eval mode, (B,4,L) fp32, without autograd: one
+        eval forward and the input-gradient launches.  x as forward() takes it (fp32 one-hot or
+        soft, or base codes -- then the gradient is with respect to the one-hot the model ran on,
+        the reverse complement's for BaseCodes(..., reverse_complement=True))."""
+        if self.training:
+            raise RuntimeError("input_gradient is an eval-mode path; call model.eval()")
+        _, token = self._launch_eval_keep(x)
+        return self._launch_input_grad(dlogits, token)
+
+    def _launch_train(self, x, keep_mask=None, validate=None):
         dev = self._device()
         x = self._prep_input(x, dev)
         B = x.shape[0]
@@ -574,7 +647,7 @@ class ExplaiNN(_Model):
         seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if self.dropout_p > 0 else 0
         with torch.cuda.device(dev):
             _lib.check(ctx.lib.explainn_forward_train(
-                ctx.handle, self._x_ptr(ctx, x, dev), B, C.byref(ps), mask_ptr, float(self.dropout_p),
+                ctx.handle, self._x_ptr(ctx, x, dev, validate), B, C.byref(ps), mask_ptr, float(self.dropout_p),
                 C.c_uint64(seed), logits.data_ptr(), self._stream(dev)))
             self._check_flags(ctx, dev, x)
         self._touched()
@@ -586,7 +659,7 @@ class ExplaiNN(_Model):
         train-mode forward (parity testing against a recorded reference mask)."""
         self._rt.pending = keep_mask
 
-    def _launch_backward(self, dlogits, token):
+    def _launch_backward(self, dlogits, token, want_dx=False):
         if token != self._rt.token:
             raise RuntimeError("backward of a stale forward: the fused kernels keep one training "
                                "step in flight per model (call backward before the next forward)")
@@ -604,13 +677,20 @@ class ExplaiNN(_Model):
             setattr(gs, field, v.data_ptr())
         dl = dlogits.to(torch.float32).contiguous()
         B = dl.shape[0]
+        dx = None
         with torch.cuda.device(dev):
-            _lib.check(ctx.lib.explainn_backward(ctx.handle, dl.data_ptr(), B, C.byref(ps),
-                                                 C.byref(gs), int(self.freeze_top_n_filters),
-                                                 self._stream(dev)))
+            if want_dx:
+                dx = torch.empty(B, 4, self._options["sequence_length"], device=dev, dtype=torch.float32)
+                _lib.check(ctx.lib.explainn_backward_input(ctx.handle, dl.data_ptr(), B, C.byref(ps),
+                                                           C.byref(gs), int(self.freeze_top_n_filters),
+                                                           dx.data_ptr(), self._stream(dev)))
+            else:
+                _lib.check(ctx.lib.explainn_backward(ctx.handle, dl.data_ptr(), B, C.byref(ps),
+                                                     C.byref(gs), int(self.freeze_top_n_filters),
+                                                     self._stream(dev)))
         if self.grad_sync is not None:
             self.grad_sync(flat)
-        return views
+        return (views, dx) if want_dx else views
 
     # -- the façade test.py / interpret.py use -----------------------------------------------
     def _first_four_rows(self, x_rep):

@@ -89,6 +89,12 @@ void carve(explainn_ctx* c, Carver& cv) {
     cv.take(&c->lossp, 256);
     cv.take(&c->site_cnt, U4 * Bs);
     cv.take(&c->site_off, U4 * Bs);
+    const int64_t D = 2 * c->k - 1;
+    cv.take(&c->igcoef, U4 * 2);
+    cv.take(&c->igP, D * 16 * c->k);
+    cv.take(&c->igR, K4);
+    cv.take(&c->igH, D * D * 16);
+    cv.take(&c->igC, D * 4);
     cv.off = (cv.off + 255) & ~int64_t(255);
 }
 
@@ -123,7 +129,7 @@ int eval_front(explainn_ctx* c, const float* x, int B, const explainn_params* p,
     // every eval-mode entry point overwrites scratch a pending backward would read (codes, ext,
     // idx, z, bits ...): whatever train forward was in flight is gone, and its backward must fail
     // with E_STATE instead of returning the eval batch's gradients
-    c->fwd_B = 0; c->tail_B = 0;
+    c->fwd_B = 0; c->tail_B = 0; c->keep_B = 0;
     if (c->dense) {
         if (!x) { explainn_set_error("dense input mode needs x"); return EXPLAINN_E_ARG; }
         c->staged_B = 0;
@@ -261,6 +267,36 @@ extern "C" int explainn_forward_eval(explainn_ctx* c, const float* x, int B,
     return EXPLAINN_OK;
 }
 
+// Eval forward that keeps what the input gradient needs: the argmax offsets of the pooling (the
+// forward above skips storing them) next to ext and o, which every eval forward keeps.  The logits are
+// those of explainn_forward_eval, bit for bit: idx is an extra output of the same filter-bank pass.
+extern "C" int explainn_forward_eval_keep(explainn_ctx* c, const float* x, int B,
+                                          const explainn_params* p, float* logits, void* stream) {
+    TRY(check_batch(c, B));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    TRY(eval_front(c, x, B, p, s));
+    if (c->dense) TRY(launch_dense_conv_pool(c, x, p, B, s));
+    else TRY(launch_conv_pool(c, p, B, true, s));
+    TRY(launch_fc_fwd(c, p, B, false, nullptr, 0.f, 0, s));
+    TRY(launch_head_fwd(c, p, B, false, logits, nullptr, s));
+    c->keep_B = B;
+    c->keep_x = c->dense ? x : nullptr;
+    return EXPLAINN_OK;
+}
+
+extern "C" int explainn_input_grad(explainn_ctx* c, const float* dlogits, int B,
+                                   const explainn_params* p, float* dx, void* stream) {
+    TRY(check_batch(c, B));
+    if (!dlogits || !dx) { explainn_set_error("dlogits and dx are required"); return EXPLAINN_E_ARG; }
+    if (c->keep_B != B) {
+        explainn_set_error("input_grad(B=%d) without a matching forward_eval_keep (last B=%d)", B, c->keep_B);
+        return EXPLAINN_E_STATE;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    TRY(launch_ig_eval_dy(c, p, dlogits, B, s));
+    return launch_input_grad(c, p, B, false, nullptr, dx, s);
+}
+
 extern "C" int explainn_unit_outputs(explainn_ctx* c, const float* x, int B,
                                      const explainn_params* p, float* outs, void* stream) {
     TRY(check_batch(c, B));
@@ -291,7 +327,7 @@ extern "C" int explainn_stage_codes(explainn_ctx* c, const uint8_t* codes, int B
                                     int reverse_complement, void* stream) {
     TRY(check_batch(c, B));
     if (!codes) { explainn_set_error("codes is null"); return EXPLAINN_E_ARG; }
-    c->fwd_B = 0; c->tail_B = 0;       // the packed codes of a pending backward are overwritten
+    c->fwd_B = 0; c->tail_B = 0; c->keep_B = 0;   // the packed codes of a pending backward are overwritten
     return launch_pack_codes(c, codes, B, reverse_complement ? 1 : 0, static_cast<hipStream_t>(stream));
 }
 
@@ -336,7 +372,7 @@ extern "C" int explainn_forward_train(explainn_ctx* c, const float* x, int B,
         return EXPLAINN_E_ARG;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    c->fwd_B = 0;
+    c->fwd_B = 0; c->keep_B = 0;
     c->eval_valid = false;             // the train-mode folds overwrite the eval-mode tables
     // the one-hot batch is packed and the filter tables are built by one launch; a staged batch of
     // base codes (x == NULL) is already packed and only needs the tables
@@ -437,6 +473,17 @@ extern "C" int explainn_backward(explainn_ctx* c, const float* dlogits, int B,
     return backward_tail(c, B, p, g, freeze_top_n_filters, nullptr, s);
 }
 
+extern "C" int explainn_backward_input(explainn_ctx* c, const float* dlogits, int B,
+                                       const explainn_params* p, const explainn_grads* g,
+                                       int freeze_top_n_filters, float* dx, void* stream) {
+    if (!dx) { explainn_set_error("dx is null"); return EXPLAINN_E_ARG; }
+    TRY(explainn_backward(c, dlogits, B, p, g, freeze_top_n_filters, stream));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // passB left dy and the partial sums S1, S2; the BatchNorm1 statistics are those of the forward
+    TRY(launch_ig_tables(c, p, B, s));
+    return launch_input_grad(c, p, B, true, c->dense_x, dx, s);
+}
+
 extern "C" int explainn_loss_grad(explainn_ctx* c, int loss_kind, const float* logits,
                                   const float* targets, int B, float* loss_out, float* dlogits,
                                   void* stream) {
@@ -509,7 +556,7 @@ extern "C" int explainn_train_step_conv(explainn_ctx* c, int B, const explainn_p
 extern "C" int explainn_dense_input(explainn_ctx* c, int enable) {
     if (!c) { explainn_set_error("null context"); return EXPLAINN_E_ARG; }
     c->dense = enable != 0;
-    c->fwd_B = 0; c->tail_B = 0;
+    c->fwd_B = 0; c->tail_B = 0; c->keep_B = 0;
     return EXPLAINN_OK;
 }
 
@@ -517,7 +564,7 @@ extern "C" int explainn_stage_onehot(explainn_ctx* c, const float* x, int B, voi
     TRY(check_batch(c, B));
     if (!x) { explainn_set_error("x is null"); return EXPLAINN_E_ARG; }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    c->fwd_B = 0; c->tail_B = 0;        // the packed codes of a pending backward are overwritten
+    c->fwd_B = 0; c->tail_B = 0; c->keep_B = 0;   // the packed codes of a pending backward are overwritten
     TRY(launch_pack(c, x, B, true, s));  // with the bit masks: the batch may feed a train forward
     c->staged_B = B;
     return EXPLAINN_OK;

@@ -109,6 +109,14 @@ struct explainn_ctx {
                           //      zeroed by the launch in front of it (pack_tables / prep1_tables)
     int* site_cnt;        // [U4][Bs]  sites per (unit, sequence) of the current batch (filter->PWM export)
     int* site_off;        // [U4][Bs]  their exclusive scan in sequence order, plus the running total
+    // input gradient (inputgrad.hip): D = 2k-1 tap offsets / position classes
+    double* igcoef;       // [U4][2]   per-unit coefficients c_u, k_u of the train-mode dense terms
+    double* igP;          // [D][4][4][k] unit sums of filter products at tap offset d
+    double* igR;          // [4][k]
+    float* igH;           // [D classes][D][4 a'][4 a]  the H tables
+    float* igC;           // [D classes][4]             the constant table
+    int keep_B;           // batch of the last explainn_forward_eval_keep (0 = none)
+    const float* keep_x;  // its x when it ran the dense kernels (read again by explainn_input_grad)
 };
 
 enum explainn_stage {
@@ -179,6 +187,12 @@ int launch_passB(explainn_ctx* c, int B, hipStream_t s);
 int launch_conv_bwd(explainn_ctx* c, int B, hipStream_t s);
 int launch_fin_bwd(explainn_ctx* c, const explainn_params* p, const explainn_grads* g, int B,
                    int freeze_n, hipStream_t s);
+
+// input gradient (inputgrad.hip): eval-mode dy from dlogits; the train-mode tables; dx
+int launch_ig_eval_dy(explainn_ctx* c, const explainn_params* p, const float* dlogits, int B, hipStream_t s);
+int launch_ig_tables(explainn_ctx* c, const explainn_params* p, int B, hipStream_t s);
+int launch_input_grad(explainn_ctx* c, const explainn_params* p, int B, bool train, const float* dense_x,
+                      float* dx, hipStream_t s);
 
 int launch_dense_moments(explainn_ctx* c, const float* x, int B, hipStream_t s);
 int launch_dense_conv_pool(explainn_ctx* c, const float* x, const explainn_params* p, int B, hipStream_t s);

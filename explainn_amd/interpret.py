@@ -160,6 +160,59 @@ def filter_pwms(exp_model, Xs, idxs, rev_complement=False, batch_size=1024, site
             "nsites": site_total.cpu().numpy().astype(np.int64), "hit": hit}
 
 
+def input_gradients(model, Xs, target=None, batch_size=4096, rev_complement=False, times_input=False):
+    """Eval-mode input gradients (N,4,L), float32 numpy: d logit[target] / d x -- or d sum(logits)
+    / d x with target=None -- for every sequence, what `x.requires_grad_(); model(x)[:, t].sum()
+    .backward()` leaves in x.grad on the reference module, in batches on the device with no
+    autograd bookkeeping.  The saliency map; times_input=True gives gradient x input, and averaging
+    it over interpolated inputs is Integrated Gradients (soft input takes the dense kernels).
+
+    Xs: (N,4,L) one-hot or real-valued (numpy or tensor), or (N,L) uint8 base codes (0..3 = A,C,G,T,
+    4 = N).  rev_complement=True runs the model on each sequence's reverse complement and maps the
+    gradient back onto the given strand (base and position flipped), so that it multiplies the
+    given one-hot."""
+    dev = model.final.weight.device
+    T, L = model._options["n_features"], model._options["sequence_length"]
+    if target is not None and not 0 <= int(target) < T:
+        raise ValueError("target must be a task index in [0, %d)" % T)
+    codes = (torch.is_tensor(Xs) and Xs.dtype == torch.uint8) or \
+        (isinstance(Xs, np.ndarray) and Xs.dtype == np.uint8)
+    Xs = torch.as_tensor(Xs) if codes else _as_tensor(Xs)
+    out = np.zeros((len(Xs), 4, L), dtype=np.float32)
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad(), model.eval_cache():
+            for i, xb in _batches(Xs, batch_size):
+                xb = xb.to(dev, non_blocking=True)
+                B = xb.shape[0]
+                dl = torch.zeros(B, T, device=dev, dtype=torch.float32)
+                if target is None:
+                    dl.fill_(1.0)
+                else:
+                    dl[:, int(target)] = 1.0
+                if codes:
+                    from .architectures import BaseCodes
+                    dx = model.input_gradient(BaseCodes(xb, rev_complement), dl)
+                    if rev_complement:
+                        dx = dx.flip(1, 2)
+                    if times_input:
+                        onehot = torch.zeros(B, 5, L, device=dev, dtype=torch.float32)
+                        onehot.scatter_(1, xb.long().clamp(max=4).unsqueeze(1), 1.0)
+                        dx = dx * onehot[:, :4]
+                else:
+                    xb = xb.to(torch.float32)
+                    dx = model.input_gradient(xb.flip(1, 2) if rev_complement else xb, dl)
+                    if rev_complement:
+                        dx = dx.flip(1, 2)
+                    if times_input:
+                        dx = dx * xb
+                out[i:i + B] = dx.cpu().numpy()
+    finally:
+        model.train(was_training)
+    return out
+
+
 def filter_importances(outs, final_weight, idxs, hit):
     """interpret.py:176-183 + 485-490: for each unit the (T, n) importances outs*weight of the
     well-predicted sequences with at least one position above the unit's threshold.  `hit` is

@@ -112,6 +112,30 @@ int explainn_forward_train(explainn_ctx* ctx, const float* x, int B, const expla
 int explainn_backward(explainn_ctx* ctx, const float* dlogits, int B, const explainn_params* p,
                       const explainn_grads* g, int freeze_top_n_filters, void* stream);
 
+/* The input gradient: what autograd gives as x.grad after model(x) and backward(dlogits) in the
+ * reference, whose module is plain torch (saliency maps, gradient x input, Integrated Gradients,
+ * the per-base contributions TF-MoDISco reads).  dx: device, fp32 (B,4,L), OVERWRITTEN.
+ *
+ * explainn_forward_eval_keep: explainn_forward_eval (same logits, bit for bit) that also keeps the
+ * pooling's argmax offsets for explainn_input_grad.  explainn_input_grad: dlogits (B,T) -> dx for the
+ * last eval_keep forward of B sequences; EXPLAINN_E_STATE when another call came in between (any
+ * forward, explainn_stage_codes / _stage_onehot / _dense_input).  An eval forward gives no
+ * parameter gradients.
+ * explainn_backward_input: explainn_backward (the same 14 gradients, bit for bit) plus dx of the
+ * train-mode forward, through BatchNorm1's batch statistics.
+ * With x == NULL (a staged batch of base codes) dx is the gradient with respect to the one-hot tensor
+ * the forward ran on: the one-hot of the codes, or of their reverse complement when they were staged
+ * with reverse_complement != 0 (un-flip it -- dx[:, ::-1, ::-1] -- for the gradient in the staged
+ * strand's coordinates).  N columns get their gradient like any other column (the reference's x.grad
+ * there is the gradient with respect to an all-zero column).  Soft input (explainn_dense_input) gives
+ * the gradient at that x. */
+int explainn_forward_eval_keep(explainn_ctx* ctx, const float* x, int B, const explainn_params* p,
+                               float* logits, void* stream);
+int explainn_input_grad(explainn_ctx* ctx, const float* dlogits, int B, const explainn_params* p,
+                        float* dx, void* stream);
+int explainn_backward_input(explainn_ctx* ctx, const float* dlogits, int B, const explainn_params* p,
+                            const explainn_grads* g, int freeze_top_n_filters, float* dx, void* stream);
+
 /* get_loss (architectures/__init__.py:446-456), mean reduction, fused with its gradient:
  * loss_out (1 float, device) and dlogits (B,T, device). */
 int explainn_loss_grad(explainn_ctx* ctx, int loss_kind, const float* logits, const float* targets,

@@ -31,6 +31,14 @@ C2_STEP = [
     r"^conv_bwd_mm_kernel<19>", r"^fin_bwd_kernel", r"adam_kernel",
 ]
 
+# the input gradient (inputgrad.hip) at C2: an eval-mode attribution pass and a train step with dx
+# launch these; held to the same no-spill rule
+INPUT_GRAD = [
+    r"^ig_eval_dy_kernel", r"^ig_coef_kernel", r"^ig_pair_kernel", r"^ig_tables_kernel",
+    r"^input_grad_kernel<false, false>", r"^input_grad_kernel<true, false>", r"^input_grad_kernel<true, true>",
+]
+GATED = C2_STEP + INPUT_GRAD
+
 
 # Register cliffs measured in the pipeline: 1024-thread blocks of which TWO must
 # share a CU (300 units on 256 CUs take two rounds otherwise) -- 64 registers, not one more.
@@ -70,8 +78,8 @@ def main():
     # (v_writelane / v_readlane), no memory involved: reported in the table, not an error
     hard = lambda r: r.get("scratch", 0) > 0 or r.get("vgpr_spill", 0) > 0
     spilled = lambda r: hard(r) or r.get("sgpr_spill", 0) > 0
-    hot = [r for r in rows if any(re.search(p, r["name"]) for p in C2_STEP)]
-    missing = [p for p in C2_STEP if not any(re.search(p, r["name"]) for r in rows)]
+    hot = [r for r in rows if any(re.search(p, r["name"]) for p in GATED)]
+    missing = [p for p in GATED if not any(re.search(p, r["name"]) for r in rows)]
     bad = [r for r in hot if hard(r)]
     others = [r for r in rows if spilled(r) and r not in hot]
     if "--table" in sys.argv:
