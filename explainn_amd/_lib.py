@@ -51,6 +51,7 @@ EXPORTS = (
     "explainn_stage_timing", "explainn_stage_count", "explainn_stage_name", "explainn_stage_times",
     "explainn_debug_keep_bits",
     "explainn_forward_eval_keep", "explainn_input_grad", "explainn_backward_input",
+    "explainn_ism_workspace_bytes", "explainn_ism",
 )
 
 
@@ -141,6 +142,10 @@ def load():
     lib.explainn_input_grad.restype = C.c_int
     lib.explainn_backward_input.argtypes = [ctx, _fp, C.c_int, pp, gp, C.c_int, _fp, _fp]
     lib.explainn_backward_input.restype = C.c_int
+    lib.explainn_ism_workspace_bytes.argtypes = [ctx, C.c_int]
+    lib.explainn_ism_workspace_bytes.restype = C.c_int64
+    lib.explainn_ism.argtypes = [ctx, _fp, C.c_int, pp, _fp, _fp, _fp, C.c_int64, _fp]
+    lib.explainn_ism.restype = C.c_int
     lib.explainn_input_flags.argtypes = [ctx, C.POINTER(C.c_int), _fp]
     lib.explainn_input_flags.restype = C.c_int
     _lib = lib

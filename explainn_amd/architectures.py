@@ -625,6 +625,51 @@ class ExplaiNN(_Model):
         _, token = self._launch_eval_keep(x)
         return self._launch_input_grad(dlogits, token)
 
+    def in_silico_mutagenesis(self, x):
+        """In-silico mutagenesis in eval mode (explainn_ism): returns (logits (B,T), delta (B,T,4,L)),
+        device fp32 tensors, with delta[b,t,a,p] = logit_t(x_b with base a at p) - logit_t(x_b) for
+        a = A,C,G,T -- exactly 0 at the reference base -- and logits those of forward(), bit for bit.
+        x: fp32 one-hot (B,4,L), validated before anything is computed (a batch that is not one-hot
+        raises ValueError: substitutions are defined on one-hot sequences), or base codes; for
+        BaseCodes(..., reverse_complement=True) rows and positions are those of the strand the model
+        ran on.  The workspace comes from torch's caching allocator."""
+        if self.training:
+            raise RuntimeError("in_silico_mutagenesis is an eval-mode path; call model.eval()")
+        dev = self._device()
+        x = self._prep_input(x, dev)
+        B = x.shape[0]
+        T, L = self._options["n_features"], self._options["sequence_length"]
+        logits = torch.empty(B, T, device=dev, dtype=torch.float32)
+        delta = torch.empty(B, T, 4, L, device=dev, dtype=torch.float32)
+        if B == 0:
+            return logits, delta
+        self._rt.token += 1        # eval overwrites the scratch of a train forward still awaiting backward
+        ctx = self._context(B, dev)
+        ps, keep = self._params_struct(dev)
+        lib, h, stream = ctx.lib, ctx.handle, self._stream(dev)
+        with torch.cuda.device(dev):
+            if isinstance(x, BaseCodes):
+                self._x_ptr(ctx, x, dev)                  # staged: the call takes x == NULL
+            else:
+                if self.dense_input:
+                    raise ValueError("in_silico_mutagenesis needs one-hot input (dense_input is True)")
+                self._rt.calls += 1
+                _lib.check(lib.explainn_dense_input(h, 0))
+                _lib.check(lib.explainn_stage_onehot(h, x.data_ptr(), B, stream))
+                flags = C.c_int(0)
+                _lib.check(lib.explainn_input_flags(h, C.byref(flags), stream))
+                if flags.value & 1:
+                    raise ValueError(
+                        "input is not one-hot: in-silico mutagenesis substitutes bases of one-hot (A,C,G,T) "
+                        "or all-zero (N) columns, as sequence.one_hot_encode produces")
+            nbytes = int(lib.explainn_ism_workspace_bytes(h, B))
+            ws = torch.empty(max(nbytes, 1), device=dev, dtype=torch.uint8)
+            _lib.check(lib.explainn_ism(h, None, B, C.byref(ps), logits.data_ptr(), delta.data_ptr(),
+                                        ws.data_ptr(), nbytes, stream))
+            if isinstance(x, BaseCodes):
+                self._check_flags(ctx, dev, x)
+        return logits, delta
+
     def _launch_train(self, x, keep_mask=None, validate=None):
         dev = self._device()
         x = self._prep_input(x, dev)

@@ -297,6 +297,33 @@ extern "C" int explainn_input_grad(explainn_ctx* c, const float* dlogits, int B,
     return launch_input_grad(c, p, B, false, nullptr, dx, s);
 }
 
+extern "C" int64_t explainn_ism_workspace_bytes(const explainn_ctx* c, int B) {
+    if (check_batch(c, B) != EXPLAINN_OK) return 0;
+    return ism_workspace_bytes(c, B);
+}
+
+extern "C" int explainn_ism(explainn_ctx* c, const float* x, int B, const explainn_params* p,
+                            float* logits, float* delta, void* workspace, int64_t workspace_bytes,
+                            void* stream) {
+    TRY(check_batch(c, B));
+    if (!logits || !delta || !workspace) {
+        explainn_set_error("logits, delta and workspace are required");
+        return EXPLAINN_E_ARG;
+    }
+    if (c->dense) { explainn_set_error("in-silico mutagenesis works on base codes: one-hot input only"); return EXPLAINN_E_UNSUPPORTED; }
+    const int64_t need = ism_workspace_bytes(c, B);
+    if (workspace_bytes < need) {
+        explainn_set_error("ISM workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)need);
+        return EXPLAINN_E_ARG;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    TRY(eval_front(c, x, B, p, s));
+    TRY(launch_conv_pool(c, p, B, false, s));
+    TRY(launch_fc_fwd(c, p, B, false, nullptr, 0.f, 0, s));
+    TRY(launch_head_fwd(c, p, B, false, logits, nullptr, s));
+    return launch_ism(c, p, B, delta, static_cast<float*>(workspace), s);
+}
+
 extern "C" int explainn_unit_outputs(explainn_ctx* c, const float* x, int B,
                                      const explainn_params* p, float* outs, void* stream) {
     TRY(check_batch(c, B));

@@ -194,6 +194,11 @@ int launch_ig_tables(explainn_ctx* c, const explainn_params* p, int B, hipStream
 int launch_input_grad(explainn_ctx* c, const explainn_params* p, int B, bool train, const float* dense_x,
                       float* dx, hipStream_t s);
 
+// in-silico mutagenesis (ism.hip): the caller's workspace for one sub-batch of B sequences; the
+// per-unit substitution kernels and the per-task sum, sub-batch by sub-batch
+int64_t ism_workspace_bytes(const explainn_ctx* c, int B);
+int launch_ism(explainn_ctx* c, const explainn_params* p, int B, float* delta, float* ws, hipStream_t s);
+
 int launch_dense_moments(explainn_ctx* c, const float* x, int B, hipStream_t s);
 int launch_dense_conv_pool(explainn_ctx* c, const float* x, const explainn_params* p, int B, hipStream_t s);
 int launch_dense_conv_bwd(explainn_ctx* c, const float* x, int B, hipStream_t s);

@@ -213,6 +213,50 @@ def input_gradients(model, Xs, target=None, batch_size=4096, rev_complement=Fals
     return out
 
 
+def in_silico_mutagenesis(model, Xs, target=None, batch_size=4096, rev_complement=False, absolute=False):
+    """In-silico mutagenesis in eval mode, float32 numpy (N,T,4,L) -- (N,4,L) for one `target`:
+    row a at position p is logit(sequence with base a at p) - logit(sequence), 0 at the reference
+    base; absolute=True gives the mutant logits themselves.  One device pass per batch
+    (ExplaiNN.in_silico_mutagenesis) instead of 3L mutated copies through the model.
+
+    Xs: (N,4,L) one-hot (numpy or tensor) or (N,L) uint8 base codes (0..3 = A,C,G,T, 4 = N).
+    rev_complement=True runs the model on each sequence's reverse complement and maps rows and
+    positions back (base a <-> 3-a, p <-> L-1-p), so that row a at p means "base a at p of the given
+    strand"."""
+    from .architectures import BaseCodes
+    dev = model.final.weight.device
+    T, L = model._options["n_features"], model._options["sequence_length"]
+    if target is not None and not 0 <= int(target) < T:
+        raise ValueError("target must be a task index in [0, %d)" % T)
+    codes = (torch.is_tensor(Xs) and Xs.dtype == torch.uint8) or \
+        (isinstance(Xs, np.ndarray) and Xs.dtype == np.uint8)
+    Xs = torch.as_tensor(Xs) if codes else _as_tensor(Xs)
+    out = np.zeros((len(Xs), T, 4, L) if target is None else (len(Xs), 4, L), dtype=np.float32)
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad(), model.eval_cache():
+            for i, xb in _batches(Xs, batch_size):
+                xb = xb.to(dev, non_blocking=True)
+                if codes:
+                    logits, delta = model.in_silico_mutagenesis(BaseCodes(xb, rev_complement))
+                else:
+                    xb = xb.to(torch.float32)
+                    logits, delta = model.in_silico_mutagenesis(xb.flip(1, 2) if rev_complement else xb)
+                if rev_complement:
+                    delta = delta.flip(2, 3)
+                if absolute:
+                    delta = delta + logits[:, :, None, None]
+                if target is not None:
+                    delta = delta[:, int(target)]
+                out[i:i + xb.shape[0]] = delta.cpu().numpy()
+        if model.validate_input:
+            model.check_input()
+    finally:
+        model.train(was_training)
+    return out
+
+
 def filter_importances(outs, final_weight, idxs, hit):
     """interpret.py:176-183 + 485-490: for each unit the (T, n) importances outs*weight of the
     well-predicted sequences with at least one position above the unit's threshold.  `hit` is

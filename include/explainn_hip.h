@@ -136,6 +136,23 @@ int explainn_input_grad(explainn_ctx* ctx, const float* dlogits, int B, const ex
 int explainn_backward_input(explainn_ctx* ctx, const float* dlogits, int B, const explainn_params* p,
                             const explainn_grads* g, int freeze_top_n_filters, float* dx, void* stream);
 
+/* In-silico mutagenesis, eval mode: the change of every logit when one base is substituted,
+ *   delta[b,t,a,p] = logit_t(x_b with column p replaced by one-hot(a)) - logit_t(x_b),  a = A,C,G,T,
+ * fp32 (B,T,4,L) on the device, OVERWRITTEN, plus logits (B,T), bit-identical to
+ * explainn_forward_eval on the same batch (absolute mutant logits = logits[:,:,None,None] + delta).
+ * Exactly 0 at the reference base (a = the base at p), at positions whose conv windows all fall in the
+ * tail MaxPool1d(7,7) drops (p >= 7n + k - 1), and for any substitution that moves no unit's pooled
+ * extreme.  At an N position all four rows are real substitutions; substitutions to N are not
+ * computed.  x == NULL means the staged batch; for codes staged with reverse_complement != 0 the
+ * output is in the coordinates of the strand the model ran on, as for explainn_input_grad.  One-hot
+ * and base codes only: in dense input mode EXPLAINN_E_UNSUPPORTED.  Like every eval entry point it
+ * ends a pending train forward (its backward then returns EXPLAINN_E_STATE).  No host sync.
+ * workspace: device memory of at least explainn_ism_workspace_bytes(ctx, B) bytes (the caller's: the
+ * context's own scratch does not grow); larger batches run in sub-batches of that size. */
+int64_t explainn_ism_workspace_bytes(const explainn_ctx* ctx, int B);
+int explainn_ism(explainn_ctx* ctx, const float* x, int B, const explainn_params* p, float* logits,
+                 float* delta, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* get_loss (architectures/__init__.py:446-456), mean reduction, fused with its gradient:
  * loss_out (1 float, device) and dlogits (B,T, device). */
 int explainn_loss_grad(explainn_ctx* ctx, int loss_kind, const float* logits, const float* targets,

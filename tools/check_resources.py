@@ -37,7 +37,9 @@ INPUT_GRAD = [
     r"^ig_eval_dy_kernel", r"^ig_coef_kernel", r"^ig_pair_kernel", r"^ig_tables_kernel",
     r"^input_grad_kernel<false, false>", r"^input_grad_kernel<true, false>", r"^input_grad_kernel<true, true>",
 ]
-GATED = C2_STEP + INPUT_GRAD
+# in-silico mutagenesis (ism.hip) at C2: k = 19 -> four pooled windows per substitution, one task
+ISM = [r"^ism_units_kernel<4>", r"^ism_sum_kernel<1>"]
+GATED = C2_STEP + INPUT_GRAD + ISM
 
 
 # Register cliffs measured in the pipeline: 1024-thread blocks of which TWO must
