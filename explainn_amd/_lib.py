@@ -52,7 +52,12 @@ EXPORTS = (
     "explainn_debug_keep_bits",
     "explainn_forward_eval_keep", "explainn_input_grad", "explainn_backward_input",
     "explainn_ism_workspace_bytes", "explainn_ism",
+    "explainn_sync_exchange_elems", "explainn_sync_phase",
 )
+SYNC_PHASES = 8
+SYNC_ARG_FIELDS = ("x", "targets", "dlogits", "dl_scale", "B_local", "B_global", "params", "grads",
+                   "loss_kind", "dropout_p", "seed", "keep_mask", "freeze_top_n_filters", "logits",
+                   "loss_out")
 
 
 class Params(C.Structure):
@@ -68,6 +73,15 @@ class ExplainnError(RuntimeError):
 
 
 _lib = None
+
+
+class SyncArgs(C.Structure):
+    """explainn_sync_args: one sync-BN step's arguments (include/explainn_hip.h)."""
+    _fields_ = [("x", _fp), ("targets", _fp), ("dlogits", _fp), ("dl_scale", C.c_float),
+                ("B_local", C.c_int), ("B_global", C.c_int), ("params", C.POINTER(Params)),
+                ("grads", C.POINTER(Grads)), ("loss_kind", C.c_int), ("dropout_p", C.c_float),
+                ("seed", C.c_uint64), ("keep_mask", _fp), ("freeze_top_n_filters", C.c_int),
+                ("logits", _fp), ("loss_out", _fp)]
 
 
 def load():
@@ -146,6 +160,10 @@ def load():
     lib.explainn_ism_workspace_bytes.restype = C.c_int64
     lib.explainn_ism.argtypes = [ctx, _fp, C.c_int, pp, _fp, _fp, _fp, C.c_int64, _fp]
     lib.explainn_ism.restype = C.c_int
+    lib.explainn_sync_exchange_elems.argtypes = [ctx, C.c_int]
+    lib.explainn_sync_exchange_elems.restype = C.c_int64
+    lib.explainn_sync_phase.argtypes = [ctx, C.c_int, C.POINTER(SyncArgs), _fp, _fp, _fp]
+    lib.explainn_sync_phase.restype = C.c_int
     lib.explainn_input_flags.argtypes = [ctx, C.POINTER(C.c_int), _fp]
     lib.explainn_input_flags.restype = C.c_int
     _lib = lib

@@ -148,6 +148,8 @@ class _Runtime:
         self.ctx = None
         self.token = 0
         self.pending = None
+        self.sync = None         # sync-BN forward awaiting its backward (_launch_train_sync)
+        self.sync_bufs = None    # its exchange buffers
         self.x_keep = None
         self.calls = 0           # forwards since the model was built (input validation schedule)
         self.soft_seen = False   # a validating call met a batch that was not one-hot
@@ -273,6 +275,7 @@ class ExplaiNN(_Model):
         # float input); True: always dense; False: a batch that is not one-hot is an error
         self.dense_input = None
         self.grad_sync = None          # optional callable(flat_grad_tensor): multi-GPU all-reduce
+        self.sync_bn = None            # parallel.sync_batchnorm: a reducer -> full-batch BatchNorm statistics
         # rows [0:n) of the filter gradient are zeroed inside the backward kernel (what the hook of
         # selene/__init__.py:254-257, 509-515 does to the reference's gradient)
         self.freeze_top_n_filters = 0
@@ -670,7 +673,84 @@ class ExplaiNN(_Model):
                 self._check_flags(ctx, dev, x)
         return logits, delta
 
+    def _launch_train_sync(self, x, keep_mask=None):
+        """Sync-BN forward of the autograd path (parallel.sync_batchnorm): phases 1-4 of
+        explainn_sync_phase with the reducer's exchanges between them; the backward runs 5-8."""
+        from .engine import rank_seed, sync_buffers, sync_run
+        red = self.sync_bn
+        dev = self._device()
+        if self.dense_input:
+            raise ValueError("sync-BN works on one-hot input or base codes, not dense_input")
+        x = self._prep_input(x, dev)
+        B = x.shape[0]
+        if B == 0:
+            raise ValueError("Expected more than 1 value per channel when training, got input size "
+                             "[0, %d, 1]" % (FC_HIDDEN * self._options["cnn_units"]))
+        Bg = int(red.global_batch(B))
+        ctx = self._context(B, dev)
+        ps, keep = self._params_struct(dev)
+        logits = torch.empty(B, self._options["n_features"], device=dev, dtype=torch.float32)
+        mask = self._rt.pending if keep_mask is None else keep_mask
+        self._rt.pending = None
+        if mask is not None:
+            mask = mask.to(device=dev, dtype=torch.uint8).contiguous()
+            if mask.numel() != B * FC_HIDDEN * self._options["cnn_units"]:
+                raise RuntimeError("keep-mask must have shape (B, 100*cnn_units)")
+        seed = rank_seed(int(torch.randint(0, 2 ** 62, (1,)).item()), red.rank) if self.dropout_p > 0 else 0
+        bufs = sync_buffers(ctx, dev, getattr(self._rt, "sync_bufs", None))
+        self._rt.sync_bufs = bufs
+        gs = _lib.Grads()
+        with torch.cuda.device(dev):
+            a = _lib.SyncArgs(x=self._x_ptr(ctx, x, dev), B_local=B, B_global=Bg, params=C.pointer(ps),
+                              grads=C.pointer(gs), dropout_p=float(self.dropout_p), seed=seed,
+                              keep_mask=mask.data_ptr() if mask is not None else None,
+                              logits=logits.data_ptr())
+            for xb in sync_run(ctx, a, bufs, range(1, 5), self._stream(dev)):
+                red.reduce(xb)
+            self._check_flags(ctx, dev, x)
+        self._touched()
+        self._rt.token += 1
+        # the struct and everything it points at stay alive until the backward
+        self._rt.sync = (a, ps, keep, gs, mask, logits, x, self._rt.token)
+        return logits, self._rt.token
+
+    def _launch_backward_sync(self, dlogits, token):
+        """Phases 5-8: the user's criterion is a mean over this rank's B_local rows, so its dlogits
+        are scaled by B_local/B_global -- the gradient of the global mean, exact for mean-reduction
+        losses with any shard sizes.  The 14 gradients come out global: grad_sync does not run."""
+        from .engine import sync_run
+        st = getattr(self._rt, "sync", None)
+        if st is None or st[-1] != token:
+            raise RuntimeError("sync-BN backward without its sync-BN forward")
+        a, ps, keep, _, mask, logits, x, _ = st
+        dev = self._device()
+        ctx = self._rt.ctx
+        params = list(self.parameters())
+        flat = torch.empty(sum(p.numel() for p in params), device=dev, dtype=torch.float32)
+        views, off = [], 0
+        gs = _lib.Grads()
+        for field, p in zip(_lib.GRAD_FIELDS, params):
+            v = flat[off:off + p.numel()].view_as(p)
+            off += p.numel()
+            views.append(v)
+            setattr(gs, field, v.data_ptr())
+        dl = dlogits.to(torch.float32).contiguous()
+        a.dlogits = dl.data_ptr()
+        a.dl_scale = float(a.B_local) / float(a.B_global)
+        a.grads = C.pointer(gs)
+        a.freeze_top_n_filters = int(self.freeze_top_n_filters)
+        with torch.cuda.device(dev):
+            for xb in sync_run(ctx, a, self._rt.sync_bufs, range(5, 9), self._stream(dev)):
+                self.sync_bn.reduce(xb)
+        self._rt.sync = None
+        return views
+
     def _launch_train(self, x, keep_mask=None, validate=None):
+        if self.sync_bn is not None:
+            if torch.is_tensor(x) and x.requires_grad:
+                raise NotImplementedError("x.grad is not available with sync-BN (parallel.sync_batchnorm)")
+            return self._launch_train_sync(x, keep_mask)
+        self._rt.sync = None
         dev = self._device()
         x = self._prep_input(x, dev)
         B = x.shape[0]
@@ -708,6 +788,10 @@ class ExplaiNN(_Model):
         if token != self._rt.token:
             raise RuntimeError("backward of a stale forward: the fused kernels keep one training "
                                "step in flight per model (call backward before the next forward)")
+        if self._rt.sync is not None:
+            if want_dx:
+                raise NotImplementedError("x.grad is not available with sync-BN (parallel.sync_batchnorm)")
+            return self._launch_backward_sync(dlogits, token)
         dev = self._device()
         ctx = self._rt.ctx
         ps, keep = self._params_struct(dev)

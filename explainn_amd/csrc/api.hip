@@ -129,7 +129,7 @@ int eval_front(explainn_ctx* c, const float* x, int B, const explainn_params* p,
     // every eval-mode entry point overwrites scratch a pending backward would read (codes, ext,
     // idx, z, bits ...): whatever train forward was in flight is gone, and its backward must fail
     // with E_STATE instead of returning the eval batch's gradients
-    c->fwd_B = 0; c->tail_B = 0; c->keep_B = 0;
+    c->fwd_B = 0; c->tail_B = 0; c->keep_B = 0; c->sync_next = 0;
     if (c->dense) {
         if (!x) { explainn_set_error("dense input mode needs x"); return EXPLAINN_E_ARG; }
         c->staged_B = 0;
@@ -354,7 +354,7 @@ extern "C" int explainn_stage_codes(explainn_ctx* c, const uint8_t* codes, int B
                                     int reverse_complement, void* stream) {
     TRY(check_batch(c, B));
     if (!codes) { explainn_set_error("codes is null"); return EXPLAINN_E_ARG; }
-    c->fwd_B = 0; c->tail_B = 0; c->keep_B = 0;   // the packed codes of a pending backward are overwritten
+    c->fwd_B = 0; c->tail_B = 0; c->keep_B = 0; c->sync_next = 0;   // the packed codes of a pending backward are overwritten
     return launch_pack_codes(c, codes, B, reverse_complement ? 1 : 0, static_cast<hipStream_t>(stream));
 }
 
@@ -399,7 +399,7 @@ extern "C" int explainn_forward_train(explainn_ctx* c, const float* x, int B,
         return EXPLAINN_E_ARG;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    c->fwd_B = 0; c->keep_B = 0;
+    c->fwd_B = 0; c->keep_B = 0; c->sync_next = 0;
     c->eval_valid = false;             // the train-mode folds overwrite the eval-mode tables
     // the one-hot batch is packed and the filter tables are built by one launch; a staged batch of
     // base codes (x == NULL) is already packed and only needs the tables
@@ -580,10 +580,65 @@ extern "C" int explainn_train_step_conv(explainn_ctx* c, int B, const explainn_p
     return backward_conv(c, B, p, g, freeze_top_n_filters, static_cast<hipStream_t>(stream));
 }
 
+extern "C" int64_t explainn_sync_exchange_elems(const explainn_ctx* c, int phase) {
+    if (!c || phase < 1 || phase > EXPLAINN_SYNC_PHASES) return 0;
+    return sync_exchange_elems(c, phase);
+}
+
+extern "C" int explainn_sync_phase(explainn_ctx* c, int phase, const explainn_sync_args* a,
+                                   const double* exchange_in, double* exchange_out, void* stream) {
+    if (!a || !a->params || !a->grads) { explainn_set_error("sync phase: args, params and grads are required"); return EXPLAINN_E_ARG; }
+    TRY(check_batch(c, a->B_local));
+    if (phase < 1 || phase > EXPLAINN_SYNC_PHASES) {
+        explainn_set_error("sync phase %d outside 1..%d", phase, EXPLAINN_SYNC_PHASES);
+        return EXPLAINN_E_ARG;
+    }
+    if (a->B_global < 2 || a->B_global < a->B_local) {
+        explainn_set_error("sync-BN needs B_global >= max(2, B_local) (B_local %d, B_global %d)", a->B_local,
+                           a->B_global);
+        return EXPLAINN_E_ARG;
+    }
+    if (c->dense) { explainn_set_error("sync-BN works on one-hot input / base codes only (dense input mode is on)"); return EXPLAINN_E_UNSUPPORTED; }
+    if (phase == 3 && (a->dropout_p < 0.f || a->dropout_p >= 1.f)) {
+        explainn_set_error("dropout_p must be in [0,1)");
+        return EXPLAINN_E_ARG;
+    }
+    if (phase == 4 && !a->logits) { explainn_set_error("sync phase 4 needs logits"); return EXPLAINN_E_ARG; }
+    if (phase == 5) {
+        if (!a->dlogits && (!a->logits || !a->targets)) {
+            explainn_set_error("sync phase 5 needs dlogits, or logits and targets");
+            return EXPLAINN_E_ARG;
+        }
+        if (!a->dlogits && a->loss_kind != EXPLAINN_LOSS_BCE_WITH_LOGITS && a->loss_kind != EXPLAINN_LOSS_MSE) {
+            explainn_set_error("unknown loss kind %d", a->loss_kind);
+            return EXPLAINN_E_ARG;
+        }
+    }
+    // the phases run in order on one batch: each one but the first continues the one before
+    if (phase != 1 && c->sync_next != phase) {
+        explainn_set_error("sync phase %d out of order (expected %d)", phase, c->sync_next ? c->sync_next : 1);
+        return EXPLAINN_E_STATE;
+    }
+    if (phase != 1 && c->sync_B != a->B_local) {
+        explainn_set_error("sync phase %d with B_local %d, the step started with %d", phase, a->B_local, c->sync_B);
+        return EXPLAINN_E_STATE;
+    }
+    const bool needs_in = phase == 2 || phase == 3 || phase == 4 || phase == 6 || phase == 7 || phase == 8;
+    if ((needs_in && !exchange_in) || (sync_exchange_elems(c, phase) > 0 && !exchange_out)) {
+        explainn_set_error("sync phase %d: exchange buffer missing", phase);
+        return EXPLAINN_E_ARG;
+    }
+    c->sync_next = 0;
+    TRY(sync_phase(c, phase, a, exchange_in, exchange_out, static_cast<hipStream_t>(stream)));
+    c->sync_B = a->B_local;
+    c->sync_next = phase < EXPLAINN_SYNC_PHASES ? phase + 1 : 0;
+    return EXPLAINN_OK;
+}
+
 extern "C" int explainn_dense_input(explainn_ctx* c, int enable) {
     if (!c) { explainn_set_error("null context"); return EXPLAINN_E_ARG; }
     c->dense = enable != 0;
-    c->fwd_B = 0; c->tail_B = 0; c->keep_B = 0;
+    c->fwd_B = 0; c->tail_B = 0; c->keep_B = 0; c->sync_next = 0;
     return EXPLAINN_OK;
 }
 
@@ -591,7 +646,7 @@ extern "C" int explainn_stage_onehot(explainn_ctx* c, const float* x, int B, voi
     TRY(check_batch(c, B));
     if (!x) { explainn_set_error("x is null"); return EXPLAINN_E_ARG; }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    c->fwd_B = 0; c->tail_B = 0; c->keep_B = 0;   // the packed codes of a pending backward are overwritten
+    c->fwd_B = 0; c->tail_B = 0; c->keep_B = 0; c->sync_next = 0;   // the packed codes of a pending backward are overwritten
     TRY(launch_pack(c, x, B, true, s));  // with the bit masks: the batch may feed a train forward
     c->staged_B = B;
     return EXPLAINN_OK;

@@ -116,6 +116,7 @@ struct explainn_ctx {
     float* igH;           // [D classes][D][4 a'][4 a]  the H tables
     float* igC;           // [D classes][4]             the constant table
     int keep_B;           // batch of the last explainn_forward_eval_keep (0 = none)
+    int sync_next, sync_B;  // sync-BN: the phase due next (0 = none) and the step's B_local
     const float* keep_x;  // its x when it ran the dense kernels (read again by explainn_input_grad)
 };
 
@@ -203,6 +204,11 @@ int launch_dense_moments(explainn_ctx* c, const float* x, int B, hipStream_t s);
 int launch_dense_conv_pool(explainn_ctx* c, const float* x, const explainn_params* p, int B, hipStream_t s);
 int launch_dense_conv_bwd(explainn_ctx* c, const float* x, int B, hipStream_t s);
 int launch_dense_conv_act(explainn_ctx* c, const float* x, int B, float* acts, hipStream_t s);
+
+// sync-BN (syncbn.hip): the step as phases with an exchange between them
+int64_t sync_exchange_elems(const explainn_ctx* c, int phase);
+int sync_phase(explainn_ctx* c, int phase, const explainn_sync_args* a, const double* xin,
+               double* xout, hipStream_t s);
 
 int prep_configure(explainn_ctx* c);
 int bwd_configure(explainn_ctx* c);

@@ -13,6 +13,38 @@ import torch
 from . import _lib
 
 
+def sync_buffers(ctx, dev, bufs=None):
+    """The fp64 exchange buffers of the sync-BN phases of `ctx` (one per phase; phases without an
+    exchange get a placeholder).  Their sizes depend on the model's shape only: `bufs` from an
+    earlier call are reused when they still fit."""
+    lib, h = ctx.lib, ctx.handle
+    need = [int(lib.explainn_sync_exchange_elems(h, i)) for i in range(1, _lib.SYNC_PHASES + 1)]
+    if bufs is not None and all(b.numel() >= max(n, 1) for b, n in zip(bufs, need)):
+        return bufs
+    return [torch.zeros(max(n, 1), device=dev, dtype=torch.float64) for n in need]
+
+
+def sync_run(ctx, args, bufs, phases, stream):
+    """Enqueue the sync-BN phases `phases` (explainn_sync_phase) with `args`; yields each exchange
+    buffer the caller must sum over the ranks in place before resuming.  A phase reads the
+    exchange of the last exchanging phase before it."""
+    lib, h = ctx.lib, ctx.handle
+    for phase in phases:
+        prev = [q for q in range(1, phase) if int(lib.explainn_sync_exchange_elems(h, q)) > 0]
+        xin = bufs[prev[-1] - 1].data_ptr() if prev else None
+        has_out = int(lib.explainn_sync_exchange_elems(h, phase)) > 0
+        xb = bufs[phase - 1]
+        _lib.check(lib.explainn_sync_phase(h, phase, C.byref(args), xin, xb.data_ptr() if has_out else None,
+                                           stream))
+        if has_out:
+            yield xb
+
+
+def rank_seed(step_no, rank):
+    """Default dropout seed of a step: distinct per rank, so that shards do not share masks."""
+    return (step_no * 0x9E3779B97F4A7C15 + (int(rank) << 40)) & 0xFFFFFFFFFFFFFFFF
+
+
 class StepEngine:
     def __init__(self, model, max_batch, loss="binary"):
         self.model = model
@@ -51,7 +83,46 @@ class StepEngine:
         bn1_w, bn1_b): the `split` of parallel.GradAllReduce."""
         return sum(p.numel() for p in self.params[:4])
 
-    def step(self, x, y, seed=None, freeze_top_n_filters=0, grad_sync=None):
+    def sync_phases(self, x, y, B_global, seed=None, freeze_top_n_filters=0, keep_mask=None, rank=0):
+        """The sync-BN step as a generator: it enqueues phase after phase of
+        explainn_sync_phase and yields each exchange buffer (fp64, on the device) that the caller
+        must sum over the ranks in place before it resumes the generator.  When the generator is
+        exhausted this rank holds the logits of its rows, the loss of the whole batch and the
+        whole batch's 14 gradients in flat_grad (no gradient all-reduce follows).  x: this rank's
+        B_local rows; B_global: the sequences of all ranks; keep_mask: this rank's rows of a
+        (B, 100U) dropout keep-mask, or None for the built-in generator (seeded per `rank` unless
+        `seed` is given)."""
+        B = x.shape[0]
+        if seed is None:
+            self.step_no += 1
+            seed = rank_seed(self.step_no, rank)
+        m = self.model
+        if m.dense_input:
+            raise ValueError("sync-BN works on one-hot input or base codes, not dense_input")
+        if B > self.max_batch:
+            self.max_batch = B
+            self.logits = torch.empty(B, self.logits.shape[1], device=self.dev, dtype=torch.float32)
+        self.ctx = m._context(self.max_batch, self.dev)
+        if not (torch.is_tensor(x) and x.dtype == torch.float32):
+            x = m._prep_input(x, self.dev)
+        lib, h = self.ctx.lib, self.ctx.handle
+        self._xbufs = sync_buffers(self.ctx, self.dev, getattr(self, "_xbufs", None))
+        mask = None
+        if keep_mask is not None:
+            mask = keep_mask.to(device=self.dev, dtype=torch.uint8).contiguous()
+        stream = C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+        xp = m._x_ptr(self.ctx, x, self.dev)
+        a = _lib.SyncArgs(x=xp, targets=y.data_ptr(), dlogits=None, dl_scale=1.0, B_local=B,
+                          B_global=int(B_global), params=C.pointer(self.ps), grads=C.pointer(self.gs),
+                          loss_kind=self.loss_kind, dropout_p=float(m.dropout_p), seed=seed,
+                          keep_mask=mask.data_ptr() if mask is not None else None,
+                          freeze_top_n_filters=int(freeze_top_n_filters), logits=self.logits.data_ptr(),
+                          loss_out=self.loss.data_ptr())
+        yield from sync_run(self.ctx, a, self._xbufs, range(1, _lib.SYNC_PHASES + 1), stream)
+        m._touched()
+        m._rt.token += 1
+
+    def step(self, x, y, seed=None, freeze_top_n_filters=0, grad_sync=None, global_batch=None):
         """x (B,4,L) fp32 one-hot -- or base codes (uint8 (B,L) / architectures.BaseCodes) -- and
         y (B,T) fp32, both resident on the device.  Enqueues one train-mode forward + loss +
         backward; returns (logits view, loss tensor) without syncing.  With grad_sync (a
@@ -59,6 +130,17 @@ class StepEngine:
         the all-reduce of the FC/head gradients is enqueued as soon as they are final and runs
         under the filter-bank backward (explainn_train_step_fc / _conv)."""
         B = x.shape[0]
+        sync = getattr(self.model, "sync_bn", None)
+        if sync is not None:
+            # sync-BN (parallel.sync_batchnorm): full-batch statistics; every gradient comes out
+            # global, so grad_sync must not average it again
+            if grad_sync is not None:
+                raise ValueError("sync-BN steps produce the whole batch's gradients: no grad_sync")
+            Bg = sync.global_batch(B) if global_batch is None else int(global_batch)
+            for xb in self.sync_phases(x, y, Bg, seed=seed, freeze_top_n_filters=freeze_top_n_filters,
+                                       rank=sync.rank):
+                sync.reduce(xb)
+            return self.logits[:B], self.loss
         if seed is None:
             self.step_no += 1
             seed = self.step_no * 0x9E3779B97F4A7C15 & 0xFFFFFFFFFFFFFFFF

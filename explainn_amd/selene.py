@@ -32,8 +32,13 @@ class Trainer(object):
     def __init__(self, model, data_loaders, loss_criterion, metrics, optimizer, max_steps=128000,
                  patience=32000, report_stats_every_n_steps=1000, output_dir="./",
                  cpu_n_threads=1, use_cuda=False, checkpoint_resume=None, freeze_top_n_filters=0,
-                 logging_verbosity=2):
+                 logging_verbosity=2, sync_batchnorm=False):
         self.model = model
+        # opt-in sync-BN: BatchNorm statistics of the whole batch across ranks; the
+        # steps then leave the global gradients on every rank and no gradient all-reduce runs
+        self.sync_batchnorm = bool(sync_batchnorm)
+        if self.sync_batchnorm:
+            parallel.sync_batchnorm(model, parallel.ProcessGroupReducer())
         self.data_loaders = data_loaders
         self.criterion = loss_criterion
         self.metrics = metrics
@@ -144,6 +149,7 @@ class Trainer(object):
             self._engine = StepEngine(self.model, batch, loss=kind)
             if parallel.world() > 1:
                 parallel.broadcast_parameters(self.model)
+            if parallel.world() > 1 and not self.sync_batchnorm:
                 self._grad_sync = parallel.GradAllReduce(self._engine.flat_grad,
                                                          split=self._engine.conv_grad_elements)
         return self._engine
@@ -157,6 +163,7 @@ class Trainer(object):
         if self.use_cuda:
             inputs = inputs.cuda()
             targets = targets.cuda()
+        global_batch = inputs.shape[0]
         if parallel.world() > 1:
             inputs, targets = parallel.shard_batch(inputs, targets)
         if self._fused_step_available():
@@ -172,7 +179,8 @@ class Trainer(object):
                 inputs = inputs.float()
             _, loss = eng.step(inputs.contiguous(), targets.float().contiguous(),
                                seed=int(torch.randint(0, 2 ** 62, (1,)).item()),
-                               freeze_top_n_filters=self.freeze_top_n_filters)
+                               freeze_top_n_filters=self.freeze_top_n_filters,
+                               global_batch=global_batch if self.sync_batchnorm else None)
             if self._grad_sync is not None:
                 self._grad_sync()       # one all-reduce of the flat buffer
             eng.attach_grads()
@@ -187,11 +195,14 @@ class Trainer(object):
             if self.model.validate_input and (self.step <= 3 or self.step % 64 == 0):
                 self._check_input_flags()
         else:
-            if parallel.world() > 1 and self.model.grad_sync is None:
+            if parallel.world() > 1 and self.model.grad_sync is None and not self.sync_batchnorm:
                 # the autograd path of a sharded run (weighted / custom criterion): same start and
                 # the same averaged gradients as the fused path, one all-reduce per backward
                 parallel.broadcast_parameters(self.model)
                 self.model.grad_sync = parallel.average_gradients
+            if parallel.world() > 1 and self.sync_batchnorm and not getattr(self, "_synced_start", False):
+                parallel.broadcast_parameters(self.model)
+                self._synced_start = True
             predictions = self.model(inputs)
             loss = self.criterion(predictions, targets)
             self.optimizer.zero_grad()

@@ -283,6 +283,46 @@ int explainn_stage_times(explainn_ctx* ctx, float* us, int cap);
  * that way).  EXPLAINN_E_STATE without a train forward of that batch size in flight. */
 int explainn_debug_keep_bits(explainn_ctx* ctx, int B, uint32_t* out, void* stream);
 
+/* Sync-BN: a training step over R shards of one batch that computes what one
+ * device computes on the concatenated batch -- every BatchNorm takes the WHOLE batch's statistics.
+ * The step runs as EXPLAINN_SYNC_PHASES phases.  Phase i writes this rank's contribution to the
+ * exchange X_i (exchange_out: explainn_sync_exchange_elems(ctx, i) fp64, device; 0 = the phase
+ * writes none); the caller SUMS X_i over the ranks in place, in the same order on every rank, and
+ * hands the sum to the next phase that runs (exchange_in).  The layout of X_i depends on the
+ * context's shape only, never on B_local, so uneven shards add.  Phases: 1 pack + input moments,
+ * 2 BatchNorm1 + filter bank + q moments, 3 BatchNorm2 + FC, 4 BatchNorm3 + combiner (logits: the
+ * forward ends here), 5 loss gradient + head sums, 6 BatchNorm3 backward + passA, 7 mid + passB +
+ * filter-gradient sums, 8 the filter / BatchNorm1 gradients.  After phase 8 all 14 gradients are
+ * those of the whole batch on every rank: no gradient all-reduce follows.
+ *   B_local >= 1 sequences of this rank, B_global >= 2 of all ranks (the normaliser of every mean);
+ *   x: one-hot (B_local,4,L) or NULL for staged codes (phase 1); keep_mask / dropout_p / seed as in
+ *   explainn_forward_train (phase 3); logits: (B_local,T) out (phase 4, read again by phase 5);
+ *   phase 5 either takes dlogits (the caller's d loss / d logits, multiplied by dl_scale -- the
+ *   autograd path passes B_local/B_global to turn a shard-mean loss into the global mean) or, with
+ *   dlogits == NULL, computes the gradient of the global mean loss of kind loss_kind from targets;
+ *   the loss value (loss_out, device float) then comes out of phase 6.
+ * Soft (dense) input is not supported (EXPLAINN_E_UNSUPPORTED). */
+#define EXPLAINN_SYNC_PHASES 8
+typedef struct explainn_sync_args {
+    const float* x;
+    const float* targets;
+    const float* dlogits;
+    float dl_scale;
+    int B_local, B_global;
+    const explainn_params* params;
+    const explainn_grads* grads;
+    int loss_kind;
+    float dropout_p;
+    uint64_t seed;
+    const uint8_t* keep_mask;
+    int freeze_top_n_filters;
+    float* logits;
+    float* loss_out;
+} explainn_sync_args;
+int64_t explainn_sync_exchange_elems(const explainn_ctx* ctx, int phase);
+int explainn_sync_phase(explainn_ctx* ctx, int phase, const explainn_sync_args* args,
+                        const double* exchange_in, double* exchange_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
