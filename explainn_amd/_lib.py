@@ -40,20 +40,6 @@ PARAM_KEYS = {
 GRAD_FIELDS = ("conv_w", "conv_b", "bn1_w", "bn1_b", "fc1_w", "fc1_b", "bn2_w", "bn2_b",
                "fc2_w", "fc2_b", "bn3_w", "bn3_b", "final_w", "final_b")
 
-EXPORTS = (
-    "explainn_create", "explainn_destroy", "explainn_last_error", "explainn_scratch_bytes",
-    "explainn_forward_eval", "explainn_forward_train", "explainn_backward", "explainn_loss_grad",
-    "explainn_train_step", "explainn_unit_outputs", "explainn_unit_activations",
-    "explainn_input_flags", "explainn_filter_act_max", "explainn_filter_sites",
-    "explainn_pwm_scan", "explainn_stage_codes", "explainn_adam_step",
-    "explainn_train_step_fc", "explainn_train_step_conv",
-    "explainn_stage_onehot", "explainn_dense_input",
-    "explainn_stage_timing", "explainn_stage_count", "explainn_stage_name", "explainn_stage_times",
-    "explainn_debug_keep_bits",
-    "explainn_forward_eval_keep", "explainn_input_grad", "explainn_backward_input",
-    "explainn_ism_workspace_bytes", "explainn_ism",
-    "explainn_sync_exchange_elems", "explainn_sync_phase",
-)
 SYNC_PHASES = 8
 SYNC_ARG_FIELDS = ("x", "targets", "dlogits", "dl_scale", "B_local", "B_global", "params", "grads",
                    "loss_kind", "dropout_p", "seed", "keep_mask", "freeze_top_n_filters", "logits",
@@ -84,6 +70,50 @@ class SyncArgs(C.Structure):
                 ("logits", _fp), ("loss_out", _fp)]
 
 
+_ctx, _pp, _gp, _i, _i64 = C.c_void_p, C.POINTER(Params), C.POINTER(Grads), C.c_int, C.c_int64
+# every C function of the header: name -> (restype, argtypes)
+SIGNATURES = {
+    "explainn_create": (_i, [C.POINTER(_ctx), _i, _i, _i, _i, _i, _i]),
+    "explainn_destroy": (None, [_ctx]),
+    "explainn_last_error": (C.c_char_p, []),
+    "explainn_scratch_bytes": (_i64, [_ctx]),
+    "explainn_forward_eval": (_i, [_ctx, _fp, _i, _pp, _fp, _fp]),
+    "explainn_forward_train": (_i, [_ctx, _fp, _i, _pp, _fp, C.c_float, C.c_uint64, _fp, _fp]),
+    "explainn_backward": (_i, [_ctx, _fp, _i, _pp, _gp, _i, _fp]),
+    "explainn_forward_eval_keep": (_i, [_ctx, _fp, _i, _pp, _fp, _fp]),
+    "explainn_input_grad": (_i, [_ctx, _fp, _i, _pp, _fp, _fp]),
+    "explainn_backward_input": (_i, [_ctx, _fp, _i, _pp, _gp, _i, _fp, _fp]),
+    "explainn_ism_workspace_bytes": (_i64, [_ctx, _i]),
+    "explainn_ism": (_i, [_ctx, _fp, _i, _pp, _fp, _fp, _fp, _i64, _fp]),
+    "explainn_loss_grad": (_i, [_ctx, _i, _fp, _fp, _i, _fp, _fp, _fp]),
+    "explainn_train_step": (_i, [_ctx, _fp, _fp, _i, _pp, _gp, _i, C.c_float, C.c_uint64, _i, _fp, _fp,
+                                 _fp]),
+    "explainn_train_step_fc": (_i, [_ctx, _fp, _fp, _i, _pp, _gp, _i, C.c_float, C.c_uint64, _fp, _fp,
+                                    _fp]),
+    "explainn_train_step_conv": (_i, [_ctx, _i, _pp, _gp, _i, _fp]),
+    "explainn_unit_outputs": (_i, [_ctx, _fp, _i, _pp, _fp, _fp]),
+    "explainn_unit_activations": (_i, [_ctx, _fp, _i, _pp, _fp, _fp]),
+    "explainn_filter_act_max": (_i, [_ctx, _fp, _i, _pp, _fp, _fp, _fp]),
+    "explainn_filter_sites": (_i, [_ctx, _fp, _i, _pp, _fp, _fp, _i, _fp, _fp, _fp, _fp]),
+    "explainn_stage_codes": (_i, [_ctx, _fp, _i, _i, _fp]),
+    "explainn_stage_onehot": (_i, [_ctx, _fp, _i, _fp]),
+    "explainn_dense_input": (_i, [_ctx, _i]),
+    "explainn_pwm_scan": (_i, [_fp, _i, _i, _fp, _i, _i, _i, _fp, _fp]),
+    "explainn_adam_step": (_i, [_i, C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp),
+                                C.POINTER(_i64), _i64, C.c_double, C.c_double, C.c_double, C.c_double,
+                                _fp]),
+    "explainn_input_flags": (_i, [_ctx, C.POINTER(_i), _fp]),
+    "explainn_stage_timing": (_i, [_ctx, _i]),
+    "explainn_stage_count": (_i, []),
+    "explainn_stage_name": (C.c_char_p, [_i]),
+    "explainn_stage_times": (_i, [_ctx, C.POINTER(C.c_float), _i]),
+    "explainn_debug_keep_bits": (_i, [_ctx, _i, _fp, _fp]),
+    "explainn_sync_exchange_elems": (_i64, [_ctx, _i]),
+    "explainn_sync_phase": (_i, [_ctx, _i, C.POINTER(SyncArgs), _fp, _fp, _fp]),
+}
+EXPORTS = tuple(SIGNATURES)
+
+
 def load():
     """Load the shared library once; raise loudly if it is not built."""
     global _lib
@@ -94,78 +124,9 @@ def load():
             "libexplainn_hip.so is not built (%s). explainn_amd has no CPU fallback: build it "
             "with `make -C explainn_amd/csrc` (hipcc, gfx950)." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    ctx = C.c_void_p
-    pp, gp = C.POINTER(Params), C.POINTER(Grads)
-    lib.explainn_create.argtypes = [C.POINTER(ctx), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
-    lib.explainn_create.restype = C.c_int
-    lib.explainn_destroy.argtypes = [ctx]
-    lib.explainn_destroy.restype = None
-    lib.explainn_last_error.argtypes = []
-    lib.explainn_last_error.restype = C.c_char_p
-    lib.explainn_scratch_bytes.argtypes = [ctx]
-    lib.explainn_scratch_bytes.restype = C.c_int64
-    lib.explainn_forward_eval.argtypes = [ctx, _fp, C.c_int, pp, _fp, _fp]
-    lib.explainn_forward_eval.restype = C.c_int
-    lib.explainn_forward_train.argtypes = [ctx, _fp, C.c_int, pp, _fp, C.c_float, C.c_uint64, _fp, _fp]
-    lib.explainn_forward_train.restype = C.c_int
-    lib.explainn_backward.argtypes = [ctx, _fp, C.c_int, pp, gp, C.c_int, _fp]
-    lib.explainn_backward.restype = C.c_int
-    lib.explainn_loss_grad.argtypes = [ctx, C.c_int, _fp, _fp, C.c_int, _fp, _fp, _fp]
-    lib.explainn_loss_grad.restype = C.c_int
-    lib.explainn_train_step.argtypes = [ctx, _fp, _fp, C.c_int, pp, gp, C.c_int, C.c_float,
-                                        C.c_uint64, C.c_int, _fp, _fp, _fp]
-    lib.explainn_train_step.restype = C.c_int
-    lib.explainn_train_step_fc.argtypes = [ctx, _fp, _fp, C.c_int, pp, gp, C.c_int, C.c_float,
-                                           C.c_uint64, _fp, _fp, _fp]
-    lib.explainn_train_step_fc.restype = C.c_int
-    lib.explainn_train_step_conv.argtypes = [ctx, C.c_int, pp, gp, C.c_int, _fp]
-    lib.explainn_train_step_conv.restype = C.c_int
-    lib.explainn_unit_outputs.argtypes = [ctx, _fp, C.c_int, pp, _fp, _fp]
-    lib.explainn_unit_outputs.restype = C.c_int
-    lib.explainn_unit_activations.argtypes = [ctx, _fp, C.c_int, pp, _fp, _fp]
-    lib.explainn_unit_activations.restype = C.c_int
-    lib.explainn_filter_act_max.argtypes = [ctx, _fp, C.c_int, pp, _fp, _fp, _fp]
-    lib.explainn_filter_act_max.restype = C.c_int
-    lib.explainn_filter_sites.argtypes = [ctx, _fp, C.c_int, pp, _fp, _fp, C.c_int, _fp, _fp, _fp, _fp]
-    lib.explainn_filter_sites.restype = C.c_int
-    lib.explainn_stage_codes.argtypes = [ctx, _fp, C.c_int, C.c_int, _fp]
-    lib.explainn_stage_codes.restype = C.c_int
-    lib.explainn_adam_step.argtypes = [C.c_int, C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp),
-                                       C.POINTER(_fp), C.POINTER(C.c_int64), C.c_int64, C.c_double,
-                                       C.c_double, C.c_double, C.c_double, _fp]
-    lib.explainn_adam_step.restype = C.c_int
-    lib.explainn_pwm_scan.argtypes = [_fp, C.c_int, C.c_int, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp]
-    lib.explainn_pwm_scan.restype = C.c_int
-    lib.explainn_stage_onehot.argtypes = [ctx, _fp, C.c_int, _fp]
-    lib.explainn_stage_onehot.restype = C.c_int
-    lib.explainn_dense_input.argtypes = [ctx, C.c_int]
-    lib.explainn_dense_input.restype = C.c_int
-    lib.explainn_stage_timing.argtypes = [ctx, C.c_int]
-    lib.explainn_stage_timing.restype = C.c_int
-    lib.explainn_stage_count.argtypes = []
-    lib.explainn_stage_count.restype = C.c_int
-    lib.explainn_stage_name.argtypes = [C.c_int]
-    lib.explainn_stage_name.restype = C.c_char_p
-    lib.explainn_stage_times.argtypes = [ctx, C.POINTER(C.c_float), C.c_int]
-    lib.explainn_stage_times.restype = C.c_int
-    lib.explainn_debug_keep_bits.argtypes = [ctx, C.c_int, _fp, _fp]
-    lib.explainn_debug_keep_bits.restype = C.c_int
-    lib.explainn_forward_eval_keep.argtypes = [ctx, _fp, C.c_int, pp, _fp, _fp]
-    lib.explainn_forward_eval_keep.restype = C.c_int
-    lib.explainn_input_grad.argtypes = [ctx, _fp, C.c_int, pp, _fp, _fp]
-    lib.explainn_input_grad.restype = C.c_int
-    lib.explainn_backward_input.argtypes = [ctx, _fp, C.c_int, pp, gp, C.c_int, _fp, _fp]
-    lib.explainn_backward_input.restype = C.c_int
-    lib.explainn_ism_workspace_bytes.argtypes = [ctx, C.c_int]
-    lib.explainn_ism_workspace_bytes.restype = C.c_int64
-    lib.explainn_ism.argtypes = [ctx, _fp, C.c_int, pp, _fp, _fp, _fp, C.c_int64, _fp]
-    lib.explainn_ism.restype = C.c_int
-    lib.explainn_sync_exchange_elems.argtypes = [ctx, C.c_int]
-    lib.explainn_sync_exchange_elems.restype = C.c_int64
-    lib.explainn_sync_phase.argtypes = [ctx, C.c_int, C.POINTER(SyncArgs), _fp, _fp, _fp]
-    lib.explainn_sync_phase.restype = C.c_int
-    lib.explainn_input_flags.argtypes = [ctx, C.POINTER(C.c_int), _fp]
-    lib.explainn_input_flags.restype = C.c_int
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 

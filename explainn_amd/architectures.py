@@ -26,6 +26,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from .engine import flat_grads, rank_seed, sync_buffers, sync_run
 
 FC_HIDDEN = 100
 POOL = 7
@@ -140,6 +141,14 @@ class BaseCodes:
 
 VALIDATE_EVERY = 64      # deferred input validation: the sticky device flag is read every this many calls
 
+# How ExplaiNN._stage treats an fp32 batch (base codes are always staged):
+SCHEDULED = "scheduled"            # validate_input's schedule decides whether the flag is read first
+VALIDATE_FIRST = "validate-first"  # read it before computing; a soft batch takes the dense kernels
+ONEHOT_ONLY = "one-hot only"       # read it before computing; dense_input or a soft batch raises
+
+# attributes resolved against one handle's own modules: not copied, pickled or shared by a replica
+_PER_HANDLE = ("_slots", "_ps_cache", "_vkey", "_bufs")
+
 
 class _Runtime:
     """Per-model device context; never copied or pickled with the module."""
@@ -175,7 +184,7 @@ class _TrainStep(torch.autograd.Function):
         # x.grad wanted: validate this batch before computing, so that soft input takes the dense
         # kernels (and its gradient is the gradient at that x)
         want_dx = torch.is_tensor(x) and x.requires_grad
-        logits, ctx.token = model._launch_train(x, validate=True if want_dx else None)
+        logits, ctx.token = model._launch_train(x, VALIDATE_FIRST if want_dx else SCHEDULED)
         return logits
 
     @staticmethod
@@ -288,7 +297,7 @@ class ExplaiNN(_Model):
         new = self.__class__.__new__(self.__class__)
         memo[id(self)] = new
         for key, val in self.__dict__.items():
-            if key in ("_slots", "_ps_cache", "_vkey", "_bufs"):   # resolved against THIS object's modules
+            if key in _PER_HANDLE:
                 continue
             new.__dict__[key] = _Runtime() if key == "_rt" else copy.deepcopy(val, memo)
         new.linears._bind(new)
@@ -296,14 +305,15 @@ class ExplaiNN(_Model):
 
     def __getstate__(self):
         state = self.__dict__.copy()
-        for key in ("_slots", "_ps_cache", "_vkey", "_bufs"):     # ctypes tables: rebuilt on demand
+        for key in _PER_HANDLE:             # ctypes tables: rebuilt on demand
             state.pop(key, None)
         return state
 
     def __setstate__(self, state):
         super().__setstate__(state)
         self.__dict__["_rt"] = _Runtime()
-        self.__dict__.pop("_slots", None); self.__dict__.pop("_ps_cache", None)
+        for key in _PER_HANDLE:
+            self.__dict__.pop(key, None)
         self.linears._bind(self)
 
     def eval_replica(self):
@@ -317,7 +327,7 @@ class ExplaiNN(_Model):
         if r is None:
             r = self.__class__.__new__(self.__class__)
             for key, val in self.__dict__.items():
-                if key in ("_slots", "_ps_cache", "_vkey", "_bufs", "_pver"):   # resolved per handle
+                if key in _PER_HANDLE or key == "_pver":
                     continue
                 r.__dict__[key] = val
             r.__dict__["_rt"] = _Runtime()
@@ -348,11 +358,6 @@ class ExplaiNN(_Model):
             cap = max(B, ctx.max_batch if ctx is not None and ctx.geom == geom else 0)
             self._rt.ctx = _lib.Context(*geom, max_batch=cap, device=index)
         return self._rt.ctx
-
-    def _tensors(self):
-        sd = {k: v for k, v in self.named_parameters()}
-        sd.update({k: v for k, v in self.named_buffers()})
-        return sd
 
     def __setattr__(self, name, value):
         if name in ("final", "linears"):
@@ -481,61 +486,82 @@ class ExplaiNN(_Model):
         # a model that has met a soft batch once keeps validating (and routing) per call
         return v == "always" or self._rt.soft_seen or self._rt.calls <= 2
 
-    def _x_ptr(self, ctx, x, dev, validate=None):
-        """Device pointer of the batch as the C ABI wants it: base codes are staged in the context
-        and NULL ("the staged batch", include/explainn_hip.h) is returned.  An fp32 batch is, when
-        this call validates (validate_input), staged too and its validation flag read BEFORE
-        anything is computed from it: a batch that is not one-hot (the reference accepts any float
-        tensor, architectures/__init__.py:111) goes through the dense kernels instead of being
-        run as if its soft columns were N -- unless dense_input is False, which keeps the strict
-        error.  Otherwise the batch is packed inside the forward itself and the flag stays sticky
-        on the device for a later read (no host sync in the call)."""
-        lib, h, stream = ctx.lib, ctx.handle, self._stream(dev)
-        self._rt.calls += 1
+    def _stage(self, ctx, x, stream, policy=SCHEDULED):
+        """Hand the batch (from _prep_input) to the context: returns (xp, read), xp the device
+        pointer the entry point takes -- None for a batch staged in the context ("the staged batch",
+        include/explainn_hip.h) -- and read True when nothing is left for _settle: the validation
+        flag was read here, or the batch takes the dense kernels, which flag nothing.
+        Base codes are always staged.  An fp32 batch follows `policy`:
+          SCHEDULED       when this call validates (validate_input), staged and its flag read BEFORE
+                          anything is computed from it: a batch that is not one-hot (the reference
+                          accepts any float tensor, architectures/__init__.py:111) goes through the
+                          dense kernels instead of being run as if its soft columns were N -- unless
+                          dense_input is False, which keeps the strict error.  Otherwise the batch is
+                          packed inside the launch itself and the flag stays sticky on the device for
+                          a later read (no host sync in the call, SURVEY.md 8b);
+          VALIDATE_FIRST  always validated as above;
+          ONEHOT_ONLY     staged and validated; dense_input or a batch that is not one-hot raises."""
+        lib, h = ctx.lib, ctx.handle
         if isinstance(x, BaseCodes):
+            self._rt.calls += 1
             _lib.check(lib.explainn_dense_input(h, 0))
             _lib.check(lib.explainn_stage_codes(h, x.codes.data_ptr(), x.codes.shape[0],
                                                 int(x.reverse_complement), stream))
-            return None
+            return None, False
         if self.dense_input:
+            if policy == ONEHOT_ONLY:
+                raise ValueError("in_silico_mutagenesis needs one-hot input (dense_input is True)")
+            self._rt.calls += 1
             _lib.check(lib.explainn_dense_input(h, 1))
             self._rt.x_keep = x
-            return x.data_ptr()
-        if self._validate_now() if validate is None else validate:
-            _lib.check(lib.explainn_stage_onehot(h, x.data_ptr(), x.shape[0], stream))
-            flags = C.c_int(0)
-            _lib.check(lib.explainn_input_flags(h, C.byref(flags), stream))
-            if flags.value & 1:
-                self._rt.soft_seen = True
-                if self.dense_input is False:
-                    raise ValueError(
-                        "input is not one-hot: every column of x must be one-hot (A,C,G,T) or all-zero "
-                        "(N) as sequence.one_hot_encode produces (dense_input=False forbids the dense path)")
-                _lib.check(lib.explainn_dense_input(h, 1))
-                self._rt.x_keep = x            # the backward of a train forward reads x again
-                return x.data_ptr()
+            return x.data_ptr(), True
+        self._rt.calls += 1
+        if policy == SCHEDULED and not self._validate_now():
             _lib.check(lib.explainn_dense_input(h, 0))
-            return None
+            return x.data_ptr(), False
+        _lib.check(lib.explainn_stage_onehot(h, x.data_ptr(), x.shape[0], stream))
+        flags = C.c_int(0)
+        _lib.check(lib.explainn_input_flags(h, C.byref(flags), stream))
+        if flags.value & 1:
+            if policy == ONEHOT_ONLY:
+                raise ValueError(
+                    "input is not one-hot: in-silico mutagenesis substitutes bases of one-hot (A,C,G,T) "
+                    "or all-zero (N) columns, as sequence.one_hot_encode produces")
+            self._rt.soft_seen = True
+            if self.dense_input is False:
+                raise ValueError(
+                    "input is not one-hot: every column of x must be one-hot (A,C,G,T) or all-zero "
+                    "(N) as sequence.one_hot_encode produces (dense_input=False forbids the dense path)")
+            _lib.check(lib.explainn_dense_input(h, 1))
+            self._rt.x_keep = x                # the backward of a train forward reads x again
+            return x.data_ptr(), True
         _lib.check(lib.explainn_dense_input(h, 0))
-        return x.data_ptr()
+        return None, True
+
+    def _front(self, x, dev, policy=SCHEDULED, bump=True):
+        """Front half of a launch, inside the caller's torch.cuda.device(dev) with x from
+        _prep_input: bump the token (an eval launch overwrites the scratch of a train forward still
+        awaiting its backward; train forwards bump it after their launch instead), resolve context,
+        params table and stream, and stage x.  Returns (ctx, ps, keep, stream, xp, read); the
+        entry point makes its call and hands `read` to _settle."""
+        if bump:
+            self._rt.token += 1
+        ctx = self._context(x.shape[0], dev)
+        ps, keep = self._params_struct(dev)
+        stream = self._stream(dev)
+        xp, read = self._stage(ctx, x, stream, policy)
+        return ctx, ps, keep, stream, xp, read
+
+    def _settle(self, read):
+        """Back half of a launch: read the sticky flag when _stage has not and the schedule says
+        this call reads it (base codes and deferred fp32 batches; every VALIDATE_EVERY-th call
+        settles the deferred ones)."""
+        if not read and self.validate_input and (
+                self._validate_now() or self._rt.calls % VALIDATE_EVERY == 0):
+            self.check_input()
 
     def _stream(self, dev):
         return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-    def _check_flags(self, ctx, dev, x=None):
-        """After a forward was enqueued: read the sticky flag when this call is one that reads it
-        (a validating call already did for an fp32 batch -- base codes are only checked here -- and
-        every VALIDATE_EVERY-th call settles the deferred ones)."""
-        if not self.validate_input:
-            return
-        codes = isinstance(x, BaseCodes)
-        if self.dense_input and not codes:
-            return                                    # dense kernels: nothing is packed or flagged
-        now = self._validate_now()
-        if now and not codes:
-            return                                    # _x_ptr read (and cleared) the flag already
-        if now or self._rt.calls % VALIDATE_EVERY == 0:
-            self.check_input()
 
     def check_input(self):
         """Read (one host sync) and clear the sticky validation flag; raise if any batch since the
@@ -570,16 +596,13 @@ class ExplaiNN(_Model):
             return _EvalInputGrad.apply(self, x)
         x = self._prep_input(x, dev)
         B = x.shape[0]
-        if B == 0:                                   # torch returns an empty (0, T) tensor in eval
-            return torch.empty(0, self._options["n_features"], device=dev, dtype=torch.float32)
-        self._rt.token += 1        # eval overwrites the scratch of a train forward still awaiting backward
-        ctx = self._context(B, dev)
-        ps, keep = self._params_struct(dev)
         logits = torch.empty(B, self._options["n_features"], device=dev, dtype=torch.float32)
+        if B == 0:                                   # torch returns an empty (0, T) tensor in eval
+            return logits
         with torch.cuda.device(dev):
-            _lib.check(ctx.lib.explainn_forward_eval(ctx.handle, self._x_ptr(ctx, x, dev), B, C.byref(ps),
-                                                     logits.data_ptr(), self._stream(dev)))
-            self._check_flags(ctx, dev, x)
+            ctx, ps, _, stream, xp, read = self._front(x, dev)
+            _lib.check(ctx.lib.explainn_forward_eval(ctx.handle, xp, B, C.byref(ps), logits.data_ptr(), stream))
+            self._settle(read)
         return logits
 
     def _launch_eval_keep(self, x):
@@ -589,17 +612,13 @@ class ExplaiNN(_Model):
         dev = self._device()
         x = self._prep_input(x, dev)
         B = x.shape[0]
-        self._rt.token += 1
-        ctx = self._context(B, dev)
-        ps, keep = self._params_struct(dev)
         logits = torch.empty(B, self._options["n_features"], device=dev, dtype=torch.float32)
         with torch.cuda.device(dev):
-            xp = self._x_ptr(ctx, x, dev, validate=not isinstance(x, BaseCodes))
+            ctx, ps, _, stream, xp, read = self._front(x, dev, VALIDATE_FIRST)
             self._rt.x_keep = x                # a dense batch is read again by the input gradient
-            _lib.check(ctx.lib.explainn_forward_eval_keep(ctx.handle, xp, B, C.byref(ps),
-                                                          logits.data_ptr(), self._stream(dev)))
-            if isinstance(x, BaseCodes):
-                self._check_flags(ctx, dev, x)
+            _lib.check(ctx.lib.explainn_forward_eval_keep(ctx.handle, xp, B, C.byref(ps), logits.data_ptr(),
+                                                          stream))
+            self._settle(read)
         return logits, self._rt.token
 
     def _launch_input_grad(self, dlogits, token):
@@ -646,37 +665,38 @@ class ExplaiNN(_Model):
         delta = torch.empty(B, T, 4, L, device=dev, dtype=torch.float32)
         if B == 0:
             return logits, delta
-        self._rt.token += 1        # eval overwrites the scratch of a train forward still awaiting backward
-        ctx = self._context(B, dev)
-        ps, keep = self._params_struct(dev)
-        lib, h, stream = ctx.lib, ctx.handle, self._stream(dev)
         with torch.cuda.device(dev):
-            if isinstance(x, BaseCodes):
-                self._x_ptr(ctx, x, dev)                  # staged: the call takes x == NULL
-            else:
-                if self.dense_input:
-                    raise ValueError("in_silico_mutagenesis needs one-hot input (dense_input is True)")
-                self._rt.calls += 1
-                _lib.check(lib.explainn_dense_input(h, 0))
-                _lib.check(lib.explainn_stage_onehot(h, x.data_ptr(), B, stream))
-                flags = C.c_int(0)
-                _lib.check(lib.explainn_input_flags(h, C.byref(flags), stream))
-                if flags.value & 1:
-                    raise ValueError(
-                        "input is not one-hot: in-silico mutagenesis substitutes bases of one-hot (A,C,G,T) "
-                        "or all-zero (N) columns, as sequence.one_hot_encode produces")
+            ctx, ps, _, stream, xp, read = self._front(x, dev, ONEHOT_ONLY)
+            lib, h = ctx.lib, ctx.handle
             nbytes = int(lib.explainn_ism_workspace_bytes(h, B))
             ws = torch.empty(max(nbytes, 1), device=dev, dtype=torch.uint8)
-            _lib.check(lib.explainn_ism(h, None, B, C.byref(ps), logits.data_ptr(), delta.data_ptr(),
+            _lib.check(lib.explainn_ism(h, xp, B, C.byref(ps), logits.data_ptr(), delta.data_ptr(),
                                         ws.data_ptr(), nbytes, stream))
-            if isinstance(x, BaseCodes):
-                self._check_flags(ctx, dev, x)
+            self._settle(read)
         return logits, delta
 
-    def _launch_train_sync(self, x, keep_mask=None):
+    def _empty_batch_error(self):
+        # what torch's BatchNorm1d raises for an empty batch in train mode
+        return ValueError("Expected more than 1 value per channel when training, got input size "
+                          "[0, %d, 1]" % (FC_HIDDEN * self._options["cnn_units"]))
+
+    def _dropout_args(self, dev, B, rank=None):
+        """(keep_mask, seed) of a train forward: the mask of set_dropout_mask (consumed here) as the
+        kernels take it, or None; a fresh seed for the built-in generator (rank_seed'ed per rank
+        under sync-BN), 0 when dropout is off."""
+        mask, self._rt.pending = self._rt.pending, None
+        if mask is not None:
+            mask = mask.to(device=dev, dtype=torch.uint8).contiguous()
+            if mask.numel() != B * FC_HIDDEN * self._options["cnn_units"]:
+                raise RuntimeError("keep-mask must have shape (B, 100*cnn_units)")
+        if self.dropout_p > 0:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+            return mask, seed if rank is None else rank_seed(seed, rank)
+        return mask, 0
+
+    def _launch_train_sync(self, x):
         """Sync-BN forward of the autograd path (parallel.sync_batchnorm): phases 1-4 of
         explainn_sync_phase with the reducer's exchanges between them; the backward runs 5-8."""
-        from .engine import rank_seed, sync_buffers, sync_run
         red = self.sync_bn
         dev = self._device()
         if self.dense_input:
@@ -684,30 +704,21 @@ class ExplaiNN(_Model):
         x = self._prep_input(x, dev)
         B = x.shape[0]
         if B == 0:
-            raise ValueError("Expected more than 1 value per channel when training, got input size "
-                             "[0, %d, 1]" % (FC_HIDDEN * self._options["cnn_units"]))
+            raise self._empty_batch_error()
         Bg = int(red.global_batch(B))
-        ctx = self._context(B, dev)
-        ps, keep = self._params_struct(dev)
         logits = torch.empty(B, self._options["n_features"], device=dev, dtype=torch.float32)
-        mask = self._rt.pending if keep_mask is None else keep_mask
-        self._rt.pending = None
-        if mask is not None:
-            mask = mask.to(device=dev, dtype=torch.uint8).contiguous()
-            if mask.numel() != B * FC_HIDDEN * self._options["cnn_units"]:
-                raise RuntimeError("keep-mask must have shape (B, 100*cnn_units)")
-        seed = rank_seed(int(torch.randint(0, 2 ** 62, (1,)).item()), red.rank) if self.dropout_p > 0 else 0
-        bufs = sync_buffers(ctx, dev, getattr(self._rt, "sync_bufs", None))
-        self._rt.sync_bufs = bufs
+        mask, seed = self._dropout_args(dev, B, red.rank)
         gs = _lib.Grads()
         with torch.cuda.device(dev):
-            a = _lib.SyncArgs(x=self._x_ptr(ctx, x, dev), B_local=B, B_global=Bg, params=C.pointer(ps),
+            ctx, ps, keep, stream, xp, read = self._front(x, dev, bump=False)
+            bufs = self._rt.sync_bufs = sync_buffers(ctx, dev, self._rt.sync_bufs)
+            a = _lib.SyncArgs(x=xp, B_local=B, B_global=Bg, params=C.pointer(ps),
                               grads=C.pointer(gs), dropout_p=float(self.dropout_p), seed=seed,
                               keep_mask=mask.data_ptr() if mask is not None else None,
                               logits=logits.data_ptr())
-            for xb in sync_run(ctx, a, bufs, range(1, 5), self._stream(dev)):
+            for xb in sync_run(ctx, a, bufs, range(1, 5), stream):
                 red.reduce(xb)
-            self._check_flags(ctx, dev, x)
+            self._settle(read)
         self._touched()
         self._rt.token += 1
         # the struct and everything it points at stay alive until the backward
@@ -718,22 +729,13 @@ class ExplaiNN(_Model):
         """Phases 5-8: the user's criterion is a mean over this rank's B_local rows, so its dlogits
         are scaled by B_local/B_global -- the gradient of the global mean, exact for mean-reduction
         losses with any shard sizes.  The 14 gradients come out global: grad_sync does not run."""
-        from .engine import sync_run
-        st = getattr(self._rt, "sync", None)
+        st = self._rt.sync
         if st is None or st[-1] != token:
             raise RuntimeError("sync-BN backward without its sync-BN forward")
         a, ps, keep, _, mask, logits, x, _ = st
         dev = self._device()
         ctx = self._rt.ctx
-        params = list(self.parameters())
-        flat = torch.empty(sum(p.numel() for p in params), device=dev, dtype=torch.float32)
-        views, off = [], 0
-        gs = _lib.Grads()
-        for field, p in zip(_lib.GRAD_FIELDS, params):
-            v = flat[off:off + p.numel()].view_as(p)
-            off += p.numel()
-            views.append(v)
-            setattr(gs, field, v.data_ptr())
+        _, views, gs = flat_grads(list(self.parameters()), dev)
         dl = dlogits.to(torch.float32).contiguous()
         a.dlogits = dl.data_ptr()
         a.dl_scale = float(a.B_local) / float(a.B_global)
@@ -745,36 +747,25 @@ class ExplaiNN(_Model):
         self._rt.sync = None
         return views
 
-    def _launch_train(self, x, keep_mask=None, validate=None):
+    def _launch_train(self, x, policy=SCHEDULED):
         if self.sync_bn is not None:
             if torch.is_tensor(x) and x.requires_grad:
                 raise NotImplementedError("x.grad is not available with sync-BN (parallel.sync_batchnorm)")
-            return self._launch_train_sync(x, keep_mask)
+            return self._launch_train_sync(x)
         self._rt.sync = None
         dev = self._device()
         x = self._prep_input(x, dev)
         B = x.shape[0]
         if B == 0:
-            # what torch's BatchNorm1d raises for an empty batch in train mode
-            raise ValueError("Expected more than 1 value per channel when training, got input size "
-                             "[0, %d, 1]" % (FC_HIDDEN * self._options["cnn_units"]))
-        ctx = self._context(B, dev)
-        ps, keep = self._params_struct(dev)
+            raise self._empty_batch_error()
         logits = torch.empty(B, self._options["n_features"], device=dev, dtype=torch.float32)
-        mask = self._rt.pending if keep_mask is None else keep_mask
-        self._rt.pending = None
-        mask_ptr = None
-        if mask is not None:
-            mask = mask.to(device=dev, dtype=torch.uint8).contiguous()
-            if mask.numel() != B * FC_HIDDEN * self._options["cnn_units"]:
-                raise RuntimeError("keep-mask must have shape (B, 100*cnn_units)")
-            mask_ptr = mask.data_ptr()
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if self.dropout_p > 0 else 0
+        mask, seed = self._dropout_args(dev, B)
         with torch.cuda.device(dev):
+            ctx, ps, _, stream, xp, read = self._front(x, dev, policy, bump=False)
             _lib.check(ctx.lib.explainn_forward_train(
-                ctx.handle, self._x_ptr(ctx, x, dev, validate), B, C.byref(ps), mask_ptr, float(self.dropout_p),
-                C.c_uint64(seed), logits.data_ptr(), self._stream(dev)))
-            self._check_flags(ctx, dev, x)
+                ctx.handle, xp, B, C.byref(ps), mask.data_ptr() if mask is not None else None,
+                float(self.dropout_p), C.c_uint64(seed), logits.data_ptr(), stream))
+            self._settle(read)
         self._touched()
         self._rt.token += 1
         return logits, self._rt.token
@@ -795,15 +786,7 @@ class ExplaiNN(_Model):
         dev = self._device()
         ctx = self._rt.ctx
         ps, keep = self._params_struct(dev)
-        params = list(self.parameters())
-        flat = torch.empty(sum(p.numel() for p in params), device=dev, dtype=torch.float32)
-        views, off = [], 0
-        gs = _lib.Grads()
-        for field, p in zip(_lib.GRAD_FIELDS, params):
-            v = flat[off:off + p.numel()].view_as(p)
-            off += p.numel()
-            views.append(v)
-            setattr(gs, field, v.data_ptr())
+        flat, views, gs = flat_grads(list(self.parameters()), dev)
         dl = dlogits.to(torch.float32).contiguous()
         B = dl.shape[0]
         dx = None
@@ -837,14 +820,11 @@ class ExplaiNN(_Model):
         dev = self._device()
         x = self._prep_input(self._first_four_rows(x_rep), dev)
         B = x.shape[0]
-        self._rt.token += 1
-        ctx = self._context(B, dev)
-        ps, keep = self._params_struct(dev)
         outs = torch.empty(B, self._options["cnn_units"], device=dev, dtype=torch.float32)
         with torch.cuda.device(dev):
-            _lib.check(ctx.lib.explainn_unit_outputs(ctx.handle, self._x_ptr(ctx, x, dev), B, C.byref(ps),
-                                                     outs.data_ptr(), self._stream(dev)))
-            self._check_flags(ctx, dev, x)
+            ctx, ps, _, stream, xp, read = self._front(x, dev)
+            _lib.check(ctx.lib.explainn_unit_outputs(ctx.handle, xp, B, C.byref(ps), outs.data_ptr(), stream))
+            self._settle(read)
         return outs
 
     def _unit_activations(self, x_rep):
@@ -855,17 +835,14 @@ class ExplaiNN(_Model):
         x = self._prep_input(self._first_four_rows(x_rep), dev)
         B = x.shape[0]
         o = self._options
-        self._rt.token += 1
-        ctx = self._context(B, dev)
-        ps, keep = self._params_struct(dev)
         acts = torch.empty(B, o["cnn_units"], o["sequence_length"] - o["kernel_size"] + 1,
                            device=dev, dtype=torch.float32)
         with torch.cuda.device(dev):
-            _lib.check(ctx.lib.explainn_unit_activations(ctx.handle, self._x_ptr(ctx, x, dev), B, C.byref(ps),
-                                                         acts.data_ptr(), self._stream(dev)))
-            self._check_flags(ctx, dev, x)
+            ctx, ps, _, stream, xp, read = self._front(x, dev)
+            _lib.check(ctx.lib.explainn_unit_activations(ctx.handle, xp, B, C.byref(ps), acts.data_ptr(),
+                                                         stream))
+            self._settle(read)
         return acts
-
 
     # -- filter -> PWM export (interpret.py:363-459 on the device; see explainn_amd/interpret.py) --
     def _export_args(self, x, select):
@@ -878,21 +855,19 @@ class ExplaiNN(_Model):
             if select.shape != (B,) or select.device != dev:
                 raise RuntimeError("select must be a (B,) tensor on the model's device")
             select = select.to(torch.uint8).contiguous()
-        self._rt.token += 1
+        self._rt.token += 1        # (here, not in _front: before filter_sites checks its accumulators)
         return dev, x, B, select
 
     def filter_act_max(self, x, unit_max, select=None):
         """unit_max[u] (float32 [U], zeroed by the caller before the first batch) <- running max of
         the float16-rounded eval-mode activations of the selected sequences of this batch."""
         dev, x, B, select = self._export_args(x, select)
-        ctx = self._context(B, dev)
-        ps, keep = self._params_struct(dev)
         with torch.cuda.device(dev):
+            ctx, ps, _, stream, xp, read = self._front(x, dev, bump=False)
             _lib.check(ctx.lib.explainn_filter_act_max(
-                ctx.handle, self._x_ptr(ctx, x, dev), B, C.byref(ps),
-                select.data_ptr() if select is not None else None, unit_max.data_ptr(),
-                self._stream(dev)))
-            self._check_flags(ctx, dev, x)
+                ctx.handle, xp, B, C.byref(ps), select.data_ptr() if select is not None else None,
+                unit_max.data_ptr(), stream))
+            self._settle(read)
         return unit_max
 
     def filter_sites(self, x, thresholds, site_total, pfm, select=None, site_cap=1000000,
@@ -908,16 +883,14 @@ class ExplaiNN(_Model):
             if tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous():
                 raise RuntimeError("%s must be a contiguous %s tensor of shape %s on %s" % (
                     name, dt, shape, dev))
-        ctx = self._context(B, dev)
-        ps, keep = self._params_struct(dev)
         hit = torch.empty(B, U, device=dev, dtype=torch.uint8) if want_hit else None
         with torch.cuda.device(dev):
+            ctx, ps, _, stream, xp, read = self._front(x, dev, bump=False)
             _lib.check(ctx.lib.explainn_filter_sites(
-                ctx.handle, self._x_ptr(ctx, x, dev), B, C.byref(ps),
-                select.data_ptr() if select is not None else None, thresholds.data_ptr(),
-                int(site_cap), site_total.data_ptr(), pfm.data_ptr(),
-                hit.data_ptr() if hit is not None else None, self._stream(dev)))
-            self._check_flags(ctx, dev, x)
+                ctx.handle, xp, B, C.byref(ps), select.data_ptr() if select is not None else None,
+                thresholds.data_ptr(), int(site_cap), site_total.data_ptr(), pfm.data_ptr(),
+                hit.data_ptr() if hit is not None else None, stream))
+            self._settle(read)
         return hit
 
 

@@ -125,11 +125,16 @@ const char* const kStageNames[ST_COUNT] = {
         if (c->timing) { HIP_TRY(hipEventRecord(c->ev1[id], s)); c->timed |= 1u << (id); } \
     } while (0)
 
+// Drop whatever work is pending on the context -- a train forward awaiting its backward (fwd_B), a
+// train_step_fc awaiting its _conv half (tail_B), an eval_keep forward awaiting its input gradient
+// (keep_B), a sync-BN step between phases (sync_next): their calls then fail with E_STATE.
+void drop_pending(explainn_ctx* c) { c->fwd_B = 0; c->tail_B = 0; c->keep_B = 0; c->sync_next = 0; }
+
 int eval_front(explainn_ctx* c, const float* x, int B, const explainn_params* p, hipStream_t s) {
     // every eval-mode entry point overwrites scratch a pending backward would read (codes, ext,
     // idx, z, bits ...): whatever train forward was in flight is gone, and its backward must fail
     // with E_STATE instead of returning the eval batch's gradients
-    c->fwd_B = 0; c->tail_B = 0; c->keep_B = 0; c->sync_next = 0;
+    drop_pending(c);
     if (c->dense) {
         if (!x) { explainn_set_error("dense input mode needs x"); return EXPLAINN_E_ARG; }
         c->staged_B = 0;
@@ -255,13 +260,8 @@ extern "C" int explainn_forward_eval(explainn_ctx* c, const float* x, int B,
     TRY(check_batch(c, B));
     hipStream_t s = static_cast<hipStream_t>(stream);
     TRY(eval_front(c, x, B, p, s));
-    if (c->dense) {
-        TRY(launch_dense_conv_pool(c, x, p, B, s));
-        TRY(launch_fc_fwd(c, p, B, false, nullptr, 0.f, 0, s));
-        TRY(launch_head_fwd(c, p, B, false, logits, nullptr, s));
-        return EXPLAINN_OK;
-    }
-    TRY(launch_conv_pool(c, p, B, false, s));
+    if (c->dense) TRY(launch_dense_conv_pool(c, x, p, B, s));
+    else TRY(launch_conv_pool(c, p, B, false, s));
     TRY(launch_fc_fwd(c, p, B, false, nullptr, 0.f, 0, s));
     TRY(launch_head_fwd(c, p, B, false, logits, nullptr, s));
     return EXPLAINN_OK;
@@ -329,13 +329,9 @@ extern "C" int explainn_unit_outputs(explainn_ctx* c, const float* x, int B,
     TRY(check_batch(c, B));
     hipStream_t s = static_cast<hipStream_t>(stream);
     TRY(eval_front(c, x, B, p, s));
-    if (c->dense) {
-        TRY(launch_dense_conv_pool(c, x, p, B, s));
-        TRY(launch_fc_fwd(c, p, B, false, nullptr, 0.f, 0, s));
-    } else {
-        TRY(launch_conv_pool(c, p, B, false, s));
-        TRY(launch_fc_fwd(c, p, B, false, nullptr, 0.f, 0, s));
-    }
+    if (c->dense) TRY(launch_dense_conv_pool(c, x, p, B, s));
+    else TRY(launch_conv_pool(c, p, B, false, s));
+    TRY(launch_fc_fwd(c, p, B, false, nullptr, 0.f, 0, s));
     TRY(launch_head_fwd(c, p, B, false, nullptr, outs, s));
     return EXPLAINN_OK;
 }
@@ -354,7 +350,7 @@ extern "C" int explainn_stage_codes(explainn_ctx* c, const uint8_t* codes, int B
                                     int reverse_complement, void* stream) {
     TRY(check_batch(c, B));
     if (!codes) { explainn_set_error("codes is null"); return EXPLAINN_E_ARG; }
-    c->fwd_B = 0; c->tail_B = 0; c->keep_B = 0; c->sync_next = 0;   // the packed codes of a pending backward are overwritten
+    drop_pending(c);                   // the packed codes of a pending backward are overwritten
     return launch_pack_codes(c, codes, B, reverse_complement ? 1 : 0, static_cast<hipStream_t>(stream));
 }
 
@@ -399,7 +395,7 @@ extern "C" int explainn_forward_train(explainn_ctx* c, const float* x, int B,
         return EXPLAINN_E_ARG;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    c->fwd_B = 0; c->keep_B = 0; c->sync_next = 0;
+    c->fwd_B = 0; c->keep_B = 0; c->sync_next = 0;   // (not tail_B: train_step_front clears it, train_step_fc sets it)
     c->eval_valid = false;             // the train-mode folds overwrite the eval-mode tables
     // the one-hot batch is packed and the filter tables are built by one launch; a staged batch of
     // base codes (x == NULL) is already packed and only needs the tables
@@ -638,7 +634,7 @@ extern "C" int explainn_sync_phase(explainn_ctx* c, int phase, const explainn_sy
 extern "C" int explainn_dense_input(explainn_ctx* c, int enable) {
     if (!c) { explainn_set_error("null context"); return EXPLAINN_E_ARG; }
     c->dense = enable != 0;
-    c->fwd_B = 0; c->tail_B = 0; c->keep_B = 0; c->sync_next = 0;
+    drop_pending(c);
     return EXPLAINN_OK;
 }
 
@@ -646,7 +642,7 @@ extern "C" int explainn_stage_onehot(explainn_ctx* c, const float* x, int B, voi
     TRY(check_batch(c, B));
     if (!x) { explainn_set_error("x is null"); return EXPLAINN_E_ARG; }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    c->fwd_B = 0; c->tail_B = 0; c->keep_B = 0; c->sync_next = 0;   // the packed codes of a pending backward are overwritten
+    drop_pending(c);                   // the packed codes of a pending backward are overwritten
     TRY(launch_pack(c, x, B, true, s));  // with the bit masks: the batch may feed a train forward
     c->staged_B = B;
     return EXPLAINN_OK;

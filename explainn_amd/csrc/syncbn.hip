@@ -362,7 +362,7 @@ int sync_phase(explainn_ctx* c, int phase, const explainn_sync_args* a, const do
     const int U = c->U;
     switch (phase) {
         case 1:
-            c->fwd_B = 0; c->tail_B = 0; c->keep_B = 0;
+            c->fwd_B = 0; c->tail_B = 0; c->keep_B = 0;   // (not sync_next: explainn_sync_phase advances it)
             c->eval_valid = false;             // the train-mode folds overwrite the eval-mode tables
             c->dense_x = nullptr;
             if (a->x) TRY(launch_pack_tables(c, a->x, p, B, s));

@@ -45,6 +45,21 @@ def rank_seed(step_no, rank):
     return (step_no * 0x9E3779B97F4A7C15 + (int(rank) << 40)) & 0xFFFFFFFFFFFFFFFF
 
 
+def flat_grads(params, dev, zero=False):
+    """One flat fp32 buffer for the gradients of `params` (explainn_grads order), its per-parameter
+    views and the explainn_grads table pointing into it: (flat, views, gs)."""
+    alloc = torch.zeros if zero else torch.empty
+    flat = alloc(sum(p.numel() for p in params), device=dev, dtype=torch.float32)
+    views, off = [], 0
+    gs = _lib.Grads()
+    for field, p in zip(_lib.GRAD_FIELDS, params):
+        v = flat[off:off + p.numel()].view_as(p)
+        off += p.numel()
+        views.append(v)
+        setattr(gs, field, v.data_ptr())
+    return flat, views, gs
+
+
 class StepEngine:
     def __init__(self, model, max_batch, loss="binary"):
         self.model = model
@@ -53,15 +68,7 @@ class StepEngine:
         self.max_batch = max_batch
         self.ctx = model._context(max_batch, self.dev)
         self.params = list(model.parameters())
-        n = sum(p.numel() for p in self.params)
-        self.flat_grad = torch.zeros(n, device=self.dev, dtype=torch.float32)
-        self.views, off = [], 0
-        self.gs = _lib.Grads()
-        for field, p in zip(_lib.GRAD_FIELDS, self.params):
-            v = self.flat_grad[off:off + p.numel()].view_as(p)
-            off += p.numel()
-            self.views.append(v)
-            setattr(self.gs, field, v.data_ptr())
+        self.flat_grad, self.views, self.gs = flat_grads(self.params, self.dev, zero=True)
         T = model._options["n_features"]
         self.logits = torch.empty(max_batch, T, device=self.dev, dtype=torch.float32)
         self.loss = torch.zeros(1, device=self.dev, dtype=torch.float32)
@@ -83,6 +90,28 @@ class StepEngine:
         bn1_w, bn1_b): the `split` of parallel.GradAllReduce."""
         return sum(p.numel() for p in self.params[:4])
 
+    def _front(self, x):
+        """What step and sync_phases do before their launches: grow logits to the batch, re-resolve
+        the context, prepare x and stage it.  Returns (x pointer, stream).
+        The context is re-resolved every step: an eval forward with a larger batch in between
+        (validation batches larger than the train batch, selene/__init__.py:334) makes the model
+        replace its context by a bigger one, and the one cached here would be closed."""
+        m = self.model
+        B = x.shape[0]
+        if B > self.max_batch:
+            self.max_batch = B
+            self.logits = torch.empty(B, self.logits.shape[1], device=self.dev, dtype=torch.float32)
+        self.ctx = m._context(self.max_batch, self.dev)
+        if not (torch.is_tensor(x) and x.dtype == torch.float32):
+            x = m._prep_input(x, self.dev)
+        stream = C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+        # the model's own validation schedule (architectures.ExplaiNN.validate_input): the first
+        # steps read the flag before computing and route a soft batch to the dense kernels, as
+        # forward() does; later steps enqueue without a host sync and the Trainer reads the sticky
+        # flag periodically; dense_input=True goes straight to the dense kernels
+        xp, _ = m._stage(self.ctx, x, stream)
+        return xp, stream
+
     def sync_phases(self, x, y, B_global, seed=None, freeze_top_n_filters=0, keep_mask=None, rank=0):
         """The sync-BN step as a generator: it enqueues phase after phase of
         explainn_sync_phase and yields each exchange buffer (fp64, on the device) that the caller
@@ -99,19 +128,11 @@ class StepEngine:
         m = self.model
         if m.dense_input:
             raise ValueError("sync-BN works on one-hot input or base codes, not dense_input")
-        if B > self.max_batch:
-            self.max_batch = B
-            self.logits = torch.empty(B, self.logits.shape[1], device=self.dev, dtype=torch.float32)
-        self.ctx = m._context(self.max_batch, self.dev)
-        if not (torch.is_tensor(x) and x.dtype == torch.float32):
-            x = m._prep_input(x, self.dev)
-        lib, h = self.ctx.lib, self.ctx.handle
-        self._xbufs = sync_buffers(self.ctx, self.dev, getattr(self, "_xbufs", None))
         mask = None
         if keep_mask is not None:
             mask = keep_mask.to(device=self.dev, dtype=torch.uint8).contiguous()
-        stream = C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
-        xp = m._x_ptr(self.ctx, x, self.dev)
+        xp, stream = self._front(x)
+        self._xbufs = sync_buffers(self.ctx, self.dev, getattr(self, "_xbufs", None))
         a = _lib.SyncArgs(x=xp, targets=y.data_ptr(), dlogits=None, dl_scale=1.0, B_local=B,
                           B_global=int(B_global), params=C.pointer(self.ps), grads=C.pointer(self.gs),
                           loss_kind=self.loss_kind, dropout_p=float(m.dropout_p), seed=seed,
@@ -143,23 +164,9 @@ class StepEngine:
             return self.logits[:B], self.loss
         if seed is None:
             self.step_no += 1
-            seed = self.step_no * 0x9E3779B97F4A7C15 & 0xFFFFFFFFFFFFFFFF
+            seed = rank_seed(self.step_no, 0)
         m = self.model
-        # The context is re-resolved every step: an eval forward with a larger batch in between
-        # (validation batches larger than the train batch, selene/__init__.py:334) makes the model
-        # replace its context by a bigger one, and the one cached here would be closed.
-        if B > self.max_batch:
-            self.max_batch = B
-            self.logits = torch.empty(B, self.logits.shape[1], device=self.dev, dtype=torch.float32)
-        self.ctx = m._context(self.max_batch, self.dev)
-        if not (torch.is_tensor(x) and x.dtype == torch.float32):
-            x = m._prep_input(x, self.dev)
-        stream = C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
-        # the model's own validation schedule (architectures.ExplaiNN.validate_input): the first
-        # steps read the flag before computing and route a soft batch to the dense kernels, as
-        # forward() does; later steps enqueue without a host sync and the Trainer reads the sticky
-        # flag periodically; dense_input=True goes straight to the dense kernels
-        xp = m._x_ptr(self.ctx, x, self.dev)
+        xp, stream = self._front(x)
         if grad_sync is None:
             _lib.check(self.ctx.lib.explainn_train_step(
                 self.ctx.handle, xp, y.data_ptr(), B, C.byref(self.ps), C.byref(self.gs),

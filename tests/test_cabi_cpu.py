@@ -31,6 +31,24 @@ def test_header_symbols_are_exported(lib):
     assert sorted(_lib.EXPORTS) == declared
 
 
+def test_signatures_match_header_prototypes(lib):
+    """Every prototype of the header has as many ctypes argtypes as parameters and the matching
+    return kind: a missing or extra argument would otherwise be passed silently."""
+    import ctypes as C
+    from explainn_amd import _lib
+    text = open(os.path.join(ROOT, "include", "explainn_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    protos = re.findall(r"(const\s+char\s*\*|int64_t|int|void)\s+(explainn_[a-z_]+)\s*\(([^)]*)\)\s*;", text)
+    assert len(protos) == len(_lib.EXPORTS)
+    kinds = {"int": C.c_int, "int64_t": C.c_int64, "void": None, "constchar*": C.c_char_p}
+    for ret, name, params in protos:
+        params = params.strip()
+        arity = 0 if params in ("", "void") else params.count(",") + 1
+        fn = getattr(lib, name)
+        assert len(fn.argtypes) == arity, "%s: %d argtypes, %d parameters" % (name, len(fn.argtypes), arity)
+        assert fn.restype is kinds[re.sub(r"\s", "", ret)], "%s returns %s" % (name, ret)
+
+
 def test_struct_layout_matches_header():
     """ctypes Structures list the same fields, in the same order, as the C structs."""
     from explainn_amd import _lib

@@ -73,7 +73,7 @@ def main(argv=None):
     n = 10
     stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     for _ in range(n):
-        xp = m1._x_ptr(e1.ctx, x, e1.dev)
+        xp, _ = m1._stage(e1.ctx, x, stream)
         args = _lib.SyncArgs(x=xp, targets=y.data_ptr(), dl_scale=1.0, B_local=B, B_global=B,
                              params=C.pointer(e1.ps), grads=C.pointer(e1.gs), loss_kind=e1.loss_kind,
                              dropout_p=float(m1.dropout_p), seed=7, logits=e1.logits.data_ptr(),
