@@ -13,6 +13,9 @@ LIB_PATH = os.environ.get("EXPLAINN_HIP_LIB", os.path.join(_HERE, "libexplainn_h
 OK, E_ARG, E_HIP, E_BATCH1, E_STATE, E_UNSUPPORTED = 0, -1, -2, -3, -4, -5
 LOSS_BCE_WITH_LOGITS, LOSS_MSE = 0, 1
 PWM_SUM, PWM_MAX = 0, 1
+METRICS_GLOBAL, METRICS_PER_TASK = 0, 1
+METRICS_BINARY, METRICS_LINEAR = 0, 1
+METRICS_NONFINITE, METRICS_NOT_BINARY = 1, 2
 
 _fp = C.c_void_p          # device pointers travel as integers (tensor.data_ptr())
 
@@ -110,6 +113,9 @@ SIGNATURES = {
     "explainn_debug_keep_bits": (_i, [_ctx, _i, _fp, _fp]),
     "explainn_sync_exchange_elems": (_i64, [_ctx, _i]),
     "explainn_sync_phase": (_i, [_ctx, _i, C.POINTER(SyncArgs), _fp, _fp, _fp]),
+    "explainn_metrics_workspace_bytes": (_i64, [_i64, _i, _i, _i]),
+    "explainn_metrics_binary": (_i, [_fp, _fp, _i64, _i, _i, _fp, _fp, _fp, _fp, _fp, _i64, _fp]),
+    "explainn_metrics_linear": (_i, [_fp, _fp, _i64, _i, _i, _fp, _fp, _fp, _fp, _i64, _fp]),
 }
 EXPORTS = tuple(SIGNATURES)
 

@@ -32,8 +32,15 @@ class Trainer(object):
     def __init__(self, model, data_loaders, loss_criterion, metrics, optimizer, max_steps=128000,
                  patience=32000, report_stats_every_n_steps=1000, output_dir="./",
                  cpu_n_threads=1, use_cuda=False, checkpoint_resume=None, freeze_top_n_filters=0,
-                 logging_verbosity=2, sync_batchnorm=False):
+                 logging_verbosity=2, sync_batchnorm=False, device_metrics=False):
         self.model = model
+        # opt-in: validation predictions and targets stay on the device and the
+        # metrics are computed there (explainn_amd.metrics) instead of by the `metrics` callables on
+        # host copies; the names in `metrics` say which pair
+        self.device_metrics = bool(device_metrics)
+        if self.device_metrics:
+            from . import metrics as _device_metrics
+            self._device_metric_kind = _device_metrics.kind_of(metrics.keys())
         # opt-in sync-BN: BatchNorm statistics of the whole batch across ranks; the
         # steps then leave the global gradients on every rank and no gradient all-reduce runs
         self.sync_batchnorm = bool(sync_batchnorm)
@@ -259,18 +266,42 @@ class Trainer(object):
                 # after the loop
                 batch_losses.append(self.criterion(predictions, targets).reshape(1))
                 all_predictions.append(predictions.data)
+        if self.device_metrics:
+            return self._on_device(batch_losses, all_predictions, all_targets)
         losses = torch.cat(batch_losses).tolist() if batch_losses else []
         preds = torch.cat(all_predictions).cpu().numpy() if all_predictions else np.zeros((0, 0))
         tgts = torch.cat(all_targets).cpu().numpy() if all_targets else np.zeros((0, 0))
         return (np.average(losses), preds, tgts)
 
+    def _on_device(self, batch_losses, all_predictions, all_targets):
+        """device_metrics: (batch losses, predictions, targets) as device tensors, nothing read."""
+        if not all_predictions:
+            raise ValueError("device_metrics: the data loader gave no batch")
+        dev = all_predictions[0].device
+        if dev.type != "cuda":
+            raise RuntimeError("device_metrics needs the model on a HIP device (use_cuda=True). "
+                               "There is no CPU fallback.")
+        return (torch.cat(batch_losses), torch.cat(all_predictions),
+                torch.cat([t.to(dev) for t in all_targets]))
+
+    def _device_scores(self, batch_losses, predictions, targets):
+        """Loss average and both metrics of the pair from ONE device-to-host transfer.  The average is
+        numpy's over the same float32 batch losses as the host path takes, hence the same value."""
+        from . import metrics as dm
+        pair = dm._run(self._device_metric_kind, targets.reshape(-1), predictions.reshape(-1), False)
+        vals = dm.read(pair[0], pair[1], dm._wrap(batch_losses.to(torch.float64), pair[0]._call, 0))
+        scores = dict(zip(dm.NAMES[self._device_metric_kind], vals[:2]))
+        return np.average(vals[2]), {name: scores[name] for name in self.metrics}
+
     def validate(self):
         """Validation metrics on flattened predictions; best model -> best_model.pth.tar
         (selene/__init__.py:344-391)."""
         validation_loss, all_predictions, all_targets = self._evaluate_on_data("validation")
+        if self.device_metrics:
+            validation_loss, valid_scores = self._device_scores(validation_loss, all_predictions, all_targets)
         self.logger.info("Validation loss: %s" % validation_loss)
-        valid_scores = {}
-        for metric in self.metrics:
+        valid_scores = valid_scores if self.device_metrics else {}
+        for metric in ({} if self.device_metrics else self.metrics):
             score = self.metrics[metric](all_targets.flatten(), all_predictions.flatten())
             valid_scores[metric] = score if isinstance(score, float) else score[0]
         for name, score in valid_scores.items():

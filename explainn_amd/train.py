@@ -84,9 +84,12 @@ def _get_data_loader(seqs, labels, batch_size=100, shuffle=False):
 
 def _train(sequence_length, n_features, data_loaders, input_data, steps_per_epoch, cnn_units=100,
            kernel_size=19, lr=0.003, max_epochs=100, patience=10, cpu_threads=1, output_dir="./",
-           filter_weights=[], freeze=False, checkpoint_resume=None, sync_batchnorm=False):
+           filter_weights=[], freeze=False, checkpoint_resume=None, sync_batchnorm=False,
+           device_metrics=False):
     """train.py:304-342.  sync_batchnorm: BatchNorm statistics of the whole batch across
-    data-parallel ranks (selene.Trainer's keyword; off = per-shard, the reference's DDP semantics)."""
+    data-parallel ranks (selene.Trainer's keyword; off = per-shard, the reference's DDP semantics).
+    device_metrics: validation metrics computed on the device (selene.Trainer's keyword; off = the
+    reference's scikit-learn / scipy callables on host copies)."""
     freeze_top_n_filters = 0
     exp_model = ExplaiNN(cnn_units, kernel_size, sequence_length, n_features)
     loss_criterion = get_loss(input_data=input_data)
@@ -113,7 +116,7 @@ def _train(sequence_length, n_features, data_loaders, input_data, steps_per_epoc
         report_stats_every_n_steps=steps_per_epoch, output_dir=output_dir,
         cpu_n_threads=cpu_threads, use_cuda=torch.cuda.is_available(),
         checkpoint_resume=checkpoint_resume, freeze_top_n_filters=freeze_top_n_filters,
-        sync_batchnorm=sync_batchnorm)
+        sync_batchnorm=sync_batchnorm, device_metrics=device_metrics)
     trainer.train_and_validate()
     return trainer
 
@@ -168,6 +171,8 @@ def main(argv=None):
     ap.add_argument("--freeze", action="store_true")
     ap.add_argument("--sync-batchnorm", action="store_true",
                     help="data-parallel runs: BatchNorm statistics of the whole batch across ranks")
+    ap.add_argument("--device-metrics", action="store_true",
+                    help="compute the validation metrics on the GPU instead of with scikit-learn / scipy")
     args = ap.parse_args(argv)
     import pandas as pd
     start = time.time()
@@ -195,14 +200,15 @@ def main(argv=None):
             os.makedirs(d)
             _train(L, T, loaders, input_data, spe, args.cnn_units, args.kernel_size, args.lr, 5,
                    args.patience, args.cpu_threads, d, filter_weights, args.freeze,
-                   sync_batchnorm=args.sync_batchnorm)
+                   sync_batchnorm=args.sync_batchnorm, device_metrics=args.device_metrics)
         loss = pd.read_csv(os.path.join(d, "validation.txt"), sep="\t").loss.min()
         if best_model is None or loss < best_loss:
             best_loss, best_model = loss, os.path.join(d, "best_model.pth.tar")
     shutil.copy(best_model, args.output_dir)
     _train(L, T, loaders, input_data, spe, args.cnn_units, args.kernel_size, args.lr,
            args.max_epochs, args.patience, args.cpu_threads, args.output_dir, filter_weights,
-           args.freeze, best_model, sync_batchnorm=args.sync_batchnorm)
+           args.freeze, best_model, sync_batchnorm=args.sync_batchnorm,
+           device_metrics=args.device_metrics)
     if args.time_me:
         with open(os.path.join(args.output_dir, "time-train.py.txt"), "wt") as fh:
             fh.write("%.2f seconds" % (time.time() - start))

@@ -323,6 +323,36 @@ int64_t explainn_sync_exchange_elems(const explainn_ctx* ctx, int phase);
 int explainn_sync_phase(explainn_ctx* ctx, int phase, const explainn_sync_args* args,
                         const double* exchange_in, double* exchange_out, void* stream);
 
+/* Evaluation metrics on the device (the reference's test.py::_get_performances and the callables of
+ * architectures.get_metrics, which run scikit-learn / scipy on host copies).  y (targets) and s
+ * (scores): contiguous row-major fp32 (N,T) device arrays.  mode EXPLAINN_METRICS_PER_TASK: T
+ * results, one per column of length N; EXPLAINN_METRICS_GLOBAL: one result over all N*T values (the
+ * Trainer's flatten()).  A column may hold at most 2^26 values (EXPLAINN_E_ARG beyond; the size query
+ * returns the negative code).  Results are fp64 on the device (1 or T values each); no host
+ * synchronisation, no allocation: all scratch is the caller's workspace of at least
+ * explainn_metrics_workspace_bytes(N, T, mode, kind) bytes.  Same input, same bits, on every call.
+ *   binary: auroc = Mann-Whitney statistic with ties counted one half (NaN for a one-class column),
+ *           ap = average precision as scikit-learn defines it (0 for a column without a positive),
+ *           counts = int64 (positives, negatives) per result.  Both come from ONE sort.
+ *   linear: pearson (two fp64 passes) and spearman (Pearson of the average ranks); NaN for a
+ *           constant column.
+ * status (one device word, OR-ed into, never cleared here): bit 0 = a NaN or +-Inf in y or s,
+ * bit 1 = a binary target other than exactly 0 or 1.  The results are meaningless when it is set.
+ * -0.0 and +0.0 are one score; denormals are distinct values.  No context needed. */
+#define EXPLAINN_METRICS_GLOBAL 0
+#define EXPLAINN_METRICS_PER_TASK 1
+#define EXPLAINN_METRICS_BINARY 0
+#define EXPLAINN_METRICS_LINEAR 1
+#define EXPLAINN_METRICS_NONFINITE 1
+#define EXPLAINN_METRICS_NOT_BINARY 2
+int64_t explainn_metrics_workspace_bytes(int64_t N, int T, int mode, int kind);
+int explainn_metrics_binary(const float* y, const float* s, int64_t N, int T, int mode, double* auroc,
+                            double* ap, int64_t* counts, unsigned int* status, void* workspace,
+                            int64_t workspace_bytes, void* stream);
+int explainn_metrics_linear(const float* y, const float* s, int64_t N, int T, int mode, double* pearson,
+                            double* spearman, unsigned int* status, void* workspace,
+                            int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

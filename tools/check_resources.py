@@ -39,7 +39,19 @@ INPUT_GRAD = [
 ]
 # in-silico mutagenesis (ism.hip) at C2: k = 19 -> four pooled windows per substitution, one task
 ISM = [r"^ism_units_kernel<4>", r"^ism_sum_kernel<1>"]
-GATED = C2_STEP + INPUT_GRAD + ISM
+# device-side evaluation metrics (metrics.hip): every kernel of the sort, the scans and the reductions
+METRICS = [
+    r"^metrics_keys_binary_kernel", r"^metrics_keys_linear_kernel", r"^metrics_hist_kernel",
+    r"^metrics_scatter_kernel", r"^metrics_scan_reduce_kernel<HistScan>", r"^metrics_scan_sums_kernel<HistScan>",
+    r"^metrics_scan_apply_kernel<HistScan>", r"^metrics_scan_reduce_kernel<RunScan<true> >",
+    r"^metrics_scan_sums_kernel<RunScan<true> >", r"^metrics_scan_apply_kernel<RunScan<true> >",
+    r"^metrics_scan_reduce_kernel<RunScan<false> >", r"^metrics_scan_sums_kernel<RunScan<false> >",
+    r"^metrics_scan_apply_kernel<RunScan<false> >", r"^metrics_binary_terms_kernel",
+    r"^metrics_binary_final_kernel", r"^metrics_run_ends_kernel", r"^metrics_ranks_kernel",
+    r"^metrics_sums_kernel", r"^metrics_means_kernel", r"^metrics_centred_kernel",
+    r"^metrics_linear_final_kernel",
+]
+GATED = C2_STEP + INPUT_GRAD + ISM + METRICS
 
 
 # Register cliffs measured in the pipeline: 1024-thread blocks of which TWO must
