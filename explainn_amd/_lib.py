@@ -77,6 +77,8 @@ _ctx, _pp, _gp, _i, _i64 = C.c_void_p, C.POINTER(Params), C.POINTER(Grads), C.c_
 # every C function of the header: name -> (restype, argtypes)
 SIGNATURES = {
     "explainn_create": (_i, [C.POINTER(_ctx), _i, _i, _i, _i, _i, _i]),
+    "explainn_create_bank": (_i, [C.POINTER(_ctx), _i, _i, _i, _i, _i, _i, _i]),
+    "explainn_groups": (_i, [_ctx]),
     "explainn_destroy": (None, [_ctx]),
     "explainn_last_error": (C.c_char_p, []),
     "explainn_scratch_bytes": (_i64, [_ctx]),
@@ -151,14 +153,20 @@ def check(rc):
 class Context:
     """Owner of one explainn_ctx (device scratch for a fixed model geometry and max batch)."""
 
-    def __init__(self, cnn_units, kernel_size, sequence_length, n_features, max_batch, device):
+    def __init__(self, cnn_units, kernel_size, sequence_length, n_features, max_batch, device, groups=1):
+        """groups > 1: a model bank of `groups` members of cnn_units units each (explainn_create_bank)."""
         self.lib = load()
         self.geom = (cnn_units, kernel_size, sequence_length, n_features)
+        self.groups = groups
         self.max_batch = max_batch
         self.device = device
         h = C.c_void_p()
-        check(self.lib.explainn_create(C.byref(h), cnn_units, kernel_size, sequence_length,
-                                       n_features, max_batch, device))
+        if groups == 1:
+            check(self.lib.explainn_create(C.byref(h), cnn_units, kernel_size, sequence_length,
+                                           n_features, max_batch, device))
+        else:
+            check(self.lib.explainn_create_bank(C.byref(h), groups, cnn_units, kernel_size,
+                                                sequence_length, n_features, max_batch, device))
         self.handle = h
 
     def stage_timing(self, enable=True):

@@ -346,6 +346,16 @@ class ExplaiNN(_Model):
                 ".cuda()/.to('cuda'). There is no CPU fallback." % dev)
         return dev
 
+    # What a model bank (ExplaiNNBank below) answers differently: the units the kernels run on, the
+    # members of the context and the shape of the logits.
+    _groups = 1
+
+    def _units(self):
+        return self._options["cnn_units"]
+
+    def _logits_empty(self, B, dev):
+        return torch.empty(B, self._options["n_features"], device=dev, dtype=torch.float32)
+
     def _context(self, B, dev):
         o = self._options
         geom = (o["cnn_units"], o["kernel_size"], o["sequence_length"], o["n_features"])
@@ -356,7 +366,7 @@ class ExplaiNN(_Model):
                 torch.cuda.synchronize(dev)
                 ctx.close()
             cap = max(B, ctx.max_batch if ctx is not None and ctx.geom == geom else 0)
-            self._rt.ctx = _lib.Context(*geom, max_batch=cap, device=index)
+            self._rt.ctx = _lib.Context(*geom, max_batch=cap, device=index, groups=self._groups)
         return self._rt.ctx
 
     def __setattr__(self, name, value):
@@ -596,7 +606,7 @@ class ExplaiNN(_Model):
             return _EvalInputGrad.apply(self, x)
         x = self._prep_input(x, dev)
         B = x.shape[0]
-        logits = torch.empty(B, self._options["n_features"], device=dev, dtype=torch.float32)
+        logits = self._logits_empty(B, dev)
         if B == 0:                                   # torch returns an empty (0, T) tensor in eval
             return logits
         with torch.cuda.device(dev):
@@ -612,7 +622,7 @@ class ExplaiNN(_Model):
         dev = self._device()
         x = self._prep_input(x, dev)
         B = x.shape[0]
-        logits = torch.empty(B, self._options["n_features"], device=dev, dtype=torch.float32)
+        logits = self._logits_empty(B, dev)
         with torch.cuda.device(dev):
             ctx, ps, _, stream, xp, read = self._front(x, dev, VALIDATE_FIRST)
             self._rt.x_keep = x                # a dense batch is read again by the input gradient
@@ -678,7 +688,7 @@ class ExplaiNN(_Model):
     def _empty_batch_error(self):
         # what torch's BatchNorm1d raises for an empty batch in train mode
         return ValueError("Expected more than 1 value per channel when training, got input size "
-                          "[0, %d, 1]" % (FC_HIDDEN * self._options["cnn_units"]))
+                          "[0, %d, 1]" % (FC_HIDDEN * self._units()))
 
     def _dropout_args(self, dev, B, rank=None):
         """(keep_mask, seed) of a train forward: the mask of set_dropout_mask (consumed here) as the
@@ -687,7 +697,7 @@ class ExplaiNN(_Model):
         mask, self._rt.pending = self._rt.pending, None
         if mask is not None:
             mask = mask.to(device=dev, dtype=torch.uint8).contiguous()
-            if mask.numel() != B * FC_HIDDEN * self._options["cnn_units"]:
+            if mask.numel() != B * FC_HIDDEN * self._units():
                 raise RuntimeError("keep-mask must have shape (B, 100*cnn_units)")
         if self.dropout_p > 0:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
@@ -706,7 +716,7 @@ class ExplaiNN(_Model):
         if B == 0:
             raise self._empty_batch_error()
         Bg = int(red.global_batch(B))
-        logits = torch.empty(B, self._options["n_features"], device=dev, dtype=torch.float32)
+        logits = self._logits_empty(B, dev)
         mask, seed = self._dropout_args(dev, B, red.rank)
         gs = _lib.Grads()
         with torch.cuda.device(dev):
@@ -758,7 +768,7 @@ class ExplaiNN(_Model):
         B = x.shape[0]
         if B == 0:
             raise self._empty_batch_error()
-        logits = torch.empty(B, self._options["n_features"], device=dev, dtype=torch.float32)
+        logits = self._logits_empty(B, dev)
         mask, seed = self._dropout_args(dev, B)
         with torch.cuda.device(dev):
             ctx, ps, _, stream, xp, read = self._front(x, dev, policy, bump=False)
@@ -806,7 +816,7 @@ class ExplaiNN(_Model):
 
     # -- the façade test.py / interpret.py use -----------------------------------------------
     def _first_four_rows(self, x_rep):
-        U = self._options["cnn_units"]
+        U = self._units()
         if isinstance(x_rep, BaseCodes) or (torch.is_tensor(x_rep) and x_rep.dtype == torch.uint8):
             return x_rep
         if x_rep.dim() != 3 or x_rep.shape[1] not in (4, 4 * U):
@@ -820,7 +830,7 @@ class ExplaiNN(_Model):
         dev = self._device()
         x = self._prep_input(self._first_four_rows(x_rep), dev)
         B = x.shape[0]
-        outs = torch.empty(B, self._options["cnn_units"], device=dev, dtype=torch.float32)
+        outs = torch.empty(B, self._units(), device=dev, dtype=torch.float32)
         with torch.cuda.device(dev):
             ctx, ps, _, stream, xp, read = self._front(x, dev)
             _lib.check(ctx.lib.explainn_unit_outputs(ctx.handle, xp, B, C.byref(ps), outs.data_ptr(), stream))
@@ -835,7 +845,7 @@ class ExplaiNN(_Model):
         x = self._prep_input(self._first_four_rows(x_rep), dev)
         B = x.shape[0]
         o = self._options
-        acts = torch.empty(B, o["cnn_units"], o["sequence_length"] - o["kernel_size"] + 1,
+        acts = torch.empty(B, self._units(), o["sequence_length"] - o["kernel_size"] + 1,
                            device=dev, dtype=torch.float32)
         with torch.cuda.device(dev):
             ctx, ps, _, stream, xp, read = self._front(x, dev)
@@ -876,7 +886,7 @@ class ExplaiNN(_Model):
         the (B,U) uint8 "has a site" matrix when want_hit."""
         dev, x, B, select = self._export_args(x, select)
         o = self._options
-        U, k = o["cnn_units"], o["kernel_size"]
+        U, k = self._units(), o["kernel_size"]
         for name, t, shape, dt in (("thresholds", thresholds, (U,), torch.float32),
                                    ("site_total", site_total, (U,), torch.int32),
                                    ("pfm", pfm, (U, k, 4), torch.int32)):
@@ -892,6 +902,164 @@ class ExplaiNN(_Model):
                 hit.data_ptr() if hit is not None else None, stream))
             self._settle(read)
         return hit
+
+
+class _BankCombiner(nn.Module):
+    """The `final` layers of a bank's members, stacked: weight (G,T,U), bias (G,T)."""
+
+    def __init__(self, n_models, n_features, cnn_units):
+        super().__init__()
+        self.weight = nn.Parameter(torch.zeros(n_models, n_features, cnn_units))
+        self.bias = nn.Parameter(torch.zeros(n_models, n_features))
+
+    forward = _GroupedTaps.forward
+
+
+class ExplaiNNBank(ExplaiNN):
+    """A model bank: `n_models` (G) independently initialised ExplaiNN models of `cnn_units` (U) units
+    each, trained on the same batches and targets in ONE fused step (explainn_create_bank) -- the N
+    runs of train.py's --initialize, an ensemble, a seed study.  Up to the combiner the members are
+    one filter bank of G*U independent units; member g owns units [g*U, (g+1)*U).
+
+    Same sub-module names as ExplaiNN with stacked tensors (member-major): every per-unit tensor has
+    G*U where a single model has U, `final.weight` is (G,T,U), `final.bias` (G,T); `parameters()` are
+    the same 14 tensors in the same order, so FusedAdam, flat_grads and StepEngine work unchanged.
+    `num_batches_tracked` is one scalar per BatchNorm (all members step together).  `bank(x)` gives
+    (B,G,T) logits in eval and train mode; the targets of a StepEngine step are shared (B,T) and its
+    loss has G values.  `freeze_top_n_filters = n` freezes rows [0,n) of every member; the keep-mask of
+    set_dropout_mask is (B, 100*G*U).
+
+    Under the same torch seed the bank holds exactly the parameters of
+    `[ExplaiNN(...) for _ in range(n_models)]` built in that order.  `member(g)` gives a stand-alone
+    ExplaiNN with copies of member g's tensors.  What works on one model only -- x.grad,
+    input_gradient, in_silico_mutagenesis, sync-BN -- raises ValueError: run it on member(g)."""
+
+    def __init__(self, n_models, cnn_units, kernel_size, sequence_length, n_features=1):
+        if n_models < 1:
+            raise ValueError("n_models must be positive")
+        # the members first, drawing from the global generator exactly as a sequence of ExplaiNN
+        # constructors does; the stacked skeleton then draws from a forked generator
+        members = [ExplaiNN(cnn_units, kernel_size, sequence_length, n_features) for _ in range(n_models)]
+        with torch.random.fork_rng(devices=[]):
+            super().__init__(n_models * cnn_units, kernel_size, sequence_length, n_features)
+        self._groups = n_models
+        self._options = {"n_models": n_models, "cnn_units": cnn_units, "kernel_size": kernel_size,
+                         "sequence_length": sequence_length, "n_features": n_features,
+                         "weights_file": None}
+        self.final = _BankCombiner(n_models, n_features, cnn_units)
+        for g, m in enumerate(members):
+            self.load_member(g, m.state_dict())
+
+    @classmethod
+    def from_models(cls, models):
+        """The bank whose member g holds copies of models[g]'s parameters and buffers (all of one
+        shape, on the CPU or not: the bank is built on the CPU); num_batches_tracked from models[0]."""
+        models = list(models)
+        o = models[0]._options
+        geom = (o["cnn_units"], o["kernel_size"], o["sequence_length"], o["n_features"])
+        for m in models:
+            mo = m._options
+            if (mo["cnn_units"], mo["kernel_size"], mo["sequence_length"], mo["n_features"]) != geom:
+                raise ValueError("the members of a bank share (cnn_units, kernel_size, sequence_length, n_features)")
+        with torch.random.fork_rng(devices=[]):
+            bank = cls(len(models), *geom)
+        for g, m in enumerate(models):
+            bank.load_member(g, m.state_dict())
+        with torch.no_grad():
+            for key, v in models[0].state_dict().items():
+                if key.endswith("num_batches_tracked"):
+                    bank.state_dict()[key].copy_(v)
+        return bank
+
+    # -- members ---------------------------------------------------------------------------
+    def _member_options(self):
+        o = self._options
+        return {"cnn_units": o["cnn_units"], "kernel_size": o["kernel_size"],
+                "sequence_length": o["sequence_length"], "n_features": o["n_features"],
+                "weights_file": None}
+
+    def _member_view(self, key, tensor, g):
+        """Member g's part of the stacked tensor `tensor` of state_dict key `key` (a view)."""
+        if key.endswith("num_batches_tracked"):
+            return tensor
+        if key.startswith("final."):
+            return tensor[g]
+        chunk = tensor.shape[0] // self._groups
+        return tensor[g * chunk:(g + 1) * chunk]
+
+    def _check_member(self, g):
+        if not 0 <= g < self._groups:
+            raise IndexError("member %d of a bank of %d" % (g, self._groups))
+
+    def member_state_dict(self, g):
+        """Member g's tensors as the reference-compatible state_dict of a stand-alone ExplaiNN (copies)."""
+        self._check_member(g)
+        return OrderedDict((key, self._member_view(key, v, g).detach().clone())
+                           for key, v in self.state_dict().items())
+
+    def load_member(self, g, state_dict):
+        """Copy a stand-alone model's state_dict into member g (num_batches_tracked, shared by the
+        bank, is left as it is)."""
+        self._check_member(g)
+        own = self.state_dict()
+        missing = [key for key in own if key not in state_dict and not key.endswith("num_batches_tracked")]
+        if missing:
+            raise KeyError("state_dict lacks %s" % ", ".join(missing))
+        with torch.no_grad():
+            for key, v in own.items():
+                if key.endswith("num_batches_tracked"):
+                    continue
+                dst = self._member_view(key, v, g)
+                dst.copy_(state_dict[key].reshape(dst.shape))
+        self.invalidate()
+
+    def member(self, g):
+        """A stand-alone ExplaiNN holding copies of member g's parameters and buffers, on the bank's
+        device and in its mode, with its dropout / freeze / input settings."""
+        o = self._member_options()
+        with torch.random.fork_rng(devices=[]):
+            m = ExplaiNN(o["cnn_units"], o["kernel_size"], o["sequence_length"], o["n_features"])
+        m.load_state_dict(self.member_state_dict(g))
+        m.to(self.final.weight.device)
+        m.train(self.training)
+        m.dropout_p = self.dropout_p
+        m.freeze_top_n_filters = self.freeze_top_n_filters
+        m.validate_input = self.validate_input
+        m.dense_input = self.dense_input
+        return m
+
+    # -- what a bank does not do -------------------------------------------------------------
+    @staticmethod
+    def _member_only(what):
+        return ValueError("%s is not available on a model bank: run it on one member, bank.member(g)" % what)
+
+    @property
+    def sync_bn(self):
+        return None
+
+    @sync_bn.setter
+    def sync_bn(self, reducer):
+        if reducer is not None:
+            raise self._member_only("sync-BN")
+
+    def forward(self, x):
+        """(B,4,L) one-hot or base codes -> (B,G,T): member g's logits at [:, g]."""
+        if torch.is_tensor(x) and x.requires_grad:
+            raise self._member_only("x.grad")
+        return super().forward(x)
+
+    def input_gradient(self, x, dlogits):
+        raise self._member_only("input_gradient")
+
+    def in_silico_mutagenesis(self, x):
+        raise self._member_only("in_silico_mutagenesis")
+
+    # -- plumbing --------------------------------------------------------------------------
+    def _units(self):
+        return self._groups * self._options["cnn_units"]
+
+    def _logits_empty(self, B, dev):
+        return torch.empty(B, self._groups, self._options["n_features"], device=dev, dtype=torch.float32)
 
 
 class PWM(nn.Module):

@@ -81,11 +81,11 @@ void carve(explainn_ctx* c, Carver& cv) {
     cv.take(&c->dy, U4 * n * Bs);
     cv.take(&c->S12p, U * fc_ng(c->NQ) * (Bs / 16) * 2);
     cv.take(&c->Dspp, U * (Bs / 4) * K4);
-    cv.take(&c->dlogits, (int64_t)c->maxB * c->T);
+    cv.take(&c->dlogits, (int64_t)c->maxB * c->Gm * c->T);
     cv.take(&c->flags, 64);
     cv.take(&c->bn1_ticket, 64);
     cv.take(&c->dlT, (int64_t)c->T * Bs);
-    cv.take(&c->gWp, c->T > HEAD_GEMM_MIN_T ? (int64_t)head_gw_chunks(c->maxB) * c->T * (c->U + 1) : 0);
+    cv.take(&c->gWp, c->T > HEAD_GEMM_MIN_T && c->Gm == 1 ? (int64_t)head_gw_chunks(c->maxB) * c->T * (c->U + 1) : 0);
     cv.take(&c->lossp, 256);
     cv.take(&c->site_cnt, U4 * Bs);
     cv.take(&c->site_off, U4 * Bs);
@@ -155,14 +155,34 @@ int eval_front(explainn_ctx* c, const float* x, int B, const explainn_params* p,
 }
 }  // namespace
 
-extern "C" int explainn_create(explainn_ctx** out, int cnn_units, int kernel_size,
-                               int sequence_length, int n_features, int max_batch, int device) {
+// What the entry points that fold units through `final` in kernels of their own answer on a bank.
+#define NOT_ON_BANK(c, what)                                                                        \
+    do {                                                                                            \
+        if ((c) && (c)->Gm > 1) {                                                                    \
+            explainn_set_error(what " is not available on a model bank (%d members): run it on one " \
+                               "member, ExplaiNNBank.member(g)", (c)->Gm);                           \
+            return EXPLAINN_E_UNSUPPORTED;                                                          \
+        }                                                                                           \
+    } while (0)
+
+// the largest unit count the kernels in front of the head are tested at (tests/test_gpu_properties.py
+// and tests/test_gpu_bank.py: 2000 units); nothing larger has run, so nothing larger is accepted
+#define BANK_MAX_UNITS 2000
+
+static int create_ctx(explainn_ctx** out, int groups, int units_per_member, int kernel_size,
+                      int sequence_length, int n_features, int max_batch, int device) {
     if (!out) { explainn_set_error("out is null"); return EXPLAINN_E_ARG; }
     *out = nullptr;
-    if (cnn_units < 1 || n_features < 1 || max_batch < 1) {
-        explainn_set_error("cnn_units, n_features and max_batch must be positive");
+    if (groups < 1 || units_per_member < 1 || n_features < 1 || max_batch < 1) {
+        explainn_set_error("%scnn_units, n_features and max_batch must be positive", groups < 1 ? "groups, " : "");
         return EXPLAINN_E_ARG;
     }
+    if (groups > 1 && (int64_t)groups * units_per_member > BANK_MAX_UNITS) {
+        explainn_set_error("a bank of %d x %d units exceeds the %d units a context supports", groups,
+                           units_per_member, BANK_MAX_UNITS);
+        return EXPLAINN_E_UNSUPPORTED;
+    }
+    const int cnn_units = groups * units_per_member;
     if (kernel_size < 2 || kernel_size > MAX_K) {
         explainn_set_error("kernel_size %d unsupported (2..%d)", kernel_size, MAX_K);
         return EXPLAINN_E_UNSUPPORTED;
@@ -182,6 +202,7 @@ extern "C" int explainn_create(explainn_ctx** out, int cnn_units, int kernel_siz
     HIP_TRY(hipSetDevice(device));                 // (nothing allocated yet)
     explainn_ctx* c = new explainn_ctx();
     memset(c, 0, sizeof(*c));
+    c->Gm = groups; c->Um = units_per_member;
     c->U = cnn_units; c->k = kernel_size; c->L = sequence_length; c->T = n_features;
     c->maxB = max_batch; c->device = device;
     c->Lo = Lo; c->n = n; c->U4 = (cnn_units + 3) & ~3; c->Uq = c->U4 / 4;
@@ -243,6 +264,18 @@ extern "C" int explainn_create(explainn_ctx** out, int cnn_units, int kernel_siz
     return EXPLAINN_OK;
 }
 
+extern "C" int explainn_create(explainn_ctx** out, int cnn_units, int kernel_size,
+                               int sequence_length, int n_features, int max_batch, int device) {
+    return create_ctx(out, 1, cnn_units, kernel_size, sequence_length, n_features, max_batch, device);
+}
+
+extern "C" int explainn_create_bank(explainn_ctx** out, int groups, int cnn_units, int kernel_size,
+                                    int sequence_length, int n_features, int max_batch, int device) {
+    return create_ctx(out, groups, cnn_units, kernel_size, sequence_length, n_features, max_batch, device);
+}
+
+extern "C" int explainn_groups(const explainn_ctx* c) { return c ? c->Gm : 0; }
+
 extern "C" void explainn_destroy(explainn_ctx* c) {
     if (!c) return;
     for (int i = 0; i < ST_COUNT; ++i) {
@@ -272,6 +305,7 @@ extern "C" int explainn_forward_eval(explainn_ctx* c, const float* x, int B,
 // those of explainn_forward_eval, bit for bit: idx is an extra output of the same filter-bank pass.
 extern "C" int explainn_forward_eval_keep(explainn_ctx* c, const float* x, int B,
                                           const explainn_params* p, float* logits, void* stream) {
+    NOT_ON_BANK(c, "explainn_forward_eval_keep");
     TRY(check_batch(c, B));
     hipStream_t s = static_cast<hipStream_t>(stream);
     TRY(eval_front(c, x, B, p, s));
@@ -286,6 +320,7 @@ extern "C" int explainn_forward_eval_keep(explainn_ctx* c, const float* x, int B
 
 extern "C" int explainn_input_grad(explainn_ctx* c, const float* dlogits, int B,
                                    const explainn_params* p, float* dx, void* stream) {
+    NOT_ON_BANK(c, "explainn_input_grad");
     TRY(check_batch(c, B));
     if (!dlogits || !dx) { explainn_set_error("dlogits and dx are required"); return EXPLAINN_E_ARG; }
     if (c->keep_B != B) {
@@ -305,6 +340,7 @@ extern "C" int64_t explainn_ism_workspace_bytes(const explainn_ctx* c, int B) {
 extern "C" int explainn_ism(explainn_ctx* c, const float* x, int B, const explainn_params* p,
                             float* logits, float* delta, void* workspace, int64_t workspace_bytes,
                             void* stream) {
+    NOT_ON_BANK(c, "explainn_ism");
     TRY(check_batch(c, B));
     if (!logits || !delta || !workspace) {
         explainn_set_error("logits, delta and workspace are required");
@@ -461,7 +497,11 @@ int backward_conv(explainn_ctx* c, int B, const explainn_params* p, const explai
 // itself: worth a launch (~5 us) up to a few hundred sequences -- 0.120 -> 0.115 ms per step at 100
 // units x 64 sequences -- and a wash at 1024 (passA +9.6 us, head_bwd -9.6 us; MI355X), so larger
 // batches keep the per-unit kernel.
-bool head_rides_in_passA(const explainn_ctx* c, int B) { return c->T <= PA_HEAD_MAX_T && B <= 512; }
+// A bank never rides: passA's prologue has no member index ("Model bank").
+bool head_rides_in_passA(const explainn_ctx* c, int B) {
+    if (c->Gm > 1) return false;
+    return c->T <= PA_HEAD_MAX_T && B <= 512;
+}
 
 pa_head_args head_in_passA(explainn_ctx* c, const explainn_params* p, const explainn_grads* g, int mode,
                            const float* dl, int kind, const float* logits, const float* y,
@@ -499,6 +539,7 @@ extern "C" int explainn_backward(explainn_ctx* c, const float* dlogits, int B,
 extern "C" int explainn_backward_input(explainn_ctx* c, const float* dlogits, int B,
                                        const explainn_params* p, const explainn_grads* g,
                                        int freeze_top_n_filters, float* dx, void* stream) {
+    NOT_ON_BANK(c, "explainn_backward_input");
     if (!dx) { explainn_set_error("dx is null"); return EXPLAINN_E_ARG; }
     TRY(explainn_backward(c, dlogits, B, p, g, freeze_top_n_filters, stream));
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -583,6 +624,7 @@ extern "C" int64_t explainn_sync_exchange_elems(const explainn_ctx* c, int phase
 
 extern "C" int explainn_sync_phase(explainn_ctx* c, int phase, const explainn_sync_args* a,
                                    const double* exchange_in, double* exchange_out, void* stream) {
+    NOT_ON_BANK(c, "sync-BN (explainn_sync_phase)");
     if (!a || !a->params || !a->grads) { explainn_set_error("sync phase: args, params and grads are required"); return EXPLAINN_E_ARG; }
     TRY(check_batch(c, a->B_local));
     if (phase < 1 || phase > EXPLAINN_SYNC_PHASES) {

@@ -429,6 +429,7 @@ struct fin_args {
     const float* S12p; const double* m; const double* Gw; const double* mug; const double* sig1;
     const float* g1; float* g_conv_w; float* g_conv_b; float* g_bn1_w; float* g_bn1_b;
     int K4; int freeze_n; int NG;
+    int Um;                           // units per member (model bank; = U otherwise): rows [0, freeze_n) of EVERY member freeze
     int dsp_stride, dsp_count;        // Dspp[u][dsp_stride][4k]: the first dsp_count partials are live
 };
 
@@ -477,7 +478,7 @@ __device__ __forceinline__ void fin_unit(const fin_args& f, const float* __restr
         double D = 0;
         for (int q = 0; q < ngrp; ++q) D += fin_part[q][tid];
         const double val = a * (D - S1 * f.m[tid] - (S2 / sg) * (f.Gw[(size_t)u * K4 + tid] - mu * f.m[tid]));
-        f.g_conv_w[(size_t)u * K4 + tid] = (u < f.freeze_n) ? 0.f : (float)val;
+        f.g_conv_w[(size_t)u * K4 + tid] = (u % f.Um < f.freeze_n) ? 0.f : (float)val;
     }
     if (tid == 0) {
         f.g_bn1_b[u] = (float)S1;
@@ -805,7 +806,7 @@ __global__ __launch_bounds__(FIN_THREADS) void fin_bwd_kernel(const fin_args fin
 int launch_fin_bwd(explainn_ctx* c, const explainn_params* p, const explainn_grads* g, int B,
                    int freeze_n, hipStream_t s) {
     const fin_args fin = {c->S12p, c->m, c->Gw, c->mug, c->sig1, p->bn1_w, g->conv_w, g->conv_b,
-                          g->bn1_w, g->bn1_b, c->K4, freeze_n, fc_ng(c->NQ), c->dsp_stride, c->dsp_count};
+                          g->bn1_w, g->bn1_b, c->K4, freeze_n, fc_ng(c->NQ), c->Um, c->dsp_stride, c->dsp_count};
     hipLaunchKernelGGL(fin_bwd_kernel, dim3(c->U), dim3(FIN_THREADS), 0, s, fin, c->Dspp, c->Bs, B);
     LAUNCH_CHECK();
     return EXPLAINN_OK;

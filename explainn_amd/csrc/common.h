@@ -23,6 +23,7 @@ __host__ inline int head_gw_chunks(int B) { int c = (B + 127) / 128; return c < 
 
 struct explainn_ctx {
     int U, k, L, T, maxB, device;
+    int Gm, Um;           // model bank: Gm members of Um units each (U = Gm*Um); Gm = 1: a single model
     int Lo, n;            // conv output length, pooled length
     int U4, Uq;           // units rounded up to 4, number of unit quads
     int NQ, NS;           // instantiated pooled-length bucket (>= n), its row stride (mult. of 4)

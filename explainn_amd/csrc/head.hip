@@ -190,15 +190,25 @@ __global__ __launch_bounds__(256) void head_fwd_train_kernel(
 }
 
 // logits[b][t] = bf[t] + sum_u Wf[t][u] * o[u][b]; one block per (64 sequences, task): its 16
-// waves each sum a slice of the units, then the slices are added in fixed order
+// waves each sum a slice of the units, then the slices are added in fixed order.
+// BANK (a model bank of G members, explainn_create_bank): blockIdx.z = member g, U its units; the
+// block reads rows [g*U, (g+1)*U) of o, Wf[g] (T,U), bf[g] and writes logits[b][g][t] -- local unit u
+// sits where unit u of a stand-alone model does, so a member's sum has the stand-alone order.
+template <bool BANK>
 __global__ __launch_bounds__(1024) void logits_kernel(const float* __restrict__ o,
                                                       const float* __restrict__ Wf,
                                                       const float* __restrict__ bf,
                                                       float* __restrict__ logits, int U, int T,
-                                                      int Bs, int B) {
+                                                      int Bs, int B, int G) {
     __shared__ float part[16][64];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int b = blockIdx.x * 64 + lane, t = blockIdx.y;
+    if (BANK) {
+        const int g = blockIdx.z;
+        o += (size_t)g * U * Bs; Wf += (size_t)g * T * U; bf += (size_t)g * T;
+        logits += (size_t)g * T;
+    }
+    const int ldl = BANK ? G * T : T;
     const float* wr = Wf + (size_t)t * U;
     float acc = 0.f;
     for (int u0 = wv; u0 < U; u0 += 160) {             // ten units (twenty loads) in flight
@@ -220,7 +230,7 @@ __global__ __launch_bounds__(1024) void logits_kernel(const float* __restrict__ 
         float s = bf[t];
 #pragma unroll
         for (int i = 0; i < 16; ++i) s += part[i][lane];
-        logits[(size_t)b * T + t] = s;
+        logits[(size_t)b * ldl + t] = s;
     }
 }
 
@@ -230,16 +240,29 @@ __global__ __launch_bounds__(1024) void logits_kernel(const float* __restrict__ 
 // (U x NBLK pairs of doubles, a few KB from L2), normalises its 64 sequences on the fly and sums the
 // combiner; the blocks of task 0 also store zhat and o for the backward, block (0, 0) the running
 // statistics.  Same grid and summation order as logits_kernel.
+// BANK: blockIdx.z = member g and U = its units, as in logits_kernel; a block rebuilds the statistics
+// of its own member's units only (LDS U x 20 B), the blocks of task 0 OF EACH MEMBER store zhat / o,
+// block (0, 0) of each member its running statistics, member 0's the shared num_batches_tracked.
+template <bool BANK>
 __global__ __launch_bounds__(1024) void logits_bn_kernel(
     const float* __restrict__ z, const double* __restrict__ z12p, int nblk, const float* __restrict__ c2, const float* __restrict__ g3, const float* __restrict__ b3,
     float* __restrict__ rm3, float* __restrict__ rv3, int64_t* nbt, float* __restrict__ zhat,
     float* __restrict__ o, float* __restrict__ sig3, const float* __restrict__ Wf,
-    const float* __restrict__ bf, float* __restrict__ logits, int U, int T, int Bs, int B) {
+    const float* __restrict__ bf, float* __restrict__ logits, int U, int T, int Bs, int B, int G) {
     extern __shared__ float4 st4[];                   // [U] {mean, 1/sigma, gamma, beta}
     __shared__ float part[16][64];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int b = blockIdx.x * 64 + lane, t = blockIdx.y;
     const bool owner = blockIdx.x == 0 && blockIdx.y == 0;
+    if (BANK) {
+        const int g = blockIdx.z;
+        const size_t u0 = (size_t)g * U;
+        z += u0 * Bs; zhat += u0 * Bs; o += u0 * Bs; z12p += u0 * nblk * 2;
+        c2 += u0; g3 += u0; b3 += u0; rm3 += u0; rv3 += u0; sig3 += u0;
+        Wf += (size_t)g * T * U; bf += (size_t)g * T; logits += (size_t)g * T;
+        if (g != 0) nbt = nullptr;
+    }
+    const int ldl = BANK ? G * T : T;
     // the first batch of z loads does not depend on the statistics: requested before them, so that
     // the kernel's two round trips overlap (the combiner weights ride in LDS beside the statistics:
     // with them in the batch too the kernel spilled at its 128 registers)
@@ -314,7 +337,7 @@ __global__ __launch_bounds__(1024) void logits_bn_kernel(
         float s = bf[t];
 #pragma unroll
         for (int i = 0; i < 16; ++i) s += part[i][lane];
-        logits[(size_t)b * T + t] = s;
+        logits[(size_t)b * ldl + t] = s;
     }
 }
 
@@ -327,13 +350,49 @@ __global__ __launch_bounds__(256) void outs_kernel(const float* __restrict__ o,
     outs[(size_t)b * U + u] = o[(size_t)u * Bs + b];
 }
 
+// The head forward of a model bank (G > 1).  Train, T <= HEAD_GEMM_MIN_T and a member's statistics
+// fit LDS: logits_bn_kernel<true>; otherwise head_fwd_train (per unit, unchanged on G*U units) and
+// logits_kernel<true> -- also for T > HEAD_GEMM_MIN_T: a bank has no GEMM form of the combiner
+// ("Model bank").
+static int launch_bank_head_fwd(explainn_ctx* c, const explainn_params* p, int B, bool train,
+                                float* logits, float* outs, hipStream_t s) {
+    const int Um = c->Um, T = c->T;
+    const dim3 grid((B + 63) / 64, T, c->Gm);
+    if (train && logits && T <= HEAD_GEMM_MIN_T && !outs && (size_t)Um * (sizeof(float4) + sizeof(float)) <= 48 * 1024) {
+        hipLaunchKernelGGL(logits_bn_kernel<true>, grid, dim3(1024),
+                           (size_t)Um * (sizeof(float4) + sizeof(float)), s, c->z, c->z12p, fc_fwd_blocks(B, c->NQ),
+                           p->fc2_b, p->bn3_w, p->bn3_b, p->bn3_rm, p->bn3_rv, p->bn3_nbt, c->zhat,
+                           c->o, c->sig3, p->final_w, p->final_b, logits, Um, T, c->Bs, B, c->Gm);
+        LAUNCH_CHECK();
+        return EXPLAINN_OK;
+    }
+    if (train) {
+        hipLaunchKernelGGL(head_fwd_train_kernel, dim3(c->U), dim3(256), 0, s, c->z, p->fc2_b,
+                           p->bn3_w, p->bn3_b, p->bn3_rm, p->bn3_rv, p->bn3_nbt, c->zhat, c->o,
+                           c->sig3, c->Bs, B);
+        LAUNCH_CHECK();
+    }
+    if (logits) {
+        hipLaunchKernelGGL(logits_kernel<true>, grid, dim3(1024), 0, s, c->o, p->final_w,
+                           p->final_b, logits, Um, T, c->Bs, B, c->Gm);
+        LAUNCH_CHECK();
+    }
+    if (outs) {
+        hipLaunchKernelGGL(outs_kernel, dim3((B * c->U + 255) / 256), dim3(256), 0, s, c->o, outs,
+                           c->U, c->Bs, B);
+        LAUNCH_CHECK();
+    }
+    return EXPLAINN_OK;
+}
+
 int launch_head_fwd(explainn_ctx* c, const explainn_params* p, int B, bool train, float* logits,
                     float* outs, hipStream_t s) {
+    if (c->Gm > 1) return launch_bank_head_fwd(c, p, B, train, logits, outs, s);
     if (train && logits && c->T <= HEAD_GEMM_MIN_T && !outs && (size_t)c->U * (sizeof(float4) + sizeof(float)) <= 48 * 1024) {
-        hipLaunchKernelGGL(logits_bn_kernel, dim3((B + 63) / 64, c->T), dim3(1024),
+        hipLaunchKernelGGL(logits_bn_kernel<false>, dim3((B + 63) / 64, c->T), dim3(1024),
                            (size_t)c->U * (sizeof(float4) + sizeof(float)), s, c->z, c->z12p, fc_fwd_blocks(B, c->NQ),
                            p->fc2_b, p->bn3_w, p->bn3_b, p->bn3_rm, p->bn3_rv, p->bn3_nbt, c->zhat,
-                           c->o, c->sig3, p->final_w, p->final_b, logits, c->U, c->T, c->Bs, B);
+                           c->o, c->sig3, p->final_w, p->final_b, logits, c->U, c->T, c->Bs, B, 1);
         LAUNCH_CHECK();
         return EXPLAINN_OK;
     }
@@ -351,8 +410,8 @@ int launch_head_fwd(explainn_ctx* c, const explainn_params* p, int B, bool train
                            (float*)nullptr);
         LAUNCH_CHECK();
     } else if (logits) {
-        hipLaunchKernelGGL(logits_kernel, dim3((B + 63) / 64, c->T), dim3(1024), 0, s, c->o,
-                           p->final_w, p->final_b, logits, c->U, c->T, c->Bs, B);
+        hipLaunchKernelGGL(logits_kernel<false>, dim3((B + 63) / 64, c->T), dim3(1024), 0, s, c->o,
+                           p->final_w, p->final_b, logits, c->U, c->T, c->Bs, B, 1);
         LAUNCH_CHECK();
     }
     if (outs) {
@@ -441,8 +500,133 @@ __global__ __launch_bounds__(1024) void loss_kernel(const float* __restrict__ lo
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Model bank (explainn_create_bank): G members of U units each share the batch and the targets;
+// logits / dlogits are (B,G,T), final_w (G,T,U), final_b (G,T), the loss is G values.  Everything in
+// front of the head runs on G*U independent units; these kernels are the head with a member index.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ double block_sum_1024(double v, double* red16) {
+    v = wave_sum_d(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red16[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double s = 0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) s += red16[i];        // fixed order
+    return s;
+}
+
+__device__ __forceinline__ void loss_term(int kind, float x, float t, float invN, float& l, float& d) {
+    if (kind == EXPLAINN_LOSS_BCE_WITH_LOGITS) {
+        l = fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
+        d = (1.0f / (1.0f + expf(-x)) - t) * invN;
+    } else {
+        const float e = x - t;
+        l = e * e;
+        d = 2.0f * e * invN;
+    }
+}
+
+// one block per member: loss[g] = mean over its own B*T terms against the shared targets, and its
+// slice of dlogits; every thread adds its terms in index order, the block sum has a fixed order
+__global__ __launch_bounds__(1024) void bank_loss_kernel(const float* __restrict__ logits,
+                                                         const float* __restrict__ y, int kind, int B,
+                                                         int T, int G, float* __restrict__ loss,
+                                                         float* __restrict__ dlogits) {
+    __shared__ double red[16];
+    const int g = blockIdx.x, N = B * T;
+    const float invN = 1.0f / (float)N;
+    double acc = 0;
+    for (int i = threadIdx.x; i < N; i += 1024) {
+        const int b = i / T, t = i - b * T;
+        const size_t il = ((size_t)b * G + g) * T + t;
+        float l, d;
+        loss_term(kind, logits[il], y[i], invN, l, d);
+        acc += (double)l;
+        dlogits[il] = d;
+    }
+    const double tot = block_sum_1024(acc, red);
+    if (threadIdx.x == 0) loss[g] = (float)(tot / (double)N);
+}
+
+// one block per unit of the bank (unit u = member g, local unit ul): d o from the member's slice of
+// dlogits and its own Wf[g], BatchNorm3's backward per unit as head_bwd_kernel does it, the member's
+// row of d Wf, and -- in the block of the member's local unit 0 -- d bf[g] and (FUSED: d loss / d
+// logits recomputed from logits and targets, no loss launch) the member's loss value.
+template <bool FUSED>
+__global__ __launch_bounds__(256) void bank_head_bwd_kernel(
+    const float* __restrict__ dl, const float* __restrict__ logits, const float* __restrict__ y,
+    int kind, float* __restrict__ loss_out, const float* __restrict__ Wf,
+    const float* __restrict__ g3, const float* __restrict__ o, const float* __restrict__ zhat,
+    const float* __restrict__ sig3, float* __restrict__ dz, float* __restrict__ gWf,
+    float* __restrict__ gbf, float* __restrict__ gg3, float* __restrict__ gb3,
+    float* __restrict__ gc2, int Um, int T, int G, int Bs, int B) {
+    __shared__ double red[4];
+    const int u = blockIdx.x, tid = threadIdx.x;
+    const int g = u / Um, ul = u - g * Um;
+    const float* ou = o + (size_t)u * Bs;
+    const float* zh = zhat + (size_t)u * Bs;
+    float* dzu = dz + (size_t)u * Bs;
+    const float* Wg = Wf + (size_t)g * T * Um + ul;      // Wf[g][t][ul] = Wg[t * Um]
+    const float invN = 1.0f / (float)(B * T);
+    const float g3u = g3[u], sig3u = sig3[u];
+    auto dlv = [&](int b, int t) -> float {
+        const size_t il = ((size_t)b * G + g) * T + t;
+        if (!FUSED) return dl[il];
+        float l, d;
+        loss_term(kind, logits[il], y[(size_t)b * T + t], invN, l, d);
+        return d;
+    };
+    double s1 = 0, s2 = 0;
+    for (int b = tid; b < B; b += 256) {
+        float dob = 0.f;
+        for (int t = 0; t < T; ++t) dob = fmaf(dlv(b, t), Wg[(size_t)t * Um], dob);
+        const float d3 = ou[b] > 0.f ? dob : 0.f;
+        dzu[b] = d3;
+        s1 += (double)d3;
+        s2 = fma((double)d3, (double)zh[b], s2);
+    }
+    const double S1 = block_sum_256(s1, red);
+    const double S2 = block_sum_256(s2, red);
+    const float m1 = (float)(S1 / (double)B), m2 = (float)(S2 / (double)B);
+    const float sc = g3u / sig3u;
+    for (int b = tid; b < B; b += 256) dzu[b] = sc * (dzu[b] - m1 - zh[b] * m2);   // (own writes only)
+    if (tid == 0) { gg3[u] = (float)S2; gb3[u] = (float)S1; gc2[u] = 0.f; }
+    for (int t = 0; t < T; ++t) {                          // T, ul are block-uniform: so are the barriers
+        double a = 0, cb = 0;
+        for (int b = tid; b < B; b += 256) {
+            const float d = dlv(b, t);
+            a = fma((double)d, (double)ou[b], a);
+            cb += (double)d;
+        }
+        const double tot = block_sum_256(a, red);
+        if (tid == 0) gWf[((size_t)g * T + t) * Um + ul] = (float)tot;
+        if (ul == 0) {
+            const double ct = block_sum_256(cb, red);
+            if (tid == 0) gbf[(size_t)g * T + t] = (float)ct;
+        }
+    }
+    if (FUSED && ul == 0) {
+        double acc = 0;
+        for (int i = tid; i < B * T; i += 256) {
+            const int b = i / T, t = i - b * T;
+            float l, d;
+            loss_term(kind, logits[((size_t)b * G + g) * T + t], y[i], invN, l, d);
+            acc += (double)l;
+        }
+        const double tot = block_sum_256(acc, red);
+        if (tid == 0) loss_out[g] = (float)(tot / (double)(B * T));
+    }
+}
+
 int launch_loss(explainn_ctx* c, int kind, const float* logits, const float* y, int B, float* loss,
                 float* dlogits, hipStream_t s) {
+    if (c->Gm > 1) {
+        hipLaunchKernelGGL(bank_loss_kernel, dim3(c->Gm), dim3(1024), 0, s, logits, y, kind, B, c->T,
+                           c->Gm, loss, dlogits);
+        LAUNCH_CHECK();
+        return EXPLAINN_OK;
+    }
     const int N = B * c->T;
     const int blocks = min(LOSS_BLOCKS, (N + 8191) / 8192);
     hipLaunchKernelGGL(loss_kernel<false>, dim3(blocks), dim3(1024), 0, s, logits, y, kind, N, loss, dlogits,
@@ -454,6 +638,8 @@ int launch_loss(explainn_ctx* c, int kind, const float* logits, const float* y, 
 // the training step's form: partial sums only; launch_head_bwd (which must follow) finishes the value
 int launch_loss_deferred(explainn_ctx* c, int kind, const float* logits, const float* y, int B, float* loss,
                          float* dlogits, hipStream_t s) {
+    // a bank's loss kernel finishes its G values itself: nothing is deferred
+    if (c->Gm > 1) return launch_loss(c, kind, logits, y, B, loss, dlogits, s);
     const int N = B * c->T;
     // (no last-arriver finish here, so nothing limits the block count: one or two elements per thread)
     const int blocks = min(256, (N + 1023) / 1024);
@@ -678,6 +864,15 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(
 
 int launch_head_bwd(explainn_ctx* c, const explainn_params* p, const explainn_grads* g,
                     const float* dlogits, int B, hipStream_t s) {
+    if (c->Gm > 1) {
+        // a bank takes the per-unit kernel at every T (no GEMM form: DESIGN.md section 8)
+        hipLaunchKernelGGL(bank_head_bwd_kernel<false>, dim3(c->U), dim3(256), 0, s, dlogits,
+                           (const float*)nullptr, (const float*)nullptr, 0, (float*)nullptr, p->final_w,
+                           p->bn3_w, c->o, c->zhat, c->sig3, c->dz, g->final_w, g->final_b, g->bn3_w,
+                           g->bn3_b, g->fc2_b, c->Um, c->T, c->Gm, c->Bs, B);
+        LAUNCH_CHECK();
+        return EXPLAINN_OK;
+    }
     if (c->T > HEAD_GEMM_MIN_T) {
         const int T = c->T, U = c->U;
         hipLaunchKernelGGL(transpose_dl_kernel, dim3((B + 31) / 32, (T + 31) / 32), dim3(256), 0, s,
@@ -720,6 +915,13 @@ int launch_head_bwd(explainn_ctx* c, const explainn_params* p, const explainn_gr
 int launch_head_bwd_fused_loss(explainn_ctx* c, const explainn_params* p, const explainn_grads* g,
                                int kind, const float* logits, const float* y, float* loss_out, int B,
                                hipStream_t s) {
+    if (c->Gm > 1) {
+        hipLaunchKernelGGL(bank_head_bwd_kernel<true>, dim3(c->U), dim3(256), 0, s, (const float*)nullptr,
+                           logits, y, kind, loss_out, p->final_w, p->bn3_w, c->o, c->zhat, c->sig3, c->dz,
+                           g->final_w, g->final_b, g->bn3_w, g->bn3_b, g->fc2_b, c->Um, c->T, c->Gm, c->Bs, B);
+        LAUNCH_CHECK();
+        return EXPLAINN_OK;
+    }
     hipLaunchKernelGGL(head_bwd_kernel<true>, dim3(c->U), dim3(256), 0, s, (const float*)nullptr,
                        logits, y, kind, loss_out, p->final_w, p->bn3_w, c->o, c->zhat, c->sig3, c->dz,
                        g->final_w, g->final_b, g->bn3_w, g->bn3_b, g->fc2_b, c->U, c->T, c->Bs, B);

@@ -69,9 +69,9 @@ class StepEngine:
         self.ctx = model._context(max_batch, self.dev)
         self.params = list(model.parameters())
         self.flat_grad, self.views, self.gs = flat_grads(self.params, self.dev, zero=True)
-        T = model._options["n_features"]
-        self.logits = torch.empty(max_batch, T, device=self.dev, dtype=torch.float32)
-        self.loss = torch.zeros(1, device=self.dev, dtype=torch.float32)
+        # a model bank (architectures.ExplaiNNBank): logits (B,G,T) and one loss per member
+        self.logits = model._logits_empty(max_batch, self.dev)
+        self.loss = torch.zeros(model._groups, device=self.dev, dtype=torch.float32)
         self.ps, self._keep = model._params_struct(self.dev)
         self.step_no = 0
 
@@ -100,7 +100,7 @@ class StepEngine:
         B = x.shape[0]
         if B > self.max_batch:
             self.max_batch = B
-            self.logits = torch.empty(B, self.logits.shape[1], device=self.dev, dtype=torch.float32)
+            self.logits = self.model._logits_empty(B, self.dev)
         self.ctx = m._context(self.max_batch, self.dev)
         if not (torch.is_tensor(x) and x.dtype == torch.float32):
             x = m._prep_input(x, self.dev)

@@ -142,3 +142,26 @@ class FusedAdam(torch.optim.Adam):
             self._sync_steps()
             self.__dict__.pop("_plans", None)
         return super().add_param_group(param_group)
+
+
+def member_state(optimizer, bank, g):
+    """The `state_dict()` of a torch.optim.Adam over member g alone, cut out of `optimizer`, an Adam
+    over `bank.parameters()` (architectures.ExplaiNNBank): member g's slices of exp_avg / exp_avg_sq
+    and the shared step count, parameter indices 0..13 in explainn_grads order -- what
+    `get_optimizer(bank.member(g).parameters()).load_state_dict` and Trainer._load_checkpoint read."""
+    sd = optimizer.state_dict()
+    names = [name for name, _ in bank.named_parameters()]
+    ids = sd["param_groups"][0]["params"]
+    if len(sd["param_groups"]) != 1 or len(ids) != len(names):
+        raise ValueError("member_state needs an optimizer with one group over bank.parameters()")
+    state = {}
+    for i, name in zip(ids, names):
+        st = sd["state"].get(i)
+        if st is None:
+            continue
+        state[i] = {key: (bank._member_view(name, v, g).detach().clone()
+                          if key in ("exp_avg", "exp_avg_sq") else
+                          (v.detach().clone() if torch.is_tensor(v) else v))
+                    for key, v in st.items()}
+    groups = [{key: (list(v) if key == "params" else v) for key, v in sd["param_groups"][0].items()}]
+    return {"state": state, "param_groups": groups}

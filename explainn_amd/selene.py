@@ -329,6 +329,185 @@ class Trainer(object):
         torch.save(state, os.path.join(self.output_dir, "best_model.pth.tar"))
 
 
+class BankRecord:
+    """Per-member bookkeeping of a bank run, kept apart from the compute: fed with the vector of G
+    validation losses of every report, it holds each member's `_min_loss` / `_best_step` exactly as
+    Trainer.validate does (strict `<`: a tie or a NaN is no improvement) and says which members'
+    files are to be written.  A member that went `patience` steps without improving is final: it
+    keeps stepping with the bank but its files are not touched again."""
+
+    def __init__(self, n_models, patience):
+        self.patience = patience
+        self.min_loss = [float("inf")] * n_models
+        self.best_step = [1] * n_models
+        self.final = [False] * n_models
+
+    def report(self, step, losses):
+        """Returns (live, improved): the members whose files still get this report's lines (those not
+        final before it) and, among them, the ones that improved (their checkpoints are due); then
+        applies the early-stopping rule of Trainer.train_and_validate member by member."""
+        live = [g for g, f in enumerate(self.final) if not f]
+        improved = []
+        for g in live:
+            loss = float(losses[g])
+            if loss < self.min_loss[g]:
+                self.min_loss[g] = loss
+                self.best_step[g] = int(step)
+                improved.append(g)
+        for g in live:
+            if step >= self.best_step[g] + self.patience:
+                self.final[g] = True
+        return live, improved
+
+    def done(self):
+        return all(self.final)
+
+
+class MemberFiles:
+    """The `init.<g>/` directories of a bank run, written from plain values: `train.txt` and
+    `validation.txt` in the column layout of metrics_logger (a header line, then one line per
+    report) and `best_model.pth.tar` with exactly the keys Trainer.validate writes."""
+
+    def __init__(self, output_dir, n_models, metric_names):
+        self.dirs = [os.path.join(output_dir, "init.%d" % g) for g in range(n_models)]
+        for d in self.dirs:
+            os.makedirs(d, exist_ok=True)
+            with open(os.path.join(d, "train.txt"), "wt") as fh:
+                fh.write("loss\n")
+            with open(os.path.join(d, "validation.txt"), "wt") as fh:
+                fh.write("\t".join(["loss"] + list(metric_names)) + "\n")
+
+    def _append(self, g, name, values):
+        with open(os.path.join(self.dirs[g], name), "at") as fh:
+            fh.write("\t".join(map(str, values)) + "\n")
+
+    def train(self, g, loss):
+        self._append(g, "train.txt", [loss])
+
+    def validation(self, g, loss, scores):
+        self._append(g, "validation.txt", [loss] + list(scores))
+
+    def checkpoint(self, g, step, options, state_dict, min_loss, optimizer_state):
+        torch.save({"step": int(step), "arch": "ExplaiNN", "options": dict(options),
+                    "state_dict": state_dict, "min_loss": min_loss, "optimizer": optimizer_state},
+                   os.path.join(self.dirs[g], "best_model.pth.tar"))
+
+
+class BankTrainer(object):
+    """Trainer for an ExplaiNNBank: every step is ONE fused step of all G members on the same batch
+    (StepEngine on the bank, one optimiser over the stacked parameters), validation is one eval pass
+    per batch for all members, and every member gets the files a Trainer run of its own would leave,
+    under `<output_dir>/init.<g>/` (MemberFiles), whenever THAT member improves.  Stops at max_steps
+    or when every member ran out of patience (BankRecord).  Members see the same batches in the same
+    order.  input_data: "binary" (BCE with logits) or anything else (MSE), as get_loss takes it."""
+
+    def __init__(self, bank, data_loaders, input_data, metrics, optimizer, max_steps=128000,
+                 patience=32000, report_stats_every_n_steps=1000, output_dir="./", cpu_n_threads=1,
+                 freeze_top_n_filters=0, logging_verbosity=2):
+        from .architectures import ExplaiNNBank
+        if not isinstance(bank, ExplaiNNBank):
+            raise TypeError("BankTrainer trains an explainn_amd.ExplaiNNBank")
+        self.model = bank
+        self.data_loaders = data_loaders
+        self.kind = "binary" if input_data == "binary" else "linear"
+        self.metrics = metrics
+        self.optimizer = optimizer
+        self.max_steps = max_steps
+        self.nth_step_report_stats = report_stats_every_n_steps
+        self.freeze_top_n_filters = freeze_top_n_filters
+        torch.set_num_threads(cpu_n_threads)
+        os.makedirs(output_dir, exist_ok=True)
+        self.output_dir = output_dir
+        self.logger = selene_logger(output_dir, logging_verbosity)
+        self.model.cuda()
+        self.record = BankRecord(bank._groups, patience)
+        self.files = MemberFiles(output_dir, bank._groups, list(metrics.keys()))
+        self._data_iterators = {k: [] for k in data_loaders}
+        self._engine = None
+        self._train_loss = []
+        self.step = 0
+
+    _get_batch = Trainer._get_batch
+
+    def train_and_validate(self):
+        for step in range(1, self.max_steps + 1):
+            self.step = step
+            self.train()
+            if step % self.nth_step_report_stats == 0:
+                self.validate()
+            if self.record.done():
+                self.logger.info("Early stopping: every member ran out of patience")
+                break
+        if self.model.validate_input and self.model.input_flags() & 1:
+            raise ValueError("input is not one-hot (see explainn_amd.ExplaiNN.forward)")
+        self.logger.handlers.clear()
+
+    def train(self):
+        if not self.model.training:
+            self.model.train()
+        inputs, targets = self._get_batch("train")
+        inputs, targets = inputs.cuda(), targets.cuda().float().contiguous()
+        if self._engine is None:
+            self._engine = StepEngine(self.model, inputs.shape[0], loss=self.kind)
+            self._engine.attach_grads()
+        if inputs.dtype != torch.uint8:
+            inputs = inputs.float()
+        _, loss = self._engine.step(inputs.contiguous(), targets,
+                                    seed=int(torch.randint(0, 2 ** 62, (1,)).item()),
+                                    freeze_top_n_filters=self.freeze_top_n_filters)
+        self.optimizer.step()
+        self._train_loss.append(loss.clone())            # (G,), read when reported
+        if self.step % self.nth_step_report_stats == 0:
+            mean = torch.stack(self._train_loss).double().mean(dim=0).tolist()
+            for g, v in enumerate(mean):
+                if not self.record.final[g]:
+                    self.files.train(g, v)
+            self.logger.info("[STEP %d] training loss per member: %s" % (self.step, mean))
+            self._train_loss = []
+
+    def member_losses(self, predictions, targets):
+        """(G,) losses of logits (B,G,T) against the shared targets (B,T): each the mean over the
+        member's own B*T terms."""
+        fn = (torch.nn.functional.binary_cross_entropy_with_logits if self.kind == "binary"
+              else torch.nn.functional.mse_loss)
+        t = targets[:, None, :].expand_as(predictions)
+        return fn(predictions, t, reduction="none").mean(dim=(0, 2))
+
+    def evaluate(self, which_data="validation"):
+        """(per-member average of the batch losses (G,), predictions (N,G,T), targets (N,T)) from one
+        eval pass per batch."""
+        self.model.eval()
+        losses, preds, tgts = [], [], []
+        with self.model.eval_cache(), torch.no_grad():
+            for inputs, targets in iter(self.data_loaders[which_data]):
+                targets = targets.cuda().float()
+                p = self.model(inputs.cuda())
+                losses.append(self.member_losses(p, targets))
+                preds.append(p.clone())
+                tgts.append(targets.clone())
+        if self.model.validate_input and self.model.input_flags() & 1:
+            raise ValueError("input is not one-hot (see explainn_amd.ExplaiNN.forward)")
+        # (float64, as Trainer's np.average of a list of floats: min_loss in the checkpoint is a numpy float64)
+        loss = np.average(torch.stack(losses).cpu().numpy().astype(np.float64), axis=0)
+        return loss, torch.cat(preds).cpu().numpy(), torch.cat(tgts).cpu().numpy()
+
+    def validate(self):
+        from .optim import member_state
+        loss, preds, tgts = self.evaluate("validation")
+        live, improved = self.record.report(self.step, loss)
+        for g in live:
+            scores = []
+            for name, fn in self.metrics.items():
+                score = fn(tgts.flatten(), preds[:, g].flatten())
+                scores.append(score if isinstance(score, float) else score[0])
+            self.files.validation(g, loss[g], scores)
+            if g in improved:
+                self.files.checkpoint(g, self.step, self.model._member_options(),
+                                      self.model.member_state_dict(g), loss[g],
+                                      member_state(self.optimizer, self.model, g))
+                self.logger.info("Updating init.%d/best_model.pth.tar (loss %s)" % (g, loss[g]))
+
+
 def _load_checkpoint_file(path):
     """Checkpoints hold tensors plus python/numpy scalars (`min_loss` is a numpy float in files the
     reference writes); allow exactly those under the safe unpickler."""

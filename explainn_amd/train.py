@@ -121,6 +121,24 @@ def _train(sequence_length, n_features, data_loaders, input_data, steps_per_epoc
     return trainer
 
 
+def _train_bank(n_models, sequence_length, n_features, data_loaders, input_data, steps_per_epoch,
+                cnn_units=100, kernel_size=19, lr=0.003, max_epochs=5, patience=10, cpu_threads=1,
+                output_dir="./"):
+    """The `--initialize` short runs as ONE bank run (selene.BankTrainer): n_models independently
+    initialised models trained on the same batches, leaving `output_dir/init.<g>/` as the
+    sequential runs do."""
+    from .architectures import ExplaiNNBank
+    from .selene import BankTrainer
+    bank = ExplaiNNBank(n_models, cnn_units, kernel_size, sequence_length, n_features)
+    trainer = BankTrainer(
+        bank, data_loaders, input_data, get_metrics(input_data=input_data),
+        get_optimizer(bank.parameters(), lr), max_steps=steps_per_epoch * max_epochs,
+        patience=steps_per_epoch * patience, report_stats_every_n_steps=steps_per_epoch,
+        output_dir=output_dir, cpu_n_threads=cpu_threads)
+    trainer.train_and_validate()
+    return trainer
+
+
 def _load_filter_weights(path):
     """train.py:183-195: a file of pre-trained filters `{id: (k,4) array}` -> (ids, [(4,k) tensors]).
     `.npz` archives are read directly; the reference's pickles go through an unpickler that only
@@ -173,7 +191,15 @@ def main(argv=None):
                     help="data-parallel runs: BatchNorm statistics of the whole batch across ranks")
     ap.add_argument("--device-metrics", action="store_true",
                     help="compute the validation metrics on the GPU instead of with scikit-learn / scipy")
+    ap.add_argument("--bank", action="store_true",
+                    help="run the --initialize short runs as ONE model bank (all initialisations in "
+                         "one fused step per batch; needs a GPU).  The members of a bank see the same "
+                         "batch order; sequential runs each draw their own shuffle")
     args = ap.parse_args(argv)
+    if args.bank and args.filter_weights:
+        ap.error("--bank cannot be combined with --filter-weights (transfer learning)")
+    if args.bank and args.sync_batchnorm:
+        ap.error("--bank cannot be combined with --sync-batchnorm")
     import pandas as pd
     start = time.time()
     os.makedirs(args.output_dir, exist_ok=True)
@@ -194,6 +220,10 @@ def main(argv=None):
         with open(os.path.join(args.output_dir, "filter-ids-from-pre-training-step.txt"), "wt") as fh:
             fh.write("\n".join(filter_ids))
     best_loss, best_model = None, None
+    if args.bank and not all(os.path.isdir(os.path.join(args.output_dir, "init.%d" % i))
+                             for i in range(args.initialize)):
+        _train_bank(args.initialize, L, T, loaders, input_data, spe, args.cnn_units, args.kernel_size,
+                    args.lr, 5, args.patience, args.cpu_threads, args.output_dir)
     for i in range(args.initialize):
         d = os.path.join(args.output_dir, "init.%d" % i)
         if not os.path.isdir(d):

@@ -85,6 +85,31 @@ typedef struct explainn_grads {
  * batches of up to max_batch sequences on HIP device `device`.  Synchronous. */
 int explainn_create(explainn_ctx** out, int cnn_units, int kernel_size, int sequence_length,
                     int n_features, int max_batch, int device);
+/* A model bank: `groups` (G) independently parameterised ExplaiNN models of cnn_units (U) units each,
+ * trained on the SAME batches and targets in one fused step -- the N initialisations of train.py's
+ * --initialize (train.py:221-255), an ensemble, a seed study.  Up to the combiner the G models are one
+ * filter bank of G*U independent units; the head has a member index.  Member g owns units
+ * [g*U, (g+1)*U).  On a bank context the entry points keep their signatures and read the arrays with
+ * the bank's shapes, member-major: every per-unit array has G*U where a single model has U (conv_w
+ * (G*U,4,k), fc1_w (100*G*U,n,1), ... keep_mask (B,100*G*U)), final_w is (G,T,U), final_b (G,T),
+ * logits / dlogits are (B,G,T), targets stay (B,T) and are shared, loss_out is G floats (each the mean
+ * over that member's own B*T terms); explainn_grads likewise.  num_batches_tracked stays one scalar
+ * per BatchNorm (all members step together).  freeze_top_n_filters = n zeroes rows [0,n) of EVERY
+ * member.  Member g's results are those of a stand-alone model with its parameters, to the rounding
+ * of the order of sums in the head.
+ * Supported on a bank: explainn_forward_eval, explainn_forward_train, explainn_backward,
+ * explainn_loss_grad, explainn_train_step, explainn_train_step_fc / _conv (the flat gradient buffer
+ * is element-wise, so a data-parallel all-reduce is unchanged), explainn_unit_outputs (B,G*U),
+ * explainn_unit_activations, the filter export (per unit), explainn_stage_codes / _stage_onehot,
+ * explainn_dense_input, explainn_input_flags, stage timing, explainn_debug_keep_bits (G*U,B,4).
+ * EXPLAINN_E_UNSUPPORTED on a bank (they fold units through `final` in kernels of their own; run them
+ * on one member's model; the context stays usable): explainn_forward_eval_keep, explainn_input_grad,
+ * explainn_backward_input, explainn_ism, explainn_sync_phase.
+ * groups == 1 is explainn_create.  More than 2000 units in all (the largest count tested): EXPLAINN_E_UNSUPPORTED. */
+int explainn_create_bank(explainn_ctx** out, int groups, int cnn_units /* per member */, int kernel_size,
+                         int sequence_length, int n_features, int max_batch, int device);
+/* number of members of the context: 1 for explainn_create */
+int explainn_groups(const explainn_ctx* ctx);
 void explainn_destroy(explainn_ctx* ctx);
 const char* explainn_last_error(void);
 /* bytes of device scratch the context holds */
