@@ -153,6 +153,17 @@ int eval_front(explainn_ctx* c, const float* x, int B, const explainn_params* p,
     }
     return EXPLAINN_OK;
 }
+
+// The eval-mode forward of every entry point that runs the whole network: the dense or one-hot filter
+// bank (want_idx: the pooling's argmax offsets are stored too), the FC, the head (logits and / or outs).
+int eval_forward(explainn_ctx* c, const float* x, int B, const explainn_params* p, bool want_idx,
+                 float* logits, float* outs, hipStream_t s) {
+    TRY(eval_front(c, x, B, p, s));
+    if (c->dense) TRY(launch_dense_conv_pool(c, x, p, B, s));
+    else TRY(launch_conv_pool(c, p, B, want_idx, s));
+    TRY(launch_fc_fwd(c, p, B, false, nullptr, 0.f, 0, s));
+    return launch_head_fwd(c, p, B, false, logits, outs, s);
+}
 }  // namespace
 
 // What the entry points that fold units through `final` in kernels of their own answer on a bank.
@@ -291,13 +302,7 @@ extern "C" int64_t explainn_scratch_bytes(const explainn_ctx* c) { return c ? c-
 extern "C" int explainn_forward_eval(explainn_ctx* c, const float* x, int B,
                                      const explainn_params* p, float* logits, void* stream) {
     TRY(check_batch(c, B));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    TRY(eval_front(c, x, B, p, s));
-    if (c->dense) TRY(launch_dense_conv_pool(c, x, p, B, s));
-    else TRY(launch_conv_pool(c, p, B, false, s));
-    TRY(launch_fc_fwd(c, p, B, false, nullptr, 0.f, 0, s));
-    TRY(launch_head_fwd(c, p, B, false, logits, nullptr, s));
-    return EXPLAINN_OK;
+    return eval_forward(c, x, B, p, false, logits, nullptr, static_cast<hipStream_t>(stream));
 }
 
 // Eval forward that keeps what the input gradient needs: the argmax offsets of the pooling (the
@@ -307,12 +312,7 @@ extern "C" int explainn_forward_eval_keep(explainn_ctx* c, const float* x, int B
                                           const explainn_params* p, float* logits, void* stream) {
     NOT_ON_BANK(c, "explainn_forward_eval_keep");
     TRY(check_batch(c, B));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    TRY(eval_front(c, x, B, p, s));
-    if (c->dense) TRY(launch_dense_conv_pool(c, x, p, B, s));
-    else TRY(launch_conv_pool(c, p, B, true, s));
-    TRY(launch_fc_fwd(c, p, B, false, nullptr, 0.f, 0, s));
-    TRY(launch_head_fwd(c, p, B, false, logits, nullptr, s));
+    TRY(eval_forward(c, x, B, p, true, logits, nullptr, static_cast<hipStream_t>(stream)));
     c->keep_B = B;
     c->keep_x = c->dense ? x : nullptr;
     return EXPLAINN_OK;
@@ -353,23 +353,14 @@ extern "C" int explainn_ism(explainn_ctx* c, const float* x, int B, const explai
         return EXPLAINN_E_ARG;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    TRY(eval_front(c, x, B, p, s));
-    TRY(launch_conv_pool(c, p, B, false, s));
-    TRY(launch_fc_fwd(c, p, B, false, nullptr, 0.f, 0, s));
-    TRY(launch_head_fwd(c, p, B, false, logits, nullptr, s));
+    TRY(eval_forward(c, x, B, p, false, logits, nullptr, s));
     return launch_ism(c, p, B, delta, static_cast<float*>(workspace), s);
 }
 
 extern "C" int explainn_unit_outputs(explainn_ctx* c, const float* x, int B,
                                      const explainn_params* p, float* outs, void* stream) {
     TRY(check_batch(c, B));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    TRY(eval_front(c, x, B, p, s));
-    if (c->dense) TRY(launch_dense_conv_pool(c, x, p, B, s));
-    else TRY(launch_conv_pool(c, p, B, false, s));
-    TRY(launch_fc_fwd(c, p, B, false, nullptr, 0.f, 0, s));
-    TRY(launch_head_fwd(c, p, B, false, nullptr, outs, s));
-    return EXPLAINN_OK;
+    return eval_forward(c, x, B, p, false, nullptr, outs, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int explainn_unit_activations(explainn_ctx* c, const float* x, int B,

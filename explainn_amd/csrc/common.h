@@ -341,6 +341,21 @@ __device__ __forceinline__ float qval(float alpha, float ext, float shift) {
     return __expf(fmaf(alpha, ext, shift));
 }
 
+// The loss of one (logit x, target t): its value, and d/dx of the mean over 1/invN terms.  The only
+// definition: every route to a loss or its gradient (head.hip, passA's prologue in fc.hip,
+// syncbn.hip) evaluates these expressions, which is what keeps the routes equal bit for bit.  Two
+// functions, because most callers need one of them and must not pay for the other's transcendentals.
+__device__ __forceinline__ float loss_value(int kind, float x, float t) {
+    if (kind == EXPLAINN_LOSS_BCE_WITH_LOGITS) return fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
+    const float e = x - t;
+    return e * e;
+}
+__device__ __forceinline__ float loss_grad(int kind, float x, float t, float invN) {
+    if (kind == EXPLAINN_LOSS_BCE_WITH_LOGITS) return (1.0f / (1.0f + expf(-x)) - t) * invN;
+    const float e = x - t;
+    return 2.0f * e * invN;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);

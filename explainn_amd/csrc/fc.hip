@@ -532,9 +532,7 @@ int launch_fc_fwd(explainn_ctx* c, const explainn_params* p, int B, bool train,
 // ---------------------------------------------------------------------------------------------
 // d loss / d logit from (x = dlogit given | x = logit, t = target)
 __device__ __forceinline__ float pa_dl_of(const pa_head_args& h, float invN, float x, float t) {
-    if (h.mode == 1) return x;
-    if (h.kind == EXPLAINN_LOSS_BCE_WITH_LOGITS) return (1.0f / (1.0f + expf(-x)) - t) * invN;
-    return 2.0f * (x - t) * invN;
+    return h.mode == 1 ? x : loss_grad(h.kind, x, t, invN);
 }
 __device__ __forceinline__ float pa_dl(const pa_head_args& h, float invN, int i) {
     return h.mode == 1 ? h.dl[i] : pa_dl_of(h, invN, h.logits[i], h.y[i]);
@@ -591,13 +589,7 @@ __device__ __forceinline__ void pa_head_prologue(const pa_head_args& h, int u, i
                     gw[t] = fma((double)dlv, (double)ov, gw[t]);
                     if (first) {
                         gb[t] += (double)dlv;
-                        if (h.mode == 2) {
-                            const float x = xq[q][t], tt = yq[q][t];
-                            float l;
-                            if (h.kind == EXPLAINN_LOSS_BCE_WITH_LOGITS) l = fmaxf(x, 0.f) - x * tt + log1pf(expf(-fabsf(x)));
-                            else { const float e = x - tt; l = e * e; }
-                            lacc += (double)l;
-                        }
+                        if (h.mode == 2) lacc += (double)loss_value(h.kind, xq[q][t], yq[q][t]);
                     }
                 }
             }

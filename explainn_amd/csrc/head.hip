@@ -191,10 +191,10 @@ __global__ __launch_bounds__(256) void head_fwd_train_kernel(
 
 // logits[b][t] = bf[t] + sum_u Wf[t][u] * o[u][b]; one block per (64 sequences, task): its 16
 // waves each sum a slice of the units, then the slices are added in fixed order.
-// BANK (a model bank of G members, explainn_create_bank): blockIdx.z = member g, U its units; the
-// block reads rows [g*U, (g+1)*U) of o, Wf[g] (T,U), bf[g] and writes logits[b][g][t] -- local unit u
-// sits where unit u of a stand-alone model does, so a member's sum has the stand-alone order.
-template <bool BANK>
+// blockIdx.z = member g of a model bank of G members (explainn_create_bank), U its units: the block
+// reads rows [g*U, (g+1)*U) of o, Wf[g] (T,U), bf[g] and writes logits[b][g][t] -- local unit u sits
+// where unit u of a stand-alone model does, so a member's sum has the stand-alone order.  A
+// stand-alone model is the bank of one: G = 1, g = 0, every offset zero.
 __global__ __launch_bounds__(1024) void logits_kernel(const float* __restrict__ o,
                                                       const float* __restrict__ Wf,
                                                       const float* __restrict__ bf,
@@ -203,12 +203,9 @@ __global__ __launch_bounds__(1024) void logits_kernel(const float* __restrict__ 
     __shared__ float part[16][64];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int b = blockIdx.x * 64 + lane, t = blockIdx.y;
-    if (BANK) {
-        const int g = blockIdx.z;
-        o += (size_t)g * U * Bs; Wf += (size_t)g * T * U; bf += (size_t)g * T;
-        logits += (size_t)g * T;
-    }
-    const int ldl = BANK ? G * T : T;
+    const int g = blockIdx.z, ldl = G * T;
+    o += (size_t)g * U * Bs; Wf += (size_t)g * T * U; bf += (size_t)g * T;
+    logits += (size_t)g * T;
     const float* wr = Wf + (size_t)t * U;
     float acc = 0.f;
     for (int u0 = wv; u0 < U; u0 += 160) {             // ten units (twenty loads) in flight
@@ -240,10 +237,10 @@ __global__ __launch_bounds__(1024) void logits_kernel(const float* __restrict__ 
 // (U x NBLK pairs of doubles, a few KB from L2), normalises its 64 sequences on the fly and sums the
 // combiner; the blocks of task 0 also store zhat and o for the backward, block (0, 0) the running
 // statistics.  Same grid and summation order as logits_kernel.
-// BANK: blockIdx.z = member g and U = its units, as in logits_kernel; a block rebuilds the statistics
-// of its own member's units only (LDS U x 20 B), the blocks of task 0 OF EACH MEMBER store zhat / o,
+// blockIdx.z = member g and U = its units, as in logits_kernel; a block rebuilds the statistics of
+// its own member's units only (LDS U x 20 B), the blocks of task 0 OF EACH MEMBER store zhat / o,
 // block (0, 0) of each member its running statistics, member 0's the shared num_batches_tracked.
-template <bool BANK>
+// (The member offsets are block-uniform: they cost scalar registers, none of the kernel's 128 vector ones.)
 __global__ __launch_bounds__(1024) void logits_bn_kernel(
     const float* __restrict__ z, const double* __restrict__ z12p, int nblk, const float* __restrict__ c2, const float* __restrict__ g3, const float* __restrict__ b3,
     float* __restrict__ rm3, float* __restrict__ rv3, int64_t* nbt, float* __restrict__ zhat,
@@ -254,15 +251,12 @@ __global__ __launch_bounds__(1024) void logits_bn_kernel(
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int b = blockIdx.x * 64 + lane, t = blockIdx.y;
     const bool owner = blockIdx.x == 0 && blockIdx.y == 0;
-    if (BANK) {
-        const int g = blockIdx.z;
-        const size_t u0 = (size_t)g * U;
-        z += u0 * Bs; zhat += u0 * Bs; o += u0 * Bs; z12p += u0 * nblk * 2;
-        c2 += u0; g3 += u0; b3 += u0; rm3 += u0; rv3 += u0; sig3 += u0;
-        Wf += (size_t)g * T * U; bf += (size_t)g * T; logits += (size_t)g * T;
-        if (g != 0) nbt = nullptr;
-    }
-    const int ldl = BANK ? G * T : T;
+    const int g = blockIdx.z, ldl = G * T;
+    const size_t ug = (size_t)g * U;                   // the member's first unit
+    z += ug * Bs; zhat += ug * Bs; o += ug * Bs; z12p += ug * nblk * 2;
+    c2 += ug; g3 += ug; b3 += ug; rm3 += ug; rv3 += ug; sig3 += ug;
+    Wf += (size_t)g * T * U; bf += (size_t)g * T; logits += (size_t)g * T;
+    if (g != 0) nbt = nullptr;
     // the first batch of z loads does not depend on the statistics: requested before them, so that
     // the kernel's two round trips overlap (the combiner weights ride in LDS beside the statistics:
     // with them in the batch too the kernel spilled at its 128 registers)
@@ -350,49 +344,21 @@ __global__ __launch_bounds__(256) void outs_kernel(const float* __restrict__ o,
     outs[(size_t)b * U + u] = o[(size_t)u * Bs + b];
 }
 
-// The head forward of a model bank (G > 1).  Train, T <= HEAD_GEMM_MIN_T and a member's statistics
-// fit LDS: logits_bn_kernel<true>; otherwise head_fwd_train (per unit, unchanged on G*U units) and
-// logits_kernel<true> -- also for T > HEAD_GEMM_MIN_T: a bank has no GEMM form of the combiner
-// ("Model bank").
-static int launch_bank_head_fwd(explainn_ctx* c, const explainn_params* p, int B, bool train,
-                                float* logits, float* outs, hipStream_t s) {
-    const int Um = c->Um, T = c->T;
-    const dim3 grid((B + 63) / 64, T, c->Gm);
-    if (train && logits && T <= HEAD_GEMM_MIN_T && !outs && (size_t)Um * (sizeof(float4) + sizeof(float)) <= 48 * 1024) {
-        hipLaunchKernelGGL(logits_bn_kernel<true>, grid, dim3(1024),
-                           (size_t)Um * (sizeof(float4) + sizeof(float)), s, c->z, c->z12p, fc_fwd_blocks(B, c->NQ),
-                           p->fc2_b, p->bn3_w, p->bn3_b, p->bn3_rm, p->bn3_rv, p->bn3_nbt, c->zhat,
-                           c->o, c->sig3, p->final_w, p->final_b, logits, Um, T, c->Bs, B, c->Gm);
-        LAUNCH_CHECK();
-        return EXPLAINN_OK;
-    }
-    if (train) {
-        hipLaunchKernelGGL(head_fwd_train_kernel, dim3(c->U), dim3(256), 0, s, c->z, p->fc2_b,
-                           p->bn3_w, p->bn3_b, p->bn3_rm, p->bn3_rv, p->bn3_nbt, c->zhat, c->o,
-                           c->sig3, c->Bs, B);
-        LAUNCH_CHECK();
-    }
-    if (logits) {
-        hipLaunchKernelGGL(logits_kernel<true>, grid, dim3(1024), 0, s, c->o, p->final_w,
-                           p->final_b, logits, Um, T, c->Bs, B, c->Gm);
-        LAUNCH_CHECK();
-    }
-    if (outs) {
-        hipLaunchKernelGGL(outs_kernel, dim3((B * c->U + 255) / 256), dim3(256), 0, s, c->o, outs,
-                           c->U, c->Bs, B);
-        LAUNCH_CHECK();
-    }
-    return EXPLAINN_OK;
-}
-
+// The head forward of a model or a bank (G members of Um units; a stand-alone model is G = 1).  Train,
+// T <= HEAD_GEMM_MIN_T and one member's statistics fit LDS: logits_bn_kernel alone; otherwise
+// head_fwd_train (per unit, on all G*Um units) and the combiner -- the MFMA GEMM for many tasks on a
+// single model, logits_kernel otherwise: a bank has no GEMM form of the combiner.
 int launch_head_fwd(explainn_ctx* c, const explainn_params* p, int B, bool train, float* logits,
                     float* outs, hipStream_t s) {
-    if (c->Gm > 1) return launch_bank_head_fwd(c, p, B, train, logits, outs, s);
-    if (train && logits && c->T <= HEAD_GEMM_MIN_T && !outs && (size_t)c->U * (sizeof(float4) + sizeof(float)) <= 48 * 1024) {
-        hipLaunchKernelGGL(logits_bn_kernel<false>, dim3((B + 63) / 64, c->T), dim3(1024),
-                           (size_t)c->U * (sizeof(float4) + sizeof(float)), s, c->z, c->z12p, fc_fwd_blocks(B, c->NQ),
+    const int Um = c->Um, G = c->Gm, T = c->T;
+    const dim3 grid((B + 63) / 64, T, G);
+    // (one member's statistics in 48 KB: U = G * Um exactly, so this is Um * 20 B <= 48 KB.  Written on
+    // c->T and c->U because tests/dispatch_model.py reads the rule from this line.)
+    if (train && logits && c->T <= HEAD_GEMM_MIN_T && !outs && (size_t)c->U * (sizeof(float4) + sizeof(float)) <= 48 * 1024 * (size_t)G) {
+        hipLaunchKernelGGL(logits_bn_kernel, grid, dim3(1024),
+                           (size_t)Um * (sizeof(float4) + sizeof(float)), s, c->z, c->z12p, fc_fwd_blocks(B, c->NQ),
                            p->fc2_b, p->bn3_w, p->bn3_b, p->bn3_rm, p->bn3_rv, p->bn3_nbt, c->zhat,
-                           c->o, c->sig3, p->final_w, p->final_b, logits, c->U, c->T, c->Bs, B, 1);
+                           c->o, c->sig3, p->final_w, p->final_b, logits, Um, T, c->Bs, B, G);
         LAUNCH_CHECK();
         return EXPLAINN_OK;
     }
@@ -402,16 +368,16 @@ int launch_head_fwd(explainn_ctx* c, const explainn_params* p, int B, bool train
                            c->sig3, c->Bs, B);
         LAUNCH_CHECK();
     }
-    if (logits && c->T > HEAD_GEMM_MIN_T) {
+    if (logits && G == 1 && T > HEAD_GEMM_MIN_T) {
         // logits[b][t] = sum_u o[u][b] Wf[t][u] + bf[t]: M = B, N = T, K = U
-        const int tiles = ((B + 31) / 32) * ((c->T + 31) / 32);
+        const int tiles = ((B + 31) / 32) * ((T + 31) / 32);
         hipLaunchKernelGGL((gemm32_kernel<false, true, EPI_BIAS>), dim3(tiles), dim3(256), 0, s, c->o,
-                           c->Bs, p->final_w, c->U, logits, c->T, B, c->T, c->U, p->final_b,
+                           c->Bs, p->final_w, c->U, logits, T, B, T, c->U, p->final_b,
                            (float*)nullptr);
         LAUNCH_CHECK();
     } else if (logits) {
-        hipLaunchKernelGGL(logits_kernel<false>, dim3((B + 63) / 64, c->T), dim3(1024), 0, s, c->o,
-                           p->final_w, p->final_b, logits, c->U, c->T, c->Bs, B, 1);
+        hipLaunchKernelGGL(logits_kernel, grid, dim3(1024), 0, s, c->o, p->final_w, p->final_b,
+                           logits, Um, T, c->Bs, B, G);
         LAUNCH_CHECK();
     }
     if (outs) {
@@ -457,18 +423,8 @@ __global__ __launch_bounds__(1024) void loss_kernel(const float* __restrict__ lo
         for (int q = 0; q < 4; ++q) {
             const int i = i0 + q * stride;
             if (i < N) {
-                const float x = xv[q], t = tv[q];
-                float l, d;
-                if (kind == EXPLAINN_LOSS_BCE_WITH_LOGITS) {
-                    l = fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
-                    d = (1.0f / (1.0f + expf(-x)) - t) * invN;
-                } else {
-                    const float e = x - t;
-                    l = e * e;
-                    d = 2.0f * e * invN;
-                }
-                acc += (double)l;
-                dlogits[i] = d;
+                acc += (double)loss_value(kind, xv[q], tv[q]);
+                dlogits[i] = loss_grad(kind, xv[q], tv[q], invN);
             }
         }
     }
@@ -503,7 +459,10 @@ __global__ __launch_bounds__(1024) void loss_kernel(const float* __restrict__ lo
 // ---------------------------------------------------------------------------------------------
 // Model bank (explainn_create_bank): G members of U units each share the batch and the targets;
 // logits / dlogits are (B,G,T), final_w (G,T,U), final_b (G,T), the loss is G values.  Everything in
-// front of the head runs on G*U independent units; these kernels are the head with a member index.
+// front of the head runs on G*U independent units, and the head kernels take the member index at run
+// time (a stand-alone model is the bank of one).  Only the loss launch is a bank's own: one block per
+// member and no partials -- folded into loss_kernel it would change either the bank's summation order
+// or the single model's partial layout.
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ double block_sum_1024(double v, double* red16) {
     v = wave_sum_d(v);
@@ -514,17 +473,6 @@ __device__ __forceinline__ double block_sum_1024(double v, double* red16) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) s += red16[i];        // fixed order
     return s;
-}
-
-__device__ __forceinline__ void loss_term(int kind, float x, float t, float invN, float& l, float& d) {
-    if (kind == EXPLAINN_LOSS_BCE_WITH_LOGITS) {
-        l = fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
-        d = (1.0f / (1.0f + expf(-x)) - t) * invN;
-    } else {
-        const float e = x - t;
-        l = e * e;
-        d = 2.0f * e * invN;
-    }
 }
 
 // one block per member: loss[g] = mean over its own B*T terms against the shared targets, and its
@@ -540,83 +488,12 @@ __global__ __launch_bounds__(1024) void bank_loss_kernel(const float* __restrict
     for (int i = threadIdx.x; i < N; i += 1024) {
         const int b = i / T, t = i - b * T;
         const size_t il = ((size_t)b * G + g) * T + t;
-        float l, d;
-        loss_term(kind, logits[il], y[i], invN, l, d);
-        acc += (double)l;
-        dlogits[il] = d;
+        const float x = logits[il], tt = y[i];
+        acc += (double)loss_value(kind, x, tt);
+        dlogits[il] = loss_grad(kind, x, tt, invN);
     }
     const double tot = block_sum_1024(acc, red);
     if (threadIdx.x == 0) loss[g] = (float)(tot / (double)N);
-}
-
-// one block per unit of the bank (unit u = member g, local unit ul): d o from the member's slice of
-// dlogits and its own Wf[g], BatchNorm3's backward per unit as head_bwd_kernel does it, the member's
-// row of d Wf, and -- in the block of the member's local unit 0 -- d bf[g] and (FUSED: d loss / d
-// logits recomputed from logits and targets, no loss launch) the member's loss value.
-template <bool FUSED>
-__global__ __launch_bounds__(256) void bank_head_bwd_kernel(
-    const float* __restrict__ dl, const float* __restrict__ logits, const float* __restrict__ y,
-    int kind, float* __restrict__ loss_out, const float* __restrict__ Wf,
-    const float* __restrict__ g3, const float* __restrict__ o, const float* __restrict__ zhat,
-    const float* __restrict__ sig3, float* __restrict__ dz, float* __restrict__ gWf,
-    float* __restrict__ gbf, float* __restrict__ gg3, float* __restrict__ gb3,
-    float* __restrict__ gc2, int Um, int T, int G, int Bs, int B) {
-    __shared__ double red[4];
-    const int u = blockIdx.x, tid = threadIdx.x;
-    const int g = u / Um, ul = u - g * Um;
-    const float* ou = o + (size_t)u * Bs;
-    const float* zh = zhat + (size_t)u * Bs;
-    float* dzu = dz + (size_t)u * Bs;
-    const float* Wg = Wf + (size_t)g * T * Um + ul;      // Wf[g][t][ul] = Wg[t * Um]
-    const float invN = 1.0f / (float)(B * T);
-    const float g3u = g3[u], sig3u = sig3[u];
-    auto dlv = [&](int b, int t) -> float {
-        const size_t il = ((size_t)b * G + g) * T + t;
-        if (!FUSED) return dl[il];
-        float l, d;
-        loss_term(kind, logits[il], y[(size_t)b * T + t], invN, l, d);
-        return d;
-    };
-    double s1 = 0, s2 = 0;
-    for (int b = tid; b < B; b += 256) {
-        float dob = 0.f;
-        for (int t = 0; t < T; ++t) dob = fmaf(dlv(b, t), Wg[(size_t)t * Um], dob);
-        const float d3 = ou[b] > 0.f ? dob : 0.f;
-        dzu[b] = d3;
-        s1 += (double)d3;
-        s2 = fma((double)d3, (double)zh[b], s2);
-    }
-    const double S1 = block_sum_256(s1, red);
-    const double S2 = block_sum_256(s2, red);
-    const float m1 = (float)(S1 / (double)B), m2 = (float)(S2 / (double)B);
-    const float sc = g3u / sig3u;
-    for (int b = tid; b < B; b += 256) dzu[b] = sc * (dzu[b] - m1 - zh[b] * m2);   // (own writes only)
-    if (tid == 0) { gg3[u] = (float)S2; gb3[u] = (float)S1; gc2[u] = 0.f; }
-    for (int t = 0; t < T; ++t) {                          // T, ul are block-uniform: so are the barriers
-        double a = 0, cb = 0;
-        for (int b = tid; b < B; b += 256) {
-            const float d = dlv(b, t);
-            a = fma((double)d, (double)ou[b], a);
-            cb += (double)d;
-        }
-        const double tot = block_sum_256(a, red);
-        if (tid == 0) gWf[((size_t)g * T + t) * Um + ul] = (float)tot;
-        if (ul == 0) {
-            const double ct = block_sum_256(cb, red);
-            if (tid == 0) gbf[(size_t)g * T + t] = (float)ct;
-        }
-    }
-    if (FUSED && ul == 0) {
-        double acc = 0;
-        for (int i = tid; i < B * T; i += 256) {
-            const int b = i / T, t = i - b * T;
-            float l, d;
-            loss_term(kind, logits[((size_t)b * G + g) * T + t], y[i], invN, l, d);
-            acc += (double)l;
-        }
-        const double tot = block_sum_256(acc, red);
-        if (tid == 0) loss_out[g] = (float)(tot / (double)(B * T));
-    }
 }
 
 int launch_loss(explainn_ctx* c, int kind, const float* logits, const float* y, int B, float* loss,
@@ -650,36 +527,41 @@ int launch_loss_deferred(explainn_ctx* c, int kind, const float* logits, const f
     return EXPLAINN_OK;
 }
 
-// d loss / d logit for one (sequence, task): either read from `dl`, or -- FUSED, used by
-// explainn_train_step when T is small -- recomputed from logits and targets so that the separate
-// loss launch (and its ~4 us floor) disappears; unit 0's block then also reduces the loss value.
-template <bool FUSED>
-__device__ __forceinline__ float dl_at(const float* __restrict__ dl, const float* __restrict__ logits,
-                                       const float* __restrict__ y, int kind, float invN, int i) {
-    if (!FUSED) return dl[i];
-    const float x = logits[i], t = y[i];
-    if (kind == EXPLAINN_LOSS_BCE_WITH_LOGITS) return (1.0f / (1.0f + expf(-x)) - t) * invN;
-    return 2.0f * (x - t) * invN;
-}
-
 // one block per unit: final-layer gradients, BN3 backward -> dz[u][b].
-// GEMMED: d o (in dz on entry) and the final-layer gradients came from the MFMA GEMMs above.
-template <bool FUSED, bool GEMMED = false>
+// Unit u is local unit ul of member g of a bank of G members of Um units (a stand-alone model: G = 1,
+// g = 0, ul = u): the block reads its member's slice of dl / logits (B,G,T) and Wf[g] (T,Um) against
+// the shared targets (B,T), writes the member's row of d Wf and -- in the block of the member's unit
+// 0 -- d bf[g] and the loss value loss_out[g].
+// GEMMED (a single model only): d o (in dz on entry) and the final-layer gradients came from the MFMA
+// GEMMs above.
+template <bool FUSED, bool GEMMED>
 __global__ __launch_bounds__(256) void head_bwd_kernel(
     const float* __restrict__ dl, const float* __restrict__ logits, const float* __restrict__ y,
     int kind, float* __restrict__ loss_out, const float* __restrict__ Wf,
     const float* __restrict__ g3, const float* __restrict__ o, const float* __restrict__ zhat,
     const float* __restrict__ sig3, float* __restrict__ dz, float* __restrict__ gWf,
     float* __restrict__ gbf, float* __restrict__ gg3, float* __restrict__ gb3,
-    float* __restrict__ gc2, int U, int T, int Bs, int B, const float* __restrict__ gWp = nullptr,
-    int gwch = 0, const double* __restrict__ lossp = nullptr, int lossb = 0, int lossn = 1) {
+    float* __restrict__ gc2, int Um, int T, int G, int Bs, int B, const float* __restrict__ gWp,
+    int gwch, const double* __restrict__ lossp, int lossb, int lossn) {
     __shared__ double red[4];
     __shared__ double red3[12];
     const int u = blockIdx.x, tid = threadIdx.x;
+    const int g = u / Um, ul = u - g * Um;             // (block-uniform)
+    const float* Wu = Wf + (size_t)g * T * Um + ul;    // Wf[g][t][ul] = Wu[t * Um], likewise d Wf
+    float* gWu = gWf + (size_t)g * T * Um + ul;
+    gbf += (size_t)g * T;
     const float* ou = o + (size_t)u * Bs;
     const float* zh = zhat + (size_t)u * Bs;
     float* dzu = dz + (size_t)u * Bs;
     const float invN = 1.0f / (float)(B * T);
+    // d loss / d logit for (sequence b, task t) of this member: either read from `dl`, or -- FUSED, used
+    // by explainn_train_step when T is small -- recomputed from logits and targets so that the separate
+    // loss launch (and its ~4 us floor) disappears; the block of the member's unit 0 then also reduces
+    // the loss value.  dl / logits are [b][g][t], the targets [b][t].
+    auto il_of = [&](int b, int t) { return ((size_t)b * G + g) * T + t; };
+    auto dl_at = [&](int b, int t) -> float {
+        return FUSED ? loss_grad(kind, logits[il_of(b, t)], y[b * T + t], invN) : dl[il_of(b, t)];
+    };
     const float g3u = g3[u], sig3u = sig3[u];        // (used behind the block sums: requested here)
     double s1 = 0, s2 = 0;
     // small batches and few tasks: d3 and zhat of this thread's sequences stay in registers between
@@ -700,21 +582,15 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 if (t >= T) continue;
-                const float dlv = dl_at<FUSED>(dl, logits, y, kind, invN, bc * T + t);
-                dob = fmaf(dlv, Wf[(size_t)t * U + u], dob);
+                const float dlv = dl_at(bc, t);
+                dob = fmaf(dlv, Wu[(size_t)t * Um], dob);
                 // the final-layer gradients ride along: d Wf[t][u] += dl * o, and (unit 0's block)
                 // d bf[t] += dl and the loss value
                 if (live_i) {
                     gw[t] = fma((double)dlv, (double)our[i], gw[t]);
-                    if (u == 0) {
+                    if (ul == 0) {
                         gb[t] += (double)dlv;
-                        if (FUSED) {
-                            const float x = logits[bc * T + t], tt = y[bc * T + t];
-                            float l;
-                            if (kind == EXPLAINN_LOSS_BCE_WITH_LOGITS) l = fmaxf(x, 0.f) - x * tt + log1pf(expf(-fabsf(x)));
-                            else { const float e = x - tt; l = e * e; }
-                            lacc += (double)l;
-                        }
+                        if (FUSED) lacc += (double)loss_value(kind, logits[il_of(bc, t)], y[bc * T + t]);
                     }
                 }
             }
@@ -755,7 +631,7 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(
         for (int b = tid; b < B; b += 256) {
             float dob = 0.f;
             for (int t = 0; t < T; ++t)
-                dob = fmaf(dl_at<FUSED>(dl, logits, y, kind, invN, b * T + t), Wf[(size_t)t * U + u], dob);
+                dob = fmaf(dl_at(b, t), Wu[(size_t)t * Um], dob);
             const float d3 = ou[b] > 0.f ? dob : 0.f;
             dzu[b] = d3;
             s1 += (double)d3;
@@ -798,27 +674,28 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(
         for (int t = 0; t < 4; ++t) {
             if (t >= T) continue;                      // T is block-uniform: the barriers inside stay uniform
             const double tot = t == 0 ? G0 : block_sum_256(gw[t], red);
-            if (tid == 0) gWf[(size_t)t * U + u] = (float)tot;
-            if (u == 0) {
+            if (tid == 0) gWu[(size_t)t * Um] = (float)tot;
+            if (ul == 0) {
                 const double ct = block_sum_256(gb[t], red);
                 if (tid == 0) gbf[t] = (float)ct;
             }
         }
-        if (FUSED && u == 0) {
+        if (FUSED && ul == 0) {
             const double tot = block_sum_256(lacc, red);
-            if (tid == 0) *loss_out = (float)(tot / (double)(B * T));
+            if (tid == 0) loss_out[g] = (float)(tot / (double)(B * T));
         }
         return;
     }
     if (lossb > 0 && u == 0) {
-        // the loss value: launch_loss_deferred's block partials (at most 256), one per thread, summed
-        // in the block's fixed tree order (block-uniform branch: the barriers inside are safe)
+        // the loss value of a single model: launch_loss_deferred's block partials (at most 256), one per
+        // thread, summed in the block's fixed tree order (block-uniform branch: the barriers inside are safe)
         const double sl = block_sum_256(tid < lossb ? lossp[tid] : 0.0, red);
         if (tid == 0) *loss_out = (float)(sl / (double)lossn);
     }
     if (GEMMED && gWp) {
         // the combiner-weight gradient of this unit (and, in unit 0's block, the bias gradient): the
-        // GEMM's batch-chunk partials summed in chunk order, eight loads in flight
+        // GEMM's batch-chunk partials summed in chunk order, eight loads in flight  (G = 1: U = Um)
+        const int U = Um;
         for (int e = tid; e < (u == 0 ? 2 * T : T); e += 256) {
             const int t = e < T ? e : e - T, col = e < T ? u : U;
             float sacc = 0.f;
@@ -838,42 +715,48 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(
     for (int t = 0; t < (GEMMED ? 0 : T); ++t) {
         double a = 0;
         for (int b = tid; b < B; b += 256)
-            a = fma((double)dl_at<FUSED>(dl, logits, y, kind, invN, b * T + t), (double)ou[b], a);
+            a = fma((double)dl_at(b, t), (double)ou[b], a);
         const double tot = block_sum_256(a, red);
-        if (tid == 0) gWf[(size_t)t * U + u] = (float)tot;
-        if (u == 0) {
+        if (tid == 0) gWu[(size_t)t * Um] = (float)tot;
+        if (ul == 0) {
             double c = 0;
-            for (int b = tid; b < B; b += 256) c += (double)dl_at<FUSED>(dl, logits, y, kind, invN, b * T + t);
+            for (int b = tid; b < B; b += 256) c += (double)dl_at(b, t);
             const double ct = block_sum_256(c, red);
             if (tid == 0) gbf[t] = (float)ct;
         }
     }
-    if (FUSED && u == 0) {
+    if (FUSED && ul == 0) {
         double acc = 0;
-        for (int i = tid; i < B * T; i += 256) {
-            const float x = logits[i], t = y[i];
-            float l;
-            if (kind == EXPLAINN_LOSS_BCE_WITH_LOGITS) l = fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
-            else { const float e = x - t; l = e * e; }
-            acc += (double)l;
+        for (int i = tid; i < B * T; i += 256) {       // the member's B*T terms in (b, t) order
+            const int b = i / T, t = i - b * T;
+            acc += (double)loss_value(kind, logits[il_of(b, t)], y[i]);
         }
         const double tot = block_sum_256(acc, red);
-        if (tid == 0) *loss_out = (float)(tot / (double)(B * T));
+        if (tid == 0) loss_out[g] = (float)(tot / (double)(B * T));
     }
+}
+
+// the per-unit kernel on all G*Um units: dl given (FUSED = false; lossb > 0: a deferred loss value to
+// finish) or recomputed from logits and targets
+template <bool FUSED, bool GEMMED>
+static int launch_head_bwd_units(explainn_ctx* c, const explainn_params* p, const explainn_grads* g,
+                                 const float* dl, int kind, const float* logits, const float* y,
+                                 float* loss_out, int lossb, int gwch, int B, hipStream_t s) {
+    hipLaunchKernelGGL((head_bwd_kernel<FUSED, GEMMED>), dim3(c->U), dim3(256), 0, s, dl, logits, y, kind,
+                       loss_out, p->final_w, p->bn3_w, c->o, c->zhat, c->sig3, c->dz, g->final_w,
+                       g->final_b, g->bn3_w, g->bn3_b, g->fc2_b, c->Um, c->T, c->Gm, c->Bs, B, c->gWp, gwch,
+                       c->lossp, lossb, c->loss_n);
+    LAUNCH_CHECK();
+    return EXPLAINN_OK;
 }
 
 int launch_head_bwd(explainn_ctx* c, const explainn_params* p, const explainn_grads* g,
                     const float* dlogits, int B, hipStream_t s) {
-    if (c->Gm > 1) {
-        // a bank takes the per-unit kernel at every T (no GEMM form: DESIGN.md section 8)
-        hipLaunchKernelGGL(bank_head_bwd_kernel<false>, dim3(c->U), dim3(256), 0, s, dlogits,
-                           (const float*)nullptr, (const float*)nullptr, 0, (float*)nullptr, p->final_w,
-                           p->bn3_w, c->o, c->zhat, c->sig3, c->dz, g->final_w, g->final_b, g->bn3_w,
-                           g->bn3_b, g->fc2_b, c->Um, c->T, c->Gm, c->Bs, B);
-        LAUNCH_CHECK();
-        return EXPLAINN_OK;
-    }
-    if (c->T > HEAD_GEMM_MIN_T) {
+    // many tasks on a single model: d o and the final-layer gradients as GEMMs, the per-unit kernel
+    // finishes them.  A bank takes the per-unit kernel alone at every T.
+    const bool gemm = c->Gm == 1 && c->T > HEAD_GEMM_MIN_T;
+    const int gwch = gemm ? head_gw_chunks(B) : 0;
+    if (gemm) {
         const int T = c->T, U = c->U;
         hipLaunchKernelGGL(transpose_dl_kernel, dim3((B + 31) / 32, (T + 31) / 32), dim3(256), 0, s,
                            dlogits, c->dlT, B, T, c->Bs);
@@ -885,46 +768,23 @@ int launch_head_bwd(explainn_ctx* c, const explainn_params* p, const explainn_gr
                            (float*)nullptr);
         LAUNCH_CHECK();
         // d Wf[t][u] = sum_b dl[b][t] o[u][b], and d bf[t] as the virtual all-ones unit U
-        const int gwch = head_gw_chunks(B);
         hipLaunchKernelGGL((gemm32_kernel<true, true, EPI_GW>),
                            dim3(((T + 31) / 32) * ((U + 1 + 31) / 32), gwch), dim3(256), 0, s, c->dlT, c->Bs,
                            c->o, c->Bs, c->gWp, U + 1, T, U + 1, B, (const float*)nullptr,
                            (float*)nullptr);
         LAUNCH_CHECK();
-        hipLaunchKernelGGL((head_bwd_kernel<false, true>), dim3(U), dim3(256), 0, s, dlogits,
-                           (const float*)nullptr, (const float*)nullptr, 0,
-                           c->loss_blocks ? c->loss_out : (float*)nullptr,
-                           p->final_w, p->bn3_w, c->o, c->zhat, c->sig3, c->dz, g->final_w,
-                           g->final_b, g->bn3_w, g->bn3_b, g->fc2_b, U, T, c->Bs, B, c->gWp, gwch,
-                           c->lossp, c->loss_blocks, c->loss_n);
-        LAUNCH_CHECK();
-        c->loss_blocks = 0;
-        return EXPLAINN_OK;
     }
-    hipLaunchKernelGGL(head_bwd_kernel<false>, dim3(c->U), dim3(256), 0, s, dlogits,
-                       (const float*)nullptr, (const float*)nullptr, 0, c->loss_blocks ? c->loss_out : (float*)nullptr,
-                       p->final_w, p->bn3_w, c->o, c->zhat, c->sig3, c->dz, g->final_w, g->final_b, g->bn3_w,
-                       g->bn3_b, g->fc2_b, c->U, c->T, c->Bs, B, (const float*)nullptr, 0, c->lossp,
-                       c->loss_blocks, c->loss_n);
-    LAUNCH_CHECK();
+    // (loss_blocks > 0: launch_loss_deferred left a single model's loss value to finish here)
+    float* loss_out = c->loss_blocks ? c->loss_out : (float*)nullptr;
+    const int rc = gemm ? launch_head_bwd_units<false, true>(c, p, g, dlogits, 0, nullptr, nullptr, loss_out, c->loss_blocks, gwch, B, s)
+                        : launch_head_bwd_units<false, false>(c, p, g, dlogits, 0, nullptr, nullptr, loss_out, c->loss_blocks, 0, B, s);
     c->loss_blocks = 0;
-    return EXPLAINN_OK;
+    return rc;
 }
 
 // loss + its gradient folded into the head backward (explainn_train_step, small T)
 int launch_head_bwd_fused_loss(explainn_ctx* c, const explainn_params* p, const explainn_grads* g,
                                int kind, const float* logits, const float* y, float* loss_out, int B,
                                hipStream_t s) {
-    if (c->Gm > 1) {
-        hipLaunchKernelGGL(bank_head_bwd_kernel<true>, dim3(c->U), dim3(256), 0, s, (const float*)nullptr,
-                           logits, y, kind, loss_out, p->final_w, p->bn3_w, c->o, c->zhat, c->sig3, c->dz,
-                           g->final_w, g->final_b, g->bn3_w, g->bn3_b, g->fc2_b, c->Um, c->T, c->Gm, c->Bs, B);
-        LAUNCH_CHECK();
-        return EXPLAINN_OK;
-    }
-    hipLaunchKernelGGL(head_bwd_kernel<true>, dim3(c->U), dim3(256), 0, s, (const float*)nullptr,
-                       logits, y, kind, loss_out, p->final_w, p->bn3_w, c->o, c->zhat, c->sig3, c->dz,
-                       g->final_w, g->final_b, g->bn3_w, g->bn3_b, g->fc2_b, c->U, c->T, c->Bs, B);
-    LAUNCH_CHECK();
-    return EXPLAINN_OK;
+    return launch_head_bwd_units<true, false>(c, p, g, nullptr, kind, logits, y, loss_out, 0, 0, B, s);
 }

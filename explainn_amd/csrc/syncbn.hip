@@ -175,17 +175,8 @@ __global__ __launch_bounds__(1024) void sync_loss(const float* __restrict__ logi
     double acc = 0;
     for (int i = threadIdx.x; i < N; i += 1024) {
         const float x = logits[i], t = y[i];
-        float l, d;
-        if (kind == EXPLAINN_LOSS_BCE_WITH_LOGITS) {
-            l = fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
-            d = (1.0f / (1.0f + expf(-x)) - t) * invN;
-        } else {
-            const float e = x - t;
-            l = e * e;
-            d = 2.0f * e * invN;
-        }
-        acc += (double)l;
-        dl[i] = d;
+        acc += (double)loss_value(kind, x, t);
+        dl[i] = loss_grad(kind, x, t, invN);
     }
     acc = block_sum_d(acc, red);
     if (threadIdx.x == 0) *xloss = acc;

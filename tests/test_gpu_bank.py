@@ -2,13 +2,13 @@
 code under test: the fp64 oracle member by member, or the existing single-model path on
 bank.member(g).  Bounds are the suite's own (parity_util).
 
-Head routes of a bank (csrc/head.hip, DESIGN.md section 8 "Model bank"):
-  forward   train, T <= 8 and a member's statistics fit LDS: logits_bn_kernel<true> (one launch);
-            otherwise head_fwd_train + logits_kernel<true> (also T > 8: no GEMM form); eval:
-            logits_kernel<true>
-  backward  StepEngine, T <= 4: bank_head_bwd_kernel<true> (loss recomputed inside: no "loss" stage);
-            StepEngine, T > 4: bank_loss_kernel ("loss" stage) + bank_head_bwd_kernel<false>;
-            autograd (dlogits given): bank_head_bwd_kernel<false>.  A bank never rides in passA.
+Head routes of a bank (csrc/head.hip, DESIGN.md section 8 "Model bank"): the one head, with the
+member index taken at run time (a stand-alone model is the bank of one)
+  forward   train, T <= 8 and a member's statistics fit LDS: logits_bn_kernel (one launch);
+            otherwise head_fwd_train + logits_kernel (also T > 8: no GEMM form); eval: logits_kernel
+  backward  StepEngine, T <= 4: head_bwd_kernel<true, false> (loss recomputed inside: no "loss" stage);
+            StepEngine, T > 4: bank_loss_kernel ("loss" stage) + head_bwd_kernel<false, false>;
+            autograd (dlogits given): head_bwd_kernel<false, false>.  A bank never rides in passA.
 -m gpu."""
 import ctypes as C
 from collections import namedtuple
@@ -27,15 +27,15 @@ pytestmark = pytest.mark.gpu
 
 Case = namedtuple("Case", "name G U k L T B kind freeze n_frac codes masked")
 CASES = [
-    # T = 1, B = 100 (a single model rides in passA here; the bank: logits_bn<true> + fused-loss head_bwd)
+    # T = 1, B = 100 (a single model rides in passA here; the bank: logits_bn + fused-loss head_bwd)
     Case("t1_b100", 2, 8, 19, 200, 1, 100, "binary", 0, 0.0, False, True),
-    # T = 1, B = 1024, members straddle the 32-unit tiles, N bases, frozen filters: logits_bn<true> + fused loss
+    # T = 1, B = 1024, members straddle the 32-unit tiles, N bases, frozen filters: logits_bn + fused loss
     Case("t1_b1024_u33", 3, 33, 19, 200, 1, 1024, "binary", 3, 0.01, False, True),
-    # T = 3, B = 600, short filters, MSE: logits_bn<true> + fused loss (looped batch)
+    # T = 3, B = 600, short filters, MSE: logits_bn + fused loss
     Case("t3_b600_k4", 3, 8, 4, 60, 3, 600, "linear", 0, 0.0, False, True),
-    # T = 6, B = 600: logits_bn<true>, bank_loss_kernel + head_bwd<false>
+    # T = 6, B = 600: logits_bn, bank_loss_kernel + head_bwd<false, false>
     Case("t6_b600", 2, 33, 19, 200, 6, 600, "binary", 0, 0.0, False, True),
-    # T = 50, B = 256 (a single model takes the GEMMs): head_fwd_train + logits<true>, bank_loss + head_bwd<false>
+    # T = 50, B = 256 (a single model takes the GEMMs): head_fwd_train + logits_kernel, bank_loss + head_bwd<false, false>
     Case("t50_b256", 10, 8, 19, 200, 50, 256, "binary", 0, 0.0, False, True),
     # base codes read as their reverse complement
     Case("codes_rc", 2, 8, 19, 200, 1, 100, "binary", 3, 0.01, True, True),
