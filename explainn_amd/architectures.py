@@ -139,6 +139,22 @@ class BaseCodes:
         return self.codes.shape
 
 
+class SequenceWindows:
+    """The windows codes[start + i*stride : ... + L], i < n_windows, of ONE device-resident sequence
+    of base codes (1-D uint8), as ExplaiNN._launch_scan takes them: the context cuts them out of the
+    sequence itself (explainn_scan), `sub_batch` of them per device pass."""
+
+    def __init__(self, codes, start, n_windows, stride, reverse_complement=False, sub_batch=4096):
+        self.codes, self.start, self.n_windows, self.stride = codes, int(start), int(n_windows), int(stride)
+        self.reverse_complement = bool(reverse_complement)
+        self.sub_batch = max(1, min(int(sub_batch), self.n_windows))
+
+    @property
+    def shape(self):
+        """(sequences per device pass, L): what _front sizes the context by."""
+        return (self.sub_batch, None)
+
+
 VALIDATE_EVERY = 64      # deferred input validation: the sticky device flag is read every this many calls
 
 # How ExplaiNN._stage treats an fp32 batch (base codes are always staged):
@@ -512,6 +528,12 @@ class ExplaiNN(_Model):
           VALIDATE_FIRST  always validated as above;
           ONEHOT_ONLY     staged and validated; dense_input or a batch that is not one-hot raises."""
         lib, h = ctx.lib, ctx.handle
+        if isinstance(x, SequenceWindows):
+            # base codes that the entry point stages itself, sub-batch by sub-batch: the flag stays
+            # sticky for _settle, as for BaseCodes
+            self._rt.calls += 1
+            _lib.check(lib.explainn_dense_input(h, 0))
+            return x.codes.data_ptr(), False
         if isinstance(x, BaseCodes):
             self._rt.calls += 1
             _lib.check(lib.explainn_dense_input(h, 0))
@@ -612,6 +634,34 @@ class ExplaiNN(_Model):
         with torch.cuda.device(dev):
             ctx, ps, _, stream, xp, read = self._front(x, dev)
             _lib.check(ctx.lib.explainn_forward_eval(ctx.handle, xp, B, C.byref(ps), logits.data_ptr(), stream))
+            self._settle(read)
+        return logits
+
+    def _launch_scan(self, win, mode=_lib.SCAN_AUTO):
+        """Eval-mode logits of the windows of a SequenceWindows (explainn_scan): (n_windows, T) --
+        (n_windows, G, T) on a bank -- fp32 on the device, row i the logit of window i (of its reverse
+        complement when win.reverse_complement).  The shared track's workspace comes from torch's
+        caching allocator."""
+        if self.training:
+            raise RuntimeError("a scan is an eval-mode path; call model.eval()")
+        dev = self._device()
+        c = win.codes
+        if not torch.is_tensor(c) or c.dtype != torch.uint8 or c.dim() != 1 or not c.is_contiguous():
+            raise RuntimeError("a scan takes a contiguous 1-D uint8 tensor of base codes")
+        if c.device != dev:
+            raise RuntimeError("input is on %s but the model is on %s" % (c.device, dev))
+        logits = self._logits_empty(win.n_windows, dev)
+        if win.n_windows == 0:
+            return logits
+        with torch.cuda.device(dev):
+            ctx, ps, _, stream, xp, read = self._front(win, dev)
+            lib, h = ctx.lib, ctx.handle
+            nbytes = int(lib.explainn_scan_workspace_bytes(h, win.n_windows, win.stride, mode))
+            _lib.check(min(nbytes, 0))
+            ws = torch.empty(max(nbytes, 1), device=dev, dtype=torch.uint8)
+            _lib.check(lib.explainn_scan(h, xp, c.numel(), win.start, win.n_windows, win.stride,
+                                         int(win.reverse_complement), C.byref(ps), logits.data_ptr(), mode,
+                                         ws.data_ptr(), nbytes, stream))
             self._settle(read)
         return logits
 

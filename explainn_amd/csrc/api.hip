@@ -381,6 +381,126 @@ extern "C" int explainn_stage_codes(explainn_ctx* c, const uint8_t* codes, int B
     return launch_pack_codes(c, codes, B, reverse_complement ? 1 : 0, static_cast<hipStream_t>(stream));
 }
 
+extern "C" int explainn_stage_windows(explainn_ctx* c, const uint8_t* seq, int64_t seq_len, int64_t start0,
+                                      int64_t step, int B, int reverse_complement, void* stream) {
+    TRY(check_batch(c, B));
+    if (!seq || seq_len < 0) { explainn_set_error("seq is null or seq_len negative"); return EXPLAINN_E_ARG; }
+    drop_pending(c);                   // the packed codes of a pending backward are overwritten
+    return launch_stage_windows(c, seq, seq_len, start0, step, B, reverse_complement ? 1 : 0,
+                                static_cast<hipStream_t>(stream));
+}
+
+// AUTO takes the shared track where it is legal and was measured faster than staging every window, by
+// more than the two legs' spreads (tools/scan_probe.py -> profiles/r11_scan_probe.json: MI355X, 10^6
+// bases, both strands, 300 and 100 units x k 19 x L 200; DESIGN.md section 8 has the table).  SHARED
+// won at stride 7, 14 and 49 on both shapes (300 units: 6.87 against 10.51 ms, 3.66 / 5.11, 1.37 / 1.51)
+// and LOST at 98 and 203 (0.94 / 0.85, 0.72 / 0.52): past m = 7 the filter bank no longer dominates
+// what a window costs and the track's extra launches and tile rounding do.
+#define SCAN_AUTO_MAX_M 7             // the largest stride / 7 at which SHARED won
+// the fewest windows per call at which SHARED was measured to win (20 405, at stride 49); nothing
+// smaller was measured, so nothing smaller is sent there
+#define SCAN_AUTO_MIN_WINDOWS 20000
+
+namespace {
+// the mode a call runs in (a negative code for a bad argument)
+int scan_resolve_mode(const explainn_ctx* c, int64_t n_windows, int64_t stride, int mode) {
+    if (!c) { explainn_set_error("null context"); return EXPLAINN_E_ARG; }
+    if (n_windows < 1 || stride < 1 || stride > (int64_t)1 << 30) {
+        explainn_set_error("scan needs n_windows >= 1 and 1 <= stride <= 2^30 (got %lld, %lld)",
+                           (long long)n_windows, (long long)stride);
+        return EXPLAINN_E_ARG;
+    }
+    if (mode == EXPLAINN_SCAN_AUTO) {
+        const bool shared = stride % POOLW == 0 && stride / POOLW <= SCAN_AUTO_MAX_M &&
+                            n_windows >= SCAN_AUTO_MIN_WINDOWS;
+        return shared ? EXPLAINN_SCAN_SHARED : EXPLAINN_SCAN_WINDOWS;
+    }
+    if (mode == EXPLAINN_SCAN_WINDOWS) return mode;
+    if (mode == EXPLAINN_SCAN_SHARED) {
+        if (stride % POOLW != 0) {
+            explainn_set_error("EXPLAINN_SCAN_SHARED needs a stride that is a multiple of %d (got %lld)", POOLW,
+                               (long long)stride);
+            return EXPLAINN_E_ARG;
+        }
+        return mode;
+    }
+    explainn_set_error("unknown scan mode %d", mode);
+    return EXPLAINN_E_ARG;
+}
+
+int64_t scan_shared_bytes(const explainn_ctx* c, int64_t n_windows, int64_t stride) {
+    const int64_t J = scan_tiles(c, n_windows, (int)(stride / POOLW));
+    return (J + c->maxB - 1) / c->maxB * scan_track_block_elems(c) * (int64_t)sizeof(float);
+}
+}  // namespace
+
+extern "C" int64_t explainn_scan_workspace_bytes(const explainn_ctx* c, int64_t n_windows, int64_t stride,
+                                                 int mode) {
+    const int m = scan_resolve_mode(c, n_windows, stride, mode);
+    if (m < 0) return m;
+    return m == EXPLAINN_SCAN_SHARED ? scan_shared_bytes(c, n_windows, stride) : 0;
+}
+
+extern "C" int explainn_scan(explainn_ctx* c, const uint8_t* seq, int64_t seq_len, int64_t start,
+                             int64_t n_windows, int64_t stride, int reverse_complement,
+                             const explainn_params* p, float* logits, int mode, void* workspace,
+                             int64_t workspace_bytes, void* stream) {
+    const int md = scan_resolve_mode(c, n_windows, stride, mode);
+    if (md < 0) return md;
+    if (!seq || seq_len < 0 || !p || !logits) {
+        explainn_set_error("seq, params and logits are required, seq_len >= 0");
+        return EXPLAINN_E_ARG;
+    }
+    if (c->dense) { explainn_set_error("a scan works on base codes: not in dense input mode"); return EXPLAINN_E_UNSUPPORTED; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int rc = reverse_complement ? 1 : 0;
+    const int64_t row = (int64_t)c->Gm * c->T;       // logits are (n_windows, [G,] T)
+    drop_pending(c);
+    if (md == EXPLAINN_SCAN_WINDOWS) {
+        for (int64_t i0 = 0; i0 < n_windows; i0 += c->maxB) {
+            const int Bw = (int)(n_windows - i0 < c->maxB ? n_windows - i0 : c->maxB);
+            TRY(launch_stage_windows(c, seq, seq_len, start + i0 * stride, stride, Bw, rc, s));
+            TRY(eval_forward(c, nullptr, Bw, p, false, logits + i0 * row, nullptr, s));
+        }
+        c->staged_B = 0;
+        return EXPLAINN_OK;
+    }
+    const int64_t need = scan_shared_bytes(c, n_windows, stride);
+    if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 255) != 0) {
+        explainn_set_error("scan workspace of %lld bytes (256-byte aligned), %lld needed", (long long)workspace_bytes,
+                           (long long)need);
+        return EXPLAINN_E_ARG;
+    }
+    // the pooled track: tiles of L bases placed 7n apart, through the filter bank in blocks of up to
+    // max_batch tiles.  Each block is the filter bank's whole output array, so the filter bank writes
+    // it straight into the workspace (its output pointer is swapped for the launch): no copy.
+    const int m = (int)(stride / POOLW), TB = c->maxB;
+    const int64_t tstep = (int64_t)POOLW * c->n, J = scan_tiles(c, n_windows, m);
+    const int64_t blk = scan_track_block_elems(c), Leff = stride * (n_windows - 1) + c->L;
+    float* track = static_cast<float*>(workspace);
+    float* const own_ext = c->ext;
+    for (int64_t j0 = 0; j0 < J; j0 += TB) {
+        const int Bt = (int)(J - j0 < TB ? J - j0 : TB);
+        // reverse strand: rc(window i) is forward window n_windows-1-i of rc(seq[start : start+Leff]),
+        // whose tile j starts L + 7n*j bases before the region's end
+        const int64_t s0 = rc ? start + Leff - c->L - tstep * j0 : start + tstep * j0;
+        TRY(launch_stage_windows(c, seq, seq_len, s0, rc ? -tstep : tstep, Bt, rc, s));
+        if (j0 == 0) TRY(eval_front(c, nullptr, Bt, p, s));
+        c->ext = track + (j0 / TB) * blk;
+        const int r = launch_conv_pool(c, p, Bt, false, s);
+        c->ext = own_ext;
+        TRY(r);
+    }
+    for (int64_t i0 = 0; i0 < n_windows; i0 += c->maxB) {
+        const int Bw = (int)(n_windows - i0 < c->maxB ? n_windows - i0 : c->maxB);
+        TRY(launch_scan_unfold(c, track, blk, J, TB, m, n_windows, i0, Bw, rc, s));
+        TRY(launch_fc_fwd(c, p, Bw, false, nullptr, 0.f, 0, s));
+        TRY(launch_head_fwd(c, p, Bw, false, logits + i0 * row, nullptr, s));
+    }
+    c->staged_B = 0;
+    return EXPLAINN_OK;
+}
+
 extern "C" int explainn_filter_act_max(explainn_ctx* c, const float* x, int B,
                                        const explainn_params* p, const uint8_t* select,
                                        float* unit_max, void* stream) {

@@ -201,6 +201,16 @@ int launch_input_grad(explainn_ctx* c, const explainn_params* p, int B, bool tra
 int64_t ism_workspace_bytes(const explainn_ctx* c, int B);
 int launch_ism(explainn_ctx* c, const explainn_params* p, int B, float* delta, float* ws, hipStream_t s);
 
+// tiled scan of a long sequence (scan.hip): windows of a device-resident sequence staged as a batch;
+// the pooled track of a run of tiles (blocks of TB tiles in the filter bank's output layout, in the
+// caller's workspace) unfolded into c->ext for windows [i0, i0 + Bw) of n_windows at stride 7m
+int launch_stage_windows(explainn_ctx* c, const uint8_t* seq, int64_t seq_len, int64_t start0, int64_t step,
+                         int B, int rc, hipStream_t s);
+int launch_scan_unfold(explainn_ctx* c, const float* track, int64_t blk_elems, int64_t J, int TB, int m,
+                       int64_t n_windows, int64_t i0, int Bw, int rc, hipStream_t s);
+int64_t scan_track_block_elems(const explainn_ctx* c);
+int64_t scan_tiles(const explainn_ctx* c, int64_t n_windows, int m);
+
 int launch_dense_moments(explainn_ctx* c, const float* x, int B, hipStream_t s);
 int launch_dense_conv_pool(explainn_ctx* c, const float* x, const explainn_params* p, int B, hipStream_t s);
 int launch_dense_conv_bwd(explainn_ctx* c, const float* x, int B, hipStream_t s);

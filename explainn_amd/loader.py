@@ -5,6 +5,7 @@ character producing a float64 (N,4,L) array), the reverse-complement augmentatio
 train.py:275-278 (a second float64 copy of the data set) and the `DataLoader(TensorDataset(...))`
 of train.py:286-295 (item-by-item batch assembly, pageable host memory):
 
+  * `read_fasta_records`: FASTA records of unequal length, one 1-D code array each (explainn_amd.scan);
   * `read_tsv_codes` / `read_fasta_codes`: file -> (N,L) uint8 base codes (0..3 = A,C,G,T, 4 =
     anything else) with ONE table lookup over the joined sequence text -- no per-sequence loop;
   * `CodesLoader`: batches of codes + targets cut with one index operation, staged in pinned
@@ -81,6 +82,21 @@ def read_fasta_codes(fasta_file):
         bad = next(i for i, s in enumerate(seqs) if len(s) != L)
         raise ValueError("record %d (%s) has length %d, expected %d" % (bad, ids[bad], len(seqs[bad]), L))
     return _LUT[np.frombuffer(joined, dtype=np.uint8)].reshape(n, L), np.array(ids)
+
+
+def read_fasta_records(fasta_file):
+    """FASTA (optionally gzipped, multi-line records, either case) -> [(id, codes 1-D uint8), ...]:
+    records of any, unequal, length -- chromosome arms, BACs, peaks -- for explainn_amd.scan.  An empty
+    record gives an empty array."""
+    with _open(fasta_file, "rb") as fh:
+        blob = fh.read()
+    out = []
+    for rec in blob.split(b">")[1:]:
+        head, _, body = rec.partition(b"\n")
+        body = body.translate(None, b"\r\n \t")
+        out.append((head.split()[0].decode() if head.split() else "",
+                    _LUT[np.frombuffer(body, dtype=np.uint8)]))
+    return out
 
 
 def rc_codes_inplace(rows, flags):

@@ -100,8 +100,8 @@ int explainn_create(explainn_ctx** out, int cnn_units, int kernel_size, int sequ
  * Supported on a bank: explainn_forward_eval, explainn_forward_train, explainn_backward,
  * explainn_loss_grad, explainn_train_step, explainn_train_step_fc / _conv (the flat gradient buffer
  * is element-wise, so a data-parallel all-reduce is unchanged), explainn_unit_outputs (B,G*U),
- * explainn_unit_activations, the filter export (per unit), explainn_stage_codes / _stage_onehot,
- * explainn_dense_input, explainn_input_flags, stage timing, explainn_debug_keep_bits (G*U,B,4).
+ * explainn_unit_activations, the filter export (per unit), explainn_stage_codes / _stage_onehot /
+ * _stage_windows, explainn_scan in every mode (logits (n_windows,G,T)), explainn_dense_input, explainn_input_flags, stage timing, explainn_debug_keep_bits (G*U,B,4).
  * EXPLAINN_E_UNSUPPORTED on a bank (they fold units through `final` in kernels of their own; run them
  * on one member's model; the context stays usable): explainn_forward_eval_keep, explainn_input_grad,
  * explainn_backward_input, explainn_ism, explainn_sync_phase.
@@ -246,6 +246,47 @@ int explainn_filter_sites(explainn_ctx* ctx, const float* x, int B, const explai
  * Other byte values are treated as N and raise bit 0 of explainn_input_flags. */
 int explainn_stage_codes(explainn_ctx* ctx, const uint8_t* codes, int B, int reverse_complement,
                          void* stream);
+
+/* Scoring a sequence longer than sequence_length (L) with overlapping windows -- what a user of the
+ * reference does by materialising every window on the host and calling predict.py.
+ *
+ * explainn_stage_windows: like explainn_stage_codes, but the batch is cut out of ONE device-resident
+ * sequence: seq holds seq_len base codes (0..3 = ACGT, 4 = N) and row b of the staged batch is
+ * seq[start0 + b*step : start0 + b*step + L]; start0 and step are signed.  A position outside
+ * [0, seq_len) reads as N and raises no flag; a byte above 4 inside it is N and raises bit 0 of
+ * explainn_input_flags.  reverse_complement != 0 reverse-complements every row on the fly.  The context
+ * then holds exactly what explainn_stage_codes would hold for the materialised (B,L) matrix: every
+ * entry point that takes x == NULL runs on it, train mode included.
+ *
+ * explainn_scan: the eval-mode logits of the windows seq[start + i*stride : ... + L],
+ * i = 0 .. n_windows-1, fp32 (n_windows,T) on the device -- (n_windows,G,T) on a bank context.  With
+ * reverse_complement != 0 row i is the logit of the reverse complement of window i.  Positions outside
+ * the sequence read as N.  No host synchronisation, no allocation; windows run in sub-batches of the
+ * context's max_batch.  Like every eval entry point it ends a pending train forward, rebuilds the folded
+ * tables only when params->version moved, and leaves no staged batch behind (x == NULL afterwards is
+ * EXPLAINN_E_STATE).  Dense input mode: EXPLAINN_E_UNSUPPORTED.  mode:
+ *   EXPLAINN_SCAN_WINDOWS  every sub-batch is staged with explainn_stage_windows and run through the
+ *                          ordinary eval forward; any stride >= 1; needs no workspace.
+ *   EXPLAINN_SCAN_SHARED   stride must be a multiple of 7 (else EXPLAINN_E_ARG; the context stays
+ *                          usable).  MaxPool1d(7,7) then pools every window on one grid, so the filter
+ *                          bank runs ONCE over the region, on tiles placed 7n apart, and every window's
+ *                          pooled vector is a slice of that track; the FC and the
+ *                          head run per window as always.  Same logits as WINDOWS, bit for bit.  The
+ *                          track lives in `workspace`: device memory, 256-byte aligned, of at least
+ *                          explainn_scan_workspace_bytes(ctx, n_windows, stride, mode) bytes (one
+ *                          filter-bank output array per max_batch tiles).
+ *   EXPLAINN_SCAN_AUTO     SHARED where it is legal and was measured faster, else WINDOWS; the size
+ *                          query resolves the same way.
+ * explainn_scan_workspace_bytes returns the negative error code for a bad argument. */
+#define EXPLAINN_SCAN_AUTO 0
+#define EXPLAINN_SCAN_WINDOWS 1
+#define EXPLAINN_SCAN_SHARED 2
+int explainn_stage_windows(explainn_ctx* ctx, const uint8_t* seq, int64_t seq_len, int64_t start0,
+                           int64_t step, int B, int reverse_complement, void* stream);
+int64_t explainn_scan_workspace_bytes(const explainn_ctx* ctx, int64_t n_windows, int64_t stride, int mode);
+int explainn_scan(explainn_ctx* ctx, const uint8_t* seq, int64_t seq_len, int64_t start, int64_t n_windows,
+                  int64_t stride, int reverse_complement, const explainn_params* p, float* logits, int mode,
+                  void* workspace, int64_t workspace_bytes, void* stream);
 
 /* The fp32 one-hot packed into the context ahead of the forward: like explainn_stage_codes, the
  * entry points then take x == NULL.  Lets the caller read explainn_input_flags BEFORE anything

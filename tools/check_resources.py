@@ -51,7 +51,9 @@ METRICS = [
     r"^metrics_sums_kernel", r"^metrics_means_kernel", r"^metrics_centred_kernel",
     r"^metrics_linear_final_kernel",
 ]
-GATED = C2_STEP + INPUT_GRAD + ISM + METRICS
+# tiled scan of a long sequence (scan.hip): the window staging and the unfold of the pooled track
+SCAN = [r"^stage_windows_kernel", r"^scan_unfold_kernel"]
+GATED = C2_STEP + INPUT_GRAD + ISM + METRICS + SCAN
 
 
 # Register cliffs measured in the pipeline: 1024-thread blocks of which TWO must
