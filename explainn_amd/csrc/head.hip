@@ -119,7 +119,7 @@ __device__ __forceinline__ void block_sum3_256(double& a, double& b, double& c, 
 
 // The register path of head_fwd_train: this thread's RBX z values stay in registers through the three
 // passes (mean, variance, normalise) -- one batch of loads instead of three passes of dependent round
-// trips over the same row.  RBX = 4 (batch <= 1024) or 16 (batch <= 4096: configuration C3).
+// trips over the same row.  RBX = HEAD_RB = 8 (batch <= 2048) or 16 (batch <= 4096: configuration C3).
 template <int RBX>
 __device__ __forceinline__ void head_fwd_train_regs(const float* __restrict__ zu, float* __restrict__ zhu,
                                                     float* __restrict__ ou, float gam, float bet, int B,

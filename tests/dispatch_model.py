@@ -25,6 +25,34 @@ forms(U, k, L, T, B, max_batch, path) returns a set of tuples, one per choice th
   ("QCH", q), ("qch_per", s)      q-moment chunks and sequences per chunk
   ("ACH", a), ("ach_per", s)      passA chunks and sequences per chunk
   ("eval_logits", "kernel"|"gemm")  the eval-mode combiner
+
+head_forms(U, T, B, path, G) with G > 1 is the head of a model bank of G members of U units: every form
+is tagged ("bank", ...), so that a bank's run of a kernel never counts for the single model's.
+
+The entry points that came after the train step have launchers of their own (ism.hip, inputgrad.hip):
+
+ism_forms(U, k, L, T, B), in-silico mutagenesis
+  ("ism_nw", NW)                  ism_units_kernel<NW>, NW = ism_nw(k)
+  ("ism_k_edge", NW, "lower"|"upper")  the smallest / largest kernel size of that NW
+  ("ism_sum", TC, "full"|"ragged"|"several")  ism_sum_kernel<TC>: the last task chunk full or not, more than one
+  ("ism_sum_trips", TC, 1|2|3, "full"|"ragged")  task chunks of ism_sum_kernel (3: one neither first nor last)
+  ("ism_subbatches", "one"|"several")  trips of launch_ism's sub-batch loop
+  ("ism_tail", r)                 positions behind the last pooled window's reach, L - (7n + k - 1)
+  ("ism_n", 1)                    one pooled window
+
+ig_forms(U, k, L, T, B, mode), the input gradient; mode eval | train | train_dense
+  ("ig", mode)                    input_grad_kernel<TRAIN, DENSE>
+  ("ig_ng", NG)                   train: row groups of passB's S12p partials that ig_coef_kernel sums
+  ("ig_chunks", "several"[, "big_n"])  train: QCH or ACH > 1 (big_n: at a pooled length of the large-n kernels)
+  ("ig_units", "partial_wave"|"partial_pass"|"several_passes")   units against IG_UT and a wave's share
+  ("ig_units_edge", mode, U)      U = a wave's share, IG_UT, and one more
+  ("ig_batch", B)                 B = 2, the 64-sequence tile and IG_DY_THREADS, and one more
+  ("ig_wmax", mode, k)            some tile of IG_POS positions needs the largest window count of that k
+  ("ig_k", mode, k)               the smallest / largest kernel size
+  ("ig_tail", mode, r)            (L - k + 1) % POOLW
+  ("ig_pos", "ragged")            L is no multiple of IG_POS
+  ("ig_wc", "ragged"|"several")   eval: pooled positions against ig_eval_dy's register chunk IG_WC
+  ("ig_n", mode, 1)               one pooled window
 """
 import collections
 import os
@@ -99,8 +127,8 @@ def parse_sources():
     c["PA_HEAD_MAX_B"] = int(m.group(1))
     c["FUSED_LOSS_MAX_T"] = int(_one(r"if \(c->T <= (\d+)\) \{\s*// few tasks: the loss gradient is recomputed",
                                      api, "fused-loss branch").group(1))
-    m = _one(r"c->T <= HEAD_GEMM_MIN_T && !outs && \(size_t\)c->U \* \(sizeof\(float4\) \+ sizeof\(float\)\) <= (\d+) \* (\d+)",
-             head, "logits_bn LDS test")
+    m = _one(r"c->T <= HEAD_GEMM_MIN_T && !outs && \(size_t\)c->U \* \(sizeof\(float4\) \+ sizeof\(float\)\) <= (\d+) \* (\d+)"
+             r" \* \(size_t\)G\)", head, "logits_bn LDS test (per member)")
     c["LOGITS_BN_LDS"] = int(m.group(1)) * int(m.group(2))
     c["LOGITS_BN_BYTES_PER_UNIT"] = 16 + 4
     m = _one(r"\} else if \(B <= (\d+) \* (\d+)\) \{\s*head_fwd_train_regs<(\d+)>", head, "head_fwd regs<16> branch")
@@ -116,6 +144,54 @@ def parse_sources():
     # explainn_create refuses a pooled length whose tables exceed a workgroup's LDS
     _one(r"static size_t prep2_lds\(int n, int NS\) \{\s*return \(size_t\)NS \* sizeof\(double\) \+ "
          r"\(\(size_t\)n \* n \+ \(size_t\)FC_H \* \(n \+ 1\)\) \* sizeof\(float\);", _src("prep.hip"), "prep2_lds")
+    # a bank (Gm > 1): never in passA, never the GEMM combiner, a loss kernel of its own; units per
+    # trip of the combiner kernels' unit loops; the unit count a bank may have
+    _one(r"bool head_rides_in_passA\(const explainn_ctx\* c, int B\) \{\s*if \(c->Gm > 1\) return false;", api,
+         "a bank never rides in passA")
+    _one(r"const bool gemm = c->Gm == 1 && c->T > HEAD_GEMM_MIN_T;", head, "head_bwd GEMM rule")
+    _one(r"if \(logits && G == 1 && T > HEAD_GEMM_MIN_T\)", head, "head_fwd GEMM rule")
+    _one(r"int launch_loss\(.*?\{\s*if \(c->Gm > 1\) \{\s*hipLaunchKernelGGL\(bank_loss_kernel", head, "bank_loss route")
+    _one(r"int launch_loss_deferred\(.*?if \(c->Gm > 1\) return launch_loss\(", head, "bank_loss route (deferred)")
+    c["LOGITS_UNITS_TRIP"] = int(_one(r"void logits_kernel\(.*?for \(int u0 = wv; u0 < U; u0 \+= (\d+)\)", head,
+                                      "logits_kernel unit loop").group(1))
+    m = _one(r"void logits_bn_kernel\(.*?constexpr int LQ = (\d+);.*?for \(int u0 = wv; u0 < U; u0 \+= (\d+) \* LQ\)",
+             head, "logits_bn_kernel unit loop")
+    c["LOGITS_BN_UNITS_TRIP"] = int(m.group(1)) * int(m.group(2))
+    c["BANK_MAX_UNITS"] = _define(api, "BANK_MAX_UNITS")
+    _one(r"if \(groups > 1 && \(int64_t\)groups \* units_per_member > BANK_MAX_UNITS\)", api, "bank unit limit")
+    # ism.hip
+    ism, ig = _src("ism.hip"), _src("inputgrad.hip")
+    m = _one(r"inline int ism_nw\(int k\) \{ return \(k \+ (\d+)\) / (\d+) \+ (\d+); \}", ism, "ism_nw")
+    c["ISM_NW_RULE"] = tuple(int(v) for v in m.groups())
+    body = _one(r"switch \(ism_nw\(c->k\)\) \{(.*?)default:", ism, "launch_ism switch").group(1)
+    c["ism_nw_cases"] = [int(v) for v in re.findall(r"case (\d+):", body)]
+    m = _one(r"if \(c->T == (\d+)\) hipLaunchKernelGGL\(\(ism_sum_kernel<(\d+)>\), ISM_SUM_ARGS\);\s*"
+             r"else if \(c->T <= (\d+)\) hipLaunchKernelGGL\(\(ism_sum_kernel<(\d+)>\), ISM_SUM_ARGS\);\s*"
+             r"else hipLaunchKernelGGL\(\(ism_sum_kernel<(\d+)>\), ISM_SUM_ARGS\);", ism, "ism_sum dispatch")
+    t1, tc1, t2, tc2, tc3 = (int(v) for v in m.groups())
+    assert t1 == 1
+    c["ism_sum_rules"] = [(t1, tc1), (t2, tc2), (None, tc3)]      # (largest T, TC), in order
+    c["ISM_WS_CAP"] = 1 << int(_one(r"#define ISM_WS_CAP \(1LL << (\d+)\)", ism, "ISM_WS_CAP").group(1))
+    m = _one(r"int ism_sub_batch\(.*?per = \(int64_t\)c->U \* 4 \* c->L \* \(int64_t\)sizeof\(float\);\s*"
+             r"int64_t s = ISM_WS_CAP / per / (\d+) \* \1;\s*if \(s < \1\) s = \1;", ism, "ism_sub_batch")
+    c["ISM_SUB_STEP"] = int(m.group(1))
+    _one(r"inline int ism_pend\(int k, int n, int L\) \{ return min\(L, POOLW \* n \+ k - 1\); \}", ism, "ism_pend")
+    # inputgrad.hip
+    for name in ("IG_POS", "IG_UT", "IG_WMAX", "IG_DY_THREADS", "IG_WC"):
+        c[name] = _define(ig, name)
+    _one(r"int wlo = P0 - k - 5;\s*wlo = wlo <= 0 \? 0 : \(wlo \+ 6\) / 7;\s*"
+         r"const int whi = min\(n - 1, \(P0 \+ IG_POS - 1\) / POOLW\);", ig, "input_grad window range")
+    _one(r"const int ub = u0 \+ \(IG_UT / 4\) \* wave", ig, "input_grad wave share")
+    c["IG_SEQS"] = int(_one(r"const dim3 grid\(\(B \+ (\d+)\) / (\d+), \(c->L \+ IG_POS - 1\) / IG_POS\);", ig,
+                            "input_grad grid").group(2))
+    # common.h: passB's row groups
+    m = _one(r"constexpr int fc_nw16\(int NQ\) \{ return \(NQ \+ (\d+)\) / (\d+); \}", common, "fc_nw16")
+    assert int(m.group(1)) == int(m.group(2)) - 1
+    c["FC_TILE"] = int(m.group(2))
+    m = _one(r"constexpr int fc_wgt\(int NQ\) \{ return fc_nw16\(NQ\) <= (\d+) \? fc_nw16\(NQ\) : (\d+); \}", common, "fc_wgt")
+    c["FC_WGT_SMALL"], c["FC_WGT"] = int(m.group(1)), int(m.group(2))
+    _one(r"constexpr int fc_ng\(int NQ\) \{ return \(fc_nw16\(NQ\) \+ fc_wgt\(NQ\) - 1\) / fc_wgt\(NQ\); \}", common, "fc_ng")
+    _one(r"hipLaunchKernelGGL\(ig_coef_kernel,.*?c->igcoef, fc_ng\(c->NQ\),", ig, "ig_coef row groups")
     return c
 
 
@@ -199,9 +275,56 @@ def check_supported(U, k, L, T):
     return n
 
 
-def head_forms(U, T, B, path):
+def bank_head_forms(Um, T, B, path, G):
+    """The head of a bank of G > 1 members of Um units (launch_head_fwd, train_step_front,
+    launch_head_bwd with Gm > 1): never in passA, never a GEMM, a loss kernel of its own."""
+    f = set()
+    regs = C["HEAD_RB"] * C["HEAD_THREADS"]
+    # the LDS test reads c->U = G * Um against G times the limit: one member's share
+    if T <= C["HEAD_GEMM_MIN_T"] and G * Um * C["LOGITS_BN_BYTES_PER_UNIT"] <= C["LOGITS_BN_LDS"] * G:
+        f |= {("bank", "head_fwd", "logits_bn"), ("bank", "logits", "bn")}
+        if Um > C["LOGITS_BN_UNITS_TRIP"]:
+            f.add(("bank_units_trip", "logits_bn", "several"))
+    else:
+        if B <= regs:
+            f.add(("bank", "head_fwd", "regs%d" % C["HEAD_RB"]))
+        elif B <= C["HEAD_FWD_REGS2"] * C["HEAD_THREADS"]:
+            f.add(("bank", "head_fwd", "regs%d" % C["HEAD_FWD_REGS2"]))
+        else:
+            f.add(("bank", "head_fwd", "loop"))
+        f.add(("bank", "logits", "kernel"))
+        if Um > C["LOGITS_UNITS_TRIP"]:
+            f.add(("bank_units_trip", "logits", "several"))
+    if path != "step":
+        branch = "kernel"
+    elif T <= C["FUSED_LOSS_MAX_T"]:
+        branch = "fused_loss"
+    else:
+        branch = "bank_loss"
+    body = "inreg" if T <= C["HEAD_INREG_MAX_T"] and B <= regs else "loop"
+    f |= {("bank", "head_bwd", branch), ("bank", "head_bwd_body", body), ("bank", "head_bwd", branch, body)}
+    # the task thresholds themselves, at a batch below one block of threads (rows of the register
+    # paths that no sequence fills) or not, with one trip of the combiner's unit loop or several
+    if T in bank_task_edges():
+        trips = "several_trips" if any(v[0] == "bank_units_trip" for v in f) else "one_trip"
+        f.add(("bank", "t_edge", T, "lt_block" if B < C["HEAD_THREADS"] else "ge_block", trips))
+    if B in (regs, regs + 1, C["HEAD_FWD_REGS2"] * C["HEAD_THREADS"] + 1):
+        f.add(("bank", "b_edge", B))
+    if G * Um == C["BANK_MAX_UNITS"]:
+        f.add(("bank", "units", "limit"))
+    return f
+
+
+def bank_task_edges():
+    return sorted({C["FUSED_LOSS_MAX_T"], C["FUSED_LOSS_MAX_T"] + 1, C["HEAD_INREG_MAX_T"], C["HEAD_INREG_MAX_T"] + 1,
+                   C["HEAD_GEMM_MIN_T"], C["HEAD_GEMM_MIN_T"] + 1})
+
+
+def head_forms(U, T, B, path, G=1):
     """The head's forward and backward branches of a train step (path "autograd": forward_train +
-    explainn_backward; "step": explainn_train_step)."""
+    explainn_backward; "step": explainn_train_step).  G > 1: a bank of G members of U units each."""
+    if G > 1:
+        return bank_head_forms(U, T, B, path, G)
     f = set()
     if T <= C["HEAD_GEMM_MIN_T"] and U * C["LOGITS_BN_BYTES_PER_UNIT"] <= C["LOGITS_BN_LDS"]:
         f.add(("head_fwd", "logits_bn"))
@@ -410,4 +533,266 @@ def all_forms(cases=None, with_existing=True):
     if with_existing:
         for (U, k, L, T, B, _) in ORACLE_STEP_SHAPES:
             got |= forms(U, k, L, T, B)
+    return got
+
+
+# ---- in-silico mutagenesis (csrc/ism.hip) -------------------------------------------------------
+def ism_nw(k):
+    add, div, plus = C["ISM_NW_RULE"]
+    return (k + add) // div + plus
+
+
+def ism_sum_tc(T):
+    for tmax, tc in C["ism_sum_rules"]:
+        if tmax is None or T <= tmax:
+            return tc
+
+
+def ism_sub_batch(U, L, B):
+    step = C["ISM_SUB_STEP"]
+    s = max(C["ISM_WS_CAP"] // (U * 4 * L * 4) // step * step, step)
+    return min(s, (B + step - 1) // step * step)
+
+
+def ism_workspace_bytes(U, L, B):
+    return U * 4 * L * ism_sub_batch(U, L, B) * 4
+
+
+def ism_pend(k, n, L):
+    return min(L, C["POOLW"] * n + k - 1)
+
+
+def ism_k_range(NW):
+    ks = [k for k in range(2, C["MAX_K"] + 1) if ism_nw(k) == NW]
+    return ks[0], ks[-1]
+
+
+def ism_forms(U, k, L, T, B):
+    n = check_supported(U, k, L, T)
+    NW = ism_nw(k)
+    assert NW in C["ism_nw_cases"], "launch_ism has no case for NW = %d" % NW
+    f = {("ism_nw", NW), ("ism_tail", L - ism_pend(k, n, L))}
+    lo, hi = ism_k_range(NW)
+    if k == lo:
+        f.add(("ism_k_edge", NW, "lower"))
+    if k == hi:
+        f.add(("ism_k_edge", NW, "upper"))
+    TC = ism_sum_tc(T)
+    f.add(("ism_sum", TC, "ragged" if T % TC else "full"))
+    if T > TC:
+        f.add(("ism_sum", TC, "several"))
+    f.add(("ism_sum_trips", TC, min(3, (T + TC - 1) // TC), "ragged" if T % TC else "full"))
+    f.add(("ism_subbatches", "several" if B > ism_sub_batch(U, L, B) else "one"))
+    if n == 1:
+        f.add(("ism_n", 1))
+    return f
+
+
+IsmCase = collections.namedtuple("IsmCase", "id U k L T B ref seed")      # ref: "oracle" | "device"
+
+
+def _ism_case(U, k, L, T, B, ref="oracle"):
+    return IsmCase("ism-U%d-k%d-L%d-T%d-B%d" % (U, k, L, T, B), U, k, L, T, B, ref, (U * 131 + k * 17 + L + T) % 10007)
+
+
+def build_ism_cases():
+    cases = []
+    # both kernel sizes at every change of NW, three windows, tails 0..6, the task counts below the
+    # first ism_sum threshold and at it
+    i = 0
+    for NW in C["ism_nw_cases"]:
+        lo, hi = ism_k_range(NW)
+        for k in (lo, hi):
+            if k in (2, C["MAX_K"]):
+                continue                    # the ends come with one window below
+            cases.append(_ism_case(3 + i % 3, k, _length(3, k, i % C["POOLW"]), 1 + i % 3, 3))
+            i += 1
+    # the task chunks of ism_sum: both sides of every threshold, of the widest chunk, and three chunks
+    tmid, tc_max = C["ism_sum_rules"][1][0], C["ism_sum_rules"][-1][1]
+    for T in (tmid, tmid + 1, tc_max, tc_max + 1, 2 * tc_max + 1):
+        cases.append(_ism_case(4, 5, _length(2, 5, T % C["POOLW"]), T, 3))
+    # one window, smallest and largest kernel
+    cases.append(_ism_case(3, 2, _length(1, 2, 3), 2, 3))
+    cases.append(_ism_case(3, C["MAX_K"], _length(1, C["MAX_K"], 5), 1, 3))
+    # two trips of the sub-batch loop: the smallest U x L whose sub-batch is one step, a batch of one
+    # step and a ragged second trip
+    U, step = 1100, C["ISM_SUB_STEP"]
+    L = C["ISM_WS_CAP"] // (16 * 2 * step) // U + 1
+    cases.append(_ism_case(U, 5, L, 2, step + 6, ref="device"))
+    return cases
+
+
+ISM_CASES = build_ism_cases()
+
+
+# ---- the input gradient (csrc/inputgrad.hip) ----------------------------------------------------
+def fc_ng(NQ):
+    nw16 = (NQ + C["FC_TILE"] - 1) // C["FC_TILE"]
+    wgt = nw16 if nw16 <= C["FC_WGT_SMALL"] else C["FC_WGT"]
+    return (nw16 + wgt - 1) // wgt
+
+
+def ig_windows(P0, k, n):
+    """How many pooled windows input_grad_kernel loads for the tile of IG_POS positions at P0."""
+    w = C["POOLW"]
+    wlo = P0 - k - (w - 2)
+    wlo = 0 if wlo <= 0 else (wlo + w - 1) // w
+    whi = min(n - 1, (P0 + C["IG_POS"] - 1) // w)
+    return whi - wlo + 1
+
+
+def ig_max_windows(k):
+    """The largest window count any tile can need at kernel size k (n unbounded)."""
+    period = C["POOLW"] * C["IG_POS"]
+    return max(ig_windows(P0, k, 10 ** 6) for P0 in range(0, 4 * period + C["IG_POS"] * k, C["IG_POS"]))
+
+
+def ig_unit_edges():
+    return (C["IG_UT"] // 4, C["IG_UT"] // 4 + 1, C["IG_UT"], C["IG_UT"] + 1)
+
+
+def ig_batch_edges():
+    return (2, C["IG_SEQS"], C["IG_SEQS"] + 1, C["IG_DY_THREADS"], C["IG_DY_THREADS"] + 1)
+
+
+def ig_forms(U, k, L, T, B, mode):
+    assert mode in ("eval", "train", "train_dense")
+    n = check_supported(U, k, L, T)
+    f = {("ig", mode), ("ig_tail", mode, (L - k + 1) % C["POOLW"])}
+    if mode != "eval":
+        NQ = nq_bucket(n)
+        f.add(("ig_ng", fc_ng(NQ)))
+        if n == nq_lower(NQ) + 1:
+            f.add(("ig_ng_edge", fc_ng(NQ), "lower"))
+        q, a = chunks(U, NQ, B)
+        if q > 1 or a > 1:
+            f.add(("ig_chunks", "several"))
+            if n > C["MID_FUSED_MAX_N"]:
+                f.add(("ig_chunks", "several", "big_n"))
+    else:
+        if n % C["IG_WC"]:
+            f.add(("ig_wc", "ragged"))
+        if n > C["IG_WC"]:
+            f.add(("ig_wc", "several"))
+    if U % (C["IG_UT"] // 4):
+        f.add(("ig_units", "partial_wave"))
+    if U % C["IG_UT"]:
+        f.add(("ig_units", "partial_pass"))
+    if U > C["IG_UT"]:
+        f.add(("ig_units", "several_passes"))
+    if U in ig_unit_edges():
+        f.add(("ig_units_edge", mode, U))
+    if B in ig_batch_edges():
+        f.add(("ig_batch", B))
+    if k in (2, C["MAX_K"]):
+        f.add(("ig_k", mode, k))
+    if max(ig_windows(P0, k, n) for P0 in range(0, L, C["IG_POS"])) == ig_max_windows(k):
+        f.add(("ig_wmax", mode, k))
+    if L % C["IG_POS"]:
+        f.add(("ig_pos", "ragged"))
+    if n == 1:
+        f.add(("ig_n", mode, 1))
+    return f
+
+
+IgCase = collections.namedtuple("IgCase", "id U k L T B mode seed")
+
+
+def _ig_case(U, k, L, T, B, mode, bump=0):
+    return IgCase("ig-%s-U%d-k%d-L%d-T%d-B%d" % (mode, U, k, L, T, B), U, k, L, T, B, mode,
+                  (U * 131 + k * 17 + L + B) % 10007 + bump)
+
+
+def _ig_wmax_length(k, r):
+    """The shortest L with tail r at which some tile needs ig_max_windows(k) windows."""
+    for n in range(1, max_legal_n() + 1):
+        L = C["POOLW"] * n + k - 1 + r
+        if max(ig_windows(P0, k, n) for P0 in range(0, L, C["IG_POS"])) == ig_max_windows(k):
+            return L + (1 if L % C["IG_POS"] == 0 and r < C["POOLW"] - 1 else 0)
+    raise AssertionError("no pooled length reaches %d windows at k = %d" % (ig_max_windows(k), k))
+
+
+def build_ig_cases():
+    cases = []
+    k_max = C["MAX_K"]
+    for mode in ("train", "eval"):
+        for U in ig_unit_edges():
+            cases.append(_ig_case(U, 5, _length(2 + U % 3, 5, U % C["POOLW"]), 2, 6, mode))
+        # the widest filter with the longest tail, and the narrowest: the shortest sequence at which a
+        # tile needs the largest window count of that kernel size
+        cases.append(_ig_case(5, k_max, _ig_wmax_length(k_max, C["POOLW"] - 1), 2, 6, mode))
+        cases.append(_ig_case(5, 2, _ig_wmax_length(2, 3), 2, 6, mode))
+        cases.append(_ig_case(3, 5, _length(1, 5, 2), 1, 6, mode))                  # n = 1
+    # train: the first bucket of every fc_ng value past 1 at its lower edge (ig_ng 1 is every small case)
+    seen = {1}
+    for NQ in C["buckets"]:
+        if fc_ng(NQ) not in seen and nq_lower(NQ) + 1 <= max_legal_n():
+            seen.add(fc_ng(NQ))
+            cases.append(_ig_case(3, 5, _length(nq_lower(NQ) + 1, 5, fc_ng(NQ)), 1, 6, "train"))
+    # several batch chunks at a pooled length of the large-n kernels (inside its bucket: the lower
+    # edges are the cases above)
+    B_chunks = max(C["QCH_SEQS"], C["ACH_SEQS"]) + 5
+    cases.append(_ig_case(3, 5, _length(C["MID_FUSED_MAX_N"] + 2, 5, 1), 2, B_chunks, "train"))
+    for B in ig_batch_edges():
+        cases.append(_ig_case(4, 5, _length(3, 5, B % C["POOLW"]), 2, B, "train"))
+    # eval: pooled positions one past ig_eval_dy's register chunk
+    cases.append(_ig_case(3, 5, _length(C["IG_WC"] + 1, 5, 4), 2, 6, "eval"))
+    cases.append(_ig_case(4, k_max, _ig_wmax_length(k_max, C["POOLW"] - 1), 2, 6, "train_dense"))
+    return cases
+
+
+IG_CASES = build_ig_cases()
+
+
+# ---- the head of a model bank (csrc/head.hip with Gm > 1) ---------------------------------------
+BankCase = collections.namedtuple("BankCase", "id G U k L T B paths seed")
+
+
+def _bank_case(G, U, T, B, paths=("step",), k=5, n=2):
+    L = _length(n, k, (T + B) % C["POOLW"])
+    return BankCase("bank-G%d-U%d-T%d-B%d-%s" % (G, U, T, B, "+".join(paths)), G, U, k, L, T, B, paths,
+                    (G * 977 + U * 131 + T * 17 + B) % 10007)
+
+
+def build_bank_cases():
+    regs = C["HEAD_RB"] * C["HEAD_THREADS"]
+    regs2 = C["HEAD_FWD_REGS2"] * C["HEAD_THREADS"]
+    t_in, t_gemm = C["HEAD_INREG_MAX_T"], C["HEAD_GEMM_MIN_T"]
+    cases = [
+        _bank_case(2, 4, 2, regs + 1, BOTH),              # looped body: fused loss and dlogits given
+        _bank_case(2, 4, t_in, regs, BOTH),               # the largest register-path batch
+    ]
+    for T in bank_task_edges():
+        cases.append(_bank_case(2, 4, T, 70))
+    cases.append(_bank_case(2, 4, t_gemm + 1, regs + 1))  # head_fwd_train regs<16>
+    cases.append(_bank_case(2, 4, t_gemm + 1, regs2 + 1))  # head_fwd_train's loop
+    cases.append(_bank_case(2, C["LOGITS_UNITS_TRIP"] + 1, t_gemm + 1, 70))
+    cases.append(_bank_case(2, C["LOGITS_BN_UNITS_TRIP"] + 1, 2, 70))
+    return cases
+
+
+BANK_CASES = build_bank_cases()
+# a bank at the unit limit, checked against its members on the single-model path: (G, Um, k, L, T, B)
+BANK_LIMIT = (C["BANK_MAX_UNITS"] // 8, 8, 5, _length(2, 5, 3), 1, 70)
+
+
+def bank_case_forms(c):
+    f = set()
+    for path in c.paths:
+        f |= head_forms(c.U, c.T, c.B, path, c.G)
+    return f
+
+
+def entry_forms(ism=None, ig=None, bank=None, limit=True):
+    """The forms the ISM, input-gradient and bank case lists reach."""
+    got = set()
+    for c in (ISM_CASES if ism is None else ism):
+        got |= ism_forms(c.U, c.k, c.L, c.T, c.B)
+    for c in (IG_CASES if ig is None else ig):
+        got |= ig_forms(c.U, c.k, c.L, c.T, c.B, c.mode)
+    for c in (BANK_CASES if bank is None else bank):
+        got |= bank_case_forms(c)
+    if limit:
+        G, Um, _, _, T, B = BANK_LIMIT
+        got |= head_forms(Um, T, B, "step", G)
     return got

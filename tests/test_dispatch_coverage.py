@@ -119,3 +119,118 @@ def test_sweep_ids_are_unique_and_shapes_are_legal():
     for c in dm.CASES:
         dm.case_forms(c)                        # raises for a shape the library refuses
         assert c.B >= 2 and dm.pooled_len(c.L, c.k) >= 1
+
+
+# ---- the entry points with launchers of their own: ISM, input gradient, the head of a bank --------
+ENTRY = dm.entry_forms()
+
+
+def _missing_entry(want):
+    return sorted(set(want) - ENTRY, key=repr)
+
+
+def test_ism_source_tables_agree():
+    ks = range(2, C["MAX_K"] + 1)
+    assert sorted({dm.ism_nw(k) for k in ks}) == C["ism_nw_cases"]
+    assert [tc for _, tc in C["ism_sum_rules"]] == sorted(tc for _, tc in C["ism_sum_rules"])
+    # every tile of input_grad_kernel finds its windows in IG_WMAX slots
+    assert max(dm.ig_max_windows(k) for k in ks) <= C["IG_WMAX"]
+    assert {dm.fc_ng(NQ) for NQ in C["buckets"]} == set(range(1, max(dm.fc_ng(NQ) for NQ in C["buckets"]) + 1))
+
+
+def test_every_ism_form():
+    want = [("ism_nw", NW) for NW in C["ism_nw_cases"]]
+    want += [("ism_k_edge", NW, e) for NW in C["ism_nw_cases"] for e in ("lower", "upper")]
+    # every task chunk at both sides of the thresholds and of the widest chunk, found by evaluating the rule
+    tc_max = C["ism_sum_rules"][-1][1]
+    Ts = {1, 2 * tc_max + 1}
+    for tmax, _ in C["ism_sum_rules"]:
+        Ts |= {tmax, tmax + 1} if tmax else {tc_max, tc_max + 1}
+    for T in Ts:
+        want += [f for f in dm.ism_forms(4, 5, 40, T, 3) if f[0] in ("ism_sum", "ism_sum_trips")]
+    assert {f[1] for f in want if f[0] == "ism_sum"} == {tc for _, tc in C["ism_sum_rules"]}
+    want += [("ism_subbatches", "one"), ("ism_subbatches", "several"), ("ism_n", 1)]
+    want += [("ism_tail", r) for r in range(C["POOLW"])]
+    assert not _missing_entry(want), _missing_entry(want)
+    # the second trip of the sub-batch loop is ragged and the sub-batch is the smallest one
+    sub = [c for c in dm.ISM_CASES if c.B > dm.ism_sub_batch(c.U, c.L, c.B)]
+    assert any(dm.ism_sub_batch(c.U, c.L, c.B) == C["ISM_SUB_STEP"] and c.B % C["ISM_SUB_STEP"] for c in sub)
+
+
+def test_every_input_grad_form():
+    want = [("ig", mode) for mode in ("eval", "train", "train_dense")]
+    ngs = sorted({dm.fc_ng(NQ) for NQ in C["buckets"] if dm.nq_lower(NQ) + 1 <= dm.max_legal_n()})
+    want += [("ig_ng", g) for g in ngs] + [("ig_ng_edge", g, "lower") for g in ngs]
+    want += [("ig_chunks", "several"), ("ig_chunks", "several", "big_n")]
+    want += [("ig_units", e) for e in ("partial_wave", "partial_pass", "several_passes")]
+    want += [("ig_batch", B) for B in dm.ig_batch_edges()]
+    want += [("ig_pos", "ragged"), ("ig_wc", "ragged"), ("ig_wc", "several")]
+    for mode in ("eval", "train"):
+        want += [("ig_units_edge", mode, U) for U in dm.ig_unit_edges()]
+        want += [("ig_k", mode, k) for k in (2, C["MAX_K"])] + [("ig_wmax", mode, k) for k in (2, C["MAX_K"])]
+        want += [("ig_n", mode, 1), ("ig_tail", mode, C["POOLW"] - 1)]
+    want += [("ig_k", "train_dense", C["MAX_K"]), ("ig_wmax", "train_dense", C["MAX_K"])]
+    assert not _missing_entry(want), _missing_entry(want)
+    # the widest filter meets the longest tail in one case, per mode
+    for mode in ("eval", "train"):
+        assert any({("ig_wmax", mode, C["MAX_K"]), ("ig_tail", mode, C["POOLW"] - 1)}
+                   <= dm.ig_forms(c.U, c.k, c.L, c.T, c.B, c.mode) for c in dm.IG_CASES), mode
+
+
+def _bank_wanted():
+    """Every head form a bank can take, found by evaluating the rules over the edges of their own
+    thresholds, at the member sizes a bank of two can have under the unit limit."""
+    regs = C["HEAD_RB"] * C["HEAD_THREADS"]
+    regs2 = C["HEAD_FWD_REGS2"] * C["HEAD_THREADS"]
+    Ts = {1} | set(dm.bank_task_edges())
+    Bs = {2, regs, regs + 1, regs2, regs2 + 1}
+    Us = {1, C["LOGITS_UNITS_TRIP"] + 1, C["LOGITS_BN_UNITS_TRIP"] + 1, C["BANK_MAX_UNITS"] // 2}
+    want = set()
+    for T in Ts:
+        for B in Bs:
+            for U in Us:
+                for path in ("autograd", "step"):
+                    want |= dm.head_forms(U, T, B, path, G=2)
+    return want
+
+
+def test_every_bank_head_branch():
+    want = _bank_wanted()
+    assert all(f[0] in ("bank", "bank_units_trip") for f in want), "a bank form is not tagged"
+    # a bank never rides in passA and never takes a GEMM
+    assert not [f for f in want if "gemm" in f or any(str(v).startswith("passA") for v in f)]
+    for branch in ("logits_bn", "regs%d" % C["HEAD_RB"], "regs%d" % C["HEAD_FWD_REGS2"], "loop"):
+        assert ("bank", "head_fwd", branch) in want
+    pairs = {f[2:] for f in want if f[:2] == ("bank", "head_bwd") and len(f) == 4}
+    assert {b for b, _ in pairs} == {"fused_loss", "bank_loss", "kernel"} and {b for _, b in pairs} == {"inreg", "loop"}
+    # t_edge carries the batch class of the case list: both sides of every task threshold below one block
+    want = {f for f in want if f[:2] != ("bank", "t_edge")}
+    want |= {("bank", "t_edge", T, "lt_block", "one_trip") for T in dm.bank_task_edges()}
+    want |= {("bank", "units", "limit"), ("bank_units_trip", "logits", "several"),
+             ("bank_units_trip", "logits_bn", "several")}
+    assert not _missing_entry(want), _missing_entry(want)
+
+
+def test_bank_logits_bn_lds_test_cannot_fail():
+    """Unreachable, and reported as such: logits_bn_kernel's LDS test compares ONE member's statistics
+    with the limit, and under BANK_MAX_UNITS no member of a bank (G >= 2) is large enough to fail it.
+    So with few tasks a bank always takes logits_bn_kernel; head_fwd_train + logits_kernel is reached
+    through T > HEAD_GEMM_MIN_T alone.  Raising the unit limit past this makes the branch live."""
+    um_fail = C["LOGITS_BN_LDS"] // C["LOGITS_BN_BYTES_PER_UNIT"] + 1
+    assert 2 * um_fail > C["BANK_MAX_UNITS"], "a bank can now fail the logits_bn LDS test: add a case"
+    few = {f for f in _bank_wanted() if f[:2] == ("bank", "head_fwd")}
+    for T in range(1, C["HEAD_GEMM_MIN_T"] + 1):
+        for Um in (1, C["BANK_MAX_UNITS"] // 2):
+            assert ("bank", "head_fwd", "logits_bn") in dm.head_forms(Um, T, 70, "step", G=2)
+    assert few                                                  # (the set the loop above narrows)
+
+
+def test_every_entry_case_is_needed():
+    """Taking any one case out of the ISM, input-gradient or bank lists loses a form."""
+    for name, cases in (("ism", dm.ISM_CASES), ("ig", dm.IG_CASES), ("bank", dm.BANK_CASES)):
+        ids = [c.id for c in cases]
+        assert len(ids) == len(set(ids)), name
+        for i, c in enumerate(cases):
+            rest = cases[:i] + cases[i + 1:]
+            lost = ENTRY - dm.entry_forms(**{name: rest})
+            assert lost, "%s adds no form of its own" % c.id

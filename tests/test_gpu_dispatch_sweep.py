@@ -14,6 +14,16 @@ tests/test_dispatch_coverage.py):
   G  base codes: eval logits from uint8 codes equal the one-hot path bit for bit (group A shapes)
   H  sizes explainn_create refuses
 
+The entry points with launchers of their own are swept in tests/test_gpu_entry_sweep.py from case lists
+the same model builds (dm.ISM_CASES, dm.IG_CASES, dm.BANK_CASES, dm.BANK_LIMIT):
+
+  ISM   ism_units_kernel<NW> at both kernel sizes of every NW, ism_sum_kernel's task chunks, one
+        window, two trips of the sub-batch loop
+  IG    input gradient: passB's fc_ng row groups, several batch chunks, unit / batch / kernel-size /
+        tail edges in eval, train and soft-input mode
+  bank  the head with Gm > 1: fused loss / bank_loss / given dlogits with register and looped bodies,
+        head_fwd_train's branches, second trips of the combiner's unit loops, the 2000-unit limit
+
 Each case runs one train step and the eval forward from the updated BatchNorm buffers.  Bounds are
 the suite's own (parity_util): logits 1e-4 absolute, gradients GRAD_TOL_ORACLE relative or 3x the
 error of the reference's fp32 arithmetic, buffers GRAD_TOL_ORACLE relative; B >= 2048 uses the

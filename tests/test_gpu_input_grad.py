@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from conftest import record_margin
 from oracle import explainn_oracle as orc
 from oracle import torch_ref
 from parity_util import KNIFE, model as make_model
@@ -32,18 +33,29 @@ def _knife_rows(sd, x, training, keep):
     return (y2 < KNIFE) | (y3 < KNIFE)
 
 
-def _check(got, sd, x, training, keep, dl, what):
+def _within_cap(knife):
+    """The knife-edge exclusion stays an exception: at most a quarter of the batch's sequences, and
+    at least two are compared."""
+    return knife.sum() <= len(knife) // 4 and (~knife).sum() >= 2
+
+
+def _check(got, sd, x, training, keep, dl, what, cap=False):
+    """cap: also require _within_cap of the excluded sequences (the cases of the entry sweep, whose
+    unit counts keep the exclusion rare; the full-size shapes above exclude more)."""
     ref = _ref_dx(sd, x, training, keep, dl, torch.float64)
     r32 = _ref_dx(sd, x, training, keep, dl, torch.float32)
     # a flip moves its own sequence by a channel's share; in train mode it also moves every other
     # sequence through the batch statistics, by ~1/B of that: those stay in
     rows = ~_knife_rows(sd, x, training, keep)
+    if cap:
+        assert _within_cap(~rows), "%s: %d of %d sequences hold a knife edge" % (what, (~rows).sum(), len(rows))
     scale = np.abs(ref).max()
     if scale == 0:                 # every unit's ReLU closed: the gradient is exactly zero
         assert np.abs(got).max() == 0, what
         return
     err = np.abs(got[rows] - ref[rows]).max() / scale
     err32 = np.abs(r32[rows] - ref[rows]).max() / scale
+    record_margin("input_grad %s vs oracle" % ("train" if training else "eval"), err, max(5e-5, 3 * err32))
     assert err <= max(5e-5, 3 * err32), "%s: dx error %.3g (torch fp32 %.3g)" % (what, err, err32)
 
 

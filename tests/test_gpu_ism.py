@@ -38,13 +38,14 @@ def _ism(m, x):
     return logits.cpu().numpy(), delta.cpu().numpy()
 
 
-def _device_brute(m, codes):
-    """delta from model(x) on all 4L substituted copies (reference rows come out 0)."""
+def _device_brute(m, codes, rows=None):
+    """delta from model(x) on all 4L substituted copies (reference rows come out 0); of the sequences
+    `rows` only when given (the base logits are always those of every sequence)."""
     B, L = codes.shape
     out = []
     with torch.no_grad():
         base = m(torch.tensor(codes, device="cuda")).cpu().numpy()
-        for b in range(B):
+        for b in (range(B) if rows is None else rows):
             mut = np.repeat(codes[b:b + 1], 4 * L, axis=0)
             for a in range(4):
                 mut[a * L + np.arange(L), np.arange(L)] = a
