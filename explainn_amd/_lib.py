@@ -17,6 +17,7 @@ METRICS_GLOBAL, METRICS_PER_TASK = 0, 1
 METRICS_BINARY, METRICS_LINEAR = 0, 1
 METRICS_NONFINITE, METRICS_NOT_BINARY = 1, 2
 SCAN_AUTO, SCAN_WINDOWS, SCAN_SHARED = 0, 1, 2
+SITES_TILE = 1024         # EXPLAINN_SITES_TILE: start positions per workgroup of explainn_call_sites
 
 _fp = C.c_void_p          # device pointers travel as integers (tensor.data_ptr())
 
@@ -106,6 +107,9 @@ SIGNATURES = {
     "explainn_stage_windows": (_i, [_ctx, _fp, _i64, _i64, _i64, _i, _i, _fp]),
     "explainn_scan_workspace_bytes": (_i64, [_ctx, _i64, _i64, _i]),
     "explainn_scan": (_i, [_ctx, _fp, _i64, _i64, _i64, _i64, _i, _pp, _fp, _i, _fp, _i64, _fp]),
+    "explainn_call_sites_workspace_bytes": (_i64, [_ctx, _i64]),
+    "explainn_call_sites": (_i, [_ctx, _fp, _i64, _i64, _i64, _i64, _i, _pp, _fp, _fp, _fp, _fp, _i64, _fp,
+                                 _i64, _fp]),
     "explainn_dense_input": (_i, [_ctx, _i]),
     "explainn_pwm_scan": (_i, [_fp, _i, _i, _fp, _i, _i, _i, _fp, _fp]),
     "explainn_adam_step": (_i, [_i, C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp),

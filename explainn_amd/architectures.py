@@ -665,6 +665,56 @@ class ExplaiNN(_Model):
             self._settle(read)
         return logits
 
+    def _launch_call_sites(self, codes, thresholds, start=0, n_positions=None, period=0,
+                           reverse_complement=False, capacity=0, pos=None, score=None):
+        """Motif sites of a device-resident 1-D uint8 sequence of base codes (explainn_call_sites):
+        every (unit, start position p in [start, start + n_positions)) whose float16 activation
+        exceeds thresholds[unit] (fp32 (units,), on the device).  Returns (offsets, pos, score) on the
+        device: offsets int64 (units+1), the exclusive scan of the full per-unit counts; pos int32
+        (start-relative) and score fp32 hold the first `capacity` records, unit by unit in ascending
+        position.  capacity 0 counts only (pos and score are None); pos / score may be given as
+        buffers of at least `capacity` elements.  n_positions None: every start the sequence holds."""
+        if self.training:
+            raise NotImplementedError("calling sites is an eval-mode export path; call model.eval()")
+        dev = self._device()
+        k, U = self._options["kernel_size"], self._units()
+        if not torch.is_tensor(codes) or codes.dtype != torch.uint8 or codes.dim() != 1 or \
+                not codes.is_contiguous():
+            raise RuntimeError("sites are called on a contiguous 1-D uint8 tensor of base codes")
+        if codes.device != dev:
+            raise RuntimeError("input is on %s but the model is on %s" % (codes.device, dev))
+        if not torch.is_tensor(thresholds) or tuple(thresholds.shape) != (U,) or \
+                thresholds.dtype != torch.float32 or thresholds.device != dev or not thresholds.is_contiguous():
+            raise RuntimeError("thresholds must be a contiguous float32 tensor of shape (%d,) on %s" % (U, dev))
+        if n_positions is None:
+            n_positions = max(codes.numel() - int(start) - k + 1, 0)
+        capacity = int(capacity)
+        offsets = torch.empty(U + 1, device=dev, dtype=torch.int64)
+        if capacity > 0:
+            if pos is None:
+                pos = torch.empty(capacity, device=dev, dtype=torch.int32)
+            if score is None:
+                score = torch.empty(capacity, device=dev, dtype=torch.float32)
+            for name, t, dt in (("pos", pos, torch.int32), ("score", score, torch.float32)):
+                if t.dtype != dt or t.device != dev or t.dim() != 1 or t.numel() < capacity or \
+                        not t.is_contiguous():
+                    raise RuntimeError("%s must be a contiguous 1-D %s tensor of at least %d elements on %s"
+                                       % (name, dt, capacity, dev))
+        else:
+            pos = score = None
+        with torch.cuda.device(dev):
+            win = SequenceWindows(codes, start, 1, 1, reverse_complement, 1)
+            ctx, ps, _, stream, xp, _ = self._front(win, dev)
+            lib, h = ctx.lib, ctx.handle
+            nbytes = int(lib.explainn_call_sites_workspace_bytes(h, int(n_positions)))
+            ws = torch.empty(max(nbytes, 1), device=dev, dtype=torch.uint8)
+            _lib.check(lib.explainn_call_sites(
+                h, xp, codes.numel(), int(start), int(n_positions), int(period), int(bool(reverse_complement)),
+                C.byref(ps), thresholds.data_ptr(), offsets.data_ptr(),
+                pos.data_ptr() if pos is not None else None, score.data_ptr() if score is not None else None,
+                capacity, ws.data_ptr(), nbytes, stream))
+        return offsets, pos, score
+
     def _launch_eval_keep(self, x):
         """Eval forward that keeps what _launch_input_grad needs (explainn_forward_eval_keep: the
         same logits as forward()).  The batch is validated first, so soft input takes the dense

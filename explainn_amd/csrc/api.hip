@@ -130,6 +130,20 @@ const char* const kStageNames[ST_COUNT] = {
 // (keep_B), a sync-BN step between phases (sync_next): their calls then fail with E_STATE.
 void drop_pending(explainn_ctx* c) { c->fwd_B = 0; c->tail_B = 0; c->keep_B = 0; c->sync_next = 0; }
 
+// The folded tables depend on the parameters only: rebuilt when the caller's parameter version
+// moved (or is unknown), not per batch -- predict.py's loop and a validation pass run pack +
+// filter bank + FC + head per batch and nothing else.
+int eval_tables(explainn_ctx* c, const explainn_params* p, int B, hipStream_t s) {
+    if (!(c->eval_valid && p->version != 0 && p->version == c->eval_version)) {
+        TRY(launch_prep1_tables(c, p, s));
+        TRY(launch_prep1(c, p, B, false, s));
+        TRY(launch_prep2(c, p, B, false, s));
+        c->eval_valid = true;
+        c->eval_version = p->version;
+    }
+    return EXPLAINN_OK;
+}
+
 int eval_front(explainn_ctx* c, const float* x, int B, const explainn_params* p, hipStream_t s) {
     // every eval-mode entry point overwrites scratch a pending backward would read (codes, ext,
     // idx, z, bits ...): whatever train forward was in flight is gone, and its backward must fail
@@ -141,17 +155,7 @@ int eval_front(explainn_ctx* c, const float* x, int B, const explainn_params* p,
     } else {
         TRY(launch_pack(c, x, B, false, s));
     }
-    // The folded tables depend on the parameters only: rebuilt when the caller's parameter version
-    // moved (or is unknown), not per batch -- predict.py's loop and a validation pass run pack +
-    // filter bank + FC + head per batch and nothing else.
-    if (!(c->eval_valid && p->version != 0 && p->version == c->eval_version)) {
-        TRY(launch_prep1_tables(c, p, s));
-        TRY(launch_prep1(c, p, B, false, s));
-        TRY(launch_prep2(c, p, B, false, s));
-        c->eval_valid = true;
-        c->eval_version = p->version;
-    }
-    return EXPLAINN_OK;
+    return eval_tables(c, p, B, s);
 }
 
 // The eval-mode forward of every entry point that runs the whole network: the dense or one-hot filter
@@ -499,6 +503,48 @@ extern "C" int explainn_scan(explainn_ctx* c, const uint8_t* seq, int64_t seq_le
     }
     c->staged_B = 0;
     return EXPLAINN_OK;
+}
+
+extern "C" int64_t explainn_call_sites_workspace_bytes(const explainn_ctx* c, int64_t n_positions) {
+    if (!c || n_positions < 0 || n_positions + c->k >= (int64_t)1 << 31) return 0;
+    return sites_workspace_bytes(c, n_positions);
+}
+
+extern "C" int explainn_call_sites(explainn_ctx* c, const uint8_t* seq, int64_t seq_len, int64_t start,
+                                   int64_t n_positions, int64_t period, int reverse_complement,
+                                   const explainn_params* p, const float* thresholds, int64_t* offsets,
+                                   int32_t* pos, float* score, int64_t capacity, void* workspace,
+                                   int64_t workspace_bytes, void* stream) {
+    if (!c) { explainn_set_error("null context"); return EXPLAINN_E_ARG; }
+    if (!seq || !p || !thresholds || !offsets) {
+        explainn_set_error("seq, params, thresholds and offsets are required");
+        return EXPLAINN_E_ARG;
+    }
+    if (start < 0 || n_positions < 0 || n_positions + c->k >= (int64_t)1 << 31 ||
+        seq_len - start < n_positions + c->k - 1) {
+        explainn_set_error("call_sites needs 0 <= start, start + n_positions + k - 1 <= seq_len and "
+                           "n_positions + k < 2^31 (start %lld, n_positions %lld, k %d, seq_len %lld)",
+                           (long long)start, (long long)n_positions, c->k, (long long)seq_len);
+        return EXPLAINN_E_ARG;
+    }
+    if (period < 0 || capacity < 0) { explainn_set_error("period and capacity must not be negative"); return EXPLAINN_E_ARG; }
+    if (c->dense) { explainn_set_error("sites are called on base codes: not in dense input mode"); return EXPLAINN_E_UNSUPPORTED; }
+    const int64_t need = sites_workspace_bytes(c, n_positions);
+    if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 255) != 0) {
+        explainn_set_error("call_sites workspace of %lld bytes (256-byte aligned), %lld needed",
+                           (long long)workspace_bytes, (long long)need);
+        return EXPLAINN_E_ARG;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    drop_pending(c);
+    c->staged_B = 0;                   // nothing is staged by this call; what was staged is not kept
+    TRY(eval_tables(c, p, 1, s));
+    if (n_positions == 0) {
+        HIP_TRY(hipMemsetAsync(offsets, 0, (size_t)(c->U + 1) * sizeof(int64_t), s));
+        return EXPLAINN_OK;
+    }
+    return launch_call_sites(c, seq, start, n_positions, period, reverse_complement ? 1 : 0, thresholds,
+                             offsets, pos, score, capacity, workspace, s);
 }
 
 extern "C" int explainn_filter_act_max(explainn_ctx* c, const float* x, int B,

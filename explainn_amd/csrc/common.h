@@ -211,6 +211,12 @@ int launch_scan_unfold(explainn_ctx* c, const float* track, int64_t blk_elems, i
 int64_t scan_track_block_elems(const explainn_ctx* c);
 int64_t scan_tiles(const explainn_ctx* c, int64_t n_windows, int m);
 
+// motif sites (sites.hip): the compacted (unit, position, score) list of a range of start positions
+int64_t sites_workspace_bytes(const explainn_ctx* c, int64_t npos);
+int launch_call_sites(explainn_ctx* c, const uint8_t* seq, int64_t start, int64_t npos, int64_t period,
+                      int rc, const float* thr, int64_t* offsets, int32_t* pos, float* score,
+                      int64_t capacity, void* workspace, hipStream_t s);
+
 int launch_dense_moments(explainn_ctx* c, const float* x, int B, hipStream_t s);
 int launch_dense_conv_pool(explainn_ctx* c, const float* x, const explainn_params* p, int B, hipStream_t s);
 int launch_dense_conv_bwd(explainn_ctx* c, const float* x, int B, hipStream_t s);

@@ -1,0 +1,202 @@
+// Calling motif sites ("Motif sites"): every (unit, start position) of a
+// device-resident sequence of base codes whose float16 activation exceeds the unit's threshold, as a
+// compacted list -- what the reference gets from the dense float16 (N,U,Lo) activation array with
+// np.where (interpret.py:375-429) and writes to sites/filter<u>.fa.
+//
+// In eval mode BatchNorm1 is folded, so a unit's activation at a position depends only on the k bases
+// under it: one gather pass over the codes, tile by tile, lists the hits of every unit without a
+// window ever being cut.  The sum is the chain of conv_act_kernel (convpool.hip) and site_kernel
+// (interpret.hip) -- from 0.f, taps in j order, fp32 -- which is what makes a site here a position
+// where float16(linears[:3]) > threshold, bit for bit.
+//
+// Block = (tile of SITES_TILE positions, unit quad).  Two passes of the same kernel recompute the
+// activations instead of storing them:
+//   COUNT  sites per (unit, tile)                                            -> cnt[u][tile]
+//   scan   per unit: exclusive scan of cnt over the tiles (in place), total  -> tot[u]
+//          then offsets[u] = exclusive scan of tot over the units (int64, [units + 1])
+//   EMIT   rank = offsets[u] + cnt[u][tile] + rank inside the tile (ballots and popcounts in thread =
+//          position order); records with rank >= capacity are dropped
+// so per unit the sites ascend in position and no rank depends on the order atomics arrive in.
+#include <hip/hip_fp16.h>
+
+#include "common.h"
+
+namespace {
+
+constexpr int SITES_T = 256;
+static_assert(EXPLAINN_SITES_TILE % SITES_T == 0, "a tile is a whole number of position chunks");
+
+enum { SITES_COUNT = 0, SITES_EMIT = 1 };
+
+// float32 activation -> the float16 value numpy stores (as interpret.hip)
+__device__ __forceinline__ float as_f16(float a) { return __half2float(__float2half_rn(a)); }
+
+template <int MODE>
+__global__ __launch_bounds__(SITES_T) void sites_kernel(
+    const uint8_t* __restrict__ seq, long long start, int npos, long long period, int rc,
+    const float* __restrict__ Wt, const float* __restrict__ alpha, const float* __restrict__ shift,
+    const float* __restrict__ thr, int* __restrict__ cnt, const long long* __restrict__ offsets,
+    int* __restrict__ pos, float* __restrict__ score, long long capacity, int U, int k, int ntiles,
+    int* __restrict__ flags) {
+    extern __shared__ float4 Wsm[];            // [k][5] | codes [SITES_TILE + k - 1] bytes
+    uint8_t* cs = reinterpret_cast<uint8_t*>(Wsm + k * 5);
+    __shared__ int wtot[4][SITES_T / 64];
+    const int tile = blockIdx.x, quad = blockIdx.y, tid = threadIdx.x;
+    const int wave = tid >> 6, lane = tid & 63;
+    const int t0 = tile * EXPLAINN_SITES_TILE;              // < npos < 2^31
+    const int live_n = min(EXPLAINN_SITES_TILE, npos - t0); // start positions of this tile
+    const float4* src = reinterpret_cast<const float4*>(Wt) + (size_t)quad * k * 5;
+    for (int i = tid; i < k * 5; i += SITES_T) Wsm[i] = src[i];
+    // the tile's bases and the k-1 behind its last start: all inside [start, start + npos + k - 1),
+    // which the entry point has checked against seq_len.  The reverse strand reads the complement.
+    int bad = 0;
+    const uint8_t* sp = seq + start + t0;
+    for (int i = tid; i < live_n + k - 1; i += SITES_T) {
+        int v = sp[i];
+        if (v > 4) { v = 4; bad = 1; }
+        cs[i] = (uint8_t)(rc && v < 4 ? 3 - v : v);
+    }
+    if (MODE == SITES_COUNT && quad == 0 && bad) atomicOr(flags, 1);
+    float al[4], sh[4], th[4];
+    long long base[4];
+#pragma unroll
+    for (int uu = 0; uu < 4; ++uu) {
+        const int u = min(quad * 4 + uu, U - 1);
+        al[uu] = alpha[u];
+        sh[uu] = shift[u];
+        th[uu] = thr[u];
+        base[uu] = MODE == SITES_EMIT ? offsets[u] + cnt[(size_t)u * ntiles + tile] : 0;
+    }
+    __syncthreads();
+    // forward: tap j meets cs[p + j]; reverse: the filter on rc(seq[p : p + k]) meets the
+    // complement of cs[p + k - 1 - j] (already complemented above)
+    const int first = rc ? k - 1 : 0, step = rc ? -1 : 1;
+    int run[4] = {0, 0, 0, 0};                 // sites of this tile in earlier position chunks
+    for (int p0 = 0; p0 < live_n; p0 += SITES_T) {
+        const int p = p0 + tid;
+        bool live = p < live_n;
+        // a start whose k-mer would cross the end of its record is never a site
+        if (period > 0 && (start + t0 + p) % period > period - k) live = false;
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (live) {
+            const uint8_t* cp = cs + p + first;
+            for (int j = 0; j < k; ++j) {
+                const float4 v = Wsm[j * 5 + cp[j * step]];
+                acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+            }
+        }
+        const float av[4] = {acc.x, acc.y, acc.z, acc.w};
+        float a16[4];
+        bool hit[4];
+        int pre[4];
+#pragma unroll
+        for (int uu = 0; uu < 4; ++uu) {
+            a16[uu] = live ? as_f16(qval(al[uu], av[uu], sh[uu])) : 0.f;
+            hit[uu] = live && a16[uu] > th[uu];
+            const unsigned long long bal = __ballot(hit[uu]);
+            pre[uu] = __popcll(bal & ((1ull << lane) - 1ull));
+            if (lane == 0) wtot[uu][wave] = __popcll(bal);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int uu = 0; uu < 4; ++uu) {
+            int before = 0, total = 0;
+#pragma unroll
+            for (int w = 0; w < SITES_T / 64; ++w) {
+                const int t = wtot[uu][w];
+                before += w < wave ? t : 0;
+                total += t;
+            }
+            if (MODE == SITES_EMIT && hit[uu] && quad * 4 + uu < U) {
+                const long long rank = base[uu] + run[uu] + before + pre[uu];
+                if (rank < capacity) {
+                    pos[rank] = t0 + p;
+                    if (score) score[rank] = a16[uu];
+                }
+            }
+            run[uu] += total;
+        }
+        __syncthreads();                       // wtot is rewritten by the next chunk
+    }
+    if (MODE == SITES_COUNT && tid < 4 && quad * 4 + tid < U)
+        cnt[(size_t)(quad * 4 + tid) * ntiles + tile] = run[tid];
+}
+
+// One wavefront per unit: cnt[u][.] <- its exclusive scan over the tiles, tot[u] <- the unit's sites.
+// A unit has fewer than 2^31 sites (one per position at most), so the in-unit prefix stays int.
+__global__ __launch_bounds__(64) void sites_scan_tiles_kernel(int* __restrict__ cnt,
+                                                              long long* __restrict__ tot, int ntiles) {
+    const int u = blockIdx.x, lane = threadIdx.x;
+    int* row = cnt + (size_t)u * ntiles;
+    int running = 0;
+    for (int b0 = 0; b0 < ntiles; b0 += 64) {
+        const int b = b0 + lane;
+        const int v = b < ntiles ? row[b] : 0;
+        int inc = v;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int t = __shfl_up(inc, o, 64);
+            if (lane >= o) inc += t;
+        }
+        if (b < ntiles) row[b] = running + (inc - v);
+        running += __shfl(inc, 63, 64);
+    }
+    if (lane == 0) tot[u] = running;
+}
+
+// One wavefront: offsets[0 .. U] <- exclusive scan of the units' totals.
+__global__ __launch_bounds__(64) void sites_scan_units_kernel(const long long* __restrict__ tot,
+                                                              long long* __restrict__ offsets, int U) {
+    const int lane = threadIdx.x;
+    long long running = 0;
+    for (int u0 = 0; u0 < U; u0 += 64) {
+        const int u = u0 + lane;
+        const long long v = u < U ? tot[u] : 0;
+        long long inc = v;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const long long t = __shfl_up(inc, o, 64);
+            if (lane >= o) inc += t;
+        }
+        if (u < U) offsets[u] = running + (inc - v);
+        running += __shfl(inc, 63, 64);
+    }
+    if (lane == 0) offsets[U] = running;
+}
+
+int64_t align256(int64_t v) { return (v + 255) & ~int64_t(255); }
+int64_t sites_tiles(int64_t npos) { return (npos + EXPLAINN_SITES_TILE - 1) / EXPLAINN_SITES_TILE; }
+
+}  // namespace
+
+// the caller's workspace: cnt int [U][tiles] | tot int64 [U]
+int64_t sites_workspace_bytes(const explainn_ctx* c, int64_t npos) {
+    return align256((int64_t)c->U * sites_tiles(npos) * (int64_t)sizeof(int)) +
+           align256((int64_t)c->U * (int64_t)sizeof(long long));
+}
+
+int launch_call_sites(explainn_ctx* c, const uint8_t* seq, int64_t start, int64_t npos, int64_t period,
+                      int rc, const float* thr, int64_t* offsets, int32_t* pos, float* score,
+                      int64_t capacity, void* workspace, hipStream_t s) {
+    const int ntiles = (int)sites_tiles(npos);
+    int* cnt = static_cast<int*>(workspace);
+    long long* tot = reinterpret_cast<long long*>(static_cast<char*>(workspace) +
+                                                  align256((int64_t)c->U * ntiles * (int64_t)sizeof(int)));
+    long long* off = reinterpret_cast<long long*>(offsets);
+    const size_t sm = (size_t)c->k * 5 * sizeof(float4) + ((EXPLAINN_SITES_TILE + c->k - 1 + 15) & ~15);
+    const dim3 grid(ntiles, c->Uq);
+    hipLaunchKernelGGL(sites_kernel<SITES_COUNT>, grid, dim3(SITES_T), sm, s, seq, (long long)start, (int)npos,
+                       (long long)period, rc, c->Wt, c->alpha, c->shift, thr, cnt, (const long long*)nullptr,
+                       (int*)nullptr, (float*)nullptr, 0ll, c->U, c->k, ntiles, c->flags);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(sites_scan_tiles_kernel, dim3(c->U), dim3(64), 0, s, cnt, tot, ntiles);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(sites_scan_units_kernel, dim3(1), dim3(64), 0, s, tot, off, c->U);
+    LAUNCH_CHECK();
+    if (pos == nullptr || capacity <= 0) return EXPLAINN_OK;
+    hipLaunchKernelGGL(sites_kernel<SITES_EMIT>, grid, dim3(SITES_T), sm, s, seq, (long long)start, (int)npos,
+                       (long long)period, rc, c->Wt, c->alpha, c->shift, thr, cnt, off, pos, score,
+                       (long long)capacity, c->U, c->k, ntiles, c->flags);
+    LAUNCH_CHECK();
+    return EXPLAINN_OK;
+}

@@ -160,6 +160,75 @@ def filter_pwms(exp_model, Xs, idxs, rev_complement=False, batch_size=1024, site
             "nsites": site_total.cpu().numpy().astype(np.int64), "hit": hit}
 
 
+def _onehot_to_codes(x):
+    """(M,4,L) one-hot -> (M,L) uint8 base codes; a column that is not one-hot (all-zero = N) -> 4."""
+    x = np.asarray(x)
+    onehot = (x.max(axis=1) == 1) & (x.sum(axis=1) == 1)
+    return np.where(onehot, x.argmax(axis=1), 4).astype(np.uint8)
+
+
+def filter_site_list(exp_model, Xs, idxs, thresholds, rev_complement=False, site_cap=SITE_CAP):
+    """The site lists behind filter_pwms' count matrices (interpret.py:375-429): for every unit the
+    first site_cap sites as an int64 (n,3) array of (sequence index, position, strand).
+
+    Xs, idxs, rev_complement as in filter_pwms; thresholds: (U,), e.g. filter_pwms(...)["thresholds"].
+    The selected rows are gathered in idxs order -- with rev_complement the rows of the reverse half
+    (idxs + N/2) follow those of the forward half, as the reference iterates -- and flattened to one
+    code sequence on which sites.call_sites runs with period = L: a site never crosses two rows.
+    Sequence index is the value from idxs; strand is +1 for a forward-half row and -1 for a
+    reverse-half row, whose position counts along that (already reverse-complemented) row."""
+    from .sites import call_sites
+    L = exp_model._options["sequence_length"]
+    idxs = np.asarray(idxs, dtype=np.int64)
+    half = len(Xs) // 2 if rev_complement else len(Xs)
+    rows = np.concatenate([idxs, idxs + half]) if rev_complement else idxs
+    U = exp_model._units()
+    if len(rows) == 0:
+        return [np.zeros((0, 3), dtype=np.int64) for _ in range(U)]
+    X = Xs.cpu().numpy() if torch.is_tensor(Xs) else np.asarray(Xs)
+    codes = _onehot_to_codes(X[rows]).reshape(-1)
+    was_training = exp_model.training
+    exp_model.eval()
+    try:
+        calls = call_sites(exp_model, codes, np.asarray(thresholds, dtype=np.float32), strands="fwd", period=L)
+    finally:
+        exp_model.train(was_training)
+    out = []
+    for u in range(U):
+        start = calls.unit(u)[0][:site_cap]
+        row = start // L
+        out.append(np.stack([idxs[row % len(idxs)], start % L,
+                             np.where(row < len(idxs), 1, -1)], axis=1).astype(np.int64))
+    return out
+
+
+def site_kmers(Xs, site_list_u, k, rev_complement=False):
+    """The k-mer under every site of one unit's list (filter_site_list), read from the row the site was
+    found on (the reverse-half row for strand -1); a column that is not one-hot prints as N."""
+    half = len(Xs) // 2 if rev_complement else len(Xs)
+    X = Xs.cpu().numpy() if torch.is_tensor(Xs) else np.asarray(Xs)
+    letters = np.frombuffer(b"ACGTN", dtype=np.uint8)
+    out = []
+    for idx, p, strand in site_list_u:
+        row = idx + (half if strand < 0 else 0)
+        out.append(letters[_onehot_to_codes(X[row:row + 1, :, p:p + k])[0]].tobytes().decode())
+    return out
+
+
+def write_sites(output_dir, site_lists, kmers, thresholds):
+    """The --sites outputs: thresholds.tsv (`filter`, `threshold`: the input of `python -m
+    explainn_amd.sites`) and sites/filter<u>.fa, one k-mer per site in list order
+    (interpret.py:375-429).  biopython is not available in this image, so the record header
+    ('><sequence index>_<strand>_<position>') is a plain restatement and is not pinned by a fixture."""
+    from .sites import write_thresholds
+    os.makedirs(os.path.join(output_dir, "sites"), exist_ok=True)
+    write_thresholds(os.path.join(output_dir, "thresholds.tsv"), thresholds)
+    for u, (lst, kms) in enumerate(zip(site_lists, kmers)):
+        with open(os.path.join(output_dir, "sites", "filter%d.fa" % u), "wt") as fh:
+            for (idx, p, strand), kmer in zip(lst, kms):
+                fh.write(">%d_%s_%d\n%s\n" % (idx, "+" if strand > 0 else "-", p, kmer))
+
+
 def input_gradients(model, Xs, target=None, batch_size=4096, rev_complement=False, times_input=False):
     """Eval-mode input gradients (N,4,L), float32 numpy: d logit[target] / d x -- or d sum(logits)
     / d x with target=None -- for every sequence, what `x.requires_grad_(); model(x)[:, t].sum()
@@ -281,9 +350,10 @@ def format_jaspar(pfm_u, matrix_id, name):
 
 
 def interpret(exp_model, seqs, labels, name, output_dir="./", batch_size=100, rev_complement=False,
-              input_data=None):
+              input_data=None, sites=False):
     """The filter-level part of interpret.py's main (interpret.py:128-235): output-layer weights,
-    filter importances and one JASPAR motif per filter, written under output_dir."""
+    filter importances and one JASPAR motif per filter, written under output_dir.  sites=True also
+    writes thresholds.tsv and sites/filter<u>.fa (write_sites)."""
     import pandas as pd
     if input_data is None:
         input_data = "binary" if np.unique(labels[:, 0]).size == 2 else "linear"
@@ -310,6 +380,11 @@ def interpret(exp_model, seqs, labels, name, output_dir="./", batch_size=100, re
         with open(os.path.join(output_dir, "motifs", "filter%d.jaspar" % u), "wt") as fh:
             if res["nsites"][u] > 0:          # the reference leaves the file empty when no site
                 fh.write(format_jaspar(res["pfm"][u], "filter%d" % u, name))
+    if sites:
+        k = exp_model._options["kernel_size"]
+        lists = filter_site_list(exp_model, seqs, idxs, res["thresholds"], rev_complement)
+        write_sites(output_dir, lists, [site_kmers(seqs, lst, k, rev_complement) for lst in lists],
+                    res["thresholds"])
     return res
 
 
@@ -326,11 +401,14 @@ def main(argv=None):
     ap.add_argument("-o", "--output-dir", default="./")
     ap.add_argument("-r", "--rev-complement", action="store_true")
     ap.add_argument("-t", "--time-me", action="store_true")
+    ap.add_argument("--sites", action="store_true",
+                    help="also write thresholds.tsv and sites/filter<u>.fa (one k-mer per site)")
     args = ap.parse_args(argv)
     t0 = time.time()
     seqs, labels, _ = _get_seqs_labels_ids(args.training_file, args.debugging, args.rev_complement)
     model = _load_model(args.model_file)
-    interpret(model, seqs, labels, args.name, args.output_dir, args.batch_size, args.rev_complement)
+    interpret(model, seqs, labels, args.name, args.output_dir, args.batch_size, args.rev_complement,
+              sites=args.sites)
     if args.time_me:
         with open(os.path.join(args.output_dir, "time-interpret.py.txt"), "wt") as fh:
             fh.write("%.2f seconds" % (time.time() - t0))

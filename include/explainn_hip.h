@@ -288,6 +288,40 @@ int explainn_scan(explainn_ctx* ctx, const uint8_t* seq, int64_t seq_len, int64_
                   int64_t stride, int reverse_complement, const explainn_params* p, float* logits, int mode,
                   void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Calling motif sites: every (unit, start position) of a device-resident sequence of base codes
+ * (0..3 = ACGT, 4 = N, as explainn_scan takes it) whose eval-mode activation, rounded to float16 as
+ * the reference stores it, exceeds the unit's threshold -- the positions np.where finds in the dense
+ * float16 activation array (interpret.py:375-429), without that array.  For unit u and start p
+ *     a16(u,p) = float16(exp(alpha[u] * sum_{j<k} w[u][j][seq[p+j]] + shift[u]))
+ * (the value model.linears[:3] gives at that position of any window that holds the k-mer, bit for
+ * bit; N contributes 0), and (u,p) is a site when a16 > thresholds[u].  The call covers the starts
+ * p = start .. start + n_positions - 1.  With reverse_complement != 0 the activation at p is that of
+ * the filter on the reverse complement of seq[p : p+k] -- what the forward pass gives at position
+ * len-k-p of the reverse-complemented sequence; positions stay in forward coordinates.  period > 0:
+ * seq is a concatenation of records of `period` bases, and a start with p mod period > period - k (its
+ * k-mer would cross a record boundary) is never a site.  A byte above 4 reads as N and raises bit 0 of
+ * explainn_input_flags.
+ *
+ * units = the context's filter-bank width (G*U on a bank context); thresholds: fp32 [units], device.
+ * offsets: int64 [units+1], device, always written: the exclusive scan of the FULL per-unit site
+ * counts.  pos (int32, start-relative) and score (a16 as fp32; may be NULL): record offsets[u] + r is
+ * the r-th site of unit u in ascending position; records with index >= capacity are not written
+ * (offsets still tells the truth).  pos == NULL: count only.  The order is a function of the input
+ * alone (counts and scans; no rank depends on the arrival order of an atomic).
+ * workspace: device memory, 256-byte aligned, of explainn_call_sites_workspace_bytes(ctx, n_positions)
+ * bytes.  No host synchronisation, no allocation.  EXPLAINN_E_ARG unless 0 <= start,
+ * start + n_positions + k - 1 <= seq_len and n_positions + k < 2^31.  Like every eval entry point it
+ * ends a pending train forward, rebuilds the folded tables only when params->version moved, and
+ * leaves no staged batch behind.  Dense input mode: EXPLAINN_E_UNSUPPORTED.
+ * EXPLAINN_SITES_TILE: start positions per workgroup (tests place their sequence ends around it). */
+#define EXPLAINN_SITES_TILE 1024
+int64_t explainn_call_sites_workspace_bytes(const explainn_ctx* ctx, int64_t n_positions);
+int explainn_call_sites(explainn_ctx* ctx, const uint8_t* seq, int64_t seq_len, int64_t start,
+                        int64_t n_positions, int64_t period, int reverse_complement,
+                        const explainn_params* p, const float* thresholds, int64_t* offsets, int32_t* pos,
+                        float* score, int64_t capacity, void* workspace, int64_t workspace_bytes,
+                        void* stream);
+
 /* The fp32 one-hot packed into the context ahead of the forward: like explainn_stage_codes, the
  * entry points then take x == NULL.  Lets the caller read explainn_input_flags BEFORE anything
  * depends on the batch -- and route a batch that is not one-hot to the dense kernels (next entry)
