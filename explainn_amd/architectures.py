@@ -155,6 +155,56 @@ class SequenceWindows:
         return (self.sub_batch, None)
 
 
+class EditedWindows:
+    """Windows of ONE device-resident sequence of base codes (1-D uint8) at arbitrary starts, each with
+    at most one edit spliced in, as ExplaiNN._launch_score_edits takes them (explainn_score_edits,
+    include/explainn_hip.h has the row definition).  All tables are contiguous tensors on the codes'
+    device: row_start int64 (rows,), row_edit int32 (rows,) with -1 = no edit; pos int64, ref_len /
+    alt_len / alt_off int32 (edits,); alt uint8, the pool of alt base codes.  `sub_batch` rows run per
+    device pass."""
+
+    _TABLES = (("row_start", torch.int64), ("row_edit", torch.int32), ("pos", torch.int64),
+               ("ref_len", torch.int32), ("alt_len", torch.int32), ("alt_off", torch.int32), ("alt", torch.uint8))
+
+    def __init__(self, codes, row_start, row_edit, pos, ref_len, alt_len, alt_off, alt,
+                 reverse_complement=False, sub_batch=4096):
+        self.codes = codes
+        self.row_start, self.row_edit = row_start, row_edit
+        self.pos, self.ref_len, self.alt_len, self.alt_off, self.alt = pos, ref_len, alt_len, alt_off, alt
+        self.reverse_complement = bool(reverse_complement)
+        self.n_rows = int(row_start.numel())
+        self.sub_batch = max(1, min(int(sub_batch), self.n_rows))
+
+    @property
+    def shape(self):
+        """(sequences per device pass, L): what _front sizes the context by."""
+        return (self.sub_batch, None)
+
+    def check(self, dev):
+        c = self.codes
+        if not torch.is_tensor(c) or c.dtype != torch.uint8 or c.dim() != 1 or not c.is_contiguous():
+            raise RuntimeError("edited windows take a contiguous 1-D uint8 tensor of base codes")
+        if c.device != dev:
+            raise RuntimeError("input is on %s but the model is on %s" % (c.device, dev))
+        for name, dt in self._TABLES:
+            t = getattr(self, name)
+            if not torch.is_tensor(t) or t.dtype != dt or t.dim() != 1 or not t.is_contiguous() or t.device != dev:
+                raise RuntimeError("%s must be a contiguous 1-D %s tensor on %s" % (name, dt, dev))
+        if self.row_edit.numel() != self.n_rows:
+            raise RuntimeError("row_start and row_edit must have one entry per row")
+        if not self.pos.numel() == self.ref_len.numel() == self.alt_len.numel() == self.alt_off.numel():
+            raise RuntimeError("pos, ref_len, alt_len and alt_off must have one entry per edit")
+
+    def struct(self):
+        """The explainn_edits of these tables (valid while this object lives)."""
+        ed = _lib.Edits()
+        for name, _ in self._TABLES:
+            t = getattr(self, name)
+            setattr(ed, name, t.data_ptr() if t.numel() else None)
+        ed.n_edits, ed.alt_bytes = self.pos.numel(), self.alt.numel()
+        return ed
+
+
 VALIDATE_EVERY = 64      # deferred input validation: the sticky device flag is read every this many calls
 
 # How ExplaiNN._stage treats an fp32 batch (base codes are always staged):
@@ -528,7 +578,7 @@ class ExplaiNN(_Model):
           VALIDATE_FIRST  always validated as above;
           ONEHOT_ONLY     staged and validated; dense_input or a batch that is not one-hot raises."""
         lib, h = ctx.lib, ctx.handle
-        if isinstance(x, SequenceWindows):
+        if isinstance(x, (SequenceWindows, EditedWindows)):
             # base codes that the entry point stages itself, sub-batch by sub-batch: the flag stays
             # sticky for _settle, as for BaseCodes
             self._rt.calls += 1
@@ -664,6 +714,26 @@ class ExplaiNN(_Model):
                                          ws.data_ptr(), nbytes, stream))
             self._settle(read)
         return logits
+
+    def _launch_score_edits(self, ew, want_outs=False):
+        """Eval-mode logits of the rows of an EditedWindows (explainn_score_edits): (rows, T) --
+        (rows, G, T) on a bank -- fp32 on the device; with want_outs also the per-unit outputs
+        (rows, units), units = G*U on a bank, from the same pass: returns (logits, outs)."""
+        if self.training:
+            raise RuntimeError("scoring edits is an eval-mode path; call model.eval()")
+        dev = self._device()
+        ew.check(dev)
+        logits = self._logits_empty(ew.n_rows, dev)
+        outs = torch.empty(ew.n_rows, self._units(), device=dev, dtype=torch.float32) if want_outs else None
+        if ew.n_rows > 0:
+            with torch.cuda.device(dev):
+                ctx, ps, _, stream, xp, read = self._front(ew, dev)
+                ed = ew.struct()
+                _lib.check(ctx.lib.explainn_score_edits(
+                    ctx.handle, xp, ew.codes.numel(), C.byref(ed), ew.n_rows, int(ew.reverse_complement),
+                    C.byref(ps), logits.data_ptr(), outs.data_ptr() if want_outs else None, stream))
+                self._settle(read)
+        return (logits, outs) if want_outs else logits
 
     def _launch_call_sites(self, codes, thresholds, start=0, n_positions=None, period=0,
                            reverse_complement=False, capacity=0, pos=None, score=None):

@@ -13,15 +13,15 @@
 // is the slice [m*i, m*i + n) of ONE pooled track, which the filter bank computes once, on tiles
 // (windows of the same length L placed 7n apart: tile j's pooled value w is track entry n*j + w).
 #include "common.h"
+#include "stage_tile.h"
 
-#define SW_WAVES 8          // wavefronts per stage_windows block (64 rows x 64 positions), as PACK_WAVES
 // Rows of one block overlap in the sequence when |step| < 64: the bytes the block needs are then one
 // run of 63*|step| + 64 <= SW_SEG bytes, read once, coalesced, into LDS.  With |step| >= 64 the rows'
 // 64-byte runs are disjoint: each wave reads its rows' runs directly (64 contiguous bytes per load).
 #define SW_SEG 4096
 
 // Must write exactly what pack_tile<true> (pack.hip) writes for the materialised matrix: codesT, pk2,
-// nmask, bm and the flag; the second half below is that function's, on the same 64 x 64 tile.
+// nmask, bm and the flag; the second half (stage_tile.h) is that function's, on the same 64 x 64 tile.
 __global__ __launch_bounds__(64 * SW_WAVES) void stage_windows_kernel(
     const uint8_t* __restrict__ seq, long long seq_len, long long start0, long long step, int rc,
     uint8_t* __restrict__ codesT, uint32_t* __restrict__ pk2, uint32_t* __restrict__ nmask, int B, int L,
@@ -78,42 +78,7 @@ __global__ __launch_bounds__(64 * SW_WAVES) void stage_windows_kernel(
         }
     }
     __syncthreads();
-    for (int pp = q; pp < 64; pp += SW_WAVES) {
-        const int po = p0 + pp;
-        if (po < L) codesT[(size_t)po * Bs + b0 + lane] = tile[lane][pp];
-    }
-    if (q < 4) {
-        uint32_t w2 = 0, nm = 0;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const uint32_t c = tile[lane][16 * q + i];
-            w2 |= (c > 3u ? 1u : c) << (2 * i);
-        }
-        const int wi = (p0 >> 4) + q;
-        if (wi < PW) pk2[(size_t)wi * Bs + b0 + lane] = w2;
-        if (q < 2) {
-#pragma unroll
-            for (int i = 0; i < 32; ++i) nm |= (tile[lane][32 * q + i] > 3u ? 1u : 0u) << i;
-            const int ni = (p0 >> 5) + q;
-            if (ni < NW) nmask[(size_t)ni * Bs + b0 + lane] = nm;
-        }
-    }
-    if (bm != nullptr && q >= SW_WAVES - 4) {
-        const int qq = q - (SW_WAVES - 4);
-        const bool live = b0 + lane < B;
-        unsigned long long mine = 0ull;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const uint32_t c = tile[lane][16 * qq + i];
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                const unsigned long long bal = __ballot(live && c == (uint32_t)a);
-                mine = (lane == 16 * a + i) ? bal : mine;
-            }
-        }
-        const int a = lane >> 4, pq = p0 + 16 * qq + (lane & 15);
-        if (pq < Lp) bm[((size_t)a * ((B + 63) / 64) + bx) * Lp + pq] = mine;
-    }
+    stage_tile_store(tile, lane, q, bx, b0, p0, codesT, pk2, nmask, B, L, Bs, PW, NW, bm, Lp);
     if (bad) atomicOr(flags, 1);
 }
 

@@ -1,0 +1,320 @@
+"""What does this variant do?  Reference and alternative allele of SNVs and short indels, scored on
+the device.
+
+The reference has no such entry point: its users build both haplotype windows of every variant on the
+host, transfer a (2V, L) matrix for 1-byte edits and call predict.py; in-silico mutagenesis computes
+all 3L substitutions of a window where one is asked for, and cannot express an indel.  Here the
+sequence goes to the device once as base codes (1 byte per base); a row table (window start, edit
+index) and an edit table (pos, ref_len, alt_len, alt bases) follow, 12 bytes per row and 20 per
+variant, and the windows are cut and edited there (explainn_score_edits, include/explainn_hip.h).
+
+    res = score_variants(model, codes, pos, ref_len, alts, shifts=range(7), unit_effects=True)
+    res["delta"]     # (V, T): alt - ref, strands and window placements averaged
+    res["units"]     # (V, units, T): the units (motifs) that carry it; sums to delta over units
+
+MaxPool1d(7,7) puts its grid at the window start, so a variant's effect depends on its phase mod 7
+inside the window: `shifts` slides the window (both alleles alike) and the scores are averaged.
+
+`python -m explainn_amd.variants MODEL FASTA VCF` writes one TSV row per variant and class.
+"""
+import argparse
+import contextlib
+import sys
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from .architectures import EditedWindows
+
+_CHUNK_PASSES = 32           # rows per device call, at most: this many sub-batches of `batch_size` rows
+_MAX_POOL = (1 << 31) - 1    # bytes the alt pool may hold (explainn_edits.alt_bytes < 2^31)
+
+Variant = namedtuple("Variant", "chrom pos id ref alt")      # pos 0-based; ref / alt as written in the file
+
+
+def window_start(pos, ref_len, alt_len, L, shift=0):
+    """Start of the window both alleles of a variant are scored in: the longer allele is centred
+    (then slid by `shift`).  The start is left of `pos` or at it, so it means the same base on both
+    haplotypes: the left flank is identical, and after an indel the right flank slides."""
+    return pos - (L - np.maximum(ref_len, alt_len)) // 2 + shift
+
+
+def build_tables(pos, ref_len, alts, L, shifts=(0,)):
+    """The tables of explainn_score_edits for V variants and S shifts, as numpy arrays:
+    row_start int64 / row_edit int32 of 2*V*S rows -- row (v*S + s)*2 is the reference window of variant
+    v at shift s (row_edit -1), the next row its alternative allele (row_edit v) -- and one edit per
+    variant: pos int64, ref_len / alt_len / alt_off int32, alt uint8 (the alt alleles end to end)."""
+    pos = np.asarray(pos, dtype=np.int64).reshape(-1)
+    ref_len = np.asarray(ref_len, dtype=np.int64).reshape(-1)
+    V = len(pos)
+    if len(ref_len) != V or len(alts) != V:
+        raise ValueError("pos, ref_len and alts must have one entry per variant")
+    shifts = np.asarray(list(shifts), dtype=np.int64)
+    if shifts.size == 0:
+        raise ValueError("shifts must hold at least one window placement")
+    alts = [np.asarray(a, dtype=np.uint8).reshape(-1) for a in alts]
+    alt_len = np.fromiter((len(a) for a in alts), dtype=np.int64, count=V)
+    if (ref_len < 0).any():
+        raise ValueError("ref_len must not be negative")
+    alt = np.concatenate(alts) if V else np.zeros(0, dtype=np.uint8)
+    if alt.size > _MAX_POOL or (V and max(int(ref_len.max()), int(alt_len.max())) > _MAX_POOL):
+        raise ValueError("alleles of %d bytes exceed the alt pool's limit of 2^31 - 1" % alt.size)
+    alt_off = np.cumsum(alt_len) - alt_len
+    start = window_start(pos, ref_len, alt_len, L)[:, None] + shifts[None, :]          # (V,S)
+    row_start = np.repeat(start.reshape(-1), 2)
+    row_edit = np.stack((np.full((V, len(shifts)), -1, dtype=np.int64),
+                         np.broadcast_to(np.arange(V, dtype=np.int64)[:, None], (V, len(shifts)))), axis=-1)
+    return {"row_start": row_start, "row_edit": row_edit.reshape(-1).astype(np.int32), "pos": pos,
+            "ref_len": ref_len.astype(np.int32), "alt_len": alt_len.astype(np.int32),
+            "alt_off": alt_off.astype(np.int32), "alt": alt.astype(np.uint8)}
+
+
+def chunks(n_variants, n_shifts, limit_rows):
+    """[(first variant, count), ...]: the variants in runs whose 2*n_shifts*count rows stay within
+    limit_rows (one variant where even that does not fit).  A variant's rows never straddle a run, so a
+    run's shifts are averaged on the device; the rows of the runs are exactly the rows of the whole."""
+    per = max(1, int(limit_rows) // (2 * n_shifts))
+    return [(v0, min(per, n_variants - v0)) for v0 in range(0, n_variants, per)]
+
+
+def _check_ref_alleles(codes_d, pos, ref_len, check_ref):
+    """VCF REF alleles against codes[pos : pos + ref_len], compared on the device."""
+    V = len(pos)
+    if len(check_ref) != V:
+        raise ValueError("check_ref must have one allele per variant")
+    refs = [np.asarray(r, dtype=np.uint8).reshape(-1) for r in check_ref]
+    lens = np.fromiter((len(r) for r in refs), dtype=np.int64, count=V)
+    wrong = np.flatnonzero(lens != ref_len)
+    if wrong.size == 0 and lens.sum() > 0:
+        owner = np.repeat(np.arange(V, dtype=np.int64), lens)
+        within = np.arange(lens.sum(), dtype=np.int64) - np.repeat(np.cumsum(lens) - lens, lens)
+        dev = codes_d.device
+        at = torch.from_numpy(pos[owner] + within).to(dev)
+        differ = codes_d[at] != torch.from_numpy(np.concatenate(refs)).to(dev)
+        wrong = np.unique(owner[differ.cpu().numpy()])
+    if wrong.size:
+        raise ValueError("%d variant(s) whose REF allele is not what the sequence holds at pos; the first: %s"
+                         % (wrong.size, ", ".join("#%d at %d" % (v, pos[v]) for v in wrong[:5])))
+
+
+def _final_rows(model):
+    """final.weight as (T, units) with global unit indices: a bank's (G,T,U) member by member."""
+    w = model.final.weight.detach()
+    return w if w.dim() == 2 else w.permute(1, 0, 2).reshape(w.shape[1], -1)
+
+
+def score_variants(model, codes, pos, ref_len, alts, shifts=(0,), strands="both", batch_size=4096,
+                   check_ref=None, unit_effects=False, apply_sigmoid=False, chunk_rows=None):
+    """Eval-mode predictions of the reference and the alternative allele of V variants of one sequence.
+
+    codes: 1-D uint8 base codes (0..3 = A,C,G,T, 4 = N), numpy array or tensor, host or device; it goes
+    to the device once, whole.  Variant v replaces codes[pos[v] : pos[v] + ref_len[v]] (0-based) by
+    alts[v], a uint8 code array: SNV, MNV, insertion (ref_len 0), deletion (empty alt) or any ref -> alt
+    replacement.  Both alleles are scored in the window window_start() places, once per shift of
+    `shifts`; positions outside the sequence read as N.  Returns a dict:
+      ref, alt  (V, S, T, 4) float64 in predict()'s order [Fwd, Rev, Mean, Max] -- (V, S, G, T, 4) for an
+                ExplaiNNBank -- each row what predict() gives on the materialised window;
+      delta     (V, T) / (V, G, T): the mean over shifts of alt[..., 2] - ref[..., 2] (column 0 with
+                strands="fwd", which leaves columns 1..3 NaN);
+      units     with unit_effects: (V, units, T) float32, (outs_alt - outs_ref)[v,u] * final.weight[t,u]
+                averaged over strands and shifts (before any sigmoid).  The bias cancels, so
+                units.sum(1) is delta to fp32 rounding; on a bank units are global indices (member g
+                owns [g*U, (g+1)*U)) weighted by their own member's rows, and member g's delta is the
+                sum over its units.
+    check_ref: the VCF REF alleles as code arrays; a mismatch with the sequence raises ValueError.
+    The two strands run on the model and its eval_replica() on two streams, as in scan(); the rows go
+    to the device in chunks of at most 32 * batch_size rows (chunk_rows overrides it)."""
+    if strands not in ("both", "fwd"):
+        raise ValueError("strands must be 'both' or 'fwd' (got %r)" % (strands,))
+    L = model._options["sequence_length"]
+    batch_size = max(1, int(batch_size))
+    device = model.final.weight.device
+    data = codes if torch.is_tensor(codes) else torch.as_tensor(np.ascontiguousarray(codes))
+    if data.dtype != torch.uint8 or data.dim() != 1:
+        raise ValueError("codes must be a 1-D uint8 array of base codes")
+    shifts = tuple(int(s) for s in shifts)
+    tab = build_tables(pos, ref_len, alts, L, shifts)
+    V, S = len(tab["pos"]), len(shifts)
+    if V and (tab["pos"].min() < 0 or (tab["pos"] + tab["ref_len"]).max() > data.shape[0]):
+        bad = np.flatnonzero((tab["pos"] < 0) | (tab["pos"] + tab["ref_len"] > data.shape[0]))
+        raise ValueError("%d variant(s) outside the sequence of %d bases (0 <= pos, pos + ref_len <= length); "
+                         "the first: #%d at %d" % (bad.size, data.shape[0], bad[0], tab["pos"][bad[0]]))
+    shape = tuple(model._logits_empty(0, torch.device("cpu")).shape[1:])
+    units = model._units()
+    res = {"ref": np.full((V, S) + shape + (4,), np.nan), "alt": np.full((V, S) + shape + (4,), np.nan),
+           "delta": np.zeros((V,) + shape)}
+    if unit_effects:
+        res["units"] = np.zeros((V, units, shape[-1]), dtype=np.float32)
+    if V == 0:
+        return res
+    both = strands == "both"
+    cur = torch.cuda.current_stream(device)
+    rep = side = None
+    if both:
+        rep = model.eval_replica()
+        if model._rt.side_stream is None:
+            model._rt.side_stream = torch.cuda.Stream(device)
+        side = model._rt.side_stream
+    seq_d = data.to(device).contiguous()
+    if check_ref is not None:
+        _check_ref_alleles(seq_d, tab["pos"], tab["ref_len"].astype(np.int64), check_ref)
+    dt = {k: torch.from_numpy(v).to(device) for k, v in tab.items()}
+    wrows = _final_rows(model) if unit_effects else None
+    limit = int(chunk_rows) if chunk_rows is not None else _CHUNK_PASSES * batch_size
+    with torch.no_grad(), model.eval_cache(), (rep.eval_cache() if both else contextlib.nullcontext()):
+        for v0, cnt in chunks(V, S, limit):
+            r0, r1 = 2 * S * v0, 2 * S * (v0 + cnt)
+
+            def rows(rc):
+                return EditedWindows(seq_d, dt["row_start"][r0:r1], dt["row_edit"][r0:r1], dt["pos"],
+                                     dt["ref_len"], dt["alt_len"], dt["alt_off"], dt["alt"], rc, batch_size)
+
+            if both:
+                side.wait_stream(cur)                           # the tables are on the device
+                with torch.cuda.stream(side):
+                    rev = rep._launch_score_edits(rows(True), unit_effects)
+            fwd = model._launch_score_edits(rows(False), unit_effects)
+            if both:
+                cur.wait_stream(side)
+                for t in (rev if unit_effects else (rev,)):
+                    t.record_stream(cur)
+            if unit_effects:
+                (fwd, ofwd), orev = fwd, None
+                if both:
+                    rev, orev = rev
+                d = ofwd[1::2] - ofwd[0::2]                     # (cnt*S, units): alt - ref
+                if both:
+                    d = (d + (orev[1::2] - orev[0::2])) / 2
+                d = d.reshape(cnt, S, units).mean(dim=1)
+                res["units"][v0:v0 + cnt] = (d[:, :, None] * wrows.t()[None, :, :]).cpu().numpy()
+            if both:
+                full = torch.stack((fwd, rev, (fwd + rev) / 2, torch.maximum(fwd, rev)), dim=-1)
+                full = full.reshape((cnt, S, 2) + shape + (4,)).cpu().numpy()
+                res["ref"][v0:v0 + cnt], res["alt"][v0:v0 + cnt] = full[:, :, 0], full[:, :, 1]
+            else:
+                one = fwd.reshape((cnt, S, 2) + shape).cpu().numpy()
+                res["ref"][v0:v0 + cnt, ..., 0], res["alt"][v0:v0 + cnt, ..., 0] = one[:, :, 0], one[:, :, 1]
+    if model.validate_input:
+        if both:
+            rep.check_input()
+        model.check_input()
+    if apply_sigmoid:
+        for key in ("ref", "alt"):
+            res[key] = torch.sigmoid(torch.from_numpy(res[key])).numpy()
+    col = 2 if both else 0
+    res["delta"] = (res["alt"][..., col] - res["ref"][..., col]).mean(axis=1)
+    return res
+
+
+def _is_symbolic(allele):
+    return allele in ("", ".", "*") or allele.startswith("<") or "[" in allele or "]" in allele
+
+
+def read_vcf(path):
+    """VCF (plain or gzipped text) -> (variants, skipped): the columns CHROM POS ID REF ALT of every
+    record as Variant(chrom, pos, id, ref, alt) with pos 0-based, one per ALT allele of a multi-allelic
+    line; `skipped` counts the alleles left out: symbolic alleles (<DEL>, ...), the overlapping-deletion
+    star, breakends (any allele with a bracket) and the missing allele '.'."""
+    from .loader import _open
+    out, skipped = [], 0
+    with _open(path, "rt") as fh:
+        for line in fh:
+            if not line.strip() or line.startswith("#"):
+                continue
+            f = line.rstrip("\r\n").split("\t")
+            if len(f) < 5:
+                raise ValueError("VCF line with fewer than 5 columns: %r" % line[:80])
+            chrom, pos, vid, ref = f[0], int(f[1]) - 1, f[2], f[3]
+            for alt in f[4].split(","):
+                if _is_symbolic(alt) or _is_symbolic(ref):
+                    skipped += 1
+                else:
+                    out.append(Variant(chrom, pos, vid, ref, alt))
+    return out, skipped
+
+
+def allele_codes(allele):
+    """An allele string -> uint8 base codes: ACGT in either case, every other letter (N and the other
+    IUPAC codes) -> 4."""
+    from .sequence import _LUT
+    return _LUT[np.frombuffer(allele.encode("ascii", "replace"), dtype=np.uint8)]
+
+
+def score_records(model, records, variants, **kwargs):
+    """score_variants() per FASTA record: records [(id, codes), ...] (loader.read_fasta_records),
+    variants a list of Variant.  Returns (index, results): results[j] is the dict of the variants
+    index[j] (positions in `variants`, file order kept) of one record; variants whose chromosome is
+    not among the records appear in no index."""
+    by = {}
+    for i, v in enumerate(variants):
+        by.setdefault(v.chrom, []).append(i)
+    index, results = [], []
+    for rid, codes in records:
+        idx = by.get(rid)
+        if not idx:
+            continue
+        refs = [allele_codes(variants[i].ref) for i in idx]
+        kw = dict(kwargs)
+        if kw.pop("check_ref", True):
+            kw["check_ref"] = refs
+        results.append(score_variants(model, codes, [variants[i].pos for i in idx], [len(r) for r in refs],
+                                      [allele_codes(variants[i].alt) for i in idx], **kw))
+        index.append(idx)
+    return index, results
+
+
+def main(argv=None):
+    """Variants of a VCF on the sequences of a FASTA -> TSV (Chrom, Pos, Id, Ref, Alt, Class, RefFwd,
+    RefRev, RefMean, AltFwd, AltRev, AltMean, Delta), one row per variant and class, window placements
+    averaged; Pos is the VCF's (1-based)."""
+    ap = argparse.ArgumentParser(prog="python -m explainn_amd.variants", description=main.__doc__)
+    ap.add_argument("model_file")
+    ap.add_argument("fasta_file")
+    ap.add_argument("vcf_file")
+    ap.add_argument("-o", "--output-file")
+    ap.add_argument("--shifts", type=int, default=7, help="window placements 0..S-1 (default 7: one pooling period)")
+    ap.add_argument("--strands", choices=("both", "fwd"), default="both")
+    ap.add_argument("--top-units", type=int, default=0, metavar="K",
+                    help="add a column Units: unit:effect of the K largest |effect|")
+    ap.add_argument("--apply-sigmoid", action="store_true")
+    ap.add_argument("--no-check-ref", action="store_true")
+    args = ap.parse_args(argv)
+    if args.shifts < 1:
+        ap.error("--shifts must be at least 1")
+    from .loader import read_fasta_records
+    from .predict import _load_model
+    variants, skipped = read_vcf(args.vcf_file)
+    records = read_fasta_records(args.fasta_file)
+    model = _load_model(args.model_file)
+    index, results = score_records(model, records, variants, shifts=tuple(range(args.shifts)),
+                                   strands=args.strands, unit_effects=args.top_units > 0,
+                                   apply_sigmoid=args.apply_sigmoid, check_ref=not args.no_check_ref)
+    where = {i: (res, j) for idx, res in zip(index, results) for j, i in enumerate(idx)}
+    if skipped or len(where) < len(variants):
+        sys.stderr.write("%d symbolic allele(s) skipped, %d variant(s) on sequences the FASTA does not hold\n"
+                         % (skipped, len(variants) - len(where)))
+    fh = open(args.output_file, "w") if args.output_file else sys.stdout
+    try:
+        fh.write("Chrom\tPos\tId\tRef\tAlt\tClass\tRefFwd\tRefRev\tRefMean\tAltFwd\tAltRev\tAltMean\tDelta"
+                 + ("\tUnits" if args.top_units > 0 else "") + "\n")
+        for i, v in enumerate(variants):
+            if i not in where:
+                continue
+            res, j = where[i]
+            ref, alt = res["ref"][j].mean(axis=0), res["alt"][j].mean(axis=0)        # (T,4): shifts averaged
+            for t in range(ref.shape[0]):
+                row = [v.chrom, str(v.pos + 1), v.id, v.ref, v.alt, str(t)]
+                row += [repr(float(x)) for x in (*ref[t, :3], *alt[t, :3], res["delta"][j, t])]
+                if args.top_units > 0:
+                    eff = res["units"][j, :, t]
+                    top = np.argsort(-np.abs(eff), kind="stable")[:args.top_units]
+                    row.append(",".join("%d:%s" % (u, repr(float(eff[u]))) for u in top))
+                fh.write("\t".join(row) + "\n")
+    finally:
+        if fh is not sys.stdout:
+            fh.close()
+
+
+if __name__ == "__main__":
+    main()

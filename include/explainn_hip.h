@@ -101,7 +101,8 @@ int explainn_create(explainn_ctx** out, int cnn_units, int kernel_size, int sequ
  * explainn_loss_grad, explainn_train_step, explainn_train_step_fc / _conv (the flat gradient buffer
  * is element-wise, so a data-parallel all-reduce is unchanged), explainn_unit_outputs (B,G*U),
  * explainn_unit_activations, the filter export (per unit), explainn_stage_codes / _stage_onehot /
- * _stage_windows, explainn_scan in every mode (logits (n_windows,G,T)), explainn_dense_input, explainn_input_flags, stage timing, explainn_debug_keep_bits (G*U,B,4).
+ * _stage_windows / _stage_edited_windows, explainn_scan in every mode (logits (n_windows,G,T)),
+ * explainn_score_edits (logits (n_rows,G,T), outs (n_rows,G*U)), explainn_dense_input, explainn_input_flags, stage timing, explainn_debug_keep_bits (G*U,B,4).
  * EXPLAINN_E_UNSUPPORTED on a bank (they fold units through `final` in kernels of their own; run them
  * on one member's model; the context stays usable): explainn_forward_eval_keep, explainn_input_grad,
  * explainn_backward_input, explainn_ism, explainn_sync_phase.
@@ -287,6 +288,60 @@ int64_t explainn_scan_workspace_bytes(const explainn_ctx* ctx, int64_t n_windows
 int explainn_scan(explainn_ctx* ctx, const uint8_t* seq, int64_t seq_len, int64_t start, int64_t n_windows,
                   int64_t stride, int reverse_complement, const explainn_params* p, float* logits, int mode,
                   void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Scoring sequence variants: the batch rows are windows of ONE device-resident sequence at arbitrary
+ * starts, each with at most one edit (an SNV, MNV, insertion, deletion or any ref -> alt replacement)
+ * spliced in on the device -- what a user of the reference does by building both haplotype windows of
+ * every variant on the host.  All pointers of explainn_edits are device pointers.
+ *
+ * Row b is defined by row_start[b] (int64, signed) and row_edit[b] (int32: an index into the edit
+ * table, negative = no edit, a plain reference window).  Edit e has pos[e] (int64, 0-based, reference
+ * coordinates), ref_len[e] >= 0, alt_len[e] >= 0 and alt_off[e], an offset into the byte pool `alt` of
+ * base codes (alt_bytes of them, < 2^31).  The haplotype is
+ *     H = seq[:pos] + alt[alt_off : alt_off + alt_len] + seq[pos + ref_len:]
+ * and row b is H[row_start : row_start + L]: row_start counts in haplotype coordinates, which equal
+ * reference coordinates whenever row_start <= pos.  For output position q, g = row_start + q, the base is
+ *     seq[g]                        when g < pos,
+ *     alt[alt_off + g - pos]        when g < pos + alt_len,
+ *     seq[g - alt_len + ref_len]    otherwise.
+ * A source index outside [0, seq_len) reads as N and raises no flag, as in explainn_stage_windows.  A
+ * byte above 4, in seq inside the range or in alt, reads as N and raises bit 0 of explainn_input_flags.
+ * The tables are never read by the host, so the kernel stays memory-safe on a bad one: a row whose
+ * row_edit >= n_edits, or whose edit has a negative length or an alt run that leaves the pool
+ * (alt_off < 0 or alt_off + alt_len > alt_bytes), reads as N throughout and raises bit 0.
+ * reverse_complement != 0 reverse-complements the row after the edit.  One edit per row: a haplotype
+ * of several variants is not expressible.
+ *
+ * explainn_stage_edited_windows stages rows row0 .. row0 + B - 1 of the tables.  The context then holds
+ * exactly what explainn_stage_codes would hold for the materialised (B,L) matrix: every entry point
+ * that takes x == NULL runs on it, train mode included.
+ *
+ * explainn_score_edits: the eval-mode results of rows 0 .. n_rows-1, in sub-batches of the context's
+ * max_batch: logits fp32 (n_rows,T) -- (n_rows,G,T) on a bank context -- and / or outs, the per-unit
+ * outputs of explainn_unit_outputs, fp32 (n_rows,units), units = G*U on a bank.  Either may be NULL, not
+ * both (EXPLAINN_E_ARG; the context stays usable).  Row by row the results are those of
+ * explainn_stage_edited_windows followed by explainn_forward_eval / explainn_unit_outputs, bit for bit.
+ * No host synchronisation, no allocation.  Like every eval entry point it ends a pending train
+ * forward, rebuilds the folded tables only when params->version moved, and leaves no staged batch
+ * behind.  Dense input mode: EXPLAINN_E_UNSUPPORTED. */
+typedef struct explainn_edits {
+    const int64_t* row_start;
+    const int32_t* row_edit;
+    const int64_t* pos;
+    const int32_t* ref_len;
+    const int32_t* alt_len;
+    const int32_t* alt_off;
+    const uint8_t* alt;
+    int64_t n_edits;
+    int64_t alt_bytes;
+} explainn_edits;
+int explainn_stage_edited_windows(explainn_ctx* ctx, const uint8_t* seq, int64_t seq_len,
+                                  const explainn_edits* edits, int64_t row0, int B, int reverse_complement,
+                                  void* stream);
+int explainn_score_edits(explainn_ctx* ctx, const uint8_t* seq, int64_t seq_len, const explainn_edits* edits,
+                         int64_t n_rows, int reverse_complement, const explainn_params* p,
+                         float* logits /* (n_rows,[G,]T) or NULL */, float* outs /* (n_rows,units) or NULL */,
+                         void* stream);
 
 /* Calling motif sites: every (unit, start position) of a device-resident sequence of base codes
  * (0..3 = ACGT, 4 = N, as explainn_scan takes it) whose eval-mode activation, rounded to float16 as

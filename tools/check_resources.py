@@ -53,7 +53,9 @@ METRICS = [
 ]
 # tiled scan of a long sequence (scan.hip): the window staging and the unfold of the pooled track
 SCAN = [r"^stage_windows_kernel", r"^scan_unfold_kernel"]
-GATED = C2_STEP + INPUT_GRAD + ISM + METRICS + SCAN
+# variant effects (variants.hip): the staging of edited windows
+VARIANTS = [r"^stage_edits_kernel"]
+GATED = C2_STEP + INPUT_GRAD + ISM + METRICS + SCAN + VARIANTS
 
 
 # Register cliffs measured in the pipeline: 1024-thread blocks of which TWO must
