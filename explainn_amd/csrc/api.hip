@@ -87,6 +87,13 @@ void carve(explainn_ctx* c, Carver& cv) {
     cv.take(&c->dlT, (int64_t)c->T * Bs);
     cv.take(&c->gWp, c->T > HEAD_GEMM_MIN_T && c->Gm == 1 ? (int64_t)head_gw_chunks(c->maxB) * c->T * (c->U + 1) : 0);
     cv.take(&c->lossp, 256);
+    {
+        // (a bank and T > PA_HEAD_MAX_T never take the route that uses them)
+        const bool sums = c->Gm == 1 && c->T <= PA_HEAD_MAX_T;
+        const int64_t blks = (c->maxB + 63) / 64;
+        cv.take(&c->hp, sums ? U * blks * (2 + PA_HEAD_MAX_T) : 0);
+        cv.take(&c->hb, sums ? blks * (1 + PA_HEAD_MAX_T) : 0);
+    }
     cv.take(&c->site_cnt, U4 * Bs);
     cv.take(&c->site_off, U4 * Bs);
     const int64_t D = 2 * c->k - 1;
@@ -627,9 +634,12 @@ extern "C" int explainn_filter_sites(explainn_ctx* c, const float* x, int B, con
     return launch_filter_sites(c, B, select, thresholds, site_cap, site_total, pfm, hit, s);
 }
 
-extern "C" int explainn_forward_train(explainn_ctx* c, const float* x, int B,
-                                      const explainn_params* p, const uint8_t* keep_mask,
-                                      float dropout_p, uint64_t seed, float* logits, void* stream) {
+namespace {
+// the train forward; head_sums: the combiner launch also leaves the head backward's batch sums of a
+// training step with targets sums_y (head_sums_in_combiner below decides, nobody else)
+int forward_train(explainn_ctx* c, const float* x, int B, const explainn_params* p,
+                  const uint8_t* keep_mask, float dropout_p, uint64_t seed, float* logits,
+                  bool head_sums, const float* sums_y, int loss_kind, void* stream) {
     TRY(check_batch(c, B));
     if (B == 1) {
         // torch raises here (BatchNorm over one value); the reason for train.py:297-302
@@ -678,9 +688,17 @@ extern "C" int explainn_forward_train(explainn_ctx* c, const float* x, int B,
     STAGE(ST_QMOM, launch_qmoments(c, B, s));
     STAGE(ST_PREP2, launch_prep2(c, p, B, true, s));
     STAGE(ST_FC_FWD, launch_fc_fwd(c, p, B, true, keep_mask, dropout_p, seed, s));
-    STAGE(ST_HEAD_FWD, launch_head_fwd(c, p, B, true, logits, nullptr, s));
+    if (head_sums) STAGE(ST_HEAD_FWD, launch_head_fwd_sums(c, p, B, logits, sums_y, loss_kind, s));
+    else STAGE(ST_HEAD_FWD, launch_head_fwd(c, p, B, true, logits, nullptr, s));
     c->fwd_B = B;
     return EXPLAINN_OK;
+}
+}  // namespace
+
+extern "C" int explainn_forward_train(explainn_ctx* c, const float* x, int B,
+                                      const explainn_params* p, const uint8_t* keep_mask,
+                                      float dropout_p, uint64_t seed, float* logits, void* stream) {
+    return forward_train(c, x, B, p, keep_mask, dropout_p, seed, logits, false, nullptr, 0, stream);
 }
 
 namespace {
@@ -707,11 +725,28 @@ int backward_conv(explainn_ctx* c, int B, const explainn_params* p, const explai
 // 2 = from the loss).  Every passA wave then makes the full-batch pass of BatchNorm3's backward
 // itself: worth a launch (~5 us) up to a few hundred sequences -- 0.120 -> 0.115 ms per step at 100
 // units x 64 sequences -- and a wash at 1024 (passA +9.6 us, head_bwd -9.6 us; MI355X), so larger
-// batches keep the per-unit kernel.
+// batches keep the per-unit kernel, or in the training step take head_sums_in_combiner below.
 // A bank never rides: passA's prologue has no member index ("Model bank").
 bool head_rides_in_passA(const explainn_ctx* c, int B) {
     if (c->Gm > 1) return false;
     return c->T <= PA_HEAD_MAX_T && B <= 512;
+}
+
+// Few tasks and a LARGER batch: the head backward's two batch sums per unit are formed where the
+// data already sits in registers -- the combiner launch of the forward (head.hip, logits_bn_kernel<T>:
+// per block of 64 sequences, partials) -- and passA adds the partials up and forms dz in its main loop
+// (fc.hip, HEAD == 2): the per-unit head backward launch (9.3 us at 300 units x 1024 sequences) goes.
+// Only the training step can take it (the combiner needs the targets); a bank, sync-BN, caller-given
+// dlogits, T > PA_HEAD_MAX_T and batches that ride in passA keep their routes.
+// EXPLAINN_HEAD_PARTIALS=0|1 (read per step, so that one process can run both) forces the per-unit
+// kernel / this route wherever it is legal.  Default: on for one task -- measured at 300 x 1024,
+// 100 x 1024 and 300 x 2048.  Two to four tasks were measured faster at
+// 300 x 1024 only, and their kernels spill registers in some pooled-length buckets: off unless asked for.
+bool head_sums_in_combiner(const explainn_ctx* c, int B, const float* logits, const float* targets) {
+    if (c->Gm > 1 || c->T > PA_HEAD_MAX_T || c->T > HEAD_GEMM_MIN_T || !logits || !targets || B < 2) return false;
+    if (head_rides_in_passA(c, B) || !head_sums_fit(c)) return false;
+    if (const char* e = getenv("EXPLAINN_HEAD_PARTIALS")) return atoi(e) != 0;
+    return c->T == 1;
 }
 
 pa_head_args head_in_passA(explainn_ctx* c, const explainn_params* p, const explainn_grads* g, int mode,
@@ -780,8 +815,20 @@ int train_step_front(explainn_ctx* c, const float* x, const float* targets, int 
         return EXPLAINN_E_ARG;
     }
     if (c) c->tail_B = 0;
-    TRY(explainn_forward_train(c, x, B, p, nullptr, dropout_p, seed, logits, stream));
+    TRY(check_batch(c, B));
     hipStream_t s = static_cast<hipStream_t>(stream);
+    if (head_sums_in_combiner(c, B, logits, targets)) {
+        // few tasks, batch > 512: loss gradient and batch-sum partials ride in the combiner launch of
+        // the forward, passA finishes them -- no head backward launch
+        TRY(forward_train(c, x, B, p, nullptr, dropout_p, seed, logits, true, targets, loss_kind, stream));
+        const pa_sums_args ps = {c->zhat, c->dlogits, c->dz, p->final_w, p->bn3_w, p->bn3_b, c->sig3,
+                                 c->T, (B + 63) / 64, c->hp, c->hb,
+                                 g->final_w, g->final_b, g->bn3_w, g->bn3_b, g->fc2_b, loss_out};
+        STAGE(ST_PASSA, launch_passA_sums(c, B, ps, s));
+        STAGE(ST_MID, launch_mid_bwd(c, p, g, B, s));
+        return EXPLAINN_OK;
+    }
+    TRY(explainn_forward_train(c, x, B, p, nullptr, dropout_p, seed, logits, stream));
     if (head_rides_in_passA(c, B)) {
         // few tasks, small batch: loss, loss gradient and head backward all ride in passA's prologue
         const pa_head_args h = head_in_passA(c, p, g, 2, nullptr, loss_kind, logits, targets, loss_out);

@@ -97,6 +97,9 @@ struct explainn_ctx {
     int loss_blocks, loss_n; float* loss_out;   // a deferred loss value (launch_loss_deferred -> launch_head_bwd)
     float* gWp;           // [HEAD_GW_CHUNKS][T][U+1]  batch-chunk partials of the combiner-weight gradient
     double* lossp;        // [64]      per-block partial sums of the loss
+    double* hp;           // [U][ceil(maxB/64)][6] the combiner launch's per-block partials of the head backward's
+                          //           batch sums: {sum d3, sum d3 zhat, sum dl[t] o (t < T)} (head.hip -> passA)
+    double* hb;           // [ceil(maxB/64)][5]    per block: sum_b dl[b][t] (t < T), then its loss terms
     int staged_B;         // batch size of the codes explainn_stage_codes() staged, 0 = none
     // eval-mode tables (filter tables, BatchNorm1/2 folds, FC1 fragments) held in the scratch are
     // those of parameter version eval_version; a train-mode forward overwrites them
@@ -163,6 +166,12 @@ int launch_fc_fwd(explainn_ctx* c, const explainn_params* p, int B, bool train,
                   const uint8_t* keep_mask, float drop_p, uint64_t seed, hipStream_t s);
 int launch_head_fwd(explainn_ctx* c, const explainn_params* p, int B, bool train, float* logits,
                     float* outs, hipStream_t s);
+// The train forward's combiner launch with the head backward's batch sums riding in it (head.hip): the
+// loss gradient to c->dlogits, per-block partials to c->hp / c->hb; passA finishes them (fc.hip).
+// head_sums_fit: the launch's LDS (statistics + T weight rows) fits.
+bool head_sums_fit(const explainn_ctx* c);
+int launch_head_fwd_sums(explainn_ctx* c, const explainn_params* p, int B, float* logits, const float* y,
+                         int kind, hipStream_t s);
 int launch_loss_deferred(explainn_ctx* c, int kind, const float* logits, const float* y, int B, float* loss,
                          float* dlogits, hipStream_t s);
 int launch_loss(explainn_ctx* c, int kind, const float* logits, const float* y, int B,
@@ -182,7 +191,17 @@ struct pa_head_args {
     const float *Wf, *g3, *o, *zhat, *sig3;
     float *dz, *gWf, *gbf, *gg3, *gb3, *gc2;
 };
+// The third head-backward route (few tasks, batch > 512): the combiner launch left per-block partials
+// of the batch sums (hp, hb; nblk blocks of 64 sequences) and the loss gradient dl; a passA wave adds
+// its unit's partials and forms dz in its main loop.  The first line is what that loop reads.
+struct pa_sums_args {
+    const float *zhat, *dl; float* dz; const float *Wf, *g3, *b3, *sig3;
+    int T, nblk;
+    const double *hp, *hb;
+    float *gWf, *gbf, *gg3, *gb3, *gc2, *loss_out;
+};
 int launch_passA(explainn_ctx* c, int B, const pa_head_args* head, hipStream_t s);
+int launch_passA_sums(explainn_ctx* c, int B, const pa_sums_args& ps, hipStream_t s);
 int launch_mid_bwd(explainn_ctx* c, const explainn_params* p, const explainn_grads* g, int B,
                    hipStream_t s);
 int launch_passB(explainn_ctx* c, int B, hipStream_t s);

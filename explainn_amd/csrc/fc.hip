@@ -633,6 +633,48 @@ __device__ __forceinline__ void pa_head_prologue(const pa_head_args& h, int u, i
     }
 }
 
+// HEAD == 2: the unit's nblk per-block partials {sum d3, sum d3 zhat, sum dl[t] o} added up, one per
+// lane and trip, lanes by butterfly: fixed order, fp64.  Out: the scalars of the dz formula, wave-uniform
+// (scalar registers).  The owner wave (chunk 0, wave 0, group 0) writes the unit's parameter gradients,
+// that of unit 0 also the combiner bias gradient and the loss value from the blocks' sums in hb.
+__device__ __forceinline__ float pa_uniform(float v) {
+    return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
+}
+__device__ __forceinline__ void pa_sums_prologue(const pa_sums_args& ps, int u, int ch, int grp, int lane, int B,
+                                                 int U, float& m1, float& m2, float& sc, float& g3u, float& b3u,
+                                                 float (&wf)[PA_HEAD_MAX_T]) {
+    const int T = ps.T, K = 2 + T, nblk = ps.nblk;
+    const double* __restrict__ hu = ps.hp + (size_t)u * nblk * K;
+    const bool owner = ch == 0 && grp == 0;
+    double s1 = 0, s2 = 0;
+    for (int i = lane; i < nblk; i += 64) { s1 += hu[i * K]; s2 += hu[i * K + 1]; }
+    g3u = pa_uniform(ps.g3[u]); b3u = pa_uniform(ps.b3[u]);
+    const float sg = ps.sig3[u];
+#pragma unroll
+    for (int t = 0; t < PA_HEAD_MAX_T; ++t) wf[t] = t < T ? pa_uniform(ps.Wf[(size_t)t * U + u]) : 0.f;
+    const double S1 = wave_sum_d(s1), S2 = wave_sum_d(s2);
+    m1 = pa_uniform((float)(S1 / (double)B)); m2 = pa_uniform((float)(S2 / (double)B));
+    sc = pa_uniform(g3u / sg);
+    if (!owner) return;
+    if (lane == 0) { ps.gg3[u] = (float)S2; ps.gb3[u] = (float)S1; ps.gc2[u] = 0.f; }
+    for (int t = 0; t < T; ++t) {
+        double a = 0;
+        for (int i = lane; i < nblk; i += 64) a += hu[i * K + 2 + t];
+        const double tot = wave_sum_d(a);
+        if (lane == 0) ps.gWf[(size_t)t * U + u] = (float)tot;
+    }
+    if (u != 0) return;
+    for (int t = 0; t <= T; ++t) {                      // (t == T: the loss terms)
+        double a = 0;
+        for (int i = lane; i < nblk; i += 64) a += ps.hb[i * (T + 1) + t];
+        const double tot = wave_sum_d(a);
+        if (lane == 0) {
+            if (t < T) ps.gbf[t] = (float)tot;
+            else *ps.loss_out = (float)(tot / (double)(B * T));
+        }
+    }
+}
+
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 #define PA_LD 72                     // bf16 elements per row of the X image (64 sequences + 8 pad)
@@ -641,7 +683,7 @@ __host__ __device__ constexpr int pa_wgt(int NQ) { return pa_nw16(NQ) <= 2 ? pa_
 __host__ __device__ constexpr int pa_ng(int NQ) { return (pa_nw16(NQ) + pa_wgt(NQ) - 1) / pa_wgt(NQ); }
 
 #define PA_WAVES 2                    // wavefronts per passA workgroup: their tiles are added in LDS before the store
-// HEAD: the instantiation that carries the head backward in its prologue (few tasks, batch <= 512).
+// HEAD == 1: the instantiation that carries the head backward in its prologue (few tasks, batch <= 512).
 // The plain one -- what the headline shape launches -- does not hold pa_head_args' 18 pointers in
 // SGPRs across the main loop: with them passA<26> spilled 88 SGPRs and 12 VGPRs (20 B of scratch per
 // lane, tools/check_resources.py now fails the build on that).
@@ -664,7 +706,16 @@ __device__ __forceinline__ void pa_transform(float (&rq)[ROWS], float dzv, float
     }
 }
 
-template <int NQ, bool HEAD>
+// HEAD >= 2 (few tasks, batch > 512): the combiner launch left the loss gradient dl and, per block of 64
+// sequences, partials of the unit's batch sums (head.hip, head_sums).  The wave adds its unit's
+// partials (one per lane, requested behind the first super-tile's loads and waited for with them), and
+// the main loop fetches zhat and dl[b][0..T) where the plain form fetches dz: dz = sc (d3 - m1 - zhat m2)
+// is a handful of instructions per sequence in front of the transform.  The waves of row group 0 store
+// it for passB.  Only what the loop reads stays live across it: the unit's two rows, dl, T weights
+// and five scalars, all in scalar registers.  HEAD == 2 is the one-task form, HEAD == 3 that of two to
+// PA_HEAD_MAX_T tasks: the loop holds a register per task for dl, and with four of them passA<26> spilled
+// at the 168 registers of three waves per SIMD.
+template <int NQ, int HEAD>
 __global__ __launch_bounds__(64 * PA_WAVES, pa_wgt(NQ) <= 2 ? 3 : 2) void passA_kernel(const float* __restrict__ ext,
                                                    const float* __restrict__ alpha,
                                                    const float* __restrict__ shift,
@@ -672,7 +723,8 @@ __global__ __launch_bounds__(64 * PA_WAVES, pa_wgt(NQ) <= 2 ? 3 : 2) void passA_
                                                    const uint4* __restrict__ bits,
                                                    float* __restrict__ EQp,
                                                    float* __restrict__ Sep, int n, int Bs, int B,
-                                                   int ACH, const pa_head_args h, int U) {
+                                                   int ACH, const pa_head_args h, int U,
+                                                   const pa_sums_args ps) {
     constexpr int NS = ns_stride(NQ), WGT = pa_wgt(NQ), ROWS = 16 * WGT;
     // per wave: the X image [piece][row][sequence] bf16 and the bit words [sequence][4]; the region of
     // wave 1 doubles as the buffer its accumulator tile crosses to wave 0 in at the end
@@ -692,9 +744,18 @@ __global__ __launch_bounds__(64 * PA_WAVES, pa_wgt(NQ) <= 2 ? 3 : 2) void passA_
     const int bbeg = min(B, ch * per + wave * (per / PA_WAVES)), bend = min(B, bbeg + per / PA_WAVES);
     const float a1 = alpha[u], sh1 = shift[u];
     const float* __restrict__ eu = ext + (size_t)u * n * Bs;
-    const float* __restrict__ dzu = dz + (size_t)u * Bs;
+    // (HEAD >= 2 never reads dz: its main loop forms the values and writes them through ps.dz)
+    const float* __restrict__ dzu = HEAD >= 2 ? nullptr : dz + (size_t)u * Bs;
     const uint4* __restrict__ bu = bits + (size_t)u * Bs;
-    if (HEAD) pa_head_prologue(h, u, ch + wave, grp, lane, bbeg, bend, Bs, B, U);     // (owner: chunk 0, wave 0)
+    if (HEAD == 1) pa_head_prologue(h, u, ch + wave, grp, lane, bbeg, bend, Bs, B, U);     // (owner: chunk 0, wave 0)
+    // HEAD == 2: what the main loop reads (the names the prologue alone needs die in front of it)
+    constexpr int HTM = HEAD == 2 ? 1 : PA_HEAD_MAX_T;
+    const int HT = HEAD == 2 ? 1 : HEAD == 3 ? ps.T : 0;
+    const float* __restrict__ zhu = ps.zhat + (size_t)u * Bs;
+    const float* __restrict__ dlp = ps.dl;
+    float* __restrict__ dzw = ps.dz + (size_t)u * Bs;
+    float hm1 = 0.f, hm2 = 0.f, hsc = 0.f, hg3 = 0.f, hb3 = 0.f, hwf[PA_HEAD_MAX_T] = {0.f, 0.f, 0.f, 0.f};
+    float rzh = 0.f, rdl[HTM] = {};
     f32x4 acc[FC_MT][WGT];
 #pragma unroll
     for (int t = 0; t < FC_MT; ++t)
@@ -728,10 +789,18 @@ __global__ __launch_bounds__(64 * PA_WAVES, pa_wgt(NQ) <= 2 ? 3 : 2) void passA_
 #pragma unroll
         for (int i = 0; i < ROWS; ++i)
             rq[i] = *reinterpret_cast<const float*>(eb + (__umul24(rstride, (uint32_t)min(w0 + i, n - 1)) + boff));
-        rdz = dzu[bc];
+        if constexpr (HEAD >= 2) {
+            rzh = zhu[bc];
+#pragma unroll
+            for (int t = 0; t < HTM; ++t)
+                if (t < HT) rdl[t] = dlp[bc * HT + t];
+        } else {
+            rdz = dzu[bc];
+        }
     };
     STAMP(0);
     if (bbeg < bend) fetch(bbeg, 0);
+    if (HEAD >= 2) pa_sums_prologue(ps, u, ch + wave, grp, lane, B, U, hm1, hm2, hsc, hg3, hb3, hwf);
     int slot = 0;
     for (int b0 = bbeg; b0 < bend; b0 += 64, slot ^= 1) {
         const uint32_t* tw = tw0 + slot * 256;
@@ -740,7 +809,19 @@ __global__ __launch_bounds__(64 * PA_WAVES, pa_wgt(NQ) <= 2 ? 3 : 2) void passA_
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         {
             // X[b][w] = dz q (w < n), dz (w == n: the Se column), 0 beyond; dead lanes carry zeros
-            const float dzv = (b0 + lane < bend) ? rdz : 0.f;
+            float dzv;
+            if constexpr (HEAD < 2) {
+                dzv = (b0 + lane < bend) ? rdz : 0.f;
+            } else {
+                float dob = 0.f;
+#pragma unroll
+                for (int t = 0; t < HTM; ++t)
+                    if (t < HT) dob = fmaf(rdl[t], hwf[t], dob);
+                // (o > 0 by the forward's own expression for o)
+                const float d3 = fmaf(hg3, rzh, hb3) > 0.f ? dob : 0.f;
+                dzv = (b0 + lane < bend) ? hsc * (d3 - hm1 - rzh * hm2) : 0.f;
+                if (grp == 0 && b0 + lane < bend) dzw[b0 + lane] = dzv;
+            }
             // one copy of the row loop per row group, chosen by ONE branch: inside a copy the row
             // index is a compile-time constant (see pa_transform)
             if constexpr (pa_ng(NQ) == 1) pa_transform<NQ, 0, ROWS>(rq, dzv, a1, sh1, n);
@@ -858,13 +939,30 @@ int launch_passA(explainn_ctx* c, int B, const pa_head_args* head, hipStream_t s
     if (head) h = *head;
 #define CALL(N)                                                                                  \
     if (h.mode)                                                                                  \
-        hipLaunchKernelGGL((passA_kernel<N, true>), dim3(c->ACH, c->U, pa_ng(N)), dim3(64 * PA_WAVES), 0, s, \
+        hipLaunchKernelGGL((passA_kernel<N, 1>), dim3(c->ACH, c->U, pa_ng(N)), dim3(64 * PA_WAVES), 0, s, \
                            c->ext, c->alpha, c->shift, c->dz, c->bits, c->EQp, c->Sep, c->n, c->Bs, \
-                           B, c->ACH, h, c->U);                                                  \
+                           B, c->ACH, h, c->U, pa_sums_args{});                                  \
     else                                                                                         \
-        hipLaunchKernelGGL((passA_kernel<N, false>), dim3(c->ACH, c->U, pa_ng(N)), dim3(64 * PA_WAVES), 0, s, \
+        hipLaunchKernelGGL((passA_kernel<N, 0>), dim3(c->ACH, c->U, pa_ng(N)), dim3(64 * PA_WAVES), 0, s, \
                            c->ext, c->alpha, c->shift, c->dz, c->bits, c->EQp, c->Sep, c->n, c->Bs, \
-                           B, c->ACH, h, c->U)
+                           B, c->ACH, h, c->U, pa_sums_args{})
+    NQ_DISPATCH(c->NQ, CALL);
+#undef CALL
+    LAUNCH_CHECK();
+    return EXPLAINN_OK;
+}
+
+// the forms that finish the batch sums the combiner launch left (HEAD == 2: one task, 3: several)
+int launch_passA_sums(explainn_ctx* c, int B, const pa_sums_args& ps, hipStream_t s) {
+#define CALL(N)                                                                                  \
+    if (ps.T == 1)                                                                               \
+        hipLaunchKernelGGL((passA_kernel<N, 2>), dim3(c->ACH, c->U, pa_ng(N)), dim3(64 * PA_WAVES), 0, s, \
+                           c->ext, c->alpha, c->shift, c->dz, c->bits, c->EQp, c->Sep, c->n, c->Bs, \
+                           B, c->ACH, pa_head_args{}, c->U, ps);                                 \
+    else                                                                                         \
+        hipLaunchKernelGGL((passA_kernel<N, 3>), dim3(c->ACH, c->U, pa_ng(N)), dim3(64 * PA_WAVES), 0, s, \
+                           c->ext, c->alpha, c->shift, c->dz, c->bits, c->EQp, c->Sep, c->n, c->Bs, \
+                           B, c->ACH, pa_head_args{}, c->U, ps)
     NQ_DISPATCH(c->NQ, CALL);
 #undef CALL
     LAUNCH_CHECK();

@@ -241,15 +241,126 @@ __global__ __launch_bounds__(1024) void logits_kernel(const float* __restrict__ 
 // its own member's units only (LDS U x 20 B), the blocks of task 0 OF EACH MEMBER store zhat / o,
 // block (0, 0) of each member its running statistics, member 0's the shared num_batches_tracked.
 // (The member offsets are block-uniform: they cost scalar registers, none of the kernel's 128 vector ones.)
+//
+// TT > 0 is the form of the training step with few tasks and more than 512 sequences (G = 1, grid.y =
+// 1): the block sums all TT tasks of its 64 sequences (TT weight rows in LDS, the sums of task t in
+// the order the block of task t has above, so the logits keep their bits), and with the logits of
+// its sequences in hand goes on to the loss gradient and its share of the head backward's batch sums
+// (head_sums below): the per-unit head backward launch that re-read all of this disappears.
+struct head_sums_args {
+    const float* y; int kind;          // targets (B,T), loss kind
+    float* dl;                         // out: d loss / d logits (B,T)
+    double *hp, *hb;                   // out: per-block partials (common.h)
+};
+
+// The block's part of the head backward, entered with the logits s[t] of sequence b in wave 0.
+// Wave 0: dl = loss_grad for its 64 sequences (0 for the dead ones), to memory and through LDS to
+// everybody; the block's sums of dl and of the loss terms to hb.  Then every thread takes (unit, eight
+// sequences): zhat back from memory (this block stored it; two 16-byte loads per unit, three units in
+// flight), o by the forward's own expression, and in fp64, sequence order
+//   s1 = sum d3,  s2 = sum d3 zhat,  gw[t] = sum dl[b][t] o     d3 = o > 0 ? sum_t dl[b][t] Wf[t][u] : 0
+// the eight threads of a unit are adjacent lanes: three butterfly steps, one store of 2 + T doubles
+// per (unit, block).  Plain stores: passA, the next launch but one, adds the blocks up.
+template <int T>
+__device__ __forceinline__ void head_sums(const head_sums_args& hs, const float (&s)[T], float4* st4,
+                                          const float* wl, const float* zhat, int U, int Bs, int B) {
+    __shared__ float dls[T][64];
+    const int tid = threadIdx.x, lane = tid & 63, blk = blockIdx.x;
+    STAMP(2);
+    if (tid < 64) {                                    // wave 0
+        const int b = blk * 64 + lane;
+        const float invN = 1.0f / (float)(B * T);
+        double lacc = 0;
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            float d = 0.f;
+            if (b < B) {
+                const float yv = hs.y[b * T + t];
+                d = loss_grad(hs.kind, s[t], yv, invN);
+                lacc += (double)loss_value(hs.kind, s[t], yv);
+                hs.dl[b * T + t] = d;
+            }
+            dls[t][lane] = d;
+            const double sd = wave_sum_d((double)d);
+            if (lane == 0) hs.hb[blk * (T + 1) + t] = sd;
+        }
+        const double sl = wave_sum_d(lacc);
+        if (lane == 0) hs.hb[blk * (T + 1) + T] = sl;
+    }
+    __syncthreads();
+    STAMP(3);
+    constexpr int PC = T <= 2 ? 3 : 2;                 // units per thread and round trip (three with four tasks spilled)
+    const int seg = tid & 7, b0 = blk * 64 + 8 * seg, nb = gridDim.x;
+    for (int c0 = tid >> 3; c0 < U; c0 += 128 * PC) {
+        float zv[PC][8];
+#pragma unroll
+        for (int q = 0; q < PC; ++q) {
+            const float4* src = reinterpret_cast<const float4*>(zhat + (size_t)min(c0 + 128 * q, U - 1) * Bs + b0);
+            const float4 v0 = src[0], v1 = src[1];
+            zv[q][0] = v0.x; zv[q][1] = v0.y; zv[q][2] = v0.z; zv[q][3] = v0.w;
+            zv[q][4] = v1.x; zv[q][5] = v1.y; zv[q][6] = v1.z; zv[q][7] = v1.w;
+        }
+#pragma unroll
+        for (int q = 0; q < PC; ++q)
+#pragma unroll
+            for (int i = 0; i < 8; ++i) KEEP(zv[q][i]);
+        STAMP_AFTER_LOADS(4);
+#pragma unroll
+        for (int q = 0; q < PC; ++q) {
+            const int u = c0 + 128 * q, uc = min(u, U - 1);
+            const float4 sv = st4[uc];
+            float wf[T];
+#pragma unroll
+            for (int t = 0; t < T; ++t) wf[t] = wl[t * U + uc];
+            double s1 = 0, s2 = 0, gw[T];
+#pragma unroll
+            for (int t = 0; t < T; ++t) gw[t] = 0;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                // (a dead sequence's zhat was never stored: whatever the memory holds is masked here.
+                // Its dl is 0, so its finite o and d3 = 0 add nothing: one select per element, not three)
+                const float zh = b0 + i < B ? zv[q][i] : 0.f;
+                const float ov = fmaxf(fmaf(sv.z, zh, sv.w), 0.f);
+                float dob = 0.f;
+#pragma unroll
+                for (int t = 0; t < T; ++t) {
+                    const float dlv = dls[t][8 * seg + i];
+                    dob = fmaf(dlv, wf[t], dob);
+                    gw[t] = fma((double)dlv, (double)ov, gw[t]);
+                }
+                const float d3 = ov > 0.f ? dob : 0.f;
+                s1 += (double)d3;
+                s2 = fma((double)d3, (double)zh, s2);
+            }
+#pragma unroll
+            for (int off = 1; off < 8; off <<= 1) {
+                s1 += __shfl_xor(s1, off, 64);
+                s2 += __shfl_xor(s2, off, 64);
+#pragma unroll
+                for (int t = 0; t < T; ++t) gw[t] += __shfl_xor(gw[t], off, 64);
+            }
+            if (seg == 0 && u < U) {
+                double* dst = hs.hp + ((size_t)u * nb + blk) * (2 + T);
+                dst[0] = s1; dst[1] = s2;
+#pragma unroll
+                for (int t = 0; t < T; ++t) dst[2 + t] = gw[t];
+            }
+        }
+    }
+}
+
+template <int TT>
 __global__ __launch_bounds__(1024) void logits_bn_kernel(
     const float* __restrict__ z, const double* __restrict__ z12p, int nblk, const float* __restrict__ c2, const float* __restrict__ g3, const float* __restrict__ b3,
     float* __restrict__ rm3, float* __restrict__ rv3, int64_t* nbt, float* __restrict__ zhat,
     float* __restrict__ o, float* __restrict__ sig3, const float* __restrict__ Wf,
-    const float* __restrict__ bf, float* __restrict__ logits, int U, int T, int Bs, int B, int G) {
+    const float* __restrict__ bf, float* __restrict__ logits, int U, int T, int Bs, int B, int G,
+    const head_sums_args hs) {
+    constexpr int NT = TT ? TT : 1;                   // tasks the block sums
     extern __shared__ float4 st4[];                   // [U] {mean, 1/sigma, gamma, beta}
-    __shared__ float part[16][64];
+    __shared__ float part[NT][16][64];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int b = blockIdx.x * 64 + lane, t = blockIdx.y;
+    const int b = blockIdx.x * 64 + lane, t = TT ? 0 : blockIdx.y;
     const bool owner = blockIdx.x == 0 && blockIdx.y == 0;
     const int g = blockIdx.z, ldl = G * T;
     const size_t ug = (size_t)g * U;                   // the member's first unit
@@ -262,7 +373,8 @@ __global__ __launch_bounds__(1024) void logits_bn_kernel(
     // with them in the batch too the kernel spilled at its 128 registers)
     constexpr int LQ = 20;
     const float* wr = Wf + (size_t)t * U;
-    float* wl = reinterpret_cast<float*>(st4 + U);      // [U] combiner weights of task t
+    float* wl = reinterpret_cast<float*>(st4 + U);      // [NT][U] combiner weights of task t (+ tt)
+    STAMP(0);
     float zq0[LQ];
 #pragma unroll
     for (int q = 0; q < LQ; ++q)
@@ -282,7 +394,8 @@ __global__ __launch_bounds__(1024) void logits_bn_kernel(
         const double var = fmax(s2 / (double)B - mean * mean, 0.0);
         const double sg = sqrt(var + BN_EPS_D);
         st4[u] = make_float4((float)mean, (float)(1.0 / sg), g3[u], b3[u]);
-        wl[u] = wr[u];
+#pragma unroll
+        for (int tt = 0; tt < NT; ++tt) wl[tt * U + u] = wr[(size_t)tt * U + u];
         if (owner) {
             sig3[u] = (float)sg;
             rm3[u] = (float)((1 - BN_MOM_D) * (double)rm3[u] + BN_MOM_D * (mean + (double)c2[u]));
@@ -292,7 +405,9 @@ __global__ __launch_bounds__(1024) void logits_bn_kernel(
     }
     __syncthreads();
     const bool store = t == 0 && b < B;
-    float acc = 0.f;
+    float acc[NT];
+#pragma unroll
+    for (int tt = 0; tt < NT; ++tt) acc[tt] = 0.f;
     // twenty units (forty loads) in flight per wave: the 300 units of the headline shape are one
     // memory round trip per wave (ten at a time made two dependent ones in a kernel that is nothing
     // but round trips)
@@ -321,17 +436,31 @@ __global__ __launch_bounds__(1024) void logits_bn_kernel(
                     const uint32_t off = (uint32_t)u * (uint32_t)Bs + (uint32_t)b;
                     zhat[off] = zh; o[off] = ov;
                 }
-                acc = fmaf(wl[u], ov, acc);
+#pragma unroll
+                for (int tt = 0; tt < NT; ++tt) acc[tt] = fmaf(wl[tt * U + u], ov, acc[tt]);
             }
         }
     }
-    part[wv][lane] = acc;
-    __syncthreads();
-    if (wv == 0 && b < B) {
-        float s = bf[t];
 #pragma unroll
-        for (int i = 0; i < 16; ++i) s += part[i][lane];
-        logits[(size_t)b * ldl + t] = s;
+    for (int tt = 0; tt < NT; ++tt) part[tt][wv][lane] = acc[tt];
+    __syncthreads();
+    STAMP(1);
+    float sum[NT];
+#pragma unroll
+    for (int tt = 0; tt < NT; ++tt) sum[tt] = 0.f;
+    if (wv == 0 && b < B) {
+#pragma unroll
+        for (int tt = 0; tt < NT; ++tt) {
+            float s = bf[t + tt];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) s += part[tt][i][lane];
+            logits[(size_t)b * ldl + t + tt] = s;
+            sum[tt] = s;
+        }
+    }
+    if constexpr (TT > 0) {
+        head_sums<NT>(hs, sum, st4, wl, zhat, U, Bs, B);
+        STAMP(5);
     }
 }
 
@@ -355,10 +484,10 @@ int launch_head_fwd(explainn_ctx* c, const explainn_params* p, int B, bool train
     // (one member's statistics in 48 KB: U = G * Um exactly, so this is Um * 20 B <= 48 KB.  Written on
     // c->T and c->U because tests/dispatch_model.py reads the rule from this line.)
     if (train && logits && c->T <= HEAD_GEMM_MIN_T && !outs && (size_t)c->U * (sizeof(float4) + sizeof(float)) <= 48 * 1024 * (size_t)G) {
-        hipLaunchKernelGGL(logits_bn_kernel, grid, dim3(1024),
+        hipLaunchKernelGGL(logits_bn_kernel<0>, grid, dim3(1024),
                            (size_t)Um * (sizeof(float4) + sizeof(float)), s, c->z, c->z12p, fc_fwd_blocks(B, c->NQ),
                            p->fc2_b, p->bn3_w, p->bn3_b, p->bn3_rm, p->bn3_rv, p->bn3_nbt, c->zhat,
-                           c->o, c->sig3, p->final_w, p->final_b, logits, Um, T, c->Bs, B, G);
+                           c->o, c->sig3, p->final_w, p->final_b, logits, Um, T, c->Bs, B, G, head_sums_args{});
         LAUNCH_CHECK();
         return EXPLAINN_OK;
     }
@@ -388,6 +517,34 @@ int launch_head_fwd(explainn_ctx* c, const explainn_params* p, int B, bool train
     return EXPLAINN_OK;
 }
 
+
+// The combiner launch of the training step that also leaves the head backward's per-block partials
+// (logits_bn_kernel<T>, a single model with T <= PA_HEAD_MAX_T tasks): LDS = statistics + T weight rows.
+bool head_sums_fit(const explainn_ctx* c) {
+    return (size_t)c->U * (sizeof(float4) + c->T * sizeof(float)) <= 40 * 1024;
+}
+
+int launch_head_fwd_sums(explainn_ctx* c, const explainn_params* p, int B, float* logits, const float* y,
+                         int kind, hipStream_t s) {
+    const int U = c->U, T = c->T;
+    const head_sums_args hs = {y, kind, c->dlogits, c->hp, c->hb};
+    const size_t lds = (size_t)U * (sizeof(float4) + T * sizeof(float));
+#define CALL(TT)                                                                                      \
+    hipLaunchKernelGGL(logits_bn_kernel<TT>, dim3((B + 63) / 64), dim3(1024), lds, s, c->z, c->z12p,   \
+                       fc_fwd_blocks(B, c->NQ), p->fc2_b, p->bn3_w, p->bn3_b, p->bn3_rm, p->bn3_rv,    \
+                       p->bn3_nbt, c->zhat, c->o, c->sig3, p->final_w, p->final_b, logits, U, T, c->Bs, \
+                       B, 1, hs)
+    switch (T) {
+        case 1: CALL(1); break;
+        case 2: CALL(2); break;
+        case 3: CALL(3); break;
+        case 4: CALL(4); break;
+        default: explainn_set_error("head sums in the combiner launch: %d tasks", T); return EXPLAINN_E_UNSUPPORTED;
+    }
+#undef CALL
+    LAUNCH_CHECK();
+    return EXPLAINN_OK;
+}
 
 // loss + dlogits; up to LOSS_BLOCKS blocks write one partial sum each, the last block to finish adds
 // them in index order -> deterministic whatever the arrival order

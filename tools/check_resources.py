@@ -26,8 +26,11 @@ FIELDS = {"TotalSGPRs": "sgpr", "VGPRs": "vgpr", "AGPRs": "agpr", "ScratchSize [
 # demangled-name patterns.  Templated kernels are matched on their C2 instantiation.
 C2_STEP = [
     r"^pack_tables_kernel", r"^conv_pool_mm_kernel<5, 2,",   # (input moments + BatchNorm1 fold inside conv_pool)
-    r"^qmom_kernel<26>", r"^prep2_kernel<true>", r"^fc_fwd_bf_kernel<26, 2>", r"^logits_bn_kernel",
-    r"^head_bwd_kernel<true, false>", r"^passA_kernel<26, false>", r"^mid_fused_kernel", r"^passB_kernel<26>",
+    r"^qmom_kernel<26>", r"^prep2_kernel<true>", r"^fc_fwd_bf_kernel<26, 2>",
+    # the head backward's batch sums ride in the combiner launch (<1>: one task) and are finished in
+    # passA (<26, 2>); <0>, head_bwd and <26, 0> are the same step with EXPLAINN_HEAD_PARTIALS=0
+    r"^logits_bn_kernel<1>", r"^passA_kernel<26, 2>", r"^logits_bn_kernel<0>",
+    r"^head_bwd_kernel<true, false>", r"^passA_kernel<26, 0>", r"^mid_fused_kernel", r"^passB_kernel<26>",
     r"^conv_bwd_mm_kernel<19>", r"^fin_bwd_kernel", r"adam_kernel",
 ]
 
@@ -60,7 +63,9 @@ GATED = C2_STEP + INPUT_GRAD + ISM + METRICS + SCAN + VARIANTS
 
 # Register cliffs measured in the pipeline: 1024-thread blocks of which TWO must
 # share a CU (300 units on 256 CUs take two rounds otherwise) -- 64 registers, not one more.
-VGPR_CAP = {r"^mid_fused_kernel": 64, r"^prep2_kernel<true>": 64}
+# passA: three waves per SIMD (512 registers / 3, in allocation units of 8).
+VGPR_CAP = {r"^mid_fused_kernel": 64, r"^prep2_kernel<true>": 64,
+            r"^passA_kernel<26, 0>": 168, r"^passA_kernel<26, 2>": 168}
 
 
 def demangle(names):
@@ -115,7 +120,7 @@ def main():
     for r in rows:
         for pat, cap in VGPR_CAP.items():
             if re.search(pat, r["name"]) and r.get("vgpr", 0) + r.get("agpr", 0) > cap:
-                print("check_resources: ERROR: %s uses %d registers, over its cap of %d (two blocks per CU)"
+                print("check_resources: ERROR: %s uses %d registers, over its cap of %d (an occupancy step)"
                       % (r["name"], r.get("vgpr", 0) + r.get("agpr", 0), cap))
                 rc = 1
     for p in missing:

@@ -31,6 +31,7 @@ void explainn_set_error(const char* fmt, ...) { va_list ap; va_start(ap, fmt); v
 #include "../explainn_amd/csrc/prep.hip"
 #include "../explainn_amd/csrc/fc.hip"
 #include "../explainn_amd/csrc/bwd.hip"
+#include "../explainn_amd/csrc/head.hip"
 #include "../explainn_amd/csrc/convpool.hip"
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); exit(1);} } while (0)
 
@@ -115,6 +116,12 @@ int main() {
     double* mug = (double*)dalloc(U * 8); double* sig1 = (double*)dalloc(U * 8); std::vector<double> one(U, 1.0); CK(hipMemcpy(sig1, one.data(), U * 8, hipMemcpyHostToDevice));
     float* dy = (float*)dalloc((size_t)U * n * Bs * 4); float* S12p = (float*)dalloc((size_t)U * (Bs / 16) * 2 * 4);
     float* fz = (float*)dalloc(U * 4);
+    // head sums: zeros / ones per unit, targets, loss gradient, logits, the partial buffers
+    float* fz300 = (float*)dalloc(U * 4); float* g3one = (float*)dalloc(U * 4); float* zhat = (float*)dalloc((size_t)U * Bs * 4);
+    { std::vector<float> h1(U, 1.0f); CK(hipMemcpy(g3one, h1.data(), U * 4, hipMemcpyHostToDevice)); }
+    float* hst = (float*)dalloc(3 * U * 4); float* hout = (float*)dalloc(6 * U * 4);   // running statistics / sigma3; the owner waves' outputs
+    float* hy = (float*)dalloc(B * 4); float* hdl = (float*)dalloc(B * 4); float* hlog = (float*)dalloc(B * 4);
+    double* hp = (double*)dalloc((size_t)U * ((B + 63) / 64) * 6 * 8); double* hb = (double*)dalloc(((B + 63) / 64) * 5 * 8);
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1)); float ms;
     for (int rep = 0; rep < 2; ++rep) {
         CK(hipMemset(fz, 0, 4));
@@ -130,9 +137,25 @@ int main() {
         if (rep) report("fc_fwd", 4 * U * 4, 5, ms);
         clear_stamps();
         CK(hipEventRecord(e0));
-        hipLaunchKernelGGL((passA_kernel<26, false>), dim3(ACH, U, 1), dim3(64 * PA_WAVES), 0, 0, ext, alpha, shift, dz, bits, EQp, Sep, n, Bs, B, ACH, pa_head_args{}, U);
+        hipLaunchKernelGGL((passA_kernel<26, 0>), dim3(ACH, U, 1), dim3(64 * PA_WAVES), 0, 0, ext, alpha, shift, dz, bits, EQp, Sep, n, Bs, B, ACH, pa_head_args{}, U, pa_sums_args{});
         CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1)); CK(hipEventElapsedTime(&ms, e0, e1));
         if (rep) report("passA", ACH * U * PA_WAVES, 4, ms);
+        // the head backward's batch sums in the combiner launch (stamps: 0 start, 1 logits summed, 2 -> 3
+        // wave 0's loss gradient + barrier, 4 zhat back from memory, 5 end) and passA's form that finishes them
+        {
+            const head_sums_args hs = {hy, 0, hdl, hp, hb};
+            clear_stamps();
+            CK(hipEventRecord(e0));
+            hipLaunchKernelGGL(logits_bn_kernel<1>, dim3((B + 63) / 64), dim3(1024), (size_t)U * 20, 0, z, z12p, 4, fz300, g3one, fz300, hst, hst + U, (int64_t*)nullptr, zhat, o, hst + 2 * U, g3one, fz300, hlog, U, 1, Bs, B, 1, hs);
+            CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1)); CK(hipEventElapsedTime(&ms, e0, e1));
+            if (rep) report("logits_bn<1>", (B + 63) / 64 * 16, 6, ms);
+            const pa_sums_args ps = {zhat, hdl, dz, g3one, g3one, fz300, g3one, 1, (B + 63) / 64, hp, hb, hout, hout + U, hout + 2 * U, hout + 3 * U, hout + 4 * U, hout + 5 * U};
+            clear_stamps();
+            CK(hipEventRecord(e0));
+            hipLaunchKernelGGL((passA_kernel<26, 2>), dim3(ACH, U, 1), dim3(64 * PA_WAVES), 0, 0, ext, alpha, shift, dz, bits, EQp, Sep, n, Bs, B, ACH, pa_head_args{}, U, ps);
+            CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1)); CK(hipEventElapsedTime(&ms, e0, e1));
+            if (rep) report("passA<2>", ACH * U * PA_WAVES, 4, ms);
+        }
         clear_stamps();
         CK(hipEventRecord(e0));
         hipLaunchKernelGGL(passB_kernel<26>, dim3(4, units_grid(U), 1), dim3(256), passB_lds<26>(), 0, ext, alpha, shift, dz, bits, Tt, M, k0p, mug, sig1, dy, S12p, n, Bs, B, U); // (tables passed as fragment-ordered stand-ins)
