@@ -84,6 +84,16 @@ class Edits(C.Structure):
     _fields_ = [(f, _fp) for f in EDIT_FIELDS[:7]] + [(f, C.c_int64) for f in EDIT_FIELDS[7:]]
 
 
+HAPLOTYPE_FIELDS = ("row_start", "row_first", "row_count", "edit_index", "pos", "ref_len", "alt_len", "alt_off",
+                    "alt", "n_index", "n_edits", "alt_bytes")
+
+
+class Haplotypes(C.Structure):
+    """explainn_haplotypes: the row table, the index lists, the edit table and the alt pool of
+    explainn_score_haplotypes (device pointers; include/explainn_hip.h)."""
+    _fields_ = [(f, _fp) for f in HAPLOTYPE_FIELDS[:9]] + [(f, C.c_int64) for f in HAPLOTYPE_FIELDS[9:]]
+
+
 _ctx, _pp, _gp, _i, _i64 = C.c_void_p, C.POINTER(Params), C.POINTER(Grads), C.c_int, C.c_int64
 # every C function of the header: name -> (restype, argtypes)
 SIGNATURES = {
@@ -118,6 +128,8 @@ SIGNATURES = {
     "explainn_scan": (_i, [_ctx, _fp, _i64, _i64, _i64, _i64, _i, _pp, _fp, _i, _fp, _i64, _fp]),
     "explainn_stage_edited_windows": (_i, [_ctx, _fp, _i64, C.POINTER(Edits), _i64, _i, _i, _fp]),
     "explainn_score_edits": (_i, [_ctx, _fp, _i64, C.POINTER(Edits), _i64, _i, _pp, _fp, _fp, _fp]),
+    "explainn_stage_haplotype_windows": (_i, [_ctx, _fp, _i64, C.POINTER(Haplotypes), _i64, _i, _i, _fp]),
+    "explainn_score_haplotypes": (_i, [_ctx, _fp, _i64, C.POINTER(Haplotypes), _i64, _i, _pp, _fp, _fp, _fp]),
     "explainn_call_sites_workspace_bytes": (_i64, [_ctx, _i64]),
     "explainn_call_sites": (_i, [_ctx, _fp, _i64, _i64, _i64, _i64, _i, _pp, _fp, _fp, _fp, _fp, _i64, _fp,
                                  _i64, _fp]),

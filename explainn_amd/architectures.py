@@ -180,7 +180,7 @@ class EditedWindows:
         """(sequences per device pass, L): what _front sizes the context by."""
         return (self.sub_batch, None)
 
-    def check(self, dev):
+    def _check_tensors(self, dev):
         c = self.codes
         if not torch.is_tensor(c) or c.dtype != torch.uint8 or c.dim() != 1 or not c.is_contiguous():
             raise RuntimeError("edited windows take a contiguous 1-D uint8 tensor of base codes")
@@ -190,6 +190,9 @@ class EditedWindows:
             t = getattr(self, name)
             if not torch.is_tensor(t) or t.dtype != dt or t.dim() != 1 or not t.is_contiguous() or t.device != dev:
                 raise RuntimeError("%s must be a contiguous 1-D %s tensor on %s" % (name, dt, dev))
+
+    def check(self, dev):
+        self._check_tensors(dev)
         if self.row_edit.numel() != self.n_rows:
             raise RuntimeError("row_start and row_edit must have one entry per row")
         if not self.pos.numel() == self.ref_len.numel() == self.alt_len.numel() == self.alt_off.numel():
@@ -203,6 +206,44 @@ class EditedWindows:
             setattr(ed, name, t.data_ptr() if t.numel() else None)
         ed.n_edits, ed.alt_bytes = self.pos.numel(), self.alt.numel()
         return ed
+
+
+class HaplotypeWindows(EditedWindows):
+    """Windows of ONE device-resident sequence of base codes at arbitrary starts, each carrying a RUN of
+    edits, as ExplaiNN._launch_score_haplotypes takes them (explainn_score_haplotypes,
+    include/explainn_hip.h has the run algebra and the ordering rule).  Contiguous tensors on the codes'
+    device: row_start int64, row_first int64, row_count int32 (rows,); edit_index int32, the rows' runs
+    as indices into the edit table; pos int64, ref_len / alt_len / alt_off int32 (edits,); alt uint8.
+    Row b carries the edits edit_index[row_first[b] : row_first[b] + row_count[b]]."""
+
+    _TABLES = (("row_start", torch.int64), ("row_first", torch.int64), ("row_count", torch.int32),
+               ("edit_index", torch.int32), ("pos", torch.int64), ("ref_len", torch.int32),
+               ("alt_len", torch.int32), ("alt_off", torch.int32), ("alt", torch.uint8))
+
+    def __init__(self, codes, row_start, row_first, row_count, edit_index, pos, ref_len, alt_len, alt_off, alt,
+                 reverse_complement=False, sub_batch=4096):
+        self.codes = codes
+        self.row_start, self.row_first, self.row_count, self.edit_index = row_start, row_first, row_count, edit_index
+        self.pos, self.ref_len, self.alt_len, self.alt_off, self.alt = pos, ref_len, alt_len, alt_off, alt
+        self.reverse_complement = bool(reverse_complement)
+        self.n_rows = int(row_start.numel())
+        self.sub_batch = max(1, min(int(sub_batch), self.n_rows))
+
+    def check(self, dev):
+        self._check_tensors(dev)
+        if self.row_first.numel() != self.n_rows or self.row_count.numel() != self.n_rows:
+            raise RuntimeError("row_start, row_first and row_count must have one entry per row")
+        if not self.pos.numel() == self.ref_len.numel() == self.alt_len.numel() == self.alt_off.numel():
+            raise RuntimeError("pos, ref_len, alt_len and alt_off must have one entry per edit")
+
+    def struct(self):
+        """The explainn_haplotypes of these tables (valid while this object lives)."""
+        hp = _lib.Haplotypes()
+        for name, _ in self._TABLES:
+            t = getattr(self, name)
+            setattr(hp, name, t.data_ptr() if t.numel() else None)
+        hp.n_index, hp.n_edits, hp.alt_bytes = self.edit_index.numel(), self.pos.numel(), self.alt.numel()
+        return hp
 
 
 VALIDATE_EVERY = 64      # deferred input validation: the sticky device flag is read every this many calls
@@ -731,6 +772,26 @@ class ExplaiNN(_Model):
                 ed = ew.struct()
                 _lib.check(ctx.lib.explainn_score_edits(
                     ctx.handle, xp, ew.codes.numel(), C.byref(ed), ew.n_rows, int(ew.reverse_complement),
+                    C.byref(ps), logits.data_ptr(), outs.data_ptr() if want_outs else None, stream))
+                self._settle(read)
+        return (logits, outs) if want_outs else logits
+
+    def _launch_score_haplotypes(self, hw, want_outs=False):
+        """Eval-mode logits of the rows of a HaplotypeWindows (explainn_score_haplotypes): (rows, T) --
+        (rows, G, T) on a bank -- fp32 on the device; with want_outs also the per-unit outputs
+        (rows, units), units = G*U on a bank, from the same pass: returns (logits, outs)."""
+        if self.training:
+            raise RuntimeError("scoring haplotypes is an eval-mode path; call model.eval()")
+        dev = self._device()
+        hw.check(dev)
+        logits = self._logits_empty(hw.n_rows, dev)
+        outs = torch.empty(hw.n_rows, self._units(), device=dev, dtype=torch.float32) if want_outs else None
+        if hw.n_rows > 0:
+            with torch.cuda.device(dev):
+                ctx, ps, _, stream, xp, read = self._front(hw, dev)
+                hp = hw.struct()
+                _lib.check(ctx.lib.explainn_score_haplotypes(
+                    ctx.handle, xp, hw.codes.numel(), C.byref(hp), hw.n_rows, int(hw.reverse_complement),
                     C.byref(ps), logits.data_ptr(), outs.data_ptr() if want_outs else None, stream))
                 self._settle(read)
         return (logits, outs) if want_outs else logits

@@ -566,6 +566,64 @@ extern "C" int explainn_score_edits(explainn_ctx* c, const uint8_t* seq, int64_t
     return EXPLAINN_OK;
 }
 
+namespace {
+// what can be checked of haplotype tables without reading them (their arrays live on the device)
+int check_haplotypes(const uint8_t* seq, int64_t seq_len, const explainn_haplotypes* hp, int64_t row0) {
+    if (!seq || seq_len < 0) { explainn_set_error("seq is null or seq_len negative"); return EXPLAINN_E_ARG; }
+    if (!hp || !hp->row_start || !hp->row_first || !hp->row_count || row0 < 0) {
+        explainn_set_error("haplotypes, its row_start, row_first and row_count are required, row0 >= 0");
+        return EXPLAINN_E_ARG;
+    }
+    if (hp->n_index < 0 || hp->n_edits < 0 || hp->alt_bytes < 0 || hp->alt_bytes >= (int64_t)1 << 31) {
+        explainn_set_error("haplotypes needs n_index >= 0, n_edits >= 0 and 0 <= alt_bytes < 2^31 (got %lld, %lld, %lld)",
+                           (long long)hp->n_index, (long long)hp->n_edits, (long long)hp->alt_bytes);
+        return EXPLAINN_E_ARG;
+    }
+    if (hp->n_index > 0 && !hp->edit_index) {
+        explainn_set_error("edit_index is null but n_index is %lld", (long long)hp->n_index);
+        return EXPLAINN_E_ARG;
+    }
+    if (hp->n_edits > 0 && (!hp->pos || !hp->ref_len || !hp->alt_len || !hp->alt_off)) {
+        explainn_set_error("an edit table of %lld edits needs pos, ref_len, alt_len and alt_off", (long long)hp->n_edits);
+        return EXPLAINN_E_ARG;
+    }
+    if (hp->alt_bytes > 0 && !hp->alt) { explainn_set_error("alt is null but alt_bytes is %lld", (long long)hp->alt_bytes); return EXPLAINN_E_ARG; }
+    return EXPLAINN_OK;
+}
+}  // namespace
+
+extern "C" int explainn_stage_haplotype_windows(explainn_ctx* c, const uint8_t* seq, int64_t seq_len,
+                                                const explainn_haplotypes* haps, int64_t row0, int B,
+                                                int reverse_complement, void* stream) {
+    TRY(check_batch(c, B));
+    TRY(check_haplotypes(seq, seq_len, haps, row0));
+    drop_pending(c);                   // the packed codes of a pending backward are overwritten
+    return launch_stage_haplotypes(c, seq, seq_len, haps, row0, B, reverse_complement ? 1 : 0,
+                                   static_cast<hipStream_t>(stream));
+}
+
+extern "C" int explainn_score_haplotypes(explainn_ctx* c, const uint8_t* seq, int64_t seq_len,
+                                         const explainn_haplotypes* haps, int64_t n_rows, int reverse_complement,
+                                         const explainn_params* p, float* logits, float* outs, void* stream) {
+    if (!c) { explainn_set_error("null context"); return EXPLAINN_E_ARG; }
+    if (n_rows < 1 || !p) { explainn_set_error("score_haplotypes needs n_rows >= 1 and params"); return EXPLAINN_E_ARG; }
+    if (!logits && !outs) { explainn_set_error("score_haplotypes needs logits or outs (both are null)"); return EXPLAINN_E_ARG; }
+    TRY(check_haplotypes(seq, seq_len, haps, 0));
+    if (c->dense) { explainn_set_error("haplotypes are scored on base codes: not in dense input mode"); return EXPLAINN_E_UNSUPPORTED; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int rc = reverse_complement ? 1 : 0;
+    const int64_t row = (int64_t)c->Gm * c->T;       // logits are (n_rows, [G,] T), outs (n_rows, units)
+    drop_pending(c);
+    for (int64_t i0 = 0; i0 < n_rows; i0 += c->maxB) {
+        const int Bw = (int)(n_rows - i0 < c->maxB ? n_rows - i0 : c->maxB);
+        TRY(launch_stage_haplotypes(c, seq, seq_len, haps, i0, Bw, rc, s));
+        TRY(eval_forward(c, nullptr, Bw, p, false, logits ? logits + i0 * row : nullptr,
+                         outs ? outs + i0 * c->U : nullptr, s));
+    }
+    c->staged_B = 0;
+    return EXPLAINN_OK;
+}
+
 extern "C" int64_t explainn_call_sites_workspace_bytes(const explainn_ctx* c, int64_t n_positions) {
     if (!c || n_positions < 0 || n_positions + c->k >= (int64_t)1 << 31) return 0;
     return sites_workspace_bytes(c, n_positions);

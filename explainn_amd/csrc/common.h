@@ -233,6 +233,9 @@ int64_t scan_tiles(const explainn_ctx* c, int64_t n_windows, int m);
 // variant effects (variants.hip): rows [row0, row0 + B) of an edit table's row table staged as a batch
 int launch_stage_edits(explainn_ctx* c, const uint8_t* seq, int64_t seq_len, const explainn_edits* ed,
                        int64_t row0, int B, int rc, hipStream_t s);
+// haplotypes (haplotypes.hip): the same for rows that carry a run of edits each
+int launch_stage_haplotypes(explainn_ctx* c, const uint8_t* seq, int64_t seq_len, const explainn_haplotypes* hp,
+                            int64_t row0, int B, int rc, hipStream_t s);
 
 // motif sites (sites.hip): the compacted (unit, position, score) list of a range of start positions
 int64_t sites_workspace_bytes(const explainn_ctx* c, int64_t npos);

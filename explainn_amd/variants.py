@@ -15,7 +15,16 @@ variant, and the windows are cut and edited there (explainn_score_edits, include
 MaxPool1d(7,7) puts its grid at the window start, so a variant's effect depends on its phase mod 7
 inside the window: `shifts` slides the window (both alleles alike) and the scores are averaged.
 
-`python -m explainn_amd.variants MODEL FASTA VCF` writes one TSV row per variant and class.
+A window that carries several variants at once -- two variants 50 bases apart, a person's phased
+genotype over a region -- goes through score_haplotypes(): the same per-variant edit table, and per
+haplotype a list of the variants it carries (explainn_score_haplotypes).
+
+    res = score_haplotypes(model, codes, pos, ref_len, alts, haplotypes=[[0, 3, 4], [3]], starts=[1000, 1200])
+    res["hap"]       # (H, R, T, 4): haplotype h in the window at starts[r]
+    res["delta"]     # (H, R, T): haplotype - reference
+
+`python -m explainn_amd.variants MODEL FASTA VCF` writes one TSV row per variant and class; with
+`--haplotypes --regions BED` one row per region, sample, haplotype and class from the VCF's genotypes.
 """
 import argparse
 import contextlib
@@ -25,7 +34,7 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from .architectures import EditedWindows
+from .architectures import EditedWindows, HaplotypeWindows
 
 _CHUNK_PASSES = 32           # rows per device call, at most: this many sub-batches of `batch_size` rows
 _MAX_POOL = (1 << 31) - 1    # bytes the alt pool may hold (explainn_edits.alt_bytes < 2^31)
@@ -104,6 +113,36 @@ def _final_rows(model):
     return w if w.dim() == 2 else w.permute(1, 0, 2).reshape(w.shape[1], -1)
 
 
+def _strand_handles(model, both):
+    """(current stream, eval replica, side stream) of the two-stream strand handling; the last two None
+    for the forward strand alone."""
+    device = model.final.weight.device
+    cur = torch.cuda.current_stream(device)
+    if not both:
+        return cur, None, None
+    rep = model.eval_replica()
+    if model._rt.side_stream is None:
+        model._rt.side_stream = torch.cuda.Stream(device)
+    return cur, rep, model._rt.side_stream
+
+
+def _launch_strands(model, handles, launch, unit_effects):
+    """launch(m, reverse_complement) on the model and, when both strands are asked for, on its replica
+    on the side stream at the same time: (fwd, rev), rev None for the forward strand alone."""
+    cur, rep, side = handles
+    rev = None
+    if rep is not None:
+        side.wait_stream(cur)                           # the tables are on the device
+        with torch.cuda.stream(side):
+            rev = launch(rep, True)
+    fwd = launch(model, False)
+    if rep is not None:
+        cur.wait_stream(side)
+        for t in (rev if unit_effects else (rev,)):
+            t.record_stream(cur)
+    return fwd, rev
+
+
 def score_variants(model, codes, pos, ref_len, alts, shifts=(0,), strands="both", batch_size=4096,
                    check_ref=None, unit_effects=False, apply_sigmoid=False, chunk_rows=None):
     """Eval-mode predictions of the reference and the alternative allele of V variants of one sequence.
@@ -149,13 +188,8 @@ def score_variants(model, codes, pos, ref_len, alts, shifts=(0,), strands="both"
     if V == 0:
         return res
     both = strands == "both"
-    cur = torch.cuda.current_stream(device)
-    rep = side = None
-    if both:
-        rep = model.eval_replica()
-        if model._rt.side_stream is None:
-            model._rt.side_stream = torch.cuda.Stream(device)
-        side = model._rt.side_stream
+    handles = _strand_handles(model, both)
+    rep = handles[1]
     seq_d = data.to(device).contiguous()
     if check_ref is not None:
         _check_ref_alleles(seq_d, tab["pos"], tab["ref_len"].astype(np.int64), check_ref)
@@ -166,19 +200,12 @@ def score_variants(model, codes, pos, ref_len, alts, shifts=(0,), strands="both"
         for v0, cnt in chunks(V, S, limit):
             r0, r1 = 2 * S * v0, 2 * S * (v0 + cnt)
 
-            def rows(rc):
-                return EditedWindows(seq_d, dt["row_start"][r0:r1], dt["row_edit"][r0:r1], dt["pos"],
-                                     dt["ref_len"], dt["alt_len"], dt["alt_off"], dt["alt"], rc, batch_size)
+            def launch(m, rc):
+                return m._launch_score_edits(
+                    EditedWindows(seq_d, dt["row_start"][r0:r1], dt["row_edit"][r0:r1], dt["pos"], dt["ref_len"],
+                                  dt["alt_len"], dt["alt_off"], dt["alt"], rc, batch_size), unit_effects)
 
-            if both:
-                side.wait_stream(cur)                           # the tables are on the device
-                with torch.cuda.stream(side):
-                    rev = rep._launch_score_edits(rows(True), unit_effects)
-            fwd = model._launch_score_edits(rows(False), unit_effects)
-            if both:
-                cur.wait_stream(side)
-                for t in (rev if unit_effects else (rev,)):
-                    t.record_stream(cur)
+            fwd, rev = _launch_strands(model, handles, launch, unit_effects)
             if unit_effects:
                 (fwd, ofwd), orev = fwd, None
                 if both:
@@ -207,6 +234,167 @@ def score_variants(model, codes, pos, ref_len, alts, shifts=(0,), strands="both"
     return res
 
 
+def build_haplotype_tables(pos, ref_len, alts, haplotypes, starts, L):
+    """The tables of explainn_score_haplotypes for H haplotypes in R windows, as numpy arrays.
+
+    pos / ref_len / alts: the V variants, as build_tables takes them; they become the edit table (pos
+    int64, ref_len / alt_len / alt_off int32, alt uint8), one record per variant.  haplotypes: H integer
+    arrays, the variants each haplotype carries, in any order; each is sorted by position (stable, so
+    two insertions at one position keep their order) and two carried variants that overlap raise
+    ValueError.  starts: the R window left edges, in reference coordinates.
+
+    Row h*R + r is haplotype h in the window at starts[r]: row_start = starts[r], and its run (row_first
+    int64, row_count int32, into edit_index int32, the sorted lists end to end) holds the haplotype's
+    variants from the first with pos >= starts[r] while they begin inside the window,
+    hstart < starts[r] + L -- later ones cannot reach it, earlier ones lie left of it.  A carried variant
+    with pos < starts[r] < pos + ref_len straddles the left edge: the window would begin inside its alt
+    allele, at no reference coordinate; it is left out and counted in straddling (H, R)."""
+    tab = build_tables(pos, ref_len, alts, L)
+    epos, eref, ealt = tab["pos"], tab["ref_len"].astype(np.int64), tab["alt_len"].astype(np.int64)
+    V = len(epos)
+    starts = np.asarray(starts, dtype=np.int64).reshape(-1)
+    H, R = len(haplotypes), len(starts)
+    lists, first, count = [], np.zeros((H, R), dtype=np.int64), np.zeros((H, R), dtype=np.int64)
+    straddling = np.zeros((H, R), dtype=np.int64)
+    offset = 0
+    for h, carried in enumerate(haplotypes):
+        idx = np.asarray(carried, dtype=np.int64).reshape(-1)
+        if idx.size and (idx.min() < 0 or idx.max() >= V):
+            raise ValueError("haplotype %d carries a variant outside 0..%d" % (h, V - 1))
+        idx = idx[np.argsort(epos[idx], kind="stable")]
+        p, end = epos[idx], epos[idx] + eref[idx]
+        clash = np.flatnonzero(end[:-1] > p[1:])
+        if clash.size:
+            a, b = idx[clash[0]], idx[clash[0] + 1]
+            raise ValueError("haplotype %d carries overlapping variants #%d at %d (ref_len %d) and #%d at %d"
+                             % (h, a, epos[a], eref[a], b, epos[b]))
+        # where each variant begins on the haplotype that carries all of them: pos + the shift of those before
+        shift = np.concatenate((np.zeros(1, np.int64), np.cumsum(ealt[idx] - eref[idx])))
+        hstart = p + shift[:-1]
+        f = np.searchsorted(p, starts, side="left")
+        # the run's own coordinates start at its first edit: the shift before it does not count
+        stop = np.searchsorted(hstart, starts + L + shift[f], side="left")
+        first[h], count[h] = offset + f, np.maximum(stop - f, 0)
+        if idx.size:
+            straddling[h] = (f > 0) & (end[np.maximum(f - 1, 0)] > starts)
+        lists.append(idx)
+        offset += idx.size
+    edit_index = np.concatenate(lists + [np.zeros(0, np.int64)])
+    if edit_index.size > _MAX_POOL:
+        raise ValueError("haplotype lists of %d entries exceed 2^31 - 1" % edit_index.size)
+    out = {"row_start": np.tile(starts, H), "row_first": first.reshape(-1),
+           "row_count": count.reshape(-1).astype(np.int32), "edit_index": edit_index.astype(np.int32)}
+    out.update({k: tab[k] for k in ("pos", "ref_len", "alt_len", "alt_off", "alt")})
+    out["straddling"] = straddling
+    return out
+
+
+_HAP_TABLES = ("row_start", "row_first", "row_count", "edit_index", "pos", "ref_len", "alt_len", "alt_off", "alt")
+
+
+def score_haplotypes(model, codes, pos, ref_len, alts, haplotypes, starts, strands="both", batch_size=4096,
+                     check_ref=None, unit_effects=False, apply_sigmoid=False, chunk_rows=None):
+    """Eval-mode predictions of H haplotypes of one sequence in R windows, each haplotype carrying any
+    number of the V variants (codes, pos, ref_len, alts, check_ref as score_variants takes them;
+    haplotypes and starts as build_haplotype_tables).  Returns a dict:
+      hap         (H, R, T, 4) float64 in predict()'s order [Fwd, Rev, Mean, Max] -- (H, R, G, T, 4) for
+                  an ExplaiNNBank -- each row what predict() gives on the materialised window;
+      ref         (R, T, 4): the reference windows, each scored once;
+      delta       (H, R, T): hap[..., 2] - ref[..., 2] (column 0 with strands="fwd", which leaves
+                  columns 1..3 NaN);
+      straddling  (H, R): the carried variants left out of a row because the window's left edge lies
+                  inside their REF allele (build_haplotype_tables);
+      units       with unit_effects: (H, R, units, T) float32, (outs_hap - outs_ref)[u] * final.weight[t,u]
+                  averaged over strands; sums over units to delta to fp32 rounding (score_variants has
+                  the bank layout).
+    Strands, streams and chunking are score_variants': the rows go to the device in chunks of at most
+    32 * batch_size rows (chunk_rows overrides it), the reference windows first."""
+    if strands not in ("both", "fwd"):
+        raise ValueError("strands must be 'both' or 'fwd' (got %r)" % (strands,))
+    L = model._options["sequence_length"]
+    batch_size = max(1, int(batch_size))
+    device = model.final.weight.device
+    data = codes if torch.is_tensor(codes) else torch.as_tensor(np.ascontiguousarray(codes))
+    if data.dtype != torch.uint8 or data.dim() != 1:
+        raise ValueError("codes must be a 1-D uint8 array of base codes")
+    tab = build_haplotype_tables(pos, ref_len, alts, haplotypes, starts, L)
+    V, H = len(tab["pos"]), len(haplotypes)
+    R = len(tab["row_start"]) // H if H else len(np.asarray(starts).reshape(-1))
+    if V and (tab["pos"].min() < 0 or (tab["pos"] + tab["ref_len"]).max() > data.shape[0]):
+        bad = np.flatnonzero((tab["pos"] < 0) | (tab["pos"] + tab["ref_len"] > data.shape[0]))
+        raise ValueError("%d variant(s) outside the sequence of %d bases (0 <= pos, pos + ref_len <= length); "
+                         "the first: #%d at %d" % (bad.size, data.shape[0], bad[0], tab["pos"][bad[0]]))
+    # the reference windows are rows of their own, without a run, ahead of the haplotypes' rows
+    ref_start = np.asarray(starts, dtype=np.int64).reshape(-1)
+    tab["row_start"] = np.concatenate((ref_start, tab["row_start"]))
+    tab["row_first"] = np.concatenate((np.zeros(R, np.int64), tab["row_first"]))
+    tab["row_count"] = np.concatenate((np.zeros(R, np.int32), tab["row_count"]))
+    shape = tuple(model._logits_empty(0, torch.device("cpu")).shape[1:])
+    units = model._units()
+    rows = R + H * R
+    scores = np.full((rows,) + shape + (4,), np.nan)
+    res = {"straddling": tab["straddling"]}
+    if unit_effects:
+        res["units"] = np.zeros((H * R, units, shape[-1]), dtype=np.float32)
+    if rows:
+        both = strands == "both"
+        handles = _strand_handles(model, both)
+        rep = handles[1]
+        seq_d = data.to(device).contiguous()
+        if check_ref is not None:
+            _check_ref_alleles(seq_d, tab["pos"], tab["ref_len"].astype(np.int64), check_ref)
+        dt = {k: torch.from_numpy(tab[k]).to(device) for k in _HAP_TABLES}
+        wrows = _final_rows(model) if unit_effects else None
+        limit = max(1, int(chunk_rows) if chunk_rows is not None else _CHUNK_PASSES * batch_size)
+        # the reference rows in chunks of their own, so that a chunk of haplotype rows finds them all
+        spans = [(r0, min(r0 + limit, R)) for r0 in range(0, R, limit)]
+        spans += [(r0, min(r0 + limit, rows)) for r0 in range(R, rows, limit)]
+        ref_parts, ref_outs = ([], []), None
+        with torch.no_grad(), model.eval_cache(), (rep.eval_cache() if both else contextlib.nullcontext()):
+            for r0, r1 in spans:
+
+                def launch(m, rc):
+                    return m._launch_score_haplotypes(
+                        HaplotypeWindows(seq_d, dt["row_start"][r0:r1], dt["row_first"][r0:r1],
+                                         dt["row_count"][r0:r1], dt["edit_index"], dt["pos"], dt["ref_len"],
+                                         dt["alt_len"], dt["alt_off"], dt["alt"], rc, batch_size), unit_effects)
+
+                fwd, rev = _launch_strands(model, handles, launch, unit_effects)
+                if unit_effects:
+                    (fwd, ofwd), orev = fwd, None
+                    if both:
+                        rev, orev = rev
+                    if r0 < R:
+                        ref_parts[0].append(ofwd)
+                        ref_parts[1].append(orev)
+                    else:
+                        if ref_outs is None:
+                            ref_outs = (torch.cat(ref_parts[0]), torch.cat(ref_parts[1]) if both else None)
+                        window = torch.arange(r0 - R, r1 - R, device=device) % R
+                        d = ofwd - ref_outs[0][window]                  # (rows, units): hap - ref
+                        if both:
+                            d = (d + (orev - ref_outs[1][window])) / 2
+                        res["units"][r0 - R:r1 - R] = (d[:, :, None] * wrows.t()[None, :, :]).cpu().numpy()
+                if both:
+                    full = torch.stack((fwd, rev, (fwd + rev) / 2, torch.maximum(fwd, rev)), dim=-1)
+                    scores[r0:r1] = full.cpu().numpy()
+                else:
+                    scores[r0:r1, ..., 0] = fwd.cpu().numpy()
+        if model.validate_input:
+            if both:
+                rep.check_input()
+            model.check_input()
+    if apply_sigmoid:
+        scores = torch.sigmoid(torch.from_numpy(scores)).numpy()
+    res["ref"] = scores[:R]
+    res["hap"] = scores[R:].reshape((H, R) + shape + (4,))
+    col = 2 if strands == "both" else 0
+    res["delta"] = res["hap"][..., col] - res["ref"][None, ..., col]
+    if unit_effects:
+        res["units"] = res["units"].reshape(H, R, units, shape[-1])
+    return res
+
+
 def _is_symbolic(allele):
     return allele in ("", ".", "*") or allele.startswith("<") or "[" in allele or "]" in allele
 
@@ -232,6 +420,134 @@ def read_vcf(path):
                 else:
                     out.append(Variant(chrom, pos, vid, ref, alt))
     return out, skipped
+
+
+def read_vcf_genotypes(path, samples=None):
+    """VCF with genotypes -> (variants, sample_names, carried, unphased).  variants: as read_vcf makes
+    them, one Variant per usable ALT allele (symbolic alleles have no row).  sample_names: the samples
+    read, in file order, or the names given in `samples` (a name the file lacks raises ValueError).
+    carried: uint8 (alleles, samples, 2), 1 where haplotype h of sample s carries ALT-allele row a.  A
+    phased call a|b is placed as written; an unphased call that is homozygous for one ALT allele goes on
+    both haplotypes; an unphased heterozygous call goes on neither and is counted, per sample, in
+    unphased (samples,); '.' is the reference allele; a haploid call fills haplotype 0."""
+    from .loader import _open
+    import re
+    out, rows, names, cols = [], [], None, None
+    with _open(path, "rt") as fh:
+        for line in fh:
+            if not line.strip() or line.startswith("##"):
+                continue
+            f = line.rstrip("\r\n").split("\t")
+            if line.startswith("#"):
+                have = f[9:]
+                names = list(have) if samples is None else list(samples)
+                missing = [n for n in names if n not in have]
+                if missing:
+                    raise ValueError("sample(s) not in the VCF: %s" % ", ".join(missing))
+                cols = [9 + have.index(n) for n in names]
+                unphased = np.zeros(len(names), dtype=np.int64)
+                continue
+            if names is None:
+                raise ValueError("VCF record before the #CHROM header line")
+            if len(f) < 5:
+                raise ValueError("VCF line with fewer than 5 columns: %r" % line[:80])
+            chrom, pos, vid, ref = f[0], int(f[1]) - 1, f[2], f[3]
+            fmt = f[8].split(":") if len(f) > 8 else []
+            if names and "GT" not in fmt:
+                raise ValueError("VCF record without a GT field: %r" % line[:80])
+            calls = []
+            for s, c in enumerate(cols):
+                if c >= len(f):
+                    raise ValueError("VCF line with fewer sample columns than the header: %r" % line[:80])
+                text = f[c].split(":")[fmt.index("GT")]
+                al = [None if a in (".", "") else int(a) for a in re.split(r"[|/]", text)]
+                if len(al) > 2:
+                    raise ValueError("genotype %r: more than two haplotypes are not supported" % text)
+                phased = len(al) == 1 or "|" in text
+                if not phased and al[0] != al[1] and any(a for a in al):
+                    unphased[s] += 1
+                calls.append((al, phased))
+            for k, alt in enumerate(f[4].split(","), start=1):
+                if _is_symbolic(alt) or _is_symbolic(ref):
+                    continue
+                out.append(Variant(chrom, pos, vid, ref, alt))
+                row = np.zeros((len(names), 2), dtype=np.uint8)
+                for s, (al, phased) in enumerate(calls):
+                    if phased:
+                        for h, a in enumerate(al):
+                            row[s, h] = a == k
+                    elif al[0] == al[1] == k:
+                        row[s] = 1
+                rows.append(row)
+    if names is None:
+        raise ValueError("VCF without a #CHROM header line")
+    carried = np.stack(rows) if rows else np.zeros((0, len(names), 2), dtype=np.uint8)
+    return out, names, carried, unphased
+
+
+def read_bed(path):
+    """BED (plain or gzipped text) -> [(chrom, start, end), ...], 0-based half-open as written."""
+    from .loader import _open
+    out = []
+    with _open(path, "rt") as fh:
+        for line in fh:
+            f = line.split()
+            if not f or f[0].startswith("#") or f[0] in ("track", "browser"):
+                continue
+            if len(f) < 3:
+                raise ValueError("BED line with fewer than 3 columns: %r" % line[:80])
+            out.append((f[0], int(f[1]), int(f[2])))
+    return out
+
+
+def _haplotypes_main(args, ap):
+    """--haplotypes: every sample's two haplotypes in the window centred on each BED region -> TSV
+    (Chrom, Start, End, Sample, Hap, Class, RefMean, HapFwd, HapRev, HapMean, Delta), one row per
+    region, sample, haplotype (1, 2) and class; regions in file order."""
+    if not args.regions:
+        ap.error("--haplotypes needs --regions BED")
+    from .loader import read_fasta_records
+    from .predict import _load_model
+    variants, names, carried, unphased = read_vcf_genotypes(
+        args.vcf_file, args.samples.split(",") if args.samples else None)
+    regions = read_bed(args.regions)
+    records = read_fasta_records(args.fasta_file)
+    model = _load_model(args.model_file)
+    L = model._options["sequence_length"]
+    if unphased.sum():
+        sys.stderr.write("%d unphased heterozygous call(s) left on the reference allele\n" % unphased.sum())
+    lines = {}
+    for rid, codes in records:
+        idx = [i for i, v in enumerate(variants) if v.chrom == rid]
+        reg = [j for j, r in enumerate(regions) if r[0] == rid]
+        if not reg:
+            continue
+        refs = [allele_codes(variants[i].ref) for i in idx]
+        haps = [np.flatnonzero(carried[idx, s, h]) for s in range(len(names)) for h in (0, 1)]
+        starts = [(regions[j][1] + regions[j][2]) // 2 - L // 2 for j in reg]
+        res = score_haplotypes(model, codes, [variants[i].pos for i in idx], [len(r) for r in refs],
+                               [allele_codes(variants[i].alt) for i in idx], haps, starts, strands=args.strands,
+                               apply_sigmoid=args.apply_sigmoid, check_ref=None if args.no_check_ref else refs)
+        for r, j in enumerate(reg):
+            rows = []
+            for s, name in enumerate(names):
+                for h in (0, 1):
+                    hap, ref = res["hap"][2 * s + h, r], res["ref"][r]
+                    for t in range(ref.shape[0]):
+                        row = [rid, str(regions[j][1]), str(regions[j][2]), name, str(h + 1), str(t)]
+                        row += [repr(float(x)) for x in (ref[t, 2], *hap[t, :3], res["delta"][2 * s + h, r, t])]
+                        rows.append("\t".join(row) + "\n")
+            lines[j] = rows
+    if len(lines) < len(regions):
+        sys.stderr.write("%d region(s) on sequences the FASTA does not hold\n" % (len(regions) - len(lines)))
+    fh = open(args.output_file, "w") if args.output_file else sys.stdout
+    try:
+        fh.write("Chrom\tStart\tEnd\tSample\tHap\tClass\tRefMean\tHapFwd\tHapRev\tHapMean\tDelta\n")
+        for j in sorted(lines):
+            fh.writelines(lines[j])
+    finally:
+        if fh is not sys.stdout:
+            fh.close()
 
 
 def allele_codes(allele):
@@ -279,7 +595,13 @@ def main(argv=None):
                     help="add a column Units: unit:effect of the K largest |effect|")
     ap.add_argument("--apply-sigmoid", action="store_true")
     ap.add_argument("--no-check-ref", action="store_true")
+    ap.add_argument("--haplotypes", action="store_true",
+                    help="score the samples' phased haplotypes (GT) in the windows centred on --regions")
+    ap.add_argument("--regions", metavar="BED")
+    ap.add_argument("--samples", metavar="A,B", help="with --haplotypes: these samples only")
     args = ap.parse_args(argv)
+    if args.haplotypes:
+        return _haplotypes_main(args, ap)
     if args.shifts < 1:
         ap.error("--shifts must be at least 1")
     from .loader import read_fasta_records

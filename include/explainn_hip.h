@@ -101,8 +101,9 @@ int explainn_create(explainn_ctx** out, int cnn_units, int kernel_size, int sequ
  * explainn_loss_grad, explainn_train_step, explainn_train_step_fc / _conv (the flat gradient buffer
  * is element-wise, so a data-parallel all-reduce is unchanged), explainn_unit_outputs (B,G*U),
  * explainn_unit_activations, the filter export (per unit), explainn_stage_codes / _stage_onehot /
- * _stage_windows / _stage_edited_windows, explainn_scan in every mode (logits (n_windows,G,T)),
- * explainn_score_edits (logits (n_rows,G,T), outs (n_rows,G*U)), explainn_dense_input, explainn_input_flags, stage timing, explainn_debug_keep_bits (G*U,B,4).
+ * _stage_windows / _stage_edited_windows / _stage_haplotype_windows, explainn_scan in every mode
+ * (logits (n_windows,G,T)), explainn_score_edits and explainn_score_haplotypes (logits (n_rows,G,T),
+ * outs (n_rows,G*U)), explainn_dense_input, explainn_input_flags, stage timing, explainn_debug_keep_bits (G*U,B,4).
  * EXPLAINN_E_UNSUPPORTED on a bank (they fold units through `final` in kernels of their own; run them
  * on one member's model; the context stays usable): explainn_forward_eval_keep, explainn_input_grad,
  * explainn_backward_input, explainn_ism, explainn_sync_phase.
@@ -310,7 +311,7 @@ int explainn_scan(explainn_ctx* ctx, const uint8_t* seq, int64_t seq_len, int64_
  * row_edit >= n_edits, or whose edit has a negative length or an alt run that leaves the pool
  * (alt_off < 0 or alt_off + alt_len > alt_bytes), reads as N throughout and raises bit 0.
  * reverse_complement != 0 reverse-complements the row after the edit.  One edit per row: a haplotype
- * of several variants is not expressible.
+ * of several variants goes through explainn_haplotypes below.
  *
  * explainn_stage_edited_windows stages rows row0 .. row0 + B - 1 of the tables.  The context then holds
  * exactly what explainn_stage_codes would hold for the materialised (B,L) matrix: every entry point
@@ -342,6 +343,72 @@ int explainn_score_edits(explainn_ctx* ctx, const uint8_t* seq, int64_t seq_len,
                          int64_t n_rows, int reverse_complement, const explainn_params* p,
                          float* logits /* (n_rows,[G,]T) or NULL */, float* outs /* (n_rows,units) or NULL */,
                          void* stream);
+
+/* Scoring haplotypes: as above, but a row carries a RUN of edits -- two variants in one window, a
+ * phased genotype over a region, two insertions at a varying distance.  All pointers of
+ * explainn_haplotypes are device pointers.
+ *
+ * The edit table (pos, ref_len, alt_len, alt_off, the pool alt of alt_bytes < 2^31 base codes; n_edits
+ * records) is that of explainn_edits: one record per variant.  A haplotype is a list of int32 indices
+ * into it, so a carried variant costs 4 bytes per haplotype: row b has row_start[b] (int64, signed),
+ * row_first[b] (int64, an index into edit_index) and row_count[b] (int32, >= 0), and its edits are
+ *     e_i = edit_index[row_first[b] + i],   i < row_count[b],   in list order.
+ * The run must be ordered and non-overlapping: pos[e_i] + ref_len[e_i] <= pos[e_{i+1}].  Abutting edits
+ * are legal; so are two insertions (ref_len 0) at one position, which apply in list order.  With
+ * pos_i, ref_i, alt_i the fields of e_i and c = row_count[b] the haplotype is
+ *     H = seq[:pos_0] + alt_0 + seq[pos_0 + ref_0 : pos_1] + alt_1 + ... + seq[pos_{c-1} + ref_{c-1}:]
+ * and row b is H[row_start : row_start + L]: row_start counts in the coordinates of that H, which equal
+ * reference coordinates up to the run's first edit.  In closed form, with
+ *     shift_i = sum_{m<i} (alt_len_m - ref_len_m),   hstart_i = pos_i + shift_i   (nondecreasing in i),
+ * for output position q, g = row_start + q, the base is
+ *     seq[g]                           when g < hstart_0,
+ *     alt[alt_off_i + g - hstart_i]    when hstart_i <= g < hstart_i + alt_len_i,
+ *     seq[g - shift_{i+1}]             otherwise, i the last edit with hstart_i <= g
+ * in wrapping 64-bit arithmetic.  reverse_complement != 0 reverse-complements the row after the edits.
+ * A source index outside [0, seq_len) reads as N and raises no flag; a byte above 4, in seq inside the
+ * range or in alt, reads as N and raises bit 0 of explainn_input_flags.  row_count == 0 is a plain
+ * reference window, and a run of one edit stages bit for bit what explainn_stage_edited_windows stages
+ * for that edit.
+ *
+ * The tables are never read by the host, so the kernel stays memory-safe on a bad one: no index becomes
+ * an address before it is range-checked, and a row with row_count < 0, row_first < 0 or row_first +
+ * row_count > n_index, an edit_index outside [0, n_edits), an edit with a negative length or an alt run
+ * that leaves the pool (alt_off < 0 or alt_off + alt_len > alt_bytes), or a run that violates the
+ * ordering rule reads as N throughout and raises bit 0; the other rows of the batch are unaffected.
+ *
+ * row_count has no cap, but a row's whole run is walked (and validated) by every 64-position tile of
+ * the row, 64 edits at a time, so the cost of a row grows with its run length: start a run near the
+ * window -- at the first variant at or right of row_start -- not at the chromosome's start.
+ *
+ * explainn_stage_haplotype_windows stages rows row0 .. row0 + B - 1.  The context then holds exactly what
+ * explainn_stage_codes would hold for the materialised (B,L) matrix: every entry point that takes
+ * x == NULL runs on it, train mode included; a pending train forward is dropped.
+ *
+ * explainn_score_haplotypes is explainn_score_edits on these rows: logits fp32 (n_rows,T) --
+ * (n_rows,G,T) on a bank context -- and / or outs fp32 (n_rows,units); either may be NULL, not both
+ * (EXPLAINN_E_ARG; the context stays usable).  Sub-batches of max_batch, no host synchronisation, no
+ * allocation, no staged batch left behind.  Dense input mode: EXPLAINN_E_UNSUPPORTED. */
+typedef struct explainn_haplotypes {
+    const int64_t* row_start;
+    const int64_t* row_first;
+    const int32_t* row_count;
+    const int32_t* edit_index;
+    const int64_t* pos;
+    const int32_t* ref_len;
+    const int32_t* alt_len;
+    const int32_t* alt_off;
+    const uint8_t* alt;
+    int64_t n_index;
+    int64_t n_edits;
+    int64_t alt_bytes;
+} explainn_haplotypes;
+int explainn_stage_haplotype_windows(explainn_ctx* ctx, const uint8_t* seq, int64_t seq_len,
+                                     const explainn_haplotypes* haps, int64_t row0, int B,
+                                     int reverse_complement, void* stream);
+int explainn_score_haplotypes(explainn_ctx* ctx, const uint8_t* seq, int64_t seq_len,
+                              const explainn_haplotypes* haps, int64_t n_rows, int reverse_complement,
+                              const explainn_params* p, float* logits /* (n_rows,[G,]T) or NULL */,
+                              float* outs /* (n_rows,units) or NULL */, void* stream);
 
 /* Calling motif sites: every (unit, start position) of a device-resident sequence of base codes
  * (0..3 = ACGT, 4 = N, as explainn_scan takes it) whose eval-mode activation, rounded to float16 as

@@ -58,7 +58,9 @@ METRICS = [
 SCAN = [r"^stage_windows_kernel", r"^scan_unfold_kernel"]
 # variant effects (variants.hip): the staging of edited windows
 VARIANTS = [r"^stage_edits_kernel"]
-GATED = C2_STEP + INPUT_GRAD + ISM + METRICS + SCAN + VARIANTS
+# haplotypes (haplotypes.hip): the staging of windows that carry a run of edits
+HAPLOTYPES = [r"^stage_haplotypes_kernel"]
+GATED = C2_STEP + INPUT_GRAD + ISM + METRICS + SCAN + VARIANTS + HAPLOTYPES
 
 
 # Register cliffs measured in the pipeline: 1024-thread blocks of which TWO must
