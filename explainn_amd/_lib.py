@@ -16,6 +16,7 @@ PWM_SUM, PWM_MAX = 0, 1
 METRICS_GLOBAL, METRICS_PER_TASK = 0, 1
 METRICS_BINARY, METRICS_LINEAR = 0, 1
 METRICS_NONFINITE, METRICS_NOT_BINARY = 1, 2
+IG_BASELINE_ZERO, IG_BASELINE_UNIFORM, IG_BASELINE_CODES = 0, 1, 2
 SCAN_AUTO, SCAN_WINDOWS, SCAN_SHARED = 0, 1, 2
 SITES_TILE = 1024         # EXPLAINN_SITES_TILE: start positions per workgroup of explainn_call_sites
 
@@ -111,6 +112,8 @@ SIGNATURES = {
     "explainn_backward_input": (_i, [_ctx, _fp, _i, _pp, _gp, _i, _fp, _fp]),
     "explainn_ism_workspace_bytes": (_i64, [_ctx, _i]),
     "explainn_ism": (_i, [_ctx, _fp, _i, _pp, _fp, _fp, _fp, _i64, _fp]),
+    "explainn_integrated_gradients_workspace_bytes": (_i64, [_ctx, _i]),
+    "explainn_integrated_gradients": (_i, [_ctx, _fp, _i, _pp, _i, _fp, _fp, _i, _fp, _fp, _fp, _fp, _i64, _fp]),
     "explainn_loss_grad": (_i, [_ctx, _i, _fp, _fp, _i, _fp, _fp, _fp]),
     "explainn_train_step": (_i, [_ctx, _fp, _fp, _i, _pp, _gp, _i, C.c_float, C.c_uint64, _i, _fp, _fp,
                                  _fp]),

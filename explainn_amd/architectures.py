@@ -633,7 +633,8 @@ class ExplaiNN(_Model):
             return None, False
         if self.dense_input:
             if policy == ONEHOT_ONLY:
-                raise ValueError("in_silico_mutagenesis needs one-hot input (dense_input is True)")
+                raise ValueError("in_silico_mutagenesis and integrated_gradients need one-hot input "
+                                 "(dense_input is True)")
             self._rt.calls += 1
             _lib.check(lib.explainn_dense_input(h, 1))
             self._rt.x_keep = x
@@ -649,7 +650,8 @@ class ExplaiNN(_Model):
             if policy == ONEHOT_ONLY:
                 raise ValueError(
                     "input is not one-hot: in-silico mutagenesis substitutes bases of one-hot (A,C,G,T) "
-                    "or all-zero (N) columns, as sequence.one_hot_encode produces")
+                    "or all-zero (N) columns, as sequence.one_hot_encode produces (integrated_gradients "
+                    "walks its path between such columns too)")
             self._rt.soft_seen = True
             if self.dense_input is False:
                 raise ValueError(
@@ -915,6 +917,76 @@ class ExplaiNN(_Model):
                                         ws.data_ptr(), nbytes, stream))
             self._settle(read)
         return logits, delta
+
+    def integrated_gradients_workspace_bytes(self, B):
+        """Bytes of workspace integrated_gradients() runs a batch of B sequences with
+        (explainn_integrated_gradients_workspace_bytes); the value for B = 64 is the smallest
+        workspace the call accepts."""
+        dev = self._device()
+        with torch.cuda.device(dev):
+            ctx = self._context(B, dev)
+            return int(ctx.lib.explainn_integrated_gradients_workspace_bytes(ctx.handle, B))
+
+    def integrated_gradients(self, x, dlogits, baseline="zero", steps=32, workspace=None):
+        """Integrated Gradients in eval mode (explainn_integrated_gradients): returns (ig (B,4,L),
+        logits_x (B,T), logits_base (B,T)), device fp32 tensors, with
+        ig = (x - x') * mean over the nodes a_s = (s + 1/2)/steps of d sum(dlogits * model(x_a)) / dx
+        along x_a = x' + a (x - x'), in one device pass: the path is walked in the space of the conv
+        sums, which are linear in x.  logits_x / logits_base are the logits at the two ends from the
+        same pass, so sum(ig) - (dlogits * (logits_x - logits_base)).sum(1) is the convergence delta.
+        x: fp32 one-hot (B,4,L), validated before anything is computed, or base codes; for
+        BaseCodes(..., reverse_complement=True) rows and positions are those of the strand the model
+        ran on, and the baseline codes are reverse-complemented with the batch.
+        baseline: "zero" (all-zero columns), "uniform" (0.25 everywhere) or a uint8 (B,L) tensor of base
+        codes on the model's device (0..3, 4 = N); where it equals x the result is exactly 0.
+        workspace: an optional uint8 device tensor (at least integrated_gradients_workspace_bytes(64)
+        bytes: the batch runs in the sub-batches it holds); by default from torch's caching allocator."""
+        if self.training:
+            raise RuntimeError("integrated_gradients is an eval-mode path; call model.eval()")
+        steps = int(steps)
+        if steps < 1:
+            raise ValueError("integrated_gradients needs steps >= 1 (got %d)" % steps)
+        dev = self._device()
+        x = self._prep_input(x, dev)
+        B = x.shape[0]
+        T, L = self._options["n_features"], self._options["sequence_length"]
+        codes = None
+        if isinstance(baseline, str):
+            kinds = {"zero": _lib.IG_BASELINE_ZERO, "uniform": _lib.IG_BASELINE_UNIFORM}
+            if baseline not in kinds:
+                raise ValueError("baseline must be 'zero', 'uniform' or a uint8 (B, %d) tensor of base codes" % L)
+            kind = kinds[baseline]
+        else:
+            kind = _lib.IG_BASELINE_CODES
+            if not torch.is_tensor(baseline) or baseline.dtype != torch.uint8 or tuple(baseline.shape) != (B, L):
+                raise ValueError("baseline codes must be a uint8 tensor of shape (%d, %d), got %s" % (
+                    B, L, tuple(baseline.shape) if hasattr(baseline, "shape") else type(baseline).__name__))
+            if baseline.device != dev:
+                raise RuntimeError("baseline is on %s but the model is on %s" % (baseline.device, dev))
+            codes = baseline.detach().contiguous()
+        dl = dlogits.to(device=dev, dtype=torch.float32).contiguous()
+        if tuple(dl.shape) != (B, T):
+            raise ValueError("dlogits must have shape (%d, %d), got %s" % (B, T, tuple(dl.shape)))
+        ig = torch.empty(B, 4, L, device=dev, dtype=torch.float32)
+        lx = torch.empty(B, T, device=dev, dtype=torch.float32)
+        lb = torch.empty(B, T, device=dev, dtype=torch.float32)
+        if B == 0:
+            return ig, lx, lb
+        with torch.cuda.device(dev):
+            ctx, ps, _, stream, xp, read = self._front(x, dev, ONEHOT_ONLY)
+            lib, h = ctx.lib, ctx.handle
+            if workspace is None:
+                nbytes = int(lib.explainn_integrated_gradients_workspace_bytes(h, B))
+                workspace = torch.empty(max(nbytes, 1), device=dev, dtype=torch.uint8)
+            elif not torch.is_tensor(workspace) or workspace.dtype != torch.uint8 or workspace.device != dev \
+                    or not workspace.is_contiguous():
+                raise RuntimeError("workspace must be a contiguous uint8 tensor on %s" % dev)
+            _lib.check(lib.explainn_integrated_gradients(
+                h, xp, B, C.byref(ps), kind, codes.data_ptr() if codes is not None else None, dl.data_ptr(),
+                steps, ig.data_ptr(), lx.data_ptr(), lb.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                stream))
+            self._settle(read)
+        return ig, lx, lb
 
     def _empty_batch_error(self):
         # what torch's BatchNorm1d raises for an empty batch in train mode
@@ -1284,6 +1356,9 @@ class ExplaiNNBank(ExplaiNN):
 
     def in_silico_mutagenesis(self, x):
         raise self._member_only("in_silico_mutagenesis")
+
+    def integrated_gradients(self, x, dlogits, baseline="zero", steps=32, workspace=None):
+        raise self._member_only("integrated_gradients")
 
     # -- plumbing --------------------------------------------------------------------------
     def _units(self):

@@ -368,6 +368,40 @@ extern "C" int explainn_ism(explainn_ctx* c, const float* x, int B, const explai
     return launch_ism(c, p, B, delta, static_cast<float*>(workspace), s);
 }
 
+extern "C" int64_t explainn_integrated_gradients_workspace_bytes(const explainn_ctx* c, int B) {
+    if (check_batch(c, B) != EXPLAINN_OK) return 0;
+    return pathgrad_workspace_bytes(c, B);
+}
+
+extern "C" int explainn_integrated_gradients(explainn_ctx* c, const float* x, int B, const explainn_params* p,
+                                             int baseline_kind, const uint8_t* baseline_codes,
+                                             const float* dlogits, int steps, float* ig, float* logits_x,
+                                             float* logits_base, void* workspace, int64_t workspace_bytes,
+                                             void* stream) {
+    NOT_ON_BANK(c, "explainn_integrated_gradients");
+    TRY(check_batch(c, B));
+    if (!dlogits || !ig || !logits_x || !logits_base || !workspace) {
+        explainn_set_error("dlogits, ig, logits_x, logits_base and workspace are required");
+        return EXPLAINN_E_ARG;
+    }
+    if (steps < 1) { explainn_set_error("integrated gradients need steps >= 1 (got %d)", steps); return EXPLAINN_E_ARG; }
+    if (baseline_kind != EXPLAINN_IG_BASELINE_ZERO && baseline_kind != EXPLAINN_IG_BASELINE_UNIFORM &&
+        baseline_kind != EXPLAINN_IG_BASELINE_CODES) {
+        explainn_set_error("unknown baseline kind %d", baseline_kind);
+        return EXPLAINN_E_ARG;
+    }
+    if (baseline_kind == EXPLAINN_IG_BASELINE_CODES && !baseline_codes) {
+        explainn_set_error("baseline kind `codes` needs baseline_codes");
+        return EXPLAINN_E_ARG;
+    }
+    if (c->dense) { explainn_set_error("integrated gradients walk a path between base codes: one-hot input only"); return EXPLAINN_E_UNSUPPORTED; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int rc = x ? 0 : c->staged_rc;
+    TRY(eval_front(c, x, B, p, s));
+    return launch_pathgrad(c, p, B, baseline_kind, baseline_codes, rc, dlogits, steps, ig, logits_x, logits_base,
+                           workspace, workspace_bytes, s);
+}
+
 extern "C" int explainn_unit_outputs(explainn_ctx* c, const float* x, int B,
                                      const explainn_params* p, float* outs, void* stream) {
     TRY(check_batch(c, B));
@@ -389,7 +423,8 @@ extern "C" int explainn_stage_codes(explainn_ctx* c, const uint8_t* codes, int B
     TRY(check_batch(c, B));
     if (!codes) { explainn_set_error("codes is null"); return EXPLAINN_E_ARG; }
     drop_pending(c);                   // the packed codes of a pending backward are overwritten
-    return launch_pack_codes(c, codes, B, reverse_complement ? 1 : 0, static_cast<hipStream_t>(stream));
+    c->staged_rc = reverse_complement ? 1 : 0;
+    return launch_pack_codes(c, codes, B, c->staged_rc, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int explainn_stage_windows(explainn_ctx* c, const uint8_t* seq, int64_t seq_len, int64_t start0,
@@ -397,6 +432,7 @@ extern "C" int explainn_stage_windows(explainn_ctx* c, const uint8_t* seq, int64
     TRY(check_batch(c, B));
     if (!seq || seq_len < 0) { explainn_set_error("seq is null or seq_len negative"); return EXPLAINN_E_ARG; }
     drop_pending(c);                   // the packed codes of a pending backward are overwritten
+    c->staged_rc = reverse_complement ? 1 : 0;
     return launch_stage_windows(c, seq, seq_len, start0, step, B, reverse_complement ? 1 : 0,
                                 static_cast<hipStream_t>(stream));
 }
@@ -540,6 +576,7 @@ extern "C" int explainn_stage_edited_windows(explainn_ctx* c, const uint8_t* seq
     TRY(check_batch(c, B));
     TRY(check_edits(seq, seq_len, edits, row0));
     drop_pending(c);                   // the packed codes of a pending backward are overwritten
+    c->staged_rc = reverse_complement ? 1 : 0;
     return launch_stage_edits(c, seq, seq_len, edits, row0, B, reverse_complement ? 1 : 0,
                               static_cast<hipStream_t>(stream));
 }
@@ -598,6 +635,7 @@ extern "C" int explainn_stage_haplotype_windows(explainn_ctx* c, const uint8_t* 
     TRY(check_batch(c, B));
     TRY(check_haplotypes(seq, seq_len, haps, row0));
     drop_pending(c);                   // the packed codes of a pending backward are overwritten
+    c->staged_rc = reverse_complement ? 1 : 0;
     return launch_stage_haplotypes(c, seq, seq_len, haps, row0, B, reverse_complement ? 1 : 0,
                                    static_cast<hipStream_t>(stream));
 }
@@ -1003,6 +1041,7 @@ extern "C" int explainn_stage_onehot(explainn_ctx* c, const float* x, int B, voi
     drop_pending(c);                   // the packed codes of a pending backward are overwritten
     TRY(launch_pack(c, x, B, true, s));  // with the bit masks: the batch may feed a train forward
     c->staged_B = B;
+    c->staged_rc = 0;
     return EXPLAINN_OK;
 }
 

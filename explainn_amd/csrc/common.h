@@ -122,6 +122,7 @@ struct explainn_ctx {
     int keep_B;           // batch of the last explainn_forward_eval_keep (0 = none)
     int sync_next, sync_B;  // sync-BN: the phase due next (0 = none) and the step's B_local
     const float* keep_x;  // its x when it ran the dense kernels (read again by explainn_input_grad)
+    int staged_rc;        // the staged codes are the reverse complement of the rows that were given
 };
 
 enum explainn_stage {
@@ -219,6 +220,14 @@ int launch_input_grad(explainn_ctx* c, const explainn_params* p, int B, bool tra
 // per-unit substitution kernels and the per-task sum, sub-batch by sub-batch
 int64_t ism_workspace_bytes(const explainn_ctx* c, int B);
 int launch_ism(explainn_ctx* c, const explainn_params* p, int B, float* delta, float* ws, hipStream_t s);
+
+// Integrated Gradients (pathgrad.hip): the workspace the call is meant to run with; the path walk in
+// conv-sum space, the endpoint logits and the transposed convolution, sub-batch by sub-batch (the
+// sub-batch is what the caller's workspace holds).  The batch's codes are in c->codesT.
+int64_t pathgrad_workspace_bytes(const explainn_ctx* c, int B);
+int launch_pathgrad(explainn_ctx* c, const explainn_params* p, int B, int kind, const uint8_t* base_codes,
+                    int rc, const float* dlogits, int steps, float* ig, float* logits_x, float* logits_base,
+                    void* ws, int64_t ws_bytes, hipStream_t s);
 
 // tiled scan of a long sequence (scan.hip): windows of a device-resident sequence staged as a batch;
 // the pooled track of a run of tiles (blocks of TB tiles in the filter bank's output layout, in the

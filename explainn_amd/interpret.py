@@ -233,8 +233,8 @@ def input_gradients(model, Xs, target=None, batch_size=4096, rev_complement=Fals
     """Eval-mode input gradients (N,4,L), float32 numpy: d logit[target] / d x -- or d sum(logits)
     / d x with target=None -- for every sequence, what `x.requires_grad_(); model(x)[:, t].sum()
     .backward()` leaves in x.grad on the reference module, in batches on the device with no
-    autograd bookkeeping.  The saliency map; times_input=True gives gradient x input, and averaging
-    it over interpolated inputs is Integrated Gradients (soft input takes the dense kernels).
+    autograd bookkeeping.  The saliency map; times_input=True gives gradient x input.  Integrated
+    Gradients are integrated_gradients() below: one device pass along the path, not a loop over this.
 
     Xs: (N,4,L) one-hot or real-valued (numpy or tensor), or (N,L) uint8 base codes (0..3 = A,C,G,T,
     4 = N).  rev_complement=True runs the model on each sequence's reverse complement and maps the
@@ -280,6 +280,88 @@ def input_gradients(model, Xs, target=None, batch_size=4096, rev_complement=Fals
     finally:
         model.train(was_training)
     return out
+
+
+def integrated_gradients(model, Xs, baselines="zero", target=None, steps=32, batch_size=4096,
+                         rev_complement=False, return_delta=False):
+    """Integrated Gradients in eval mode, float32 numpy (N,4,L): (x - x') times the mean over `steps`
+    midpoint nodes of d logit[target] / dx -- d sum(logits) / dx with target=None -- along the
+    straight path from the baseline x' to x, one device pass per batch
+    (ExplaiNN.integrated_gradients).
+
+    Xs: (N,4,L) one-hot (numpy or tensor) or (N,L) uint8 base codes (0..3 = A,C,G,T, 4 = N).
+    baselines: "zero" (all-zero columns), "uniform" (0.25 in every row: all four rows of a position
+    are then generally non-zero), or uint8 base codes (N,L) -- or (N,R,L): R baselines per sequence,
+    e.g. sequence.dinucleotide_shuffle(codes, n=R); the result is the mean of the R attributions, each
+    multiplied by its own (x - x'_r), accumulated on the device.
+    rev_complement=True runs the model on each sequence's (and baseline's) reverse complement and
+    maps base and position back onto the given strand.
+    return_delta=True returns (ig, delta), delta (N,) the convergence delta sum(ig) - (F(x) - F(x'))
+    (the mean over the R baselines), F the target logit or the sum of the logits."""
+    from .architectures import BaseCodes
+    dev = model.final.weight.device
+    T, L = model._options["n_features"], model._options["sequence_length"]
+    if target is not None and not 0 <= int(target) < T:
+        raise ValueError("target must be a task index in [0, %d)" % T)
+    codes = (torch.is_tensor(Xs) and Xs.dtype == torch.uint8) or \
+        (isinstance(Xs, np.ndarray) and Xs.dtype == np.uint8)
+    Xs = torch.as_tensor(Xs) if codes else _as_tensor(Xs)
+    N = len(Xs)
+    base = None
+    if not isinstance(baselines, str):
+        base = torch.as_tensor(baselines)
+        if base.dtype != torch.uint8 or base.dim() not in (2, 3) or base.shape[0] != N or base.shape[-1] != L:
+            raise ValueError("baselines must be 'zero', 'uniform' or uint8 base codes of shape (%d, %d) or "
+                             "(%d, R, %d), got %s %s" % (N, L, N, L, base.dtype, tuple(base.shape)))
+        if base.dim() == 2:
+            base = base[:, None]
+        if base.shape[1] < 1:
+            raise ValueError("baselines holds no baseline per sequence")
+    elif baselines not in ("zero", "uniform"):
+        raise ValueError("baselines must be 'zero', 'uniform' or uint8 base codes")
+    R = 1 if base is None else base.shape[1]
+    out = np.zeros((N, 4, L), dtype=np.float32)
+    delta = np.zeros(N, dtype=np.float32)
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad(), model.eval_cache():
+            for i, xb in _batches(Xs, batch_size):
+                xb = xb.to(dev, non_blocking=True)
+                B = xb.shape[0]
+                dl = torch.zeros(B, T, device=dev, dtype=torch.float32)
+                if target is None:
+                    dl.fill_(1.0)
+                else:
+                    dl[:, int(target)] = 1.0
+                if codes:
+                    xin = BaseCodes(xb, rev_complement)
+                else:
+                    xb = xb.to(torch.float32)
+                    xin = xb.flip(1, 2) if rev_complement else xb
+                acc = dcc = None
+                for r in range(R):
+                    bl = baselines
+                    if base is not None:
+                        bl = base[i:i + B, r].to(dev, non_blocking=True).contiguous()
+                        if rev_complement and not codes:     # the one-hot batch was flipped here, not staged flipped
+                            bl = torch.where(bl < 4, 3 - bl, bl).flip(1)
+                    ig, lx, lb = model.integrated_gradients(xin, dl, bl, steps)
+                    d = ig.sum(dim=(1, 2)) - (dl * (lx - lb)).sum(dim=1)
+                    acc = ig if acc is None else acc.add_(ig)
+                    dcc = d if dcc is None else dcc.add_(d)
+                if R > 1:
+                    acc.div_(R)
+                    dcc.div_(R)
+                if rev_complement:
+                    acc = acc.flip(1, 2)
+                out[i:i + B] = acc.cpu().numpy()
+                delta[i:i + B] = dcc.cpu().numpy()
+        if model.validate_input:
+            model.check_input()
+    finally:
+        model.train(was_training)
+    return (out, delta) if return_delta else out
 
 
 def in_silico_mutagenesis(model, Xs, target=None, batch_size=4096, rev_complement=False, absolute=False):

@@ -87,3 +87,71 @@ def rc(seq):
 
 def rc_many(arr):
     return np.array([rc(s) for s in arr])
+
+
+def _euler_shuffle(row, rng):
+    """One dinucleotide-preserving shuffle of a 1-D code row (Altschul & Erickson 1985): a random
+    arborescence towards the last symbol fixes every other vertex's last edge, the remaining edges
+    of each vertex are shuffled, and the Euler path from the first symbol is read off."""
+    n = len(row)
+    if n < 3:
+        return row.copy()
+    last = int(row[-1])
+    succ = [[] for _ in range(5)]
+    for a, b in zip(row[:-1], row[1:]):
+        succ[int(a)].append(int(b))
+    verts = [v for v in range(5) if succ[v] or v == last]
+    while True:
+        # a last edge per vertex (other than the final one), drawn from its edges; accept when every
+        # vertex reaches the final one through them
+        pick = {v: int(rng.integers(len(succ[v]))) for v in verts if v != last and succ[v]}
+        ok = True
+        for v in pick:
+            seen, cur = set(), v
+            while cur != last and cur not in seen:
+                seen.add(cur)
+                cur = succ[cur][pick[cur]] if cur in pick else last
+            if cur != last:
+                ok = False
+                break
+        if ok:
+            break
+    order = {}
+    for v in verts:
+        edges = list(succ[v])
+        if v in pick:
+            tail = edges.pop(pick[v])
+            edges = [edges[j] for j in rng.permutation(len(edges))] + [tail]
+        else:
+            edges = [edges[j] for j in rng.permutation(len(edges))]
+        order[v] = edges
+    out = np.empty(n, dtype=row.dtype)
+    cur = int(row[0])
+    used = {v: 0 for v in verts}
+    out[0] = cur
+    for i in range(1, n):
+        nxt = order[cur][used[cur]]
+        used[cur] += 1
+        out[i] = nxt
+        cur = nxt
+    return out
+
+
+def dinucleotide_shuffle(codes, n=1, seed=0):
+    """Seeded shuffles of base-code rows that keep every dinucleotide count and the first and last
+    base (Altschul-Erickson Euler path), the usual DNA baseline of Integrated Gradients.  N (code 4)
+    is a fifth symbol.  codes: uint8 (L,) or (N,L); returns (n,L) or (N,n,L) uint8.  Host-side numpy."""
+    codes = np.asarray(codes, dtype=np.uint8)
+    if codes.ndim not in (1, 2):
+        raise ValueError("codes must be (L,) or (N, L) base codes")
+    if codes.size and codes.max() > 4:
+        raise ValueError("base codes must be 0..4")
+    if n < 1:
+        raise ValueError("n must be at least 1")
+    rows = codes[None] if codes.ndim == 1 else codes
+    out = np.empty((rows.shape[0], n, rows.shape[1]), dtype=np.uint8)
+    for i, row in enumerate(rows):
+        rng = np.random.default_rng([int(seed), i])
+        for r in range(n):
+            out[i, r] = _euler_shuffle(row, rng)
+    return out[0] if codes.ndim == 1 else out

@@ -106,7 +106,7 @@ int explainn_create(explainn_ctx** out, int cnn_units, int kernel_size, int sequ
  * outs (n_rows,G*U)), explainn_dense_input, explainn_input_flags, stage timing, explainn_debug_keep_bits (G*U,B,4).
  * EXPLAINN_E_UNSUPPORTED on a bank (they fold units through `final` in kernels of their own; run them
  * on one member's model; the context stays usable): explainn_forward_eval_keep, explainn_input_grad,
- * explainn_backward_input, explainn_ism, explainn_sync_phase.
+ * explainn_backward_input, explainn_ism, explainn_integrated_gradients, explainn_sync_phase.
  * groups == 1 is explainn_create.  More than 2000 units in all (the largest count tested): EXPLAINN_E_UNSUPPORTED. */
 int explainn_create_bank(explainn_ctx** out, int groups, int cnn_units /* per member */, int kernel_size,
                          int sequence_length, int n_features, int max_batch, int device);
@@ -179,6 +179,35 @@ int explainn_backward_input(explainn_ctx* ctx, const float* dlogits, int B, cons
 int64_t explainn_ism_workspace_bytes(const explainn_ctx* ctx, int B);
 int explainn_ism(explainn_ctx* ctx, const float* x, int B, const explainn_params* p, float* logits,
                  float* delta, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Integrated Gradients in eval mode along the straight path x' + a (x - x'), midpoint rule with
+ * `steps` nodes a_s = (s + 1/2)/steps:
+ *   ig[b,a,p] = (x - x')[b,a,p] * (1/steps) sum_s d(sum_t dlogits[b,t] logit_t)/dx[b,a,p] at node s,
+ * fp32 (B,4,L) on the device, OVERWRITTEN.  The convolution is linear in x, so the path is walked in
+ * the space of the conv sums (rebuilt from base codes at both ends) and only BatchNorm1, exp, the
+ * pooling, the per-unit FC and the head are evaluated per node; one transposed convolution maps the
+ * path-averaged gradient back to x.  Baseline x': EXPLAINN_IG_BASELINE_ZERO (all-zero columns),
+ * _UNIFORM (0.25 in all four rows of every position) or _CODES (baseline_codes: device, uint8 (B,L),
+ * 0..3, anything else = N = an all-zero column).  Where x' == x the result is exactly 0, as it is at
+ * positions whose conv windows all fall in the tail MaxPool1d(7,7) drops.  logits_x / logits_base:
+ * (B,T) logits at the two ends of the path, from the code that evaluates the nodes (within the
+ * project's 1e-4 of explainn_forward_eval, not bit-identical), so that the caller can form the
+ * convergence delta sum(ig) - sum_t dlogits (logits_x - logits_base).
+ * x == NULL means the staged batch; for codes staged with reverse_complement != 0 the output is in
+ * the coordinates of the strand the model ran on and baseline_codes are reverse-complemented the
+ * same way.  One-hot and base codes only: in dense input mode EXPLAINN_E_UNSUPPORTED.  steps < 1 or
+ * _CODES without baseline_codes: EXPLAINN_E_ARG.  Like every eval entry point it ends a pending train
+ * forward (its backward then returns EXPLAINN_E_STATE).  No host sync.  Not on a bank.
+ * workspace: device memory, the caller's; explainn_integrated_gradients_workspace_bytes(ctx, B) is
+ * the size the call is meant to run with.  Any size that holds a 64-sequence sub-batch (the value
+ * for B = 64) is accepted: the batch runs in sub-batches of the largest multiple of 64 sequences that
+ * fits, and the result does not depend on the split. */
+enum { EXPLAINN_IG_BASELINE_ZERO = 0, EXPLAINN_IG_BASELINE_UNIFORM = 1, EXPLAINN_IG_BASELINE_CODES = 2 };
+int64_t explainn_integrated_gradients_workspace_bytes(const explainn_ctx* ctx, int B);
+int explainn_integrated_gradients(explainn_ctx* ctx, const float* x, int B, const explainn_params* p,
+                                  int baseline_kind, const uint8_t* baseline_codes, const float* dlogits,
+                                  int steps, float* ig, float* logits_x, float* logits_base,
+                                  void* workspace, int64_t workspace_bytes, void* stream);
 
 /* get_loss (architectures/__init__.py:446-456), mean reduction, fused with its gradient:
  * loss_out (1 float, device) and dlogits (B,T, device). */

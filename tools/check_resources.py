@@ -42,6 +42,8 @@ INPUT_GRAD = [
 ]
 # in-silico mutagenesis (ism.hip) at C2: k = 19 -> four pooled windows per substitution, one task
 ISM = [r"^ism_units_kernel<4>", r"^ism_sum_kernel<1>"]
+# Integrated Gradients (pathgrad.hip): the path walk, the endpoint logits, the transposed convolution
+PATHGRAD = [r"^pg_base_kernel", r"^pg_path_kernel", r"^pg_logits_kernel", r"^pg_gather_kernel"]
 # device-side evaluation metrics (metrics.hip): every kernel of the sort, the scans and the reductions
 METRICS = [
     r"^metrics_keys_binary_kernel", r"^metrics_keys_linear_kernel", r"^metrics_hist_kernel",
@@ -60,7 +62,7 @@ SCAN = [r"^stage_windows_kernel", r"^scan_unfold_kernel"]
 VARIANTS = [r"^stage_edits_kernel"]
 # haplotypes (haplotypes.hip): the staging of windows that carry a run of edits
 HAPLOTYPES = [r"^stage_haplotypes_kernel"]
-GATED = C2_STEP + INPUT_GRAD + ISM + METRICS + SCAN + VARIANTS + HAPLOTYPES
+GATED = C2_STEP + INPUT_GRAD + ISM + PATHGRAD + METRICS + SCAN + VARIANTS + HAPLOTYPES
 
 
 # Register cliffs measured in the pipeline: 1024-thread blocks of which TWO must
