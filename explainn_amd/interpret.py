@@ -283,7 +283,7 @@ def input_gradients(model, Xs, target=None, batch_size=4096, rev_complement=Fals
 
 
 def integrated_gradients(model, Xs, baselines="zero", target=None, steps=32, batch_size=4096,
-                         rev_complement=False, return_delta=False):
+                         rev_complement=False, return_delta=False, n_shuffles=10, seed=0):
     """Integrated Gradients in eval mode, float32 numpy (N,4,L): (x - x') times the mean over `steps`
     midpoint nodes of d logit[target] / dx -- d sum(logits) / dx with target=None -- along the
     straight path from the baseline x' to x, one device pass per batch
@@ -293,7 +293,13 @@ def integrated_gradients(model, Xs, baselines="zero", target=None, steps=32, bat
     baselines: "zero" (all-zero columns), "uniform" (0.25 in every row: all four rows of a position
     are then generally non-zero), or uint8 base codes (N,L) -- or (N,R,L): R baselines per sequence,
     e.g. sequence.dinucleotide_shuffle(codes, n=R); the result is the mean of the R attributions, each
-    multiplied by its own (x - x'_r), accumulated on the device.
+    multiplied by its own (x - x'_r), accumulated on the device.  "shuffle": n_shuffles
+    dinucleotide-preserving shuffles of every sequence, drawn on the device batch by batch
+    (sequence.dinucleotide_shuffle_device with `seed` and the batch offset as row0, so the result does
+    not depend on batch_size): the same arrays as passing dinucleotide_shuffle_device(codes, n_shuffles,
+    seed) as baselines, with nothing but the result crossing to the host.  Its random stream is not the
+    host dinucleotide_shuffle's.  One-hot Xs are converted to codes once (a column that is not one-hot
+    shuffles as N).  n_shuffles and seed are ignored for every other kind of baseline.
     rev_complement=True runs the model on each sequence's (and baseline's) reverse complement and
     maps base and position back onto the given strand.
     return_delta=True returns (ig, delta), delta (N,) the convergence delta sum(ig) - (F(x) - F(x'))
@@ -317,9 +323,16 @@ def integrated_gradients(model, Xs, baselines="zero", target=None, steps=32, bat
             base = base[:, None]
         if base.shape[1] < 1:
             raise ValueError("baselines holds no baseline per sequence")
-    elif baselines not in ("zero", "uniform"):
-        raise ValueError("baselines must be 'zero', 'uniform' or uint8 base codes")
-    R = 1 if base is None else base.shape[1]
+    elif baselines not in ("zero", "uniform", "shuffle"):
+        raise ValueError("baselines must be 'zero', 'uniform', 'shuffle' or uint8 base codes")
+    shuffle = isinstance(baselines, str) and baselines == "shuffle"
+    if shuffle:
+        if n_shuffles < 1:
+            raise ValueError("n_shuffles must be at least 1")
+        from .sequence import dinucleotide_shuffle_device
+        # the codes the shuffles are drawn from: Xs itself, or the one-hot converted once
+        src = Xs if codes else torch.from_numpy(_onehot_to_codes(Xs.cpu().numpy()))
+    R = n_shuffles if shuffle else 1 if base is None else base.shape[1]
     out = np.zeros((N, 4, L), dtype=np.float32)
     delta = np.zeros(N, dtype=np.float32)
     was_training = model.training
@@ -339,11 +352,15 @@ def integrated_gradients(model, Xs, baselines="zero", target=None, steps=32, bat
                 else:
                     xb = xb.to(torch.float32)
                     xin = xb.flip(1, 2) if rev_complement else xb
+                if shuffle:
+                    cb = xb if codes else src[i:i + B].to(dev, non_blocking=True)
+                    shuf = dinucleotide_shuffle_device(cb, n_shuffles, seed, row0=i)
                 acc = dcc = None
                 for r in range(R):
                     bl = baselines
-                    if base is not None:
-                        bl = base[i:i + B, r].to(dev, non_blocking=True).contiguous()
+                    if shuffle or base is not None:
+                        bl = shuf[:, r].contiguous() if shuffle else \
+                            base[i:i + B, r].to(dev, non_blocking=True).contiguous()
                         if rev_complement and not codes:     # the one-hot batch was flipped here, not staged flipped
                             bl = torch.where(bl < 4, 3 - bl, bl).flip(1)
                     ig, lx, lb = model.integrated_gradients(xin, dl, bl, steps)

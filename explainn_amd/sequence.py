@@ -155,3 +155,49 @@ def dinucleotide_shuffle(codes, n=1, seed=0):
         for r in range(n):
             out[i, r] = _euler_shuffle(row, rng)
     return out[0] if codes.ndim == 1 else out
+
+
+def dinucleotide_shuffle_device(codes, n=1, seed=0, row0=0, max_rounds=0, return_capped=False):
+    """dinucleotide_shuffle on the device (csrc/shuffle.hip): codes is a uint8 CUDA tensor (L,) or (N,L),
+    the result a uint8 tensor (n,L) or (N,n,L) on the same device, enqueued on the current stream with no
+    host synchronisation.  Same law as the host function -- every arrangement with the row's dinucleotide
+    counts, first and last base equally likely, N a fifth symbol -- but a different random stream: a
+    counter-based generator keyed by (seed, row0 + row index, shuffle index), so the shuffles of a seed
+    differ from the host's sequence by sequence, and a row's shuffles do not depend on how the rows are
+    split into calls (pass the offset of the first row as row0) or on n.  Bytes above 4 are read as N and
+    come back as 4.  max_rounds caps the cycle-popping rounds of the last-exit sampler (0: 64*L, not
+    reachable in practice); return_capped=True also returns a uint8 (n,) or (N,n) tensor, 1 where the cap
+    was hit and the row's own last exits were used instead."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib
+    if not torch.is_tensor(codes):
+        raise ValueError("codes must be a uint8 tensor of (L,) or (N, L) base codes")
+    if codes.dim() not in (1, 2):
+        raise ValueError("codes must be (L,) or (N, L) base codes")
+    if codes.dtype != torch.uint8:
+        raise ValueError("base codes must be uint8")
+    if n < 1:
+        raise ValueError("n must be at least 1")
+    if codes.device.type != "cuda":
+        raise RuntimeError("dinucleotide_shuffle_device runs only on a HIP device; call .cuda() "
+                           "(sequence.dinucleotide_shuffle is the host version)")
+    rows = (codes[None] if codes.dim() == 1 else codes).contiguous()
+    N, L = rows.shape
+    if N and L < 1:
+        raise ValueError("codes holds no positions")
+    out = torch.empty((N, n, L), dtype=torch.uint8, device=rows.device)
+    capped = torch.empty((N, n), dtype=torch.uint8, device=rows.device) if return_capped else None
+    if N:
+        lib = _lib.load()
+        with torch.cuda.device(rows.device):
+            _lib.check(lib.explainn_dinucleotide_shuffle(
+                rows.data_ptr(), N, L, int(n), int(seed) & (2 ** 64 - 1), int(row0), int(max_rounds),
+                out.data_ptr(), capped.data_ptr() if return_capped else None,
+                C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream)))
+    if codes.dim() == 1:
+        out = out[0]
+        capped = capped[0] if return_capped else None
+    return (out, capped) if return_capped else out

@@ -496,6 +496,21 @@ int explainn_dense_input(explainn_ctx* ctx, int enable);
 int explainn_pwm_scan(const float* x, int B, int L, const float* pwms, int G, int k, int scoring,
                       float* scores, void* stream);
 
+/* Dinucleotide-preserving shuffles (csrc/shuffle.hip).
+ * out[i][r][:] = r-th dinucleotide-preserving shuffle of codes[i][:]: the same first and last symbol and
+ * the same count of every ordered pair of adjacent symbols; every distinct such arrangement equally
+ * likely.  codes: device uint8 (N,L), 0..3 = A,C,G,T, anything else = N, a fifth symbol, written back
+ * as 4.  out: device uint8 (N,R,L), OVERWRITTEN.  The result is a pure function of
+ * (seed, row0 + i, r, the row's codes): independent of N, R, launch geometry and of how a caller
+ * splits its rows into calls.  capped: device uint8 (N,R) or NULL; 1 where the tree sampler reached
+ * max_rounds and the row's own last exits were used (still a valid shuffle, not a uniform one).
+ * max_rounds <= 0 means the default 64*L.  L < 3 copies the row.  N < 0, L < 1, R < 1: EXPLAINN_E_ARG.
+ * N = 0 launches nothing.  More than 2^37 (row, r) pairs in one call: EXPLAINN_E_UNSUPPORTED (split the
+ * rows).  No context, no workspace, no allocation, no host synchronisation. */
+int explainn_dinucleotide_shuffle(const uint8_t* codes, int64_t N, int L, int R, uint64_t seed,
+                                  int64_t row0, int max_rounds, uint8_t* out, uint8_t* capped,
+                                  void* stream);
+
 /* One Adam step over n_tensors parameter tensors in a single launch -- torch.optim.Adam(params, lr)
  * with its defaults, the optimiser the reference builds (architectures/__init__.py:463-464) and
  * steps at selene/__init__.py:291.  params/grads/exp_avg/exp_avg_sq: HOST arrays of n_tensors

@@ -62,7 +62,9 @@ SCAN = [r"^stage_windows_kernel", r"^scan_unfold_kernel"]
 VARIANTS = [r"^stage_edits_kernel"]
 # haplotypes (haplotypes.hip): the staging of windows that carry a run of edits
 HAPLOTYPES = [r"^stage_haplotypes_kernel"]
-GATED = C2_STEP + INPUT_GRAD + ISM + PATHGRAD + METRICS + SCAN + VARIANTS + HAPLOTYPES
+# dinucleotide-preserving shuffles (shuffle.hip): one lane per (row, shuffle), counters in LDS
+SHUFFLE = [r"^dinuc_shuffle_kernel"]
+GATED = C2_STEP + INPUT_GRAD + ISM + PATHGRAD + METRICS + SCAN + VARIANTS + HAPLOTYPES + SHUFFLE
 
 
 # Register cliffs measured in the pipeline: 1024-thread blocks of which TWO must
