@@ -62,7 +62,7 @@ struct explainn_ctx {
                           // A fragments of v_mfma_f32_32x32x16_bf16 (k = 4 tap + base), sign(gamma1) folded in
     float* ext;           // [U4 (padded to 64-unit groups)][n][Bs]  pooled extreme of the raw conv sum
     uint8_t* idx;         // [U4][n][Bs]      argmax offset 0..6 inside the pooling window
-    float* qs0;           // [U][NS]          shift for the q moments (q of sequence 0)
+    float* qs0;           // [U][NS]          shift for the q moments (geometric mean of q over the first 16 sequences)
     float* qS1p;          // [U][QCH][NS]
     float* qS2p;          // [U][QCH][NS][NS]
     double* qbar;         // [U][NS]

@@ -6,7 +6,8 @@
 //            moments (m, G):  mu = cb + w.m,  var = w'Gw - (w.m)^2  -> alpha, shift (prep1_stats);
 //            the filter taps laid out for the conv kernel come from prep1_tables.
 //   qtrans   q = exp(alpha*ext+shift) re-laid sequence-major for scalar-operand consumers.
-//   qmom     first/second moments of q over the batch (shifted by sequence 0 for conditioning).
+//   qmom     first/second moments of q over the batch (about the geometric mean of the first 16
+//            sequences' q, for conditioning).
 //   prep2    BN2 (architectures/__init__.py:90): mean/var of FC1's output from the q moments
 //            -> folded FC1 weights A2 and shift sh2.
 #include "common.h"
@@ -126,7 +127,9 @@ int launch_prep1(explainn_ctx* c, const explainn_params* p, int B, bool train, h
 
 // ---------------------------------------------------------------------------------------------
 // qmom: first/second moments of q over the batch on the exact-fp32 matrix core.
-//   S1[w'] = sum_b (q[b,w'] - s[w']),   S2[w][w'] = sum_b (q[b,w] - s[w]) (q[b,w'] - s[w']),  s = q of sequence 0
+//   S1[w'] = sum_b (q[b,w'] - s[w']),   S2[w][w'] = sum_b (q[b,w] - s[w]) (q[b,w'] - s[w']),
+//   s = exp(alpha mean(ext) + shift) over sequences 0 .. min(16, B) - 1 (qs0 holds it for prep2 and the
+//   sync-BN combine)
 // One wavefront per (unit, batch chunk, 32x32 tile of (w,w')).  The sequence index is the MFMA K
 // dimension (two sequences per v_mfma_f32_32x32x2_f32), but ext is stored batch-fastest, so each
 // super-tile of 64 sequences is fetched with coalesced row loads (lane = sequence), turned into
@@ -136,6 +139,7 @@ int launch_prep1(explainn_ctx* c, const explainn_params* p, int B, bool train, h
 typedef float f32x16q __attribute__((ext_vector_type(16)));
 typedef float f32x4q __attribute__((ext_vector_type(4)));
 #define QT_LD 65
+#define QSHIFT_SEQS 16    // sequences the shift of the q moments is taken from (one 64-byte line per row)
 #define QS_LD 66          // row stride of the small-n tile: operand reads (16 rows x 2 columns per 32 lanes) conflict-free
 
 // n <= 32: v_mfma_f32_16x16x4_f32, the upper triangle of the (at most 2 x 2) tile grid; all 16 k-steps
@@ -157,7 +161,19 @@ __global__ __launch_bounds__(64) void qmom_kernel(
     const int bbeg = ch * per, bend = min(B, bbeg + per);
     const float a1 = alpha[u], sh1 = shift[u];
     const float* __restrict__ eu = ext + (size_t)u * n * Bs;
-    // shift = q of sequence 0 (for conditioning; any constant per row would do)
+    // shift = q at the mean pooled extreme of the batch's first 16 sequences, s = exp(alpha mean(ext) + sh):
+    // the geometric mean of their q, the same in every chunk.  In exact arithmetic any constant per row
+    // would do.  In fp32 S2 carries a rounding error of eps * B * (distance of the batch from the
+    // shift)^2, and the variance prep2 takes from it is what is left after that square cancels.  q of
+    // sequence 0 was the shift at first: with a motif hit in that one sequence (q hundreds of standard
+    // deviations above the batch) BatchNorm2's variance came out 2.5e-3 off at B = 4096 and the step
+    // depended on the order of the batch.  In the exponent the same hit is 3 .. 5 standard deviations
+    // off: even among the 16 it moves their mean by a fraction of the batch's spread
+    // (tests/regime_model.py emulates both shifts).
+    // 64 lanes = (64 / ROWS) groups x ROWS rows: a lane sums 16 / groups consecutive sequences of its
+    // row from 16-byte loads, the groups are added across the wave, and each row's shift is read
+    // into an SGPR.  The 16 sequences are the 64 bytes per row that the single sequence cost too, and
+    // it is one exponential per lane where the broadcast row took ROWS.
     // (n lies in (NQLO, NQ]: rows up to NQLO always exist, rows from NQ on never do, only the rows
     // between need a run-time test -- as a test on every row the compiler made two branches per row;
     // and the row stride sits in a VGPR it cannot see through, or it hoists 32 row pointers out of
@@ -167,10 +183,16 @@ __global__ __launch_bounds__(64) void qmom_kernel(
     uint32_t rstride = (uint32_t)Bs * 4u;
     asm volatile("" : "+v"(rstride));
     const char* __restrict__ eb = reinterpret_cast<const char*>(eu);
-    float s0[ROWS];
+    constexpr int SPL = QSHIFT_SEQS * ROWS / 64;          // sequences per lane: 8 (two groups) or 4 (four)
+    const int srow = lane & (ROWS - 1), sgrp = lane / ROWS, scnt = min(QSHIFT_SEQS, B);
+    float4 sraw[SPL / 4];
+    float s0[ROWS];                   // wave-uniform: the shift of each row, one SGPR each
+    {
+        // (sequences 0 .. 15 of a row exist whatever B is: Bs >= 64, and rows are 256-byte aligned)
+        const char* __restrict__ rp = eb + (__umul24(rstride, (uint32_t)min(srow, n - 1)) + (uint32_t)(sgrp * SPL) * 4u);
 #pragma unroll
-    for (int i = 0; i < ROWS; ++i)
-        s0[i] = i < NQ ? *reinterpret_cast<const float*>(eb + __umul24(rstride, (uint32_t)min(i, n - 1))) : 0.f;
+        for (int j = 0; j < SPL / 4; ++j) sraw[j] = *reinterpret_cast<const float4*>(rp + 16 * j);
+    }
     f32x4q acc[NP];
 #pragma unroll
     for (int p = 0; p < NP; ++p) acc[p] = f32x4q{0.f, 0.f, 0.f, 0.f};
@@ -204,16 +226,22 @@ __global__ __launch_bounds__(64) void qmom_kernel(
     // (the first tile's rows are requested before the shift row is turned into q: one round trip
     // for both)
     if (bbeg < bend) issue(bbeg);
+    float ssum = 0.f;
 #pragma unroll
-    for (int i = 0; i < ROWS; ++i) KEEP(s0[i]);
-#pragma unroll
-    for (int i = 0; i < ROWS; ++i)
-        s0[i] = i <= NQLO ? qval(a1, s0[i], sh1) : (i >= NQ ? 0.f : (i < n ? qval(a1, s0[i], sh1) : 0.f));
-    if (ch == 0 && lane == 0) {
-#pragma unroll
-        for (int i = 0; i < ROWS; ++i)
-            if (i < NS) qs0[(size_t)u * NS + i] = s0[i];
+    for (int j = 0; j < SPL / 4; ++j) {
+        const float4 v = sraw[j];
+        const int b = sgrp * SPL + 4 * j;
+        ssum += b + 0 < scnt ? v.x : 0.f;
+        ssum += b + 1 < scnt ? v.y : 0.f;
+        ssum += b + 2 < scnt ? v.z : 0.f;
+        ssum += b + 3 < scnt ? v.w : 0.f;
     }
+#pragma unroll
+    for (int o = ROWS; o < 64; o <<= 1) ssum += __shfl_xor(ssum, o, 64);
+    ssum = srow < n ? qval(a1, ssum * (1.f / (float)scnt), sh1) : 0.f;
+    if (ch == 0 && lane < ROWS && lane < NS) qs0[(size_t)u * NS + lane] = ssum;   // the shift actually used
+#pragma unroll
+    for (int i = 0; i < ROWS; ++i) s0[i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ssum), i));
     if (bbeg < bend) finish();
     for (int b0 = bbeg; b0 < bend; b0 += 64) {
 #pragma unroll
@@ -293,11 +321,24 @@ __global__ __launch_bounds__(256, 2) void qmom_big_kernel(
     const int bbeg = ch * per, bend = min(B, bbeg + per);
     const float a1 = alpha[u], sh1 = shift[u];
     const float* eu = ext + (size_t)u * n * Bs;
-    for (int w = tid; w < NWT * 32; w += 256) {
-        const float raw = eu[(size_t)min(w, n - 1) * Bs];
-        const float sv = (w < n) ? qval(a1, raw, sh1) : 0.f;
-        s0s[w] = sv;
-        if (ch == 0 && w < NS) qs0[(size_t)u * NS + w] = sv;
+    // shift = q at the mean pooled extreme of the batch's first 16 sequences, as in qmom_kernel: four
+    // threads per row, one 16-byte load each (sequences 0 .. 15 of a row exist whatever B is: Bs >= 64)
+    const int scnt = min(QSHIFT_SEQS, B);
+    for (int idx = tid; idx < NWT * 32 * 4; idx += 256) {
+        const int w = idx >> 2, part = idx & 3;
+        const float4 r = *reinterpret_cast<const float4*>(eu + (size_t)min(w, n - 1) * Bs + part * 4);
+        float sv = 0.f;
+        sv += part * 4 + 0 < scnt ? r.x : 0.f;
+        sv += part * 4 + 1 < scnt ? r.y : 0.f;
+        sv += part * 4 + 2 < scnt ? r.z : 0.f;
+        sv += part * 4 + 3 < scnt ? r.w : 0.f;
+        sv += __shfl_xor(sv, 1, 64);
+        sv += __shfl_xor(sv, 2, 64);
+        sv = (w < n) ? qval(a1, sv * (1.f / (float)scnt), sh1) : 0.f;
+        if (part == 0) {
+            s0s[w] = sv;
+            if (ch == 0 && w < NS) qs0[(size_t)u * NS + w] = sv;    // the shift actually used
+        }
     }
     __syncthreads();
     f32x16q acc[NPW];

@@ -53,8 +53,8 @@ __global__ void sync_bn1_dist(const double* __restrict__ X, double* __restrict__
     else if (i < K4 * K4 + K4) m[i - K4 * K4] = X[i] / ((double)B * (double)Lo);
 }
 
-// ---- X2: qmom's chunk partials are sums about s = q of this shard's sequence 0, a shift no other
-// rank shares.  In fp64 they become sums about zero (an identity, no approximation beyond fp64
+// ---- X2: qmom's chunk partials are sums about s = the geometric mean of q over this shard's first 16
+// sequences (qs0), a shift no other rank shares.  In fp64 they become sums about zero (an identity, no approximation beyond fp64
 // rounding of the products):  sum q = S1 + B s,  sum q q' = S2 + s S1' + S1 s' + B s s'.
 // X2 = [U][NS] sum q | [U][NS][NS] sum q q'.
 __global__ __launch_bounds__(256) void sync_qmom_combine(const float* __restrict__ qs0,

@@ -74,8 +74,8 @@ def train_forward_backward(sd, x, dlogits_fn, keep=None, p=0.3):
     idx = (gw * sgn).argmax(axis=3)
     ext = np.take_along_axis(gw, idx[..., None], axis=3)[..., 0]
     q = np.exp(alpha[None, :, None] * ext + sh[None, :, None])      # (B,U,n)
-    # ---- qmoments (shifted by sequence 0) + prep2 ----
-    s0 = q[0]
+    # ---- qmoments (about q at the mean pooled extreme of the first 16 sequences) + prep2 ----
+    s0 = np.exp(alpha[None, :, None] * ext[:16].mean(axis=0, keepdims=True) + sh[None, :, None])[0]
     S1 = (q - s0).sum(0)                                            # (U,n)
     S2 = np.einsum("buw,buv->uwv", q - s0, q - s0)
     qbar = s0 + S1 / B

@@ -2,7 +2,8 @@
 numpy oracle's train-mode intermediates exactly as the combine kernels define them:
 
   X1  the integer pair counts behind G, m of the window indicator (moments_kernel: G = count/(B Lo))
-  X2  sum q, sum q q' -- from per-shard sums about the shard's own shift s = q of its sequence 0,
+  X2  sum q, sum q q' -- from per-shard sums about the shard's own shift s = the geometric mean of q over its
+      first 16 sequences,
       converted to sums about zero (sum q = S1 + B s, sum q q' = S2 + s S1' + S1 s' + B s s')
   X3  sum z, sum z^2 per unit
   X4  sum d3, sum d3 zhat per unit, the combiner gradients, the loss sum
@@ -51,7 +52,7 @@ def shard_exchanges(x, q, z, zhat, d3, k):
     C, c = window_counts(x, k)
     X2 = []
     for u in range(q.shape[1]):
-        s = q[0, u]                                   # this shard's own shift
+        s = np.exp(np.log(q[:16, u]).mean(axis=0))    # this shard's own shift
         S1, S2 = qmoments_about(q[:, u], s)
         X2.append(to_zero(S1, S2, s, B))
     return {"X1": (C, c), "X2": X2, "X3": (z.sum(0), (z * z).sum(0)),
