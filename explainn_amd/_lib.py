@@ -18,6 +18,7 @@ METRICS_BINARY, METRICS_LINEAR = 0, 1
 METRICS_NONFINITE, METRICS_NOT_BINARY = 1, 2
 IG_BASELINE_ZERO, IG_BASELINE_UNIFORM, IG_BASELINE_CODES = 0, 1, 2
 SCAN_AUTO, SCAN_WINDOWS, SCAN_SHARED = 0, 1, 2
+MOTIF_MAX_WIDTH = 64      # EXPLAINN_MOTIF_MAX_WIDTH: columns per motif of explainn_motif_compare
 SITES_TILE = 1024         # EXPLAINN_SITES_TILE: start positions per workgroup of explainn_call_sites
 
 _fp = C.c_void_p          # device pointers travel as integers (tensor.data_ptr())
@@ -139,6 +140,9 @@ SIGNATURES = {
     "explainn_dense_input": (_i, [_ctx, _i]),
     "explainn_pwm_scan": (_i, [_fp, _i, _i, _fp, _i, _i, _i, _fp, _fp]),
     "explainn_dinucleotide_shuffle": (_i, [_fp, _i64, _i, _i, C.c_uint64, _i64, _i, _fp, _fp, _fp]),
+    "explainn_motif_compare_workspace_bytes": (_i64, [_i, _i, _i]),
+    "explainn_motif_compare": (_i, [_fp, _fp, _i, _fp, _fp, _i, _i, C.c_float, _i, _i, _fp, _fp, _fp, _fp, _i64,
+                                    _fp]),
     "explainn_adam_step": (_i, [_i, C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp),
                                 C.POINTER(_i64), _i64, C.c_double, C.c_double, C.c_double, C.c_double,
                                 _fp]),

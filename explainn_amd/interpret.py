@@ -449,10 +449,11 @@ def format_jaspar(pfm_u, matrix_id, name):
 
 
 def interpret(exp_model, seqs, labels, name, output_dir="./", batch_size=100, rev_complement=False,
-              input_data=None, sites=False):
+              input_data=None, sites=False, meme=False):
     """The filter-level part of interpret.py's main (interpret.py:128-235): output-layer weights,
     filter importances and one JASPAR motif per filter, written under output_dir.  sites=True also
-    writes thresholds.tsv and sites/filter<u>.fa (write_sites)."""
+    writes thresholds.tsv and sites/filter<u>.fa (write_sites); meme=True also writes motifs/filters.meme,
+    the filters that have a site as one MEME file (motifs.write_meme), for an external Tomtom."""
     import pandas as pd
     if input_data is None:
         input_data = "binary" if np.unique(labels[:, 0]).size == 2 else "linear"
@@ -479,6 +480,11 @@ def interpret(exp_model, seqs, labels, name, output_dir="./", batch_size=100, re
         with open(os.path.join(output_dir, "motifs", "filter%d.jaspar" % u), "wt") as fh:
             if res["nsites"][u] > 0:          # the reference leaves the file empty when no site
                 fh.write(format_jaspar(res["pfm"][u], "filter%d" % u, name))
+    if meme:
+        from .motifs import write_meme
+        kept = [u for u in range(U) if res["nsites"][u] > 0]
+        write_meme(os.path.join(output_dir, "motifs", "filters.meme"),
+                   [("filter%d" % u, name, res["pfm"][u]) for u in kept], [int(res["nsites"][u]) for u in kept])
     if sites:
         k = exp_model._options["kernel_size"]
         lists = filter_site_list(exp_model, seqs, idxs, res["thresholds"], rev_complement)
@@ -502,12 +508,14 @@ def main(argv=None):
     ap.add_argument("-t", "--time-me", action="store_true")
     ap.add_argument("--sites", action="store_true",
                     help="also write thresholds.tsv and sites/filter<u>.fa (one k-mer per site)")
+    ap.add_argument("--meme", action="store_true",
+                    help="also write motifs/filters.meme (every filter with a site, MEME format)")
     args = ap.parse_args(argv)
     t0 = time.time()
     seqs, labels, _ = _get_seqs_labels_ids(args.training_file, args.debugging, args.rev_complement)
     model = _load_model(args.model_file)
     interpret(model, seqs, labels, args.name, args.output_dir, args.batch_size, args.rev_complement,
-              sites=args.sites)
+              sites=args.sites, meme=args.meme)
     if args.time_me:
         with open(os.path.join(args.output_dir, "time-interpret.py.txt"), "wt") as fh:
             fh.write("%.2f seconds" % (time.time() - t0))

@@ -1,0 +1,405 @@
+"""Compare motifs on the device: what each filter learned and which filters are the same motif.
+
+The reference sends the matrices interpret.py exports to external programs for this (Tomtom against JASPAR,
+RSAT matrix-clustering).  Here the all-pairs comparison is one device call (csrc/motifs.hip,
+explainn_motif_compare): for every (query, target) the best ungapped alignment over offsets and both strands
+by width-normalised Pearson correlation -- RSAT's `cor` and `Ncor` ("Motif
+comparison") -- and annotation, single-linkage clustering and reproducibility across the members of a model
+bank are torch reductions over that matrix.  Tomtom's p/E/q-values are not computed; `write_meme` writes the
+filters in the format an external Tomtom reads.
+
+  python -m explainn_amd.motifs annotate MOTIFS DB -o OUT.tsv
+  python -m explainn_amd.motifs cluster MOTIFS [MOTIFS ...] -o OUT.tsv
+MOTIFS / DB: a MEME file, a JASPAR file (the layout interpret.format_jaspar writes, any number of motifs),
+or a directory of filter*.jaspar.
+"""
+import argparse
+import collections
+import glob
+import os
+import re
+
+import numpy as np
+
+MAX_WIDTH = 64
+
+MotifComparison = collections.namedtuple("MotifComparison", "ncor cor offset strand overlap")
+
+
+# ---------------------------------------------------------------- files
+def read_meme(path):
+    """MEME minimal text -> [(id, name, (w,4) float64 probabilities)]."""
+    out = []
+    with open(path) as fh:
+        lines = [ln.strip() for ln in fh]
+    i = 0
+    while i < len(lines):
+        if not lines[i].startswith("MOTIF"):
+            i += 1
+            continue
+        parts = lines[i].split()
+        if len(parts) < 2:
+            raise ValueError("%s line %d: MOTIF without an identifier" % (path, i + 1))
+        ident, name = parts[1], " ".join(parts[2:])
+        i += 1
+        while i < len(lines) and not lines[i].startswith("letter-probability matrix"):
+            if lines[i].startswith("MOTIF"):
+                raise ValueError("%s: motif %s has no letter-probability matrix" % (path, ident))
+            i += 1
+        if i == len(lines):
+            raise ValueError("%s: motif %s has no letter-probability matrix" % (path, ident))
+        m = re.search(r"alength=\s*(\d+)", lines[i])
+        if m and int(m.group(1)) != 4:
+            raise ValueError("%s: motif %s is not over a 4-letter alphabet" % (path, ident))
+        m = re.search(r"\bw=\s*(\d+)", lines[i])
+        want = int(m.group(1)) if m else None
+        i += 1
+        rows = []
+        while i < len(lines) and (len(rows) < want if want is not None else not lines[i].startswith("MOTIF")):
+            vals = lines[i].split()
+            i += 1
+            if not vals:
+                continue
+            try:
+                row = [float(v) for v in vals]
+            except ValueError:
+                if want is None:
+                    break                                  # the matrix ended (a URL line, the next section)
+                raise ValueError("%s: motif %s: cannot read the row %r" % (path, ident, lines[i - 1]))
+            if len(row) != 4:
+                raise ValueError("%s: motif %s: a row of %d values" % (path, ident, len(row)))
+            rows.append(row)
+        if want is not None and len(rows) != want:
+            raise ValueError("%s: motif %s: %d rows, w= %d" % (path, ident, len(rows), want))
+        out.append((ident, name, np.array(rows, dtype=np.float64).reshape(-1, 4)))
+    return out
+
+
+def read_jaspar(path):
+    """The layout interpret.format_jaspar writes ('>id name', then 'A [ ... ]' .. 'T [ ... ]'), any number of
+    motifs in one file -> [(id, name, (w,4) float64 counts)].  An empty file gives an empty list."""
+    out, head, rows = [], None, {}
+
+    def close():
+        if head is None:
+            return
+        if sorted(rows) != list("ACGT") or len({len(v) for v in rows.values()}) != 1:
+            raise ValueError("%s: motif %s needs rows A, C, G, T of one length" % (path, head[0]))
+        out.append((head[0], head[1], np.array([rows[a] for a in "ACGT"], dtype=np.float64).T.reshape(-1, 4)))
+
+    with open(path) as fh:
+        for ln in fh:
+            ln = ln.strip()
+            if not ln:
+                continue
+            if ln.startswith(">"):
+                close()
+                parts = ln[1:].split(None, 1)
+                if not parts:
+                    raise ValueError("%s: header without an identifier" % path)
+                head, rows = (parts[0], parts[1].strip() if len(parts) > 1 else ""), {}
+                continue
+            m = re.match(r"^([ACGT])\s*\[(.*)\]\s*$", ln)
+            if not m or head is None:
+                raise ValueError("%s: cannot read %r" % (path, ln))
+            rows[m.group(1)] = [float(v) for v in m.group(2).split()]
+    close()
+    return out
+
+
+def _fmt(v):
+    return np.format_float_positional(float(v), unique=True, trim="0")
+
+
+def write_meme(path, motifs, nsites=None):
+    """[(id, name, (w,4))] -> MEME minimal text.  Columns that already sum to 1 are written as they are (every
+    digit, so read_meme returns them exactly); count columns are divided by their sum (an all-zero column
+    becomes 0.25).  nsites: one number per motif; default: the largest column sum of a count matrix, 20 (MEME's
+    own default) for probabilities."""
+    with open(path, "wt") as fh:
+        fh.write("MEME version 4\n\nALPHABET= ACGT\n\nstrands: + -\n\n"
+                 "Background letter frequencies\nA 0.25 C 0.25 G 0.25 T 0.25\n\n")
+        for i, (ident, name, m) in enumerate(motifs):
+            m = np.asarray(m, dtype=np.float64).reshape(-1, 4)
+            tot = m.sum(axis=1)
+            is_prob = bool(len(m)) and bool(np.all(np.abs(tot - 1.0) < 1e-6))
+            if nsites is not None:
+                ns = nsites[i]
+            else:
+                ns = 20 if is_prob or not len(m) else max(1, int(round(tot.max())))
+            if not is_prob:
+                m = np.where(tot[:, None] > 0, m / np.where(tot > 0, tot, 1.0)[:, None], 0.25)
+            fh.write("MOTIF %s\n" % (("%s %s" % (ident, name)).strip()))
+            fh.write("letter-probability matrix: alength= 4 w= %d nsites= %d E= 0\n" % (len(m), int(ns)))
+            for row in m:
+                fh.write(" ".join(_fmt(v) for v in row) + "\n")
+            fh.write("\n")
+
+
+def read_motifs(path):
+    """A MEME file, a JASPAR file or a directory of filter*.jaspar (in filter order; empty files, which
+    interpret writes for filters without a site, are skipped)."""
+    if os.path.isdir(path):
+        files = glob.glob(os.path.join(path, "filter*.jaspar"))
+        if not files:
+            raise ValueError("%s holds no filter*.jaspar" % path)
+        num = lambda f: int(re.search(r"filter(\d+)\.jaspar$", f).group(1)) if re.search(r"filter(\d+)\.jaspar$", f) else -1
+        out = []
+        for f in sorted(files, key=lambda f: (num(f), f)):
+            out.extend(read_jaspar(f))
+        return out
+    with open(path) as fh:
+        text = fh.read(1 << 16)
+    if re.search(r"^(MEME version|MOTIF\s)", text, re.M):
+        return read_meme(path)
+    return read_jaspar(path)
+
+
+# ---------------------------------------------------------------- packing and the device call
+def pack(motifs):
+    """[(id, name, (w,4))] or [(w,4) arrays] -> ((M,wmax,4) float32 tensor, zero padded, int32 widths), on
+    the host."""
+    import torch
+    mats = [np.asarray(m[2] if isinstance(m, tuple) else m, dtype=np.float64).reshape(-1, 4) for m in motifs]
+    wmax = max([len(m) for m in mats] + [1])
+    x = np.zeros((len(mats), wmax, 4), dtype=np.float32)
+    for i, m in enumerate(mats):
+        x[i, :len(m)] = m
+    return torch.from_numpy(x), torch.tensor([len(m) for m in mats], dtype=torch.int32)
+
+
+def _as_set(obj, device):
+    """Anything compare accepts -> (float32 (M,w,4), int32 widths[M]) on `device`."""
+    import torch
+    widths = None
+    if isinstance(obj, dict):                              # interpret.filter_pwms' result
+        x = torch.as_tensor(np.asarray(obj["pfm"]))
+        widths = (torch.as_tensor(np.asarray(obj["nsites"])) > 0).to(torch.int32) * x.shape[1]
+    elif isinstance(obj, (tuple, list)) and len(obj) == 2 and torch.is_tensor(obj[0]) and obj[0].dim() == 3:
+        x, widths = obj
+    elif isinstance(obj, (list, tuple)):
+        x, widths = pack(obj)
+    else:
+        x = torch.as_tensor(obj)
+    if x.dim() != 3 or x.shape[2] != 4:
+        raise ValueError("a motif set is (M, w, 4), rows A,C,G,T per column (got %s)" % (tuple(x.shape),))
+    x = x.to(device=device, dtype=torch.float32).contiguous()
+    if widths is None:                                     # a bare array: every motif w wide; a filter without
+        widths = (x.reshape(len(x), -1).abs().sum(dim=1) > 0).to(torch.int32) * x.shape[1]   # a site is all zero
+    widths = torch.as_tensor(widths).to(device=device, dtype=torch.int32).contiguous()
+    if widths.shape != (len(x),):
+        raise ValueError("widths must hold one entry per motif")
+    return x, widths
+
+
+def _pad(x, wmax):
+    import torch
+    if x.shape[1] == wmax:
+        return x
+    out = torch.zeros((x.shape[0], wmax, 4), dtype=x.dtype, device=x.device)
+    out[:, :x.shape[1]] = x
+    return out
+
+
+def compare(queries, targets=None, min_overlap=5, pseudocount=0.0, both_strands=True, device=None):
+    """The best alignment of every query with every target (targets=None: the queries with themselves).
+
+    queries / targets: a list from read_meme / read_jaspar / read_motifs, a list of (w,4) arrays, pack()'s
+    (tensor, widths), a (M,w,4) array or tensor (interpret.filter_pwms(...)["pfm"]: an all-zero matrix, a
+    filter with nsites == 0, is given width 0) or filter_pwms' whole result.  Returns a MotifComparison of
+    device tensors (Q,T): ncor and cor (float32), offset, strand, overlap (int16; views of one tensor).
+    Enqueued on the current stream; no host synchronisation."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib
+    if int(min_overlap) < 1:
+        raise ValueError("min_overlap must be at least 1")
+    if not float(pseudocount) >= 0:
+        raise ValueError("pseudocount must not be negative")
+    if device is None:
+        for obj in (queries, targets):
+            first = obj[0] if isinstance(obj, (tuple, list)) and len(obj) else obj
+            if torch.is_tensor(first) and first.device.type == "cuda":
+                device = first.device
+                break
+    if device is None:
+        if not torch.cuda.is_available():
+            raise RuntimeError("motifs.compare runs only on a HIP device (there is no CPU fallback)")
+        device = torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("motifs.compare runs only on a HIP device (there is no CPU fallback)")
+    q, qw = _as_set(queries, device)
+    t = tw = None
+    if targets is not None:
+        t, tw = _as_set(targets, device)
+    wmax = max(q.shape[1], t.shape[1] if t is not None else 1, 1)
+    if wmax > MAX_WIDTH:
+        raise ValueError("motifs wider than %d columns are not supported (got %d)" % (MAX_WIDTH, wmax))
+    q = _pad(q, wmax)
+    if t is not None:
+        t = _pad(t, wmax)
+    Q, T = len(q), len(t) if t is not None else len(q)
+    ncor = torch.empty((Q, T), dtype=torch.float32, device=device)      # every entry is overwritten
+    cor = torch.empty((Q, T), dtype=torch.float32, device=device)
+    align = torch.empty((Q, T, 3), dtype=torch.int16, device=device)
+    if Q and T:
+        lib = _lib.load()
+        nbytes = int(lib.explainn_motif_compare_workspace_bytes(Q, T, wmax))
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=device)
+        with torch.cuda.device(device):
+            _lib.check(lib.explainn_motif_compare(
+                q.data_ptr(), qw.data_ptr(), Q, t.data_ptr() if t is not None else None,
+                tw.data_ptr() if t is not None else None, T, wmax, float(pseudocount), int(min_overlap),
+                int(bool(both_strands)), ncor.data_ptr(), cor.data_ptr(), align.data_ptr(), ws.data_ptr(), nbytes,
+                C.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+    return MotifComparison(ncor, cor, align[..., 0], align[..., 1], align[..., 2])
+
+
+# ---------------------------------------------------------------- reductions over the comparison
+def _passing(result, min_ncor, min_cor):
+    return (result.ncor >= min_ncor) & (result.cor >= min_cor)
+
+
+def annotate(queries, database=None, top=3, min_ncor=0.4, min_cor=0.6, **compare_args):
+    """For each query up to `top` targets with Ncor >= min_ncor and cor >= min_cor, best Ncor first, ties to
+    the lower target index: a list (one entry per query) of lists of dicts(target, ncor, cor, offset, strand,
+    overlap).  `queries` may be a MotifComparison already computed (then `database` is not read).  The
+    thresholds default to the lower bounds RSAT matrix-clustering is usually run with."""
+    import torch
+    res = queries if isinstance(queries, MotifComparison) else compare(queries, database, **compare_args)
+    Q, T = res.ncor.shape
+    n = min(int(top), T)
+    if n < 1 or Q == 0:
+        return [[] for _ in range(Q)]
+    score = torch.where(_passing(res, min_ncor, min_cor), res.ncor, torch.full_like(res.ncor, float("-inf")))
+    val, idx = torch.sort(score, dim=1, descending=True, stable=True)
+    val, idx = val[:, :n], idx[:, :n]
+    pick = lambda a: torch.gather(a, 1, idx).cpu().numpy()
+    val, idxh = val.cpu().numpy(), idx.cpu().numpy()
+    cor, off, strand, ovl = pick(res.cor), pick(res.offset), pick(res.strand), pick(res.overlap)
+    return [[dict(target=int(idxh[i, j]), ncor=float(val[i, j]), cor=float(cor[i, j]), offset=int(off[i, j]),
+                  strand=int(strand[i, j]), overlap=int(ovl[i, j]))
+             for j in range(n) if np.isfinite(val[i, j])] for i in range(Q)]
+
+
+def cluster(result, min_ncor=0.4, min_cor=0.6):
+    """Single-linkage clusters of a self-comparison: the connected components of the pairs (either direction)
+    with Ncor >= min_ncor and cor >= min_cor.  Returns (labels int64 [M], representatives int64 [C]): clusters
+    are numbered 0.. in the order of their smallest member; a cluster's representative is the member with the
+    largest summed Ncor to the members of its cluster, ties to the lower index."""
+    import torch
+    M = result.ncor.shape[0]
+    if result.ncor.shape != (M, M):
+        raise ValueError("cluster needs a self-comparison (M, M)")
+    mask = _passing(result, min_ncor, min_cor)
+    mask = mask | mask.T
+    pairs = torch.nonzero(torch.triu(mask, diagonal=1)).cpu().numpy()
+    parent = list(range(M))
+
+    def find(a):
+        while parent[a] != a:
+            parent[a] = parent[parent[a]]
+            a = parent[a]
+        return a
+
+    for a, b in pairs:
+        ra, rb = find(int(a)), find(int(b))
+        if ra != rb:
+            parent[max(ra, rb)] = min(ra, rb)          # the root is the smallest member
+    roots = np.array([find(a) for a in range(M)], dtype=np.int64)
+    order = {r: c for c, r in enumerate(sorted(set(roots.tolist())))}
+    labels = np.array([order[r] for r in roots.tolist()], dtype=np.int64)
+    lab = torch.from_numpy(labels).to(result.ncor.device)
+    same = lab[:, None] == lab[None, :]
+    total = torch.where(same, result.ncor, torch.zeros_like(result.ncor)).sum(dim=1).cpu().numpy()
+    reps = np.zeros(len(order), dtype=np.int64)
+    for c in range(len(order)):
+        members = np.nonzero(labels == c)[0]
+        reps[c] = members[np.argmax(total[members])]     # the first maximum: the lower index
+    return labels, reps
+
+
+def reproducibility(pfms, nsites=None, min_ncor=0.4, min_cor=0.6, result=None, **compare_args):
+    """Which filters recur across the members of a model bank.  pfms: (G,U,k,4) count matrices, nsites: (G,U)
+    (a filter with nsites == 0 matches nothing).  Returns (count int64 (G,U): the number of OTHER members that
+    hold a filter passing both thresholds, partner int64 (G,U,G): the index of the best such filter in each
+    member, by Ncor, ties to the lower index; -1 where there is none and for the member itself).  `result`: the
+    comparison of the G*U filters (member-major) with themselves, when it has been computed already."""
+    import torch
+    pfms = np.asarray(pfms) if not torch.is_tensor(pfms) else pfms
+    G, U = int(pfms.shape[0]), int(pfms.shape[1])
+    if result is None:
+        flat = torch.as_tensor(pfms).reshape(G * U, pfms.shape[2], 4)
+        if nsites is not None:
+            ns = torch.as_tensor(np.asarray(nsites)).reshape(G * U)
+            result = compare((flat, (ns > 0).to(torch.int32) * flat.shape[1]), None, **compare_args)
+        else:
+            result = compare(flat, None, **compare_args)
+    if result.ncor.shape != (G * U, G * U):
+        raise ValueError("result must compare the %d filters with themselves" % (G * U))
+    score = torch.where(_passing(result, min_ncor, min_cor), result.ncor,
+                        torch.full_like(result.ncor, float("-inf"))).reshape(G, U, G, U)
+    best = torch.argmax(score, dim=3)
+    has = torch.isfinite(score.max(dim=3).values)
+    has = has & ~torch.eye(G, dtype=torch.bool, device=has.device)[:, None, :]
+    partner = torch.where(has, best, torch.full_like(best, -1))
+    return has.sum(dim=2).cpu().numpy().astype(np.int64), partner.cpu().numpy().astype(np.int64)
+
+
+# ---------------------------------------------------------------- command line
+def _cli_annotate(a):
+    queries, db = read_motifs(a.motifs), read_motifs(a.db)
+    hits = annotate(queries, db, top=a.top, min_ncor=a.min_ncor, min_cor=a.min_cor, min_overlap=a.min_overlap,
+                    pseudocount=a.pseudocount)
+    with open(a.output, "wt") as fh:
+        fh.write("Query\tTarget\tTargetName\tNcor\tCor\tOffset\tStrand\tOverlap\n")
+        for (qid, _, _), rows in zip(queries, hits):
+            for h in rows:
+                tid, tname, _ = db[h["target"]]
+                fh.write("%s\t%s\t%s\t%.4f\t%.4f\t%d\t%s\t%d\n" % (qid, tid, tname, h["ncor"], h["cor"], h["offset"],
+                                                                 "-" if h["strand"] else "+", h["overlap"]))
+
+
+def _cli_cluster(a):
+    motifs = []
+    for path in a.motifs:
+        motifs.extend(read_motifs(path))
+    res = compare(motifs, None, min_overlap=a.min_overlap, pseudocount=a.pseudocount)
+    labels, reps = cluster(res, a.min_ncor, a.min_cor)
+    with open(a.output, "wt") as fh:
+        fh.write("Motif\tCluster\tRepresentative\n")
+        for (ident, _, _), c in zip(motifs, labels):
+            fh.write("%s\t%d\t%s\n" % (ident, c, motifs[reps[c]][0]))
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m explainn_amd.motifs",
+                                 description="Annotate and cluster motifs by Ncor on the device")
+    sub = ap.add_subparsers(dest="command", required=True)
+
+    def common(p):
+        p.add_argument("-o", "--output", required=True)
+        p.add_argument("--min-ncor", type=float, default=0.4)
+        p.add_argument("--min-cor", type=float, default=0.6)
+        p.add_argument("--min-overlap", type=int, default=5)
+        p.add_argument("--pseudocount", type=float, default=0.0)
+
+    p = sub.add_parser("annotate", help="the best database motifs of every query motif")
+    p.add_argument("motifs")
+    p.add_argument("db")
+    p.add_argument("--top", type=int, default=3)
+    common(p)
+    p.set_defaults(run=_cli_annotate)
+    p = sub.add_parser("cluster", help="single-linkage clusters of one or more motif sets")
+    p.add_argument("motifs", nargs="+")
+    common(p)
+    p.set_defaults(run=_cli_cluster)
+    a = ap.parse_args(argv)
+    a.run(a)
+
+
+if __name__ == "__main__":
+    main()

@@ -511,6 +511,33 @@ int explainn_dinucleotide_shuffle(const uint8_t* codes, int64_t N, int L, int R,
                                   int64_t row0, int max_rounds, uint8_t* out, uint8_t* capped,
                                   void* stream);
 
+/* Motif comparison (csrc/motifs.hip): the best ungapped alignment of every query
+ * motif with every target motif by width-normalised Pearson correlation, the score RSAT compare-matrices
+ * and matrix-clustering call Ncor.
+ * A set of M motifs: fp32 (M,wmax,4), rows A,C,G,T per column, non-negative counts or probabilities, and
+ * int32 widths[M], 0 <= w <= wmax <= EXPLAINN_MOTIF_MAX_WIDTH; columns from w on are ignored.
+ * Per column f[a] = (c[a] + pc/4) / (sum c + pc), 0.25 where that denominator is 0; d = f - 0.25;
+ * n = sum_a d[a]^2.  An alignment (s, o): strand s = 1 takes the target's reverse complement; query column
+ * i meets target column i + o; over the overlap of size w, XY = sum d_q.d_t, SX = sum n_q, SY = sum n_t,
+ * cor = XY / sqrt(SX SY) (0 when SX or SY is below EXPLAINN_MOTIF_VAR_FLOOR), Ncor = cor w / (wq + wt - w).
+ * Admissible: w >= 1 and w >= min(min_overlap, wq, wt).  The best alignment is the admissible one with the
+ * largest Ncor, ties to strand 0, then to the smaller offset; a pair with a width of 0 gives zeros.
+ * both_strands == 0 searches strand 0 only.
+ * ncor, cor: fp32 (Q,T); align: int16 (Q,T,3) = offset, strand, overlap.  Outputs are OVERWRITTEN; cor and
+ * align may be NULL.  t == NULL compares the queries with themselves (T must then equal Q; t_widths is
+ * not read).  workspace: device memory, 16-byte aligned, of explainn_motif_compare_workspace_bytes(Q,T,wmax)
+ * bytes, dead after the call.  No context, no allocation, no host synchronisation; the same input gives the
+ * same bits on every call.  Q, T < 0, wmax < 1, min_overlap < 1, pseudocount < 0: EXPLAINN_E_ARG;
+ * wmax > EXPLAINN_MOTIF_MAX_WIDTH: EXPLAINN_E_UNSUPPORTED; a width outside [0,wmax] is found on the device
+ * and makes that motif one of width 0.  Q == 0 or T == 0 launches nothing. */
+#define EXPLAINN_MOTIF_MAX_WIDTH 64
+#define EXPLAINN_MOTIF_VAR_FLOOR 1e-6f
+int64_t explainn_motif_compare_workspace_bytes(int Q, int T, int wmax);
+int explainn_motif_compare(const float* q, const int32_t* q_widths, int Q, const float* t,
+                           const int32_t* t_widths, int T, int wmax, float pseudocount, int min_overlap,
+                           int both_strands, float* ncor, float* cor, int16_t* align, void* workspace,
+                           int64_t workspace_bytes, void* stream);
+
 /* One Adam step over n_tensors parameter tensors in a single launch -- torch.optim.Adam(params, lr)
  * with its defaults, the optimiser the reference builds (architectures/__init__.py:463-464) and
  * steps at selene/__init__.py:291.  params/grads/exp_avg/exp_avg_sq: HOST arrays of n_tensors

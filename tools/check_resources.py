@@ -64,7 +64,9 @@ VARIANTS = [r"^stage_edits_kernel"]
 HAPLOTYPES = [r"^stage_haplotypes_kernel"]
 # dinucleotide-preserving shuffles (shuffle.hip): one lane per (row, shuffle), counters in LDS
 SHUFFLE = [r"^dinuc_shuffle_kernel"]
-GATED = C2_STEP + INPUT_GRAD + ISM + PATHGRAD + METRICS + SCAN + VARIANTS + HAPLOTYPES + SHUFFLE
+# motif comparison (motifs.hip): the preparation and the all-pairs alignment search
+MOTIFS = [r"^motif_prep_kernel", r"^motif_compare_kernel"]
+GATED = C2_STEP + INPUT_GRAD + ISM + PATHGRAD + METRICS + SCAN + VARIANTS + HAPLOTYPES + SHUFFLE + MOTIFS
 
 
 # Register cliffs measured in the pipeline: 1024-thread blocks of which TWO must
