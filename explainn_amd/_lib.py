@@ -19,7 +19,9 @@ METRICS_NONFINITE, METRICS_NOT_BINARY = 1, 2
 IG_BASELINE_ZERO, IG_BASELINE_UNIFORM, IG_BASELINE_CODES = 0, 1, 2
 SCAN_AUTO, SCAN_WINDOWS, SCAN_SHARED = 0, 1, 2
 MOTIF_MAX_WIDTH = 64      # EXPLAINN_MOTIF_MAX_WIDTH: columns per motif of explainn_motif_compare
-SITES_TILE = 1024         # EXPLAINN_SITES_TILE: start positions per workgroup of explainn_call_sites
+MOTIF_MAX_BINS = 128      # EXPLAINN_MOTIF_MAX_BINS: score bins per column of explainn_motif_significance
+MOTIF_NO_SCORE = 255      # EXPLAINN_MOTIF_NO_SCORE: a colscore entry without a column
+SITES_TILE = 1024        # EXPLAINN_SITES_TILE: start positions per workgroup of explainn_call_sites
 
 _fp = C.c_void_p          # device pointers travel as integers (tensor.data_ptr())
 
@@ -143,6 +145,9 @@ SIGNATURES = {
     "explainn_motif_compare_workspace_bytes": (_i64, [_i, _i, _i]),
     "explainn_motif_compare": (_i, [_fp, _fp, _i, _fp, _fp, _i, _i, C.c_float, _i, _i, _fp, _fp, _fp, _fp, _i64,
                                     _fp]),
+    "explainn_motif_significance_workspace_bytes": (_i64, [_i, _i, _i, _i, _i]),
+    "explainn_motif_significance": (_i, [_fp, _fp, _i, _fp, _fp, _i, _i, C.c_float, _i, _i, _i, _fp, _fp, _fp, _fp,
+                                         _fp, _fp, _i64, _fp]),
     "explainn_adam_step": (_i, [_i, C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp),
                                 C.POINTER(_i64), _i64, C.c_double, C.c_double, C.c_double, C.c_double,
                                 _fp]),

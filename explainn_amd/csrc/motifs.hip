@@ -22,6 +22,9 @@
 //     form), so it stays fp32.
 // The order of evaluation is fixed -- strand 0 before strand 1, offsets ascending, a strictly larger Ncor
 // replaces the best -- which is the tie rule and makes the result a pure function of the input.
+//
+// The second half of the file is motif significance (explainn_motif_significance): p-values of alignment
+// scores under a per-query null, on the same preparation and conventions.
 #include "common.h"
 
 namespace {
@@ -304,5 +307,381 @@ extern "C" int explainn_motif_compare(const float* q, const int32_t* q_widths, i
     hipLaunchKernelGGL(motif_compare_kernel, dim3((unsigned)(ntt * ntq)), dim3(MC_WAVES * 64), lds, s, D, P, W, Q, Dt,
                        Pt, Wt, T, wmax, (int)ntt, min_overlap, both_strands != 0, ncor, cor, align);
     LAUNCH_CHECK();
+    return EXPLAINN_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Motif significance: p-values of the best alignment under the null of
+// Gupta et al. 2007 -- the columns of the query against every column of the database, the score of an
+// alignment the sum of quantised column correlations, its null the convolution of the per-column nulls.
+//
+// Five launches after the preparation of motif_prep_kernel (whose centred columns are turned into unit
+// columns while they are staged):
+//   motif_colscore_kernel, lane = target, 64 targets (forward columns, [column][lane] so a read is
+//     conflict-free) and MS_TQ queries in LDS: the quantised score of every query column against every column
+//     of both strand views of the lane's target, a byte each, into the workspace matrix
+//     cs[(q*wmax + i)][(s*wmax + j)*Tp + t] (Tp = T rounded up to 16; MS_NONE where the target column does
+//     not exist; rows i >= wq are not written).  The reverse-complement view needs no second copy: column j
+//     of rc(t) is column wt-1-j with its four entries reversed.
+//   motif_hist_kernel, one workgroup per query column: the histogram of its row, integer LDS atomics into one
+//     histogram per wave, summed in a fixed order.
+//   motif_null_kernel, one workgroup per (query, lo): the pmf of the sum over columns lo .. lo+w-1 for
+//     w = 1 .. wq-lo, each from the one before by one convolution (thread = support point, bins ascending,
+//     fused multiply-adds, fp64), two pmf buffers in LDS; after every w the suffix sums -- each thread sums a
+//     contiguous piece from the top, adds the pieces above it in descending order -- go to the workspace table.
+//   motif_pvalue_kernel, one lane per (query, target): strand 0 before strand 1, offsets ascending, the sum of
+//     the bytes of the overlap, the table look-up, a strictly smaller p replaces the best; then the Sidak
+//     step over the pair's admissible alignments.
+//   motif_colscore_copy_kernel: the caller's copy of the matrix without the row padding (only when asked for).
+// No float atomics anywhere and every sum in a fixed order: the result is a pure function of the input.
+namespace {
+
+constexpr int MS_TT = 64;        // targets per workgroup = lanes of a wave
+constexpr int MS_TQ = 8;         // queries per workgroup of the column scores
+constexpr int MS_WAVES = 4;
+constexpr int MS_THREADS = MS_WAVES * 64;
+constexpr int MS_HPAD = 136;     // histogram row in LDS (bins + 1 <= 129)
+
+__host__ __device__ inline int64_t ms_a(int64_t n, int bins) { return bins * (n * (n + 1) / 2) + n; }
+__host__ __device__ inline int64_t ms_c(int64_t n, int bins) {
+    return bins * (n * (n + 1) * (n + 2) / 6) + n * (n + 1) / 2;
+}
+// the suffix sums of range (lo, w) of one query: ranges ordered by lo, then by w; range (lo, w) holds w*bins+1
+__host__ __device__ inline int64_t ms_sf_off(int lo, int w, int wmax, int bins) {
+    return ms_c(wmax, bins) - ms_c(wmax - lo, bins) + ms_a(w - 1, bins);
+}
+__host__ __device__ inline int ms_tp(int T) { return (T + 15) & ~15; }
+
+// workspace: the preparation's (mc_layout) | cs [Q*wmax][S*wmax*Tp] uint8 | hist [Q*wmax][bins+1] int32 |
+// sf [Q][ms_c(wmax)] double, each 256-byte aligned
+struct ms_layout { int64_t cs, hist, sf, bytes, ld, sfq; };
+__host__ inline ms_layout ms_workspace(int64_t Q, int64_t M, int T, int wmax, int bins, int S) {
+    auto up = [](int64_t v) { return (v + 255) & ~(int64_t)255; };
+    ms_layout l;
+    l.ld = (int64_t)S * wmax * ms_tp(T);
+    l.sfq = ms_c(wmax, bins);
+    l.cs = mc_workspace(M, wmax).bytes;
+    l.hist = l.cs + up(Q * wmax * l.ld);
+    l.sf = l.hist + up(Q * wmax * (bins + 1) * 4);
+    l.bytes = l.sf + up(Q * l.sfq * 8);
+    return l;
+}
+__host__ inline size_t ms_colscore_lds(int wmax) { return (size_t)(MS_TT + MS_TQ) * wmax * 16; }
+__host__ inline size_t ms_null_lds(int wmax, int bins) {
+    return (size_t)(2 * (wmax * bins + 1) + MS_HPAD + MS_THREADS) * 8;
+}
+
+// a centred column as a unit vector; the norm in fp64, zero below the variance floor
+__device__ __forceinline__ float4 ms_unit(const float4 d) {
+    const double x = d.x, y = d.y, z = d.z, w = d.w;
+    const double n = ((x * x + y * y) + z * z) + w * w;
+    if (n < (double)EXPLAINN_MOTIF_VAR_FLOOR) return make_float4(0.f, 0.f, 0.f, 0.f);
+    const double r = 1.0 / sqrt(n);
+    return make_float4((float)(x * r), (float)(y * r), (float)(z * r), (float)(w * r));
+}
+
+// the quantised correlation of two unit columns: every operation named, so no contraction can differ
+__device__ __forceinline__ int ms_bin(const float4 q, const float4 t, float half_bins, int bins) {
+    const float c = fmaf(q.w, t.w, fmaf(q.z, t.z, fmaf(q.y, t.y, __fmul_rn(q.x, t.x))));
+    const float x = floorf(fmaf(__fadd_rn(c, 1.0f), half_bins, 0.5f));
+    return min(max((int)x, 0), bins);
+}
+
+__global__ __launch_bounds__(MS_THREADS) void motif_colscore_kernel(
+    const float4* __restrict__ Dq, const int32_t* __restrict__ Wq, int Q, const float4* __restrict__ Dt,
+    const int32_t* __restrict__ Wt, int T, int wmax, int ntt, int both, int bins, uint8_t* __restrict__ cs,
+    int64_t ld) {
+    extern __shared__ float4 ms_sm[];
+    float4* tU = ms_sm;                     // [wmax][64]   column j of target r at j*64 + r
+    float4* qU = tU + wmax * MS_TT;         // [TQ][wmax]
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int t0 = (blockIdx.x % ntt) * MS_TT, q0 = (blockIdx.x / ntt) * MS_TQ;
+    const int Tp = ms_tp(T);
+    for (int idx = tid; idx < wmax * MS_TT; idx += MS_THREADS) {
+        const int r = idx & 63, j = idx >> 6, t = t0 + r;
+        tU[idx] = t < T ? ms_unit(Dt[(size_t)t * 2 * wmax + j]) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    for (int idx = tid; idx < MS_TQ * wmax; idx += MS_THREADS) {
+        const int q = q0 + idx / wmax;
+        qU[idx] = q < Q ? ms_unit(Dq[(size_t)q * 2 * wmax + idx % wmax]) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    __syncthreads();
+    const int t = t0 + lane;
+    const int wt = t < T ? Wt[t] : 0;
+    const bool stored = t < Tp;             // the padding lanes of a row carry MS_NONE, lanes past it nothing
+    const float half_bins = 0.5f * (float)bins;
+    for (int qi = wave; qi < MS_TQ; qi += MS_WAVES) {
+        const int q = q0 + qi;
+        if (q >= Q) break;
+        const int wq = __builtin_amdgcn_readfirstlane(Wq[q]);
+        for (int i = 0; i < wq; ++i) {
+            const float4 qv = qU[qi * wmax + i];
+            uint8_t* row = cs + ((size_t)q * wmax + i) * ld + t;
+            for (int j = 0; j < wmax; ++j) {
+                int b0 = EXPLAINN_MOTIF_NO_SCORE, b1 = EXPLAINN_MOTIF_NO_SCORE;
+                if (j < wt) {
+                    b0 = ms_bin(qv, tU[j * MS_TT + lane], half_bins, bins);
+                    if (both) {
+                        const float4 r = tU[(wt - 1 - j) * MS_TT + lane];
+                        b1 = ms_bin(qv, make_float4(r.w, r.z, r.y, r.x), half_bins, bins);
+                    }
+                }
+                if (stored) {
+                    row[(size_t)j * Tp] = (uint8_t)b0;
+                    if (both) row[(size_t)(wmax + j) * Tp] = (uint8_t)b1;
+                }
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(MS_THREADS) void motif_hist_kernel(const uint8_t* __restrict__ cs, int64_t ld,
+                                                                const int32_t* __restrict__ Wq, int wmax, int bins,
+                                                                int32_t* __restrict__ hist,
+                                                                int32_t* __restrict__ hist_out) {
+    __shared__ int h[MS_WAVES][MS_HPAD];
+    const int tid = threadIdx.x, wave = tid >> 6;
+    const int row = blockIdx.x, q = row / wmax, i = row - q * wmax;
+    const int nb = bins + 1;
+    for (int b = tid; b < MS_WAVES * MS_HPAD; b += MS_THREADS) (&h[0][0])[b] = 0;
+    __syncthreads();
+    if (i < Wq[q]) {                        // uniform over the workgroup
+        const uint4* p = reinterpret_cast<const uint4*>(cs + (size_t)row * ld);   // ld is a multiple of 16
+        const int64_t n16 = ld / 16;
+        for (int64_t k = tid; k < n16; k += MS_THREADS) {
+            const uint4 v = p[k];
+            const unsigned int w4[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int m = 0; m < 4; ++m) {
+                    const int b = (w4[a] >> (8 * m)) & 255;
+                    if (b <= bins) atomicAdd(&h[wave][b], 1);
+                }
+        }
+    }
+    __syncthreads();
+    for (int b = tid; b < nb; b += MS_THREADS) {
+        const int total = (h[0][b] + h[1][b]) + (h[2][b] + h[3][b]);
+        hist[(size_t)row * nb + b] = total;
+        if (hist_out) hist_out[(size_t)row * nb + b] = total;
+    }
+}
+
+__global__ __launch_bounds__(MS_THREADS) void motif_null_kernel(const int32_t* __restrict__ hist,
+                                                                const int32_t* __restrict__ Wq, int wmax, int bins,
+                                                                double* __restrict__ sf, int64_t sfq) {
+    extern __shared__ double ms_dm[];
+    const int L = wmax * bins + 1;
+    double* cur = ms_dm;                    // the pmf of the current width
+    double* nxt = cur + L;                  // the next one; between convolutions the suffix sums on their way out
+    double* hd = nxt + L;                   // [MS_HPAD] the null of the column being added
+    double* part = hd + MS_HPAD;            // [MS_THREADS]
+    const int tid = threadIdx.x;
+    const int q = blockIdx.x / wmax, lo = blockIdx.x - q * wmax;
+    const int wq = Wq[q];
+    if (lo >= wq) return;                   // uniform over the workgroup
+    const int nb = bins + 1;
+    const int32_t* hrow = hist + ((size_t)q * wmax + lo) * nb;
+    int64_t cnt = 0;                        // N: every row of the query's histogram sums to it
+    for (int b = 0; b < nb; ++b) cnt += hrow[b];
+    if (cnt == 0) return;                   // an empty database: nothing is looked up
+    const double N = (double)cnt;
+    for (int b = tid; b < nb; b += MS_THREADS) cur[b] = (double)hrow[b] / N;
+    __syncthreads();
+    double* out = sf + (size_t)q * sfq;
+    for (int w = 1;; ++w) {
+        const int n = w * bins + 1;
+        {   // suffix sums of cur[0..n) into nxt, then out
+            const int seg = (n + MS_THREADS - 1) / MS_THREADS;
+            const int a = min(n, tid * seg), e = min(n, a + seg);
+            double local = 0.0;
+            for (int s = e - 1; s >= a; --s) local += cur[s];
+            part[tid] = local;
+            __syncthreads();
+            double run = 0.0;
+            for (int k = MS_THREADS - 1; k > tid; --k) run += part[k];
+            for (int s = e - 1; s >= a; --s) {
+                run += cur[s];
+                nxt[s] = fmin(run, 1.0);
+            }
+            __syncthreads();
+            double* dst = out + ms_sf_off(lo, w, wmax, bins);
+            for (int s = tid; s < n; s += MS_THREADS) dst[s] = nxt[s];
+        }
+        if (lo + w >= wq) break;
+        const int32_t* hnext = hist + ((size_t)q * wmax + lo + w) * nb;
+        for (int b = tid; b < nb; b += MS_THREADS) hd[b] = (double)hnext[b] / N;
+        __syncthreads();                    // hd is complete, nxt has been copied out
+        const int n2 = n + bins;
+        for (int s = tid; s < n2; s += MS_THREADS) {
+            double acc = 0.0;
+            for (int b = 0; b < nb; ++b) {
+                const double hb = hd[b];
+                if (hb == 0.0) continue;    // uniform: an empty bin adds an exact zero
+                const int k = s - b;
+                if (k >= 0 && k < n) acc = fma(cur[k], hb, acc);
+            }
+            nxt[s] = acc;
+        }
+        __syncthreads();
+        double* swap = cur; cur = nxt; nxt = swap;
+    }
+}
+
+__global__ __launch_bounds__(MS_THREADS) void motif_pvalue_kernel(
+    const uint8_t* __restrict__ cs, int64_t ld, const double* __restrict__ sf, int64_t sfq,
+    const int32_t* __restrict__ Wq, int Q, const int32_t* __restrict__ Wt, int T, int wmax, int ntt, int min_overlap,
+    int S, int bins, double* __restrict__ pvalue, int16_t* __restrict__ align, int32_t* __restrict__ score) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int t = (blockIdx.x % ntt) * MS_TT + lane;
+    const int q = (blockIdx.x / ntt) * MS_WAVES + wave;
+    if (q >= Q || t >= T) return;
+    const int Tp = ms_tp(T);
+    const int wq = __builtin_amdgcn_readfirstlane(Wq[q]);
+    const int wt = Wt[t];
+    double best = 2.0;
+    int bo = 0, bs = 0, bw = 0, bsum = 0, n_align = 0;
+    if (wq > 0 && wt > 0) {
+        const int need = max(1, min(min_overlap, min(wq, wt)));
+        const uint8_t* base = cs + (size_t)q * wmax * ld + t;
+        const double* tab = sf + (size_t)q * sfq;
+        for (int s = 0; s < S; ++s)
+            for (int o = -(wq - 1); o < wt; ++o) {
+                const int lo = max(0, -o), hi = min(wq, wt - o), w = hi - lo;
+                if (w < need) continue;
+                const uint8_t* p = base + (size_t)lo * ld + (size_t)(s * wmax + lo + o) * Tp;
+                int sum = 0;
+                for (int i = lo; i < hi; ++i, p += ld + Tp) sum += *p;
+                const double pa = tab[ms_sf_off(lo, w, wmax, bins) + sum];
+                ++n_align;
+                if (pa < best) { best = pa; bo = o; bs = s; bw = w; bsum = sum; }
+            }
+    }
+    const size_t at = (size_t)q * T + t;
+    pvalue[at] = (n_align == 0 || best >= 1.0) ? 1.0 : -expm1((double)n_align * log1p(-best));
+    if (align) {
+        align[at * 3] = (int16_t)bo;
+        align[at * 3 + 1] = (int16_t)bs;
+        align[at * 3 + 2] = (int16_t)bw;
+    }
+    if (score) score[at] = bsum;
+}
+
+__global__ __launch_bounds__(MS_THREADS) void motif_colscore_copy_kernel(const uint8_t* __restrict__ cs, int64_t ld,
+                                                                         const int32_t* __restrict__ Wq, int T,
+                                                                         int wmax, int S, int64_t total,
+                                                                         uint8_t* __restrict__ out) {
+    const int Tp = ms_tp(T);
+    const int64_t cols = (int64_t)S * wmax * T;
+    for (int64_t idx = (int64_t)blockIdx.x * MS_THREADS + threadIdx.x; idx < total;
+         idx += (int64_t)gridDim.x * MS_THREADS) {
+        const int64_t row = idx / cols, c = idx - row * cols;
+        const int64_t sj = c / T, t = c - sj * T;
+        const int q = (int)(row / wmax), i = (int)(row - (int64_t)q * wmax);
+        out[idx] = i < Wq[q] ? cs[row * ld + sj * Tp + t] : (uint8_t)EXPLAINN_MOTIF_NO_SCORE;
+    }
+}
+
+}  // namespace
+
+extern "C" int64_t explainn_motif_significance_workspace_bytes(int Q, int T, int wmax, int bins, int both_strands) {
+    if (Q < 0 || T < 0 || wmax < 1 || wmax > EXPLAINN_MOTIF_MAX_WIDTH || bins < 2 || bins > EXPLAINN_MOTIF_MAX_BINS)
+        return 0;
+    return ms_workspace(Q, (int64_t)Q + T, T, wmax, bins, both_strands ? 2 : 1).bytes;
+}
+
+extern "C" int explainn_motif_significance(const float* q, const int32_t* q_widths, int Q, const float* t,
+                                           const int32_t* t_widths, int T, int wmax, float pseudocount,
+                                           int min_overlap, int both_strands, int bins, double* pvalue,
+                                           int16_t* align, int32_t* score, uint8_t* colscore, int32_t* hist,
+                                           void* workspace, int64_t workspace_bytes, void* stream) {
+    if (Q < 0 || T < 0 || wmax < 1 || min_overlap < 1 || !(pseudocount >= 0.f) || bins < 2 ||
+        bins > EXPLAINN_MOTIF_MAX_BINS) {
+        explainn_set_error("motif_significance: need Q, T >= 0, wmax >= 1, min_overlap >= 1, pseudocount >= 0, "
+                           "2 <= bins <= %d (Q=%d T=%d wmax=%d min_overlap=%d pseudocount=%g bins=%d)",
+                           EXPLAINN_MOTIF_MAX_BINS, Q, T, wmax, min_overlap, (double)pseudocount, bins);
+        return EXPLAINN_E_ARG;
+    }
+    if (wmax > EXPLAINN_MOTIF_MAX_WIDTH) {
+        explainn_set_error("motif_significance: wmax %d exceeds %d columns", wmax, EXPLAINN_MOTIF_MAX_WIDTH);
+        return EXPLAINN_E_UNSUPPORTED;
+    }
+    if (!t && T != Q) {
+        explainn_set_error("motif_significance: t == NULL takes the queries as the database, T must equal Q (%d, %d)",
+                           T, Q);
+        return EXPLAINN_E_ARG;
+    }
+    if (Q == 0 || T == 0) return EXPLAINN_OK;
+    if (!q || !q_widths || !pvalue || (t && !t_widths)) {
+        explainn_set_error("motif_significance: q, q_widths, pvalue (and t_widths with t) must be device pointers");
+        return EXPLAINN_E_ARG;
+    }
+    const int S = both_strands ? 2 : 1;
+    const int64_t M = (int64_t)Q + (t ? T : 0);
+    const mc_layout pl = mc_workspace(M, wmax);
+    const ms_layout l = ms_workspace(Q, M, T, wmax, bins, S);
+    if (!workspace || ((uintptr_t)workspace & 15u) || workspace_bytes < l.bytes) {
+        explainn_set_error("motif_significance: workspace of %lld bytes, 16-byte aligned, needed (%lld given)",
+                           (long long)l.bytes, (long long)workspace_bytes);
+        return EXPLAINN_E_ARG;
+    }
+    const int64_t ntt = ((int64_t)T + MS_TT - 1) / MS_TT, ntq = ((int64_t)Q + MS_TQ - 1) / MS_TQ;
+    const int64_t ntw = ((int64_t)Q + MS_WAVES - 1) / MS_WAVES;
+    if (ntt * ntq > 0x7fffffffLL || ntt * ntw > 0x7fffffffLL || (int64_t)Q * wmax > 0x7fffffffLL) {
+        explainn_set_error("motif_significance: %d x %d pairs exceed one launch; split the queries", Q, T);
+        return EXPLAINN_E_UNSUPPORTED;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(workspace);
+    float4* D = reinterpret_cast<float4*>(ws + pl.d);
+    double* P = reinterpret_cast<double*>(ws + pl.p);
+    int32_t* W = reinterpret_cast<int32_t*>(ws + pl.w);
+    uint8_t* cs = reinterpret_cast<uint8_t*>(ws + l.cs);
+    int32_t* hs = reinterpret_cast<int32_t*>(ws + l.hist);
+    double* sf = reinterpret_cast<double*>(ws + l.sf);
+    hipLaunchKernelGGL(motif_prep_kernel, dim3((unsigned)((Q + 63) / 64)), dim3(64), 0, s, q, q_widths, Q, wmax,
+                       pseudocount, D, P, W);
+    LAUNCH_CHECK();
+    const float4* Dt = D;
+    const int32_t* Wt = W;
+    if (t) {
+        Dt = D + (size_t)Q * 2 * wmax;
+        Wt = W + Q;
+        hipLaunchKernelGGL(motif_prep_kernel, dim3((unsigned)((T + 63) / 64)), dim3(64), 0, s, t, t_widths, T, wmax,
+                           pseudocount, const_cast<float4*>(Dt), P + (size_t)Q * 2 * (wmax + 1),
+                           const_cast<int32_t*>(Wt));
+        LAUNCH_CHECK();
+    }
+    const size_t lds1 = ms_colscore_lds(wmax), lds3 = ms_null_lds(wmax, bins);
+    if (lds1 > 48 * 1024)
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&motif_colscore_kernel),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)ms_colscore_lds(EXPLAINN_MOTIF_MAX_WIDTH)));
+    if (lds3 > 48 * 1024)
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&motif_null_kernel),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)ms_null_lds(EXPLAINN_MOTIF_MAX_WIDTH, EXPLAINN_MOTIF_MAX_BINS)));
+    hipLaunchKernelGGL(motif_colscore_kernel, dim3((unsigned)(ntt * ntq)), dim3(MS_THREADS), lds1, s, D, W, Q, Dt, Wt,
+                       T, wmax, (int)ntt, both_strands != 0, bins, cs, l.ld);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(motif_hist_kernel, dim3((unsigned)(Q * wmax)), dim3(MS_THREADS), 0, s, cs, l.ld, W, wmax, bins,
+                       hs, hist);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(motif_null_kernel, dim3((unsigned)(Q * wmax)), dim3(MS_THREADS), lds3, s, hs, W, wmax, bins, sf,
+                       l.sfq);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(motif_pvalue_kernel, dim3((unsigned)(ntt * ntw)), dim3(MS_THREADS), 0, s, cs, l.ld, sf, l.sfq, W,
+                       Q, Wt, T, wmax, (int)ntt, min_overlap, S, bins, pvalue, align, score);
+    LAUNCH_CHECK();
+    if (colscore) {
+        const int64_t total = (int64_t)Q * wmax * S * wmax * T;
+        const int64_t blocks = (total + MS_THREADS - 1) / MS_THREADS;
+        hipLaunchKernelGGL(motif_colscore_copy_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)),
+                           dim3(MS_THREADS), 0, s, cs, l.ld, W, T, wmax, S, total, colscore);
+        LAUNCH_CHECK();
+    }
     return EXPLAINN_OK;
 }

@@ -5,10 +5,13 @@ RSAT matrix-clustering).  Here the all-pairs comparison is one device call (csrc
 explainn_motif_compare): for every (query, target) the best ungapped alignment over offsets and both strands
 by width-normalised Pearson correlation -- RSAT's `cor` and `Ncor` ("Motif
 comparison") -- and annotation, single-linkage clustering and reproducibility across the members of a model
-bank are torch reductions over that matrix.  Tomtom's p/E/q-values are not computed; `write_meme` writes the
-filters in the format an external Tomtom reads.
+bank are torch reductions over that matrix.  `significance` adds what an annotation is usually read by: the
+p-value of every pair's best alignment under the null of Gupta et al. 2007 (Tomtom with incomplete scores and
+Pearson columns; explainn_motif_significance), E-values and Benjamini-Hochberg
+q-values over the targets of each query; `annotate(by="pvalue")` ranks and filters by them.  `write_meme`
+writes the filters in the format an external Tomtom reads.
 
-  python -m explainn_amd.motifs annotate MOTIFS DB -o OUT.tsv
+  python -m explainn_amd.motifs annotate MOTIFS DB -o OUT.tsv [--by pvalue [--max-qvalue Q] [--bins B]]
   python -m explainn_amd.motifs cluster MOTIFS [MOTIFS ...] -o OUT.tsv
 MOTIFS / DB: a MEME file, a JASPAR file (the layout interpret.format_jaspar writes, any number of motifs),
 or a directory of filter*.jaspar.
@@ -23,7 +26,10 @@ import numpy as np
 
 MAX_WIDTH = 64
 
+MAX_BINS = 128
+
 MotifComparison = collections.namedtuple("MotifComparison", "ncor cor offset strand overlap")
+MotifSignificance = collections.namedtuple("MotifSignificance", "pvalue evalue qvalue offset strand overlap score")
 
 
 # ---------------------------------------------------------------- files
@@ -201,6 +207,38 @@ def _pad(x, wmax):
     return out
 
 
+def _device_for(device, sets, what):
+    """The device of a call: the one asked for, else that of the first device tensor among the sets, else the
+    current one.  There is no CPU path."""
+    import torch
+    if device is None:
+        for obj in sets:
+            first = obj[0] if isinstance(obj, (tuple, list)) and len(obj) else obj
+            if torch.is_tensor(first) and first.device.type == "cuda":
+                device = first.device
+                break
+    if device is None:
+        if not torch.cuda.is_available():
+            raise RuntimeError("motifs.%s runs only on a HIP device (there is no CPU fallback)" % what)
+        device = torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("motifs.%s runs only on a HIP device (there is no CPU fallback)" % what)
+    return device
+
+
+def _padded_sets(queries, targets, device):
+    """Both sets on the device at one common wmax: (q, qw, t or None, tw or None, wmax)."""
+    q, qw = _as_set(queries, device)
+    t = tw = None
+    if targets is not None:
+        t, tw = _as_set(targets, device)
+    wmax = max(q.shape[1], t.shape[1] if t is not None else 1, 1)
+    if wmax > MAX_WIDTH:
+        raise ValueError("motifs wider than %d columns are not supported (got %d)" % (MAX_WIDTH, wmax))
+    return _pad(q, wmax), qw, (_pad(t, wmax) if t is not None else None), tw, wmax
+
+
 def compare(queries, targets=None, min_overlap=5, pseudocount=0.0, both_strands=True, device=None):
     """The best alignment of every query with every target (targets=None: the queries with themselves).
 
@@ -218,29 +256,8 @@ def compare(queries, targets=None, min_overlap=5, pseudocount=0.0, both_strands=
         raise ValueError("min_overlap must be at least 1")
     if not float(pseudocount) >= 0:
         raise ValueError("pseudocount must not be negative")
-    if device is None:
-        for obj in (queries, targets):
-            first = obj[0] if isinstance(obj, (tuple, list)) and len(obj) else obj
-            if torch.is_tensor(first) and first.device.type == "cuda":
-                device = first.device
-                break
-    if device is None:
-        if not torch.cuda.is_available():
-            raise RuntimeError("motifs.compare runs only on a HIP device (there is no CPU fallback)")
-        device = torch.device("cuda", torch.cuda.current_device())
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError("motifs.compare runs only on a HIP device (there is no CPU fallback)")
-    q, qw = _as_set(queries, device)
-    t = tw = None
-    if targets is not None:
-        t, tw = _as_set(targets, device)
-    wmax = max(q.shape[1], t.shape[1] if t is not None else 1, 1)
-    if wmax > MAX_WIDTH:
-        raise ValueError("motifs wider than %d columns are not supported (got %d)" % (MAX_WIDTH, wmax))
-    q = _pad(q, wmax)
-    if t is not None:
-        t = _pad(t, wmax)
+    device = _device_for(device, (queries, targets), "compare")
+    q, qw, t, tw, wmax = _padded_sets(queries, targets, device)
     Q, T = len(q), len(t) if t is not None else len(q)
     ncor = torch.empty((Q, T), dtype=torch.float32, device=device)      # every entry is overwritten
     cor = torch.empty((Q, T), dtype=torch.float32, device=device)
@@ -258,17 +275,128 @@ def compare(queries, targets=None, min_overlap=5, pseudocount=0.0, both_strands=
     return MotifComparison(ncor, cor, align[..., 0], align[..., 1], align[..., 2])
 
 
+def benjamini_hochberg(pvalue):
+    """(Q,T) p-values -> (Q,T) q-values, Benjamini-Hochberg over the T entries of each row:
+    q_(k) = min_{j>=k} min(1, p_(j) T / j) with p sorted ascending (stable).  Plain torch, on the tensor's own
+    device (host tensors too)."""
+    import torch
+    p = torch.as_tensor(pvalue)
+    if p.dim() != 2:
+        raise ValueError("benjamini_hochberg takes a (Q, T) matrix of p-values")
+    T = p.shape[1]
+    if T == 0 or p.shape[0] == 0:
+        return p.clone()
+    ps, order = torch.sort(p, dim=1, stable=True)
+    rank = torch.arange(1, T + 1, dtype=p.dtype, device=p.device)
+    adj = torch.clamp(ps * T / rank, max=1.0)
+    adj = torch.flip(torch.cummin(torch.flip(adj, [1]), dim=1).values, [1])      # the minimum from the right
+    return torch.empty_like(p).scatter_(1, order, adj)
+
+
+def _significance_args(min_overlap, pseudocount, bins, workspace_bytes):
+    if int(min_overlap) < 1:
+        raise ValueError("min_overlap must be at least 1")
+    if not float(pseudocount) >= 0:
+        raise ValueError("pseudocount must not be negative")
+    if int(bins) != bins or not 2 <= int(bins) <= MAX_BINS:
+        raise ValueError("bins must be an integer in [2, %d] (got %r)" % (MAX_BINS, bins))
+    if int(workspace_bytes) < 1:
+        raise ValueError("workspace_bytes must be positive")
+
+
+def _query_chunk(lib, Q, T, wmax, bins, both, budget):
+    """The largest number of queries whose workspace fits `budget` bytes (at least 1)."""
+    size = lambda n: int(lib.explainn_motif_significance_workspace_bytes(n, T, wmax, bins, both))
+    if size(Q) <= budget:
+        return Q
+    lo, hi = 1, Q
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        lo, hi = (mid, hi) if size(mid) <= budget else (lo, mid - 1)
+    return lo
+
+
+def significance(queries, targets=None, min_overlap=5, pseudocount=0.0, both_strands=True, bins=100, device=None,
+                 workspace_bytes=512 << 20):
+    """The p-value of every query's best alignment with every target, and E- and q-values over the targets.
+
+    The statistic of Gupta et al. 2007 -- Tomtom run with -incomplete-scores and Pearson columns: the score of
+    an alignment is the sum over its overlap of the Pearson correlation of the aligned columns, quantised to
+    `bins` steps; its null is what the same query columns score against columns drawn from the database (every
+    column of every target, and of its reverse complement when both_strands; targets=None: the queries are the
+    database, a query being part of its own null); the pair's p-value is that of its smallest alignment
+    p-value after the Sidak step over the admissible alignments of the pair.  Two choices differ from the MEME
+    program: the score range is fixed at [-1,1] and not rescaled to the observed range of each query (one pass,
+    and the result is a function of the pair and the database alone), and both strands are counted in the
+    Sidak exponent.  Tomtom's default complete-scores mode and its other column functions are not offered.
+
+    Sets as for `compare`; strands, offsets, overlap and admissibility as there.  Every column inside a
+    motif's width is a column of the database, also one without counts (a uniform column): a motif that is
+    to stay out of the null has width 0.  Returns a MotifSignificance
+    of device tensors (Q,T): pvalue, evalue (pvalue T), qvalue (Benjamini-Hochberg over the targets of each
+    query), float64; offset, strand, overlap (int16, the alignment of the p-value) and score (int32, its
+    quantised sum).  Everything after the quantisation is fp64; a p-value below the fp64 range is 0.
+    workspace_bytes: the budget of device scratch; the queries are split into as many calls as it takes (one
+    query per call when even that exceeds it) and the result does not depend on the split.  Enqueued on the
+    current stream; no host synchronisation."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib
+    _significance_args(min_overlap, pseudocount, bins, workspace_bytes)
+    device = _device_for(device, (queries, targets), "significance")
+    q, qw, t, tw, wmax = _padded_sets(queries, targets, device)
+    Q, T = len(q), len(t) if t is not None else len(q)
+    both, bins = int(bool(both_strands)), int(bins)
+    pvalue = torch.empty((Q, T), dtype=torch.float64, device=device)      # every entry is overwritten
+    align = torch.empty((Q, T, 3), dtype=torch.int16, device=device)
+    score = torch.empty((Q, T), dtype=torch.int32, device=device)
+    if Q and T:
+        lib = _lib.load()
+        step = _query_chunk(lib, Q, T, wmax, bins, both, int(workspace_bytes))
+        if step < Q and t is None:                                       # the database is all of the queries
+            t, tw = q, qw
+        nbytes = int(lib.explainn_motif_significance_workspace_bytes(step, T, wmax, bins, both))
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=device)
+        with torch.cuda.device(device):
+            stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            for a in range(0, Q, step):
+                n = min(step, Q - a)
+                _lib.check(lib.explainn_motif_significance(
+                    q[a:a + n].data_ptr(), qw[a:a + n].data_ptr(), n, t.data_ptr() if t is not None else None,
+                    tw.data_ptr() if t is not None else None, T, wmax, float(pseudocount), int(min_overlap), both,
+                    bins, pvalue[a:a + n].data_ptr(), align[a:a + n].data_ptr(), score[a:a + n].data_ptr(), None,
+                    None, ws.data_ptr(), nbytes, stream))
+    return MotifSignificance(pvalue, pvalue * T, benjamini_hochberg(pvalue), align[..., 0], align[..., 1],
+                             align[..., 2], score)
+
+
 # ---------------------------------------------------------------- reductions over the comparison
 def _passing(result, min_ncor, min_cor):
     return (result.ncor >= min_ncor) & (result.cor >= min_cor)
 
 
-def annotate(queries, database=None, top=3, min_ncor=0.4, min_cor=0.6, **compare_args):
+def annotate(queries, database=None, top=3, min_ncor=0.4, min_cor=0.6, by="ncor", max_qvalue=0.05, **compare_args):
     """For each query up to `top` targets with Ncor >= min_ncor and cor >= min_cor, best Ncor first, ties to
     the lower target index: a list (one entry per query) of lists of dicts(target, ncor, cor, offset, strand,
     overlap).  `queries` may be a MotifComparison already computed (then `database` is not read).  The
-    thresholds default to the lower bounds RSAT matrix-clustering is usually run with."""
+    thresholds default to the lower bounds RSAT matrix-clustering is usually run with.
+
+    by="pvalue": up to `top` targets with qvalue <= max_qvalue instead, smallest p-value first, ties to the
+    lower target index; each hit also holds pvalue, evalue, qvalue and score, and its offset, strand and
+    overlap are those of the p-value's alignment (ncor and cor stay the pair's best by Ncor, which may be
+    another alignment; min_ncor and min_cor are not applied).  `queries` may be a MotifSignificance already
+    computed; the hits then hold no ncor and cor.  Further arguments go to `compare` (and `significance`)."""
     import torch
+    if by not in ("ncor", "pvalue"):
+        raise ValueError("by must be 'ncor' or 'pvalue' (got %r)" % (by,))
+    if by == "pvalue":
+        if not 0 <= float(max_qvalue) <= 1:
+            raise ValueError("max_qvalue must lie in [0, 1]")
+        if isinstance(queries, MotifComparison):
+            raise ValueError("by='pvalue' needs the motif sets or a MotifSignificance, not a MotifComparison")
+        return _annotate_by_pvalue(queries, database, top, float(max_qvalue), compare_args)
     res = queries if isinstance(queries, MotifComparison) else compare(queries, database, **compare_args)
     Q, T = res.ncor.shape
     n = min(int(top), T)
@@ -282,6 +410,30 @@ def annotate(queries, database=None, top=3, min_ncor=0.4, min_cor=0.6, **compare
     cor, off, strand, ovl = pick(res.cor), pick(res.offset), pick(res.strand), pick(res.overlap)
     return [[dict(target=int(idxh[i, j]), ncor=float(val[i, j]), cor=float(cor[i, j]), offset=int(off[i, j]),
                   strand=int(strand[i, j]), overlap=int(ovl[i, j]))
+             for j in range(n) if np.isfinite(val[i, j])] for i in range(Q)]
+
+
+def _annotate_by_pvalue(queries, database, top, max_qvalue, args):
+    import torch
+    if isinstance(queries, MotifSignificance):
+        sig, res = queries, None
+    else:
+        sig = significance(queries, database, **args)
+        res = compare(queries, database, **{k: v for k, v in args.items() if k not in ("bins", "workspace_bytes")})
+    Q, T = sig.pvalue.shape
+    n = min(int(top), T)
+    if n < 1 or Q == 0:
+        return [[] for _ in range(Q)]
+    key = torch.where(sig.qvalue <= max_qvalue, sig.pvalue, torch.full_like(sig.pvalue, float("inf")))
+    val, idx = torch.sort(key, dim=1, stable=True)
+    val, idx = val[:, :n], idx[:, :n]
+    pick = lambda a: torch.gather(a, 1, idx).cpu().numpy()
+    val, idxh = val.cpu().numpy(), idx.cpu().numpy()
+    cols = {k: pick(getattr(sig, k)) for k in ("pvalue", "evalue", "qvalue", "offset", "strand", "overlap", "score")}
+    if res is not None:
+        cols.update(ncor=pick(res.ncor), cor=pick(res.cor))
+    kind = dict(pvalue=float, evalue=float, qvalue=float, ncor=float, cor=float)
+    return [[dict([("target", int(idxh[i, j]))] + [(k, kind.get(k, int)(v[i, j])) for k, v in cols.items()])
              for j in range(n) if np.isfinite(val[i, j])] for i in range(Q)]
 
 
@@ -352,15 +504,21 @@ def reproducibility(pfms, nsites=None, min_ncor=0.4, min_cor=0.6, result=None, *
 # ---------------------------------------------------------------- command line
 def _cli_annotate(a):
     queries, db = read_motifs(a.motifs), read_motifs(a.db)
+    by_p = a.by == "pvalue"
+    more = dict(by="pvalue", max_qvalue=a.max_qvalue, bins=a.bins) if by_p else {}
     hits = annotate(queries, db, top=a.top, min_ncor=a.min_ncor, min_cor=a.min_cor, min_overlap=a.min_overlap,
-                    pseudocount=a.pseudocount)
+                    pseudocount=a.pseudocount, **more)
     with open(a.output, "wt") as fh:
-        fh.write("Query\tTarget\tTargetName\tNcor\tCor\tOffset\tStrand\tOverlap\n")
+        fh.write("Query\tTarget\tTargetName\tNcor\tCor\tOffset\tStrand\tOverlap%s\n"
+                 % ("\tPvalue\tEvalue\tQvalue" if by_p else ""))
         for (qid, _, _), rows in zip(queries, hits):
             for h in rows:
                 tid, tname, _ = db[h["target"]]
-                fh.write("%s\t%s\t%s\t%.4f\t%.4f\t%d\t%s\t%d\n" % (qid, tid, tname, h["ncor"], h["cor"], h["offset"],
-                                                                 "-" if h["strand"] else "+", h["overlap"]))
+                fh.write("%s\t%s\t%s\t%.4f\t%.4f\t%d\t%s\t%d" % (qid, tid, tname, h["ncor"], h["cor"], h["offset"],
+                                                               "-" if h["strand"] else "+", h["overlap"]))
+                if by_p:
+                    fh.write("\t%.3e\t%.3e\t%.3e" % (h["pvalue"], h["evalue"], h["qvalue"]))
+                fh.write("\n")
 
 
 def _cli_cluster(a):
@@ -377,7 +535,7 @@ def _cli_cluster(a):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m explainn_amd.motifs",
-                                 description="Annotate and cluster motifs by Ncor on the device")
+                                 description="Annotate and cluster motifs by Ncor or p-value on the device")
     sub = ap.add_subparsers(dest="command", required=True)
 
     def common(p):
@@ -391,6 +549,10 @@ def main(argv=None):
     p.add_argument("motifs")
     p.add_argument("db")
     p.add_argument("--top", type=int, default=3)
+    p.add_argument("--by", choices=("ncor", "pvalue"), default="ncor",
+                   help="rank by Ncor (thresholds --min-ncor, --min-cor) or by p-value (threshold --max-qvalue)")
+    p.add_argument("--max-qvalue", type=float, default=0.05)
+    p.add_argument("--bins", type=int, default=100)
     common(p)
     p.set_defaults(run=_cli_annotate)
     p = sub.add_parser("cluster", help="single-linkage clusters of one or more motif sets")

@@ -538,6 +538,40 @@ int explainn_motif_compare(const float* q, const int32_t* q_widths, int Q, const
                            int both_strands, float* ncor, float* cor, int16_t* align, void* workspace,
                            int64_t workspace_bytes, void* stream);
 
+/* Motif significance (csrc/motifs.hip): the p-value of the best alignment of
+ * every query with every target under the null of Gupta et al. 2007 (Tomtom with incomplete scores, column
+ * similarity Pearson).  Motif sets, pseudocount, strands, offsets, overlap and admissibility are those of
+ * explainn_motif_compare.  A column's unit vector is u = d / sqrt(n) (0 where n < EXPLAINN_MOTIF_VAR_FLOOR);
+ * the score of two columns is c = u_q.u_t in [-1,1], quantised to b = clamp(floor((c + 1) bins/2 + 0.5), 0,
+ * bins).  The database is every column of every target of width > 0, and of its reverse complement when
+ * both_strands; N columns.  h[q][i][b] is the share of database columns that score b against query column i;
+ * the null of the sum over query columns [lo, lo+w) is the convolution of their h, SF its upper tail
+ * (clamped to 1).  An alignment scores S = sum of b over its overlap and p_align = SF_{lo,w}(S).  The pair's
+ * alignment is the admissible one with the smallest p_align, ties to strand 0, then to the smaller offset;
+ * pvalue = 1 - (1 - p_align)^n_align over the n_align admissible alignments of the pair (both strands
+ * counted), computed as -expm1(n_align log1p(-p_align)).  A pair with a width of 0 gives pvalue 1 and zeros.
+ * The score range is fixed at [-1,1] (not rescaled per query as the MEME program does), everything after the
+ * quantisation is fp64, and a p-value below the fp64 range is reported as 0.
+ * pvalue: double (Q,T); align: int16 (Q,T,3) = offset, strand, overlap; score: int32 (Q,T) = S.  For checks
+ * of the stages: colscore: uint8 (Q,wmax,S,wmax,T), S = 2 with both_strands else 1 -- query column i of q
+ * against column j of the strand-s view of target t, EXPLAINN_MOTIF_NO_SCORE where either column does not
+ * exist (every entry is written); hist: int32 (Q,wmax,bins+1), the counts N h (zeros past a query's width).
+ * Outputs are OVERWRITTEN; align, score, colscore and hist may be NULL and are then not written.
+ * t == NULL takes the queries as the database (T must then equal Q).  workspace: device memory, 16-byte
+ * aligned, of explainn_motif_significance_workspace_bytes(Q,T,wmax,bins,both_strands) bytes (0 for arguments
+ * the call would refuse), dead after the call; it grows with Q, and the null depends on the targets alone,
+ * so a caller short of memory splits the queries and gets the same bits.  No context, no allocation, no host
+ * synchronisation; the same input gives the same bits on every call.  Errors as explainn_motif_compare's,
+ * and bins outside [2, EXPLAINN_MOTIF_MAX_BINS]: EXPLAINN_E_ARG.  Q == 0 or T == 0 launches nothing. */
+#define EXPLAINN_MOTIF_MAX_BINS 128
+#define EXPLAINN_MOTIF_NO_SCORE 255
+int64_t explainn_motif_significance_workspace_bytes(int Q, int T, int wmax, int bins, int both_strands);
+int explainn_motif_significance(const float* q, const int32_t* q_widths, int Q, const float* t,
+                                const int32_t* t_widths, int T, int wmax, float pseudocount, int min_overlap,
+                                int both_strands, int bins, double* pvalue, int16_t* align, int32_t* score,
+                                uint8_t* colscore, int32_t* hist, void* workspace, int64_t workspace_bytes,
+                                void* stream);
+
 /* One Adam step over n_tensors parameter tensors in a single launch -- torch.optim.Adam(params, lr)
  * with its defaults, the optimiser the reference builds (architectures/__init__.py:463-464) and
  * steps at selene/__init__.py:291.  params/grads/exp_avg/exp_avg_sq: HOST arrays of n_tensors

@@ -65,7 +65,9 @@ HAPLOTYPES = [r"^stage_haplotypes_kernel"]
 # dinucleotide-preserving shuffles (shuffle.hip): one lane per (row, shuffle), counters in LDS
 SHUFFLE = [r"^dinuc_shuffle_kernel"]
 # motif comparison (motifs.hip): the preparation and the all-pairs alignment search
-MOTIFS = [r"^motif_prep_kernel", r"^motif_compare_kernel"]
+MOTIFS = [r"^motif_prep_kernel", r"^motif_compare_kernel",
+          # motif significance: column scores, histograms, range nulls, alignment p-values
+          r"^motif_colscore_kernel", r"^motif_hist_kernel", r"^motif_null_kernel", r"^motif_pvalue_kernel"]
 GATED = C2_STEP + INPUT_GRAD + ISM + PATHGRAD + METRICS + SCAN + VARIANTS + HAPLOTYPES + SHUFFLE + MOTIFS
 
 
