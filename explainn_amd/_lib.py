@@ -22,6 +22,8 @@ MOTIF_MAX_WIDTH = 64      # EXPLAINN_MOTIF_MAX_WIDTH: columns per motif of expla
 MOTIF_MAX_BINS = 128      # EXPLAINN_MOTIF_MAX_BINS: score bins per column of explainn_motif_significance
 MOTIF_NO_SCORE = 255      # EXPLAINN_MOTIF_NO_SCORE: a colscore entry without a column
 SITES_TILE = 1024        # EXPLAINN_SITES_TILE: start positions per workgroup of explainn_call_sites
+ACT_BINS = 32768         # EXPLAINN_ACT_BINS: one bin per non-negative float16 bit pattern
+ACT_SPAN = 8192          # EXPLAINN_ACT_SPAN: start positions a workgroup of explainn_activation_histogram takes at a time
 
 _fp = C.c_void_p          # device pointers travel as integers (tensor.data_ptr())
 
@@ -139,6 +141,8 @@ SIGNATURES = {
     "explainn_call_sites_workspace_bytes": (_i64, [_ctx, _i64]),
     "explainn_call_sites": (_i, [_ctx, _fp, _i64, _i64, _i64, _i64, _i, _pp, _fp, _fp, _fp, _fp, _i64, _fp,
                                  _i64, _fp]),
+    "explainn_activation_histogram": (_i, [_ctx, _fp, _i64, _i64, _i64, _i64, _i, _pp, _fp, _fp]),
+    "explainn_activation_null": (_i, [_fp, _i, C.c_double, _fp, _fp, _fp, _fp]),
     "explainn_dense_input": (_i, [_ctx, _i]),
     "explainn_pwm_scan": (_i, [_fp, _i, _i, _fp, _i, _i, _i, _fp, _fp]),
     "explainn_dinucleotide_shuffle": (_i, [_fp, _i64, _i, _i, C.c_uint64, _i64, _i, _fp, _fp, _fp]),

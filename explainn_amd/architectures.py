@@ -848,6 +848,37 @@ class ExplaiNN(_Model):
                 capacity, ws.data_ptr(), nbytes, stream))
         return offsets, pos, score
 
+    def _launch_activation_histogram(self, codes, hist, start=0, n_positions=None, period=0,
+                                     reverse_complement=False):
+        """Adds, for every unit and every live start p in [start, start + n_positions) of a
+        device-resident 1-D uint8 sequence of base codes, one count to hist[unit][bit pattern of the
+        float16 activation] (explainn_activation_histogram).  hist: int64 (units, _lib.ACT_BINS) on the
+        device, added into.  Live as in _launch_call_sites: with a period, a start whose k-mer would
+        cross a record boundary is not counted.  n_positions None: every start the sequence holds.
+        Returns hist."""
+        if self.training:
+            raise NotImplementedError("the activation null is an eval-mode export path; call model.eval()")
+        dev = self._device()
+        k, U = self._options["kernel_size"], self._units()
+        if not torch.is_tensor(codes) or codes.dtype != torch.uint8 or codes.dim() != 1 or \
+                not codes.is_contiguous():
+            raise RuntimeError("activations are counted on a contiguous 1-D uint8 tensor of base codes")
+        if codes.device != dev:
+            raise RuntimeError("input is on %s but the model is on %s" % (codes.device, dev))
+        if not torch.is_tensor(hist) or tuple(hist.shape) != (U, _lib.ACT_BINS) or \
+                hist.dtype != torch.int64 or hist.device != dev or not hist.is_contiguous():
+            raise RuntimeError("hist must be a contiguous int64 tensor of shape (%d, %d) on %s"
+                               % (U, _lib.ACT_BINS, dev))
+        if n_positions is None:
+            n_positions = max(codes.numel() - int(start) - k + 1, 0)
+        with torch.cuda.device(dev):
+            win = SequenceWindows(codes, start, 1, 1, reverse_complement, 1)
+            ctx, ps, _, stream, xp, _ = self._front(win, dev)
+            _lib.check(ctx.lib.explainn_activation_histogram(
+                ctx.handle, xp, codes.numel(), int(start), int(n_positions), int(period),
+                int(bool(reverse_complement)), C.byref(ps), hist.data_ptr(), stream))
+        return hist
+
     def _launch_eval_keep(self, x):
         """Eval forward that keeps what _launch_input_grad needs (explainn_forward_eval_keep: the
         same logits as forward()).  The batch is validated first, so soft input takes the dense

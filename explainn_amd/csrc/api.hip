@@ -704,6 +704,28 @@ extern "C" int explainn_call_sites(explainn_ctx* c, const uint8_t* seq, int64_t 
                              offsets, pos, score, capacity, workspace, s);
 }
 
+extern "C" int explainn_activation_histogram(explainn_ctx* c, const uint8_t* seq, int64_t seq_len, int64_t start,
+                                             int64_t n_positions, int64_t period, int reverse_complement,
+                                             const explainn_params* p, uint64_t* hist, void* stream) {
+    if (!c) { explainn_set_error("null context"); return EXPLAINN_E_ARG; }
+    if (!seq || !p || !hist) { explainn_set_error("seq, params and hist are required"); return EXPLAINN_E_ARG; }
+    if (start < 0 || n_positions < 0 || n_positions + c->k >= (int64_t)1 << 31 ||
+        seq_len - start < n_positions + c->k - 1) {
+        explainn_set_error("activation_histogram needs 0 <= start, start + n_positions + k - 1 <= seq_len and "
+                           "n_positions + k < 2^31 (start %lld, n_positions %lld, k %d, seq_len %lld)",
+                           (long long)start, (long long)n_positions, c->k, (long long)seq_len);
+        return EXPLAINN_E_ARG;
+    }
+    if (period < 0) { explainn_set_error("period must not be negative"); return EXPLAINN_E_ARG; }
+    if (c->dense) { explainn_set_error("activations are counted on base codes: not in dense input mode"); return EXPLAINN_E_UNSUPPORTED; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    drop_pending(c);
+    c->staged_B = 0;                   // nothing is staged by this call; what was staged is not kept
+    TRY(eval_tables(c, p, 1, s));
+    if (n_positions == 0) return EXPLAINN_OK;
+    return launch_activation_histogram(c, seq, start, n_positions, period, reverse_complement ? 1 : 0, hist, s);
+}
+
 extern "C" int explainn_filter_act_max(explainn_ctx* c, const float* x, int B,
                                        const explainn_params* p, const uint8_t* select,
                                        float* unit_max, void* stream) {

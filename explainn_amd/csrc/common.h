@@ -251,6 +251,8 @@ int64_t sites_workspace_bytes(const explainn_ctx* c, int64_t npos);
 int launch_call_sites(explainn_ctx* c, const uint8_t* seq, int64_t start, int64_t npos, int64_t period,
                       int rc, const float* thr, int64_t* offsets, int32_t* pos, float* score,
                       int64_t capacity, void* workspace, hipStream_t s);
+int launch_activation_histogram(explainn_ctx* c, const uint8_t* seq, int64_t start, int64_t npos, int64_t period,
+                                int rc, uint64_t* hist, hipStream_t s);
 
 int launch_dense_moments(explainn_ctx* c, const float* x, int B, hipStream_t s);
 int launch_dense_conv_pool(explainn_ctx* c, const float* x, const explainn_params* p, int B, hipStream_t s);

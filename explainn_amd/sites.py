@@ -11,7 +11,16 @@ finds in float16(model.linears[:3](windows)), bit for bit, without the windows o
     start, strand, score = calls.unit(3)                # '+' sites ascending, then '-' sites ascending
 
 `python -m explainn_amd.sites MODEL FASTA -t thresholds.tsv` writes BED6; `thresholds.tsv` is what
-`python -m explainn_amd.interpret ... --sites` writes (0.5 x each filter's largest activation).
+`python -m explainn_amd.interpret ... --sites` writes (0.5 x each filter's largest activation) -- or,
+with an error rate behind it, what `python -m explainn_amd.calibrate` writes from an empirical null:
+
+    null = activation_null(model, background, shuffles=10)     # exact per-filter histogram of the activation
+    calls = call_sites(model, codes, null.thresholds(1e-4), null=null)
+    calls.pvalue                                        # (1 + null values >= score) / (1 + null size)
+
+The float16 activation is never negative, so its 32768 bit patterns sort like the values: the null is a
+32768-bin integer histogram per filter (explainn_activation_histogram, csrc/actnull.hip), and tails,
+thresholds and p-values are exact functions of integers.  `--null NULL.npz` adds the p-value column.
 """
 import argparse
 import contextlib
@@ -29,7 +38,7 @@ class SiteCalls:
     start of the k-mer on the forward strand), `strand` (int8, +1 / -1) and `score` (float32: the
     float16 activation).  Per unit: '+' sites in ascending start, then '-' sites in ascending start."""
 
-    def __init__(self, offsets, start, strand, score, kernel_size):
+    def __init__(self, offsets, start, strand, score, kernel_size, pvalue=None):
         self.offsets = np.asarray(offsets, dtype=np.int64)
         self.start = np.asarray(start, dtype=np.int64)
         self.strand = np.asarray(strand, dtype=np.int8)
@@ -39,6 +48,10 @@ class SiteCalls:
         if self.offsets.ndim != 1 or self.offsets[0] != 0 or np.any(np.diff(self.offsets) < 0) or \
                 not (len(self.start) == len(self.strand) == len(self.score) == n):
             raise ValueError("offsets must be an ascending scan from 0 that ends at the record count")
+        # float64 empirical p-value of every record against an ActivationNull; None without a null
+        self.pvalue = None if pvalue is None else np.asarray(pvalue, dtype=np.float64)
+        if self.pvalue is not None and self.pvalue.shape != (n,):
+            raise ValueError("pvalue must hold one value per record")
 
     @property
     def units(self):
@@ -107,7 +120,8 @@ def assemble(blocks, units, kernel_size):
     return SiteCalls(offsets, start[order], strand[order], score[order], kernel_size)
 
 
-def call_sites(model, codes, thresholds, strands="both", chunk_positions=None, max_sites=MAX_SITES, period=0):
+def call_sites(model, codes, thresholds, strands="both", chunk_positions=None, max_sites=MAX_SITES, period=0,
+               null=None):
     """Every site of every unit of `model` (an ExplaiNN, or an ExplaiNNBank: global unit indices) in
     `codes`: 1-D uint8 base codes (0..3 = A,C,G,T, 4 = N), numpy array or tensor, host or device.
 
@@ -118,9 +132,13 @@ def call_sites(model, codes, thresholds, strands="both", chunk_positions=None, m
     The sequence goes to the device in chunks of chunk_positions starts (default 2^24) that overlap by
     k - 1 bases; each chunk and strand takes a count call, one read of the total, and an emit call
     into a buffer of exactly that size.  The two strands run on the model and its eval_replica() on two
-    streams.  More than max_sites records raise ValueError.  Returns a SiteCalls."""
+    streams.  More than max_sites records raise ValueError.  null: an ActivationNull of this model; the
+    result then carries `pvalue`, the empirical p-value of every record.  Returns a SiteCalls."""
     _check_args(strands, chunk_positions, max_sites, period)
     k, units = model._options["kernel_size"], model._units()
+    if null is not None and (null.units, null.kernel_size) != (units, k):
+        raise ValueError("the null is of %d units of kernel size %d, the model of %d of %d" % (
+            null.units, null.kernel_size, units, k))
     data = codes if torch.is_tensor(codes) else torch.as_tensor(np.ascontiguousarray(codes))
     if data.dtype != torch.uint8 or data.dim() != 1:
         raise ValueError("codes must be a 1-D uint8 array of base codes")
@@ -181,7 +199,164 @@ def call_sites(model, codes, thresholds, strands="both", chunk_positions=None, m
             if both:
                 rep.check_input()
             model.check_input()
-    return assemble(blocks[1] + blocks[-1], units, k)
+    calls = assemble(blocks[1] + blocks[-1], units, k)
+    if null is not None:
+        calls.pvalue = null.pvalue(calls.unit_ids(), calls.score)
+    return calls
+
+
+ACT_BINS = 32768             # non-negative float16 bit patterns (EXPLAINN_ACT_BINS)
+ACT_INF = 0x7C00             # the pattern of +inf; the patterns above it are NaNs
+
+
+def _null_stats(hist, alpha, want_tail=False, want_thresholds=False):
+    """(tail, total, thresholds) of a device int64 (units, ACT_BINS) histogram (explainn_activation_null);
+    tail / thresholds None unless asked for."""
+    import ctypes as C
+
+    from . import _lib
+    units, dev = hist.shape[0], hist.device
+    total = torch.empty(units, device=dev, dtype=torch.int64)
+    tail = torch.empty_like(hist) if want_tail else None
+    thr = torch.empty(units, device=dev, dtype=torch.float32) if want_thresholds else None
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().explainn_activation_null(
+            hist.data_ptr(), units, float(alpha), tail.data_ptr() if want_tail else None, total.data_ptr(),
+            thr.data_ptr() if want_thresholds else None,
+            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return tail, total, thr
+
+
+class ActivationNull:
+    """The empirical null of a model's filter activations: `hist` int64 (units, 32768) on the device,
+    hist[u][b] = how many background k-mers gave unit u the float16 activation with bit pattern b;
+    `tail[u][b]` = how many gave at least that value; `total[u]` = how many there were.  Integers
+    throughout: thresholds and p-values are exact."""
+
+    def __init__(self, hist, kernel_size, strands="both", shuffles=0, seed=0):
+        if not torch.is_tensor(hist) or hist.dtype != torch.int64 or hist.dim() != 2 or \
+                hist.shape[1] != ACT_BINS or hist.device.type != "cuda":
+            raise ValueError("hist must be an int64 tensor of shape (units, %d) on a HIP device" % ACT_BINS)
+        self.hist = hist.contiguous()
+        self.kernel_size, self.strands, self.shuffles, self.seed = int(kernel_size), strands, int(shuffles), int(seed)
+        if bool(self.hist[:, ACT_INF + 1:].any()):
+            raise ValueError("the null holds NaN activations (bins above 0x7C00): the model's parameters are "
+                             "not finite")
+        self.tail, self.total, _ = _null_stats(self.hist, 0.0, want_tail=True)
+
+    @property
+    def units(self):
+        return self.hist.shape[0]
+
+    def thresholds(self, pvalue):
+        """(units,) float32: per unit the smallest float16 value t such that at most
+        floor(pvalue * total) of the null's activations are > t -- call_sites with it calls at most that
+        many of the background's positions; +inf for a unit without a null."""
+        if not 0.0 <= float(pvalue) <= 1.0:
+            raise ValueError("pvalue must be in [0, 1] (got %r)" % (pvalue,))
+        return _null_stats(self.hist, pvalue, want_thresholds=True)[2].cpu().numpy()
+
+    def pvalue(self, unit_ids, scores):
+        """float64 (n,): (1 + null activations of the unit >= float16(score)) / (1 + total): the add-one
+        empirical p-value, resolution 1 / (total + 1).  Gathered on the device; only the n values cross."""
+        unit = np.asarray(unit_ids, dtype=np.int64)
+        with np.errstate(over="ignore"):                  # a score past 65504 is +inf in float16
+            bits = (np.asarray(scores, dtype=np.float32).astype(np.float16).view(np.uint16).astype(np.int64)
+                    & (ACT_BINS - 1))
+        if unit.shape != bits.shape or unit.ndim != 1:
+            raise ValueError("unit_ids and scores must be 1-D and of one length")
+        if len(unit) == 0:
+            return np.zeros(0, dtype=np.float64)
+        if unit.min() < 0 or unit.max() >= self.units:
+            raise IndexError("unit ids outside [0, %d)" % self.units)
+        dev = self.hist.device
+        u = torch.from_numpy(unit).to(dev)
+        idx = u * ACT_BINS + torch.from_numpy(bits).to(dev)
+        tail = self.tail.view(-1)[idx].cpu().numpy()
+        total = self.total[u].cpu().numpy()
+        return (1.0 + tail.astype(np.float64)) / (1.0 + total.astype(np.float64))
+
+    def save(self, path):
+        """.npz of the non-zero (unit, bin, count) triples, the totals and how the null was drawn."""
+        nz = self.hist.nonzero()
+        with open(path, "wb") as fh:
+            np.savez(fh, unit=nz[:, 0].cpu().numpy().astype(np.int32), bin=nz[:, 1].cpu().numpy().astype(np.uint16),
+                     count=self.hist[nz[:, 0], nz[:, 1]].cpu().numpy(), total=self.total.cpu().numpy(),
+                     k=np.int64(self.kernel_size), units=np.int64(self.units), strands=np.str_(self.strands),
+                     shuffles=np.int64(self.shuffles), seed=np.int64(self.seed))
+
+    @classmethod
+    def load(cls, path, device="cuda"):
+        with np.load(path) as z:
+            hist = np.zeros((int(z["units"]), ACT_BINS), dtype=np.int64)
+            hist[z["unit"].astype(np.int64), z["bin"].astype(np.int64)] = z["count"]
+            if not np.array_equal(hist.sum(axis=1), z["total"]):
+                raise ValueError("%s: the counts do not add up to the stored totals" % path)
+            return cls(torch.from_numpy(hist).to(device), int(z["k"]), str(z["strands"]), int(z["shuffles"]),
+                       int(z["seed"]))
+
+
+def _count_activations(model, data, hist, period, shuffles, seed, both, chunk):
+    """Adds the activations of `data` (1-D uint8, host or device) -- or, with shuffles = R > 0, of R
+    dinucleotide shuffles of each of its records of `period` bases -- into hist, chunk by chunk."""
+    k = model._options["kernel_size"]
+    device = hist.device
+    strands = (False, True) if both else (False,)
+    if shuffles > 0:
+        from .sequence import dinucleotide_shuffle_device
+        rows = data.view(-1, period)
+        per = max(chunk // period, 1)
+        for r0 in range(0, rows.shape[0], per):
+            shuf = dinucleotide_shuffle_device(rows[r0:r0 + per].to(device), shuffles, seed, row0=r0).view(-1)
+            for rc in strands:
+                model._launch_activation_histogram(shuf, hist, 0, None, period, rc)
+        return
+    n_positions = max(int(data.shape[0]) - k + 1, 0)
+    for p0, cnt in position_chunks(n_positions, chunk, period):
+        piece = data[p0:p0 + cnt + k - 1].to(device).contiguous()
+        for rc in strands:
+            model._launch_activation_histogram(piece, hist, 0, cnt, period, rc)
+
+
+def _null_args(model, codes, period, shuffles, strands, chunk_positions):
+    """The checks of activation_null: returns (1-D uint8 tensor, period)."""
+    _check_args(strands, chunk_positions, 0, period)
+    data = codes if torch.is_tensor(codes) else torch.as_tensor(np.ascontiguousarray(codes))
+    if data.dtype != torch.uint8 or data.dim() not in (1, 2):
+        raise ValueError("codes must be a 1-D, or (N, L), uint8 array of base codes")
+    if data.dim() == 2:
+        if period not in (0, data.shape[1]):
+            raise ValueError("(N, L) codes mean period = L = %d (got period %d)" % (data.shape[1], period))
+        period = int(data.shape[1])
+        data = data.contiguous().view(-1)
+    if int(shuffles) < 0:
+        raise ValueError("shuffles must not be negative")
+    if shuffles > 0 and (period < 1 or data.shape[0] % period != 0):
+        raise ValueError("a shuffled background needs records: a period that divides the number of bases")
+    if model.training:
+        raise NotImplementedError("the activation null is an eval-mode export path; call model.eval()")
+    return data.contiguous(), int(period)
+
+
+def activation_null(model, codes, period=0, shuffles=0, seed=0, strands="both", chunk_positions=None):
+    """The empirical null of every unit of `model` (an ExplaiNN or an ExplaiNNBank) over a background:
+    the exact histogram of the float16 activation call_sites thresholds, at every live start of `codes`
+    (1-D uint8 with `period` as in call_sites, or (N, L): period = L), both strands counted into one
+    histogram unless strands="fwd".  shuffles = R > 0 (needs a period): the background is R
+    dinucleotide-preserving shuffles of every record, drawn on the device chunk by chunk
+    (sequence.dinucleotide_shuffle_device with `seed` and the chunk's first row as row0 -- a pure
+    function of (seed, row, r), so the result does not depend on chunk_positions) instead of the
+    records themselves.  The codes go to the device in chunks as position_chunks cuts them (whole
+    records with a period).  Returns an ActivationNull."""
+    data, period = _null_args(model, codes, period, shuffles, strands, chunk_positions)
+    device = model._device()
+    hist = torch.zeros(model._units(), ACT_BINS, device=device, dtype=torch.int64)
+    chunk = int(chunk_positions) if chunk_positions is not None else CHUNK_POSITIONS
+    with torch.no_grad(), model.eval_cache():
+        _count_activations(model, data, hist, period, int(shuffles), seed, strands == "both", chunk)
+    if model.validate_input:
+        model.check_input()
+    return ActivationNull(hist, model._options["kernel_size"], strands, shuffles, seed)
 
 
 def call_sites_records(model, records, thresholds, **kwargs):
@@ -192,10 +367,14 @@ def call_sites_records(model, records, thresholds, **kwargs):
 
 def bed_rows(seq_id, calls):
     """BED6 lines of one record: `SeqId start end filter<u> score strand`, 0-based half-open, sorted by
-    (start, filter, strand) with '+' before '-'."""
+    (start, filter, strand) with '+' before '-'.  Calls that carry p-values get them as a seventh column."""
     unit = calls.unit_ids()
     order = np.lexsort((-calls.strand, unit, calls.start))
     k = calls.kernel_size
+    if calls.pvalue is not None:
+        return ["%s\t%d\t%d\tfilter%d\t%.6g\t%s\t%.6g\n" % (
+            seq_id, calls.start[i], calls.start[i] + k, unit[i], calls.score[i],
+            "+" if calls.strand[i] > 0 else "-", calls.pvalue[i]) for i in order]
     return ["%s\t%d\t%d\tfilter%d\t%.6g\t%s\n" % (seq_id, calls.start[i], calls.start[i] + k, unit[i],
                                                 calls.score[i], "+" if calls.strand[i] > 0 else "-")
             for i in order]
@@ -237,12 +416,15 @@ def _parser():
     ap.add_argument("-t", "--thresholds", required=True, help="thresholds.tsv (filter, threshold)")
     ap.add_argument("-o", "--output-file")
     ap.add_argument("--strands", choices=("both", "fwd"), default="both")
+    ap.add_argument("--null", help="NULL.npz of `python -m explainn_amd.calibrate --save-null`: adds a seventh "
+                                   "column, the empirical p-value of the site's score")
     return ap
 
 
 def main(argv=None):
     """FASTA records of any length -> BED6 (SeqId, start, end, filter<u>, score, strand): one row per
-    motif site, 0-based half-open, sorted by (start, filter, strand) within a record."""
+    motif site, 0-based half-open, sorted by (start, filter, strand) within a record.  With --null a
+    seventh column holds the site's empirical p-value."""
     args = _parser().parse_args(argv)
     from .loader import read_fasta_records
     from .predict import _load_model
@@ -250,9 +432,11 @@ def main(argv=None):
     model = _load_model(args.model_file)
     model.eval()
     thresholds = read_thresholds(args.thresholds, model._units())
+    null = ActivationNull.load(args.null, model._device()) if args.null else None
     fh = open(args.output_file, "w") if args.output_file else sys.stdout
     try:
-        for rid, calls in call_sites_records(model, records, thresholds, strands=args.strands):
+        kwargs = {"null": null} if null is not None else {}
+        for rid, calls in call_sites_records(model, records, thresholds, strands=args.strands, **kwargs):
             fh.writelines(bed_rows(rid, calls))
     finally:
         if fh is not sys.stdout:

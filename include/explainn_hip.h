@@ -473,6 +473,41 @@ int explainn_call_sites(explainn_ctx* ctx, const uint8_t* seq, int64_t seq_len, 
                         float* score, int64_t capacity, void* workspace, int64_t workspace_bytes,
                         void* stream);
 
+/* The empirical null of the activations explainn_call_sites thresholds (csrc/actnull.hip, DESIGN.md
+ * section 8, "Calibrated sites").  a16(u,p) above is float16(exp(.)), never negative: its bit pattern is
+ * one of EXPLAINN_ACT_BINS = 32768 values that sort in the order of the values they encode (0x7C00 =
+ * +inf, the NaN patterns above it), so a unit's null is held exactly as an integer histogram.
+ *
+ * explainn_activation_histogram: for every unit u of the context (G*U on a bank context) and every live
+ * start p in [start, start + n_positions):  hist[u][bits(a16(u,p)) & 0x7FFF] += 1, with a16 the value of
+ * explainn_call_sites bit for bit.  "Live" as there: with period > 0 a start with p mod period >
+ * period - k is not counted, so every live start adds exactly one count to every unit's row.
+ * hist: device uint64 [units][EXPLAINN_ACT_BINS], ADDED INTO (the caller zeroes it once and may
+ * accumulate any number of calls, strands and chunks).  The reverse strand, N, bytes above 4 (read as N,
+ * bit 0 of explainn_input_flags), the argument checks (EXPLAINN_E_ARG), the eval-mode table handling
+ * and dense input mode (EXPLAINN_E_UNSUPPORTED) are those of explainn_call_sites.  n_positions == 0
+ * launches nothing.  No host synchronisation, no allocation, no workspace.  All additions are integer:
+ * the result is a function of the input alone.
+ * EXPLAINN_ACT_SPAN: start positions a workgroup takes at a time; a unit's spans are dealt round robin
+ * to its workgroups (tests place their sequence ends around it).
+ *
+ * explainn_activation_null: from hist [units][EXPLAINN_ACT_BINS] (device),
+ *     total[u]   = sum_b hist[u][b]
+ *     tail[u][b] = sum_{b' >= b} hist[u][b']        the null activations >= the value with pattern b
+ *     thresholds[u] = the float16 value, as fp32, of the smallest pattern b <= 0x7C00 with
+ *                     tail[u][b+1] <= m,  m = (uint64) floor(alpha * (double) total[u])
+ * (0x7C00 if there is none; +inf when total[u] == 0).  explainn_call_sites compares with a strict >, so
+ * at this threshold it calls at most m of the null's positions, and more than m one float16 value
+ * lower.  tail and thresholds may be NULL; total is required.  0 <= alpha <= 1, else EXPLAINN_E_ARG.
+ * No context, no workspace, no allocation, no host synchronisation. */
+#define EXPLAINN_ACT_BINS 32768
+#define EXPLAINN_ACT_SPAN 8192
+int explainn_activation_histogram(explainn_ctx* ctx, const uint8_t* seq, int64_t seq_len, int64_t start,
+                                  int64_t n_positions, int64_t period, int reverse_complement,
+                                  const explainn_params* p, uint64_t* hist, void* stream);
+int explainn_activation_null(const uint64_t* hist, int units, double alpha, uint64_t* tail, uint64_t* total,
+                             float* thresholds, void* stream);
+
 /* The fp32 one-hot packed into the context ahead of the forward: like explainn_stage_codes, the
  * entry points then take x == NULL.  Lets the caller read explainn_input_flags BEFORE anything
  * depends on the batch -- and route a batch that is not one-hot to the dense kernels (next entry)

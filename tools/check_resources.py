@@ -68,7 +68,9 @@ SHUFFLE = [r"^dinuc_shuffle_kernel"]
 MOTIFS = [r"^motif_prep_kernel", r"^motif_compare_kernel",
           # motif significance: column scores, histograms, range nulls, alignment p-values
           r"^motif_colscore_kernel", r"^motif_hist_kernel", r"^motif_null_kernel", r"^motif_pvalue_kernel"]
-GATED = C2_STEP + INPUT_GRAD + ISM + PATHGRAD + METRICS + SCAN + VARIANTS + HAPLOTYPES + SHUFFLE + MOTIFS
+# the activation null (actnull.hip): the LDS histogram and the tail / threshold scan
+ACTNULL = [r"^act_hist_kernel", r"^act_null_kernel"]
+GATED = C2_STEP + INPUT_GRAD + ISM + PATHGRAD + METRICS + SCAN + VARIANTS + HAPLOTYPES + SHUFFLE + MOTIFS + ACTNULL
 
 
 # Register cliffs measured in the pipeline: 1024-thread blocks of which TWO must
