@@ -726,6 +726,56 @@ extern "C" int explainn_activation_histogram(explainn_ctx* c, const uint8_t* seq
     return launch_activation_histogram(c, seq, start, n_positions, period, reverse_complement ? 1 : 0, hist, s);
 }
 
+// the checks the two spacing entry points share: the unit sets' sizes and the distance
+static int check_spacing(const char* what, int A, int P, int max_distance) {
+    if (A < 0 || P < 0 || A > 65535) {
+        explainn_set_error("%s: need 0 <= A <= 65535 anchors and P >= 0 partners (A=%d P=%d)", what, A, P);
+        return EXPLAINN_E_ARG;
+    }
+    if (max_distance < 0 || max_distance > EXPLAINN_SPACING_MAX_DISTANCE) {
+        explainn_set_error("%s: max_distance must be in [0, %d] (got %d)", what, EXPLAINN_SPACING_MAX_DISTANCE,
+                           max_distance);
+        return EXPLAINN_E_ARG;
+    }
+    return EXPLAINN_OK;
+}
+
+extern "C" int explainn_site_spacing(const int64_t* pos, const int64_t* offsets2, int U, const int32_t* anchors,
+                                     int A, const int32_t* partners, int P, int max_distance, int64_t* hist,
+                                     void* stream) {
+    TRY(check_spacing("site_spacing", A, P, max_distance));
+    if (U < 0 || (!anchors && A != U) || (!partners && P != U)) {
+        explainn_set_error("site_spacing: a null unit set means all %d units (A=%d P=%d)", U, A, P);
+        return EXPLAINN_E_ARG;
+    }
+    if (A == 0 || P == 0) return EXPLAINN_OK;
+    if (!pos || !offsets2 || !hist) {
+        explainn_set_error("site_spacing: pos, offsets2 and hist must be device pointers");
+        return EXPLAINN_E_ARG;
+    }
+    return launch_site_spacing(pos, offsets2, U, anchors, A, partners, P, max_distance, hist,
+                               static_cast<hipStream_t>(stream));
+}
+
+extern "C" int explainn_spacing_test(const int64_t* hist, int A, int P, const int32_t* anchors,
+                                     const int32_t* partners, int max_distance, int min_distance, int64_t min_count,
+                                     int64_t* total, int32_t* best_distance, int64_t* best_count, double* pvalue,
+                                     void* stream) {
+    TRY(check_spacing("spacing_test", A, P, max_distance));
+    if (min_distance < 0 || min_count < 0) {
+        explainn_set_error("spacing_test: min_distance and min_count must not be negative (%d, %lld)", min_distance,
+                           (long long)min_count);
+        return EXPLAINN_E_ARG;
+    }
+    if (A == 0 || P == 0) return EXPLAINN_OK;
+    if (!hist || !total || !best_distance || !best_count || !pvalue) {
+        explainn_set_error("spacing_test: hist and the four outputs must be device pointers");
+        return EXPLAINN_E_ARG;
+    }
+    return launch_spacing_test(hist, A, P, anchors, partners, max_distance, min_distance, min_count, total,
+                               best_distance, best_count, pvalue, static_cast<hipStream_t>(stream));
+}
+
 extern "C" int explainn_filter_act_max(explainn_ctx* c, const float* x, int B,
                                        const explainn_params* p, const uint8_t* select,
                                        float* unit_max, void* stream) {

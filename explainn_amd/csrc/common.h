@@ -253,6 +253,14 @@ int launch_call_sites(explainn_ctx* c, const uint8_t* seq, int64_t start, int64_
                       int64_t capacity, void* workspace, hipStream_t s);
 int launch_activation_histogram(explainn_ctx* c, const uint8_t* seq, int64_t start, int64_t npos, int64_t period,
                                 int rc, uint64_t* hist, hipStream_t s);
+// motif spacing (spacing.hip): distance histograms of site lists and their test; no context.  The largest
+// distance keeps a pair's 2 x (2D+1) histogram of 32-bit bins at 16 KiB of LDS.
+static_assert(EXPLAINN_SPACING_MAX_DISTANCE == 1024, "spacing.hip sizes its LDS histogram for this cap");
+int launch_site_spacing(const int64_t* pos, const int64_t* offsets2, int U, const int32_t* anchors, int A,
+                        const int32_t* partners, int P, int D, int64_t* hist, hipStream_t s);
+int launch_spacing_test(const int64_t* hist, int A, int P, const int32_t* anchors, const int32_t* partners, int D,
+                        int min_distance, int64_t min_count, int64_t* total, int32_t* best_distance,
+                        int64_t* best_count, double* pvalue, hipStream_t s);
 
 int launch_dense_moments(explainn_ctx* c, const float* x, int B, hipStream_t s);
 int launch_dense_conv_pool(explainn_ctx* c, const float* x, const explainn_params* p, int B, hipStream_t s);

@@ -508,6 +508,46 @@ int explainn_activation_histogram(explainn_ctx* ctx, const uint8_t* seq, int64_t
 int explainn_activation_null(const uint64_t* hist, int units, double alpha, uint64_t* tail, uint64_t* total,
                              float* thresholds, void* stream);
 
+/* Motif spacing (csrc/spacing.hip): which filters' sites occur together, and
+ * at what distance.  Sites come as explainn_call_sites lists them: pos holds int64 forward-strand starts,
+ * and offsets2, int64 [2U+1], cuts it into one list per (unit, strand): unit u's '+' sites are
+ * [offsets2[2u], offsets2[2u+1]), its '-' sites [offsets2[2u+1], offsets2[2u+2]), each in ascending start.
+ * For every ordered pair of DISTINCT records i, j (distinct by index, not by position), with a, b their
+ * units and s_i, s_j = +-1 their strands:
+ *     d = (pos[j] - pos[i]) * s_i        where the partner lies in the anchor's own orientation
+ *     o = 0 if s_i == s_j, else 1
+ *     |d| <= max_distance:  hist[a][b][o][d + max_distance] += 1
+ * so hist[a][b][0][D+d] == hist[b][a][0][D-d] and hist[a][b][1][D+d] == hist[b][a][1][D+d].
+ * anchors (A), partners (P): int32 unit indices on the device, in any order, overlapping or not; NULL means
+ * all units in order (A, P must then equal U); an index outside [0,U) counts nothing.  hist: device int64
+ * [A][P][2][2 max_distance + 1], ADDED INTO: the caller zeroes it once and accumulates any number of calls.
+ * The entry point knows nothing of records: the caller keeps sequences apart by spacing their coordinates
+ * more than max_distance apart.  Coordinates are int64; differences must fit int64.  A list that is not
+ * ascending gives wrong counts, never an access outside its own range; offsets2 is trusted.  A workgroup
+ * counts in 32-bit bins: lists of distinct starts, as explainn_call_sites gives them, cannot overflow one.
+ * All additions are integer: the result is a function of the input alone.  No context, no workspace, no
+ * allocation, no host synchronisation.  A, P, U < 0, A > 65535, a NULL set whose size is not U, or
+ * max_distance outside [0, EXPLAINN_SPACING_MAX_DISTANCE]: EXPLAINN_E_ARG, nothing launched.  A == 0 or
+ * P == 0 launches nothing.
+ *
+ * explainn_spacing_test: SpaMo's test of a preferred spacing, one result per (a, b, o), all [A][P][2] on
+ * the device.  The admissible bins are min_distance <= |d| <= max_distance with the counts c_d of hist,
+ * except where anchor and partner are the same unit (compared as unit indices): for o = 0 every unordered
+ * pair sits once at +d and once at -d, and only the bins d >= max(min_distance, 1) are taken; for o = 1
+ * every unordered pair sits twice in one bin, and every count is halved.  With m admissible bins:
+ *     total = n = sum c_d;  best_count = c = max c_d;  best_distance = the d of the lowest bin that holds c
+ *     pvalue = min(1, m P[Binomial(n, 1/m) >= c])      a uniform null over the bins, Bonferroni over them
+ * the tail summed in fp64 from x = c upwards as exp(lgamma(n+1) - lgamma(x+1) - lgamma(n-x+1) + x log(1/m)
+ * + (n-x) log1p(-1/m)) until a term no longer changes the sum; m == 1 gives 1.  n < max(min_count, 1) or
+ * m == 0: pvalue 1, best_count 0, best_distance 0 (total is still n).  Outputs are OVERWRITTEN.
+ * min_distance, min_count < 0 and the size checks above: EXPLAINN_E_ARG.  No host synchronisation. */
+#define EXPLAINN_SPACING_MAX_DISTANCE 1024
+int explainn_site_spacing(const int64_t* pos, const int64_t* offsets2, int U, const int32_t* anchors, int A,
+                          const int32_t* partners, int P, int max_distance, int64_t* hist, void* stream);
+int explainn_spacing_test(const int64_t* hist, int A, int P, const int32_t* anchors, const int32_t* partners,
+                          int max_distance, int min_distance, int64_t min_count, int64_t* total,
+                          int32_t* best_distance, int64_t* best_count, double* pvalue, void* stream);
+
 /* The fp32 one-hot packed into the context ahead of the forward: like explainn_stage_codes, the
  * entry points then take x == NULL.  Lets the caller read explainn_input_flags BEFORE anything
  * depends on the batch -- and route a batch that is not one-hot to the dense kernels (next entry)

@@ -70,7 +70,9 @@ MOTIFS = [r"^motif_prep_kernel", r"^motif_compare_kernel",
           r"^motif_colscore_kernel", r"^motif_hist_kernel", r"^motif_null_kernel", r"^motif_pvalue_kernel"]
 # the activation null (actnull.hip): the LDS histogram and the tail / threshold scan
 ACTNULL = [r"^act_hist_kernel", r"^act_null_kernel"]
-GATED = C2_STEP + INPUT_GRAD + ISM + PATHGRAD + METRICS + SCAN + VARIANTS + HAPLOTYPES + SHUFFLE + MOTIFS + ACTNULL
+# motif spacing (spacing.hip): the per-pair distance histogram and the binomial test
+SPACING = [r"^spacing_hist_kernel", r"^spacing_test_kernel"]
+GATED = C2_STEP + INPUT_GRAD + ISM + PATHGRAD + METRICS + SCAN + VARIANTS + HAPLOTYPES + SHUFFLE + MOTIFS + ACTNULL + SPACING
 
 
 # Register cliffs measured in the pipeline: 1024-thread blocks of which TWO must
