@@ -59,6 +59,13 @@ extern "C" int explainn_adam_step(int n_tensors, float* const* params, const flo
         return EXPLAINN_E_ARG;
     }
     if (step < 1) { explainn_set_error("adam_step: step counts from 1"); return EXPLAINN_E_ARG; }
+    // every tensor is checked before the first launch: an error in a later table must not leave the
+    // tensors of the tables in front of it stepped
+    for (int i = 0; i < n_tensors; ++i)
+        if (sizes[i] < 0 || (sizes[i] > 0 && (!params[i] || !grads[i] || !exp_avg[i] || !exp_avg_sq[i]))) {
+            explainn_set_error("adam_step: tensor %d has a null pointer or negative size", i);
+            return EXPLAINN_E_ARG;
+        }
     // bias corrections in double on the host, as torch's single-tensor Adam computes them
     const double bc1 = 1.0 - pow(beta1, (double)step);
     const double bc2 = 1.0 - pow(beta2, (double)step);
@@ -74,10 +81,6 @@ extern "C" int explainn_adam_step(int n_tensors, float* const* params, const flo
         tab.count = 0;
         tab.first_block[0] = 0;
         for (; i < n_tensors && tab.count < ADAM_MAX_TENSORS; ++i) {
-            if (sizes[i] < 0 || (sizes[i] > 0 && (!params[i] || !grads[i] || !exp_avg[i] || !exp_avg_sq[i]))) {
-                explainn_set_error("adam_step: tensor %d has a null pointer or negative size", i);
-                return EXPLAINN_E_ARG;
-            }
             if (sizes[i] == 0) continue;
             const int c = tab.count++;
             tab.p[c] = params[i]; tab.g[c] = grads[i]; tab.m[c] = exp_avg[i]; tab.v[c] = exp_avg_sq[i];

@@ -5,7 +5,7 @@ selene/__init__.py:291 steps it): the same update, all parameter tensors in ONE 
 `FusedAdam` IS a torch.optim.Adam: same constructor, same `state` / `param_groups` /
 `state_dict()` layout (so the reference's checkpoints load and save unchanged); only `step()` is
 replaced.  Option combinations the kernel does not implement (amsgrad, weight decay, maximize,
-non-fp32 or non-HIP parameters) go through torch's own Adam step."""
+non-fp32 or non-HIP parameters, non-contiguous gradients) go through torch's own Adam step."""
 import ctypes as C
 
 import torch
@@ -27,6 +27,10 @@ class FusedAdam(torch.optim.Adam):
                 return False
             if p.grad.is_sparse or p.grad.dtype != torch.float32 or p.grad.device != p.device:
                 return False
+            # judged before any group is launched: handing the whole step to torch after an earlier
+            # group has gone through the kernel would step that group twice
+            if not p.grad.is_contiguous():
+                return False
         return True
 
     def _plan(self, gi, group, params):
@@ -38,6 +42,9 @@ class FusedAdam(torch.optim.Adam):
                 all(a is b for a, b in zip(plan["params"], params)) and \
                 all(p.grad is g for p, g in zip(params, plan["grads"])):
             return plan
+        # an older plan holds the step count of its tensors in a Python int: write it back before the
+        # counts are read, or a parameter that joins late (count 0) looks uniform with the stale zeros
+        self._sync_steps()
         steps, ms, vs = [], [], []
         for p in params:
             st = self.state[p]
@@ -58,8 +65,6 @@ class FusedAdam(torch.optim.Adam):
                 "p_arr": arr(params), "g_arr": arr(grads), "m_arr": arr(ms), "v_arr": arr(vs),
                 "sizes": (C.c_int64 * n)(*[p.numel() for p in params]),
                 "uniform": len({float(t) for t in steps}) == 1, "count": int(steps[0].item())}
-        self._sync_steps()                # an older plan of this group may hold a newer count
-        plan["count"] = int(steps[0].item())
         self._plans[gi] = plan
         return plan
 
@@ -93,16 +98,10 @@ class FusedAdam(torch.optim.Adam):
             plan = self._plan(gi, group, params)
             # state tensors can be swapped under us (load_state_dict): the plan must still match
             st0 = self.state[params[0]]
-            if st0["exp_avg"] is not plan["ms"][0] or st0["step"] is not plan["steps"][0] or \
-                    any(not g.is_contiguous() for g in plan["grads"]):
+            if st0["exp_avg"] is not plan["ms"][0] or st0["step"] is not plan["steps"][0]:
                 self._sync_steps()
                 self._plans.pop(gi, None)
                 plan = self._plan(gi, group, params)
-                if any(not g.is_contiguous() for g in plan["grads"]):
-                    self._sync_steps()
-                    self.__dict__.pop("_plans", None)
-                    super().step()
-                    return loss
             # the step count lives in a Python int between steps; the per-parameter `step` tensors
             # (torch's state layout) are brought up to date when the state is read (_sync_steps)
             if plan["uniform"]:
