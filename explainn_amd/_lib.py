@@ -24,6 +24,7 @@ MOTIF_NO_SCORE = 255      # EXPLAINN_MOTIF_NO_SCORE: a colscore entry without a 
 SITES_TILE = 1024        # EXPLAINN_SITES_TILE: start positions per workgroup of explainn_call_sites
 ACT_BINS = 32768         # EXPLAINN_ACT_BINS: one bin per non-negative float16 bit pattern
 ACT_SPAN = 8192          # EXPLAINN_ACT_SPAN: start positions a workgroup of explainn_activation_histogram takes at a time
+BEST_SPAN = 256          # EXPLAINN_BEST_SPAN: starts a wavefront of explainn_record_best takes per pass over its record
 SPACING_MAX_DISTANCE = 1024   # EXPLAINN_SPACING_MAX_DISTANCE: the largest max_distance of explainn_site_spacing
 
 _fp = C.c_void_p          # device pointers travel as integers (tensor.data_ptr())
@@ -146,6 +147,10 @@ SIGNATURES = {
     "explainn_activation_null": (_i, [_fp, _i, C.c_double, _fp, _fp, _fp, _fp]),
     "explainn_site_spacing": (_i, [_fp, _fp, _i, _fp, _i, _fp, _i, _i, _fp, _fp]),
     "explainn_spacing_test": (_i, [_fp, _i, _i, _fp, _fp, _i, _i, _i64, _fp, _fp, _fp, _fp, _fp]),
+    "explainn_record_best": (_i, [_ctx, _fp, _i64, _fp, _i64, _i, _pp, _fp, _fp, _fp]),
+    "explainn_enrichment_workspace_bytes": (_i64, [_i, _i64]),
+    "explainn_enrichment_test": (_i, [_fp, _fp, _i, _i64, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp,
+                                      _i64, _fp]),
     "explainn_dense_input": (_i, [_ctx, _i]),
     "explainn_pwm_scan": (_i, [_fp, _i, _i, _fp, _i, _i, _i, _fp, _fp]),
     "explainn_dinucleotide_shuffle": (_i, [_fp, _i64, _i, _i, C.c_uint64, _i64, _i, _fp, _fp, _fp]),

@@ -848,6 +848,38 @@ class ExplaiNN(_Model):
                 capacity, ws.data_ptr(), nbytes, stream))
         return offsets, pos, score
 
+    def _launch_record_best(self, codes, rec_offsets, strands=2, want_site=True):
+        """The best site of every unit in every record (explainn_record_best).  codes: a device-resident
+        1-D uint8 tensor of base codes; rec_offsets: int64 (n_records + 1,) on the device, record r being
+        codes[rec_offsets[r] : rec_offsets[r + 1]]; strands 1 (forward) or 2 (both).  Returns (bits, site)
+        on the device, unit-major (units, n_records): bits int16, the largest float16 activation's bit
+        pattern (below 0x8000) over the record's live starts (0 without one), and site int32, (start << 1) | is_minus of
+        the site that holds it (-1 without one; None unless want_site)."""
+        if self.training:
+            raise NotImplementedError("the best sites are an eval-mode export path; call model.eval()")
+        dev = self._device()
+        U = self._units()
+        if not torch.is_tensor(codes) or codes.dtype != torch.uint8 or codes.dim() != 1 or \
+                not codes.is_contiguous():
+            raise RuntimeError("best sites are found on a contiguous 1-D uint8 tensor of base codes")
+        if codes.device != dev:
+            raise RuntimeError("input is on %s but the model is on %s" % (codes.device, dev))
+        if not torch.is_tensor(rec_offsets) or rec_offsets.dtype != torch.int64 or rec_offsets.dim() != 1 or \
+                rec_offsets.numel() < 1 or rec_offsets.device != dev or not rec_offsets.is_contiguous():
+            raise RuntimeError("rec_offsets must be a contiguous 1-D int64 tensor of n_records + 1 entries on %s" % dev)
+        if strands not in (1, 2):
+            raise ValueError("strands must be 1 (forward) or 2 (both)")
+        n = rec_offsets.numel() - 1
+        bits = torch.empty((U, n), device=dev, dtype=torch.int16)
+        site = torch.empty((U, n), device=dev, dtype=torch.int32) if want_site else None
+        with torch.cuda.device(dev):
+            win = SequenceWindows(codes, 0, 1, 1, False, 1)
+            ctx, ps, _, stream, xp, _ = self._front(win, dev)
+            _lib.check(ctx.lib.explainn_record_best(
+                ctx.handle, xp, codes.numel(), rec_offsets.data_ptr(), n, int(strands), C.byref(ps),
+                bits.data_ptr(), site.data_ptr() if want_site else None, stream))
+        return bits, site
+
     def _launch_activation_histogram(self, codes, hist, start=0, n_positions=None, period=0,
                                      reverse_complement=False):
         """Adds, for every unit and every live start p in [start, start + n_positions) of a

@@ -726,6 +726,29 @@ extern "C" int explainn_activation_histogram(explainn_ctx* c, const uint8_t* seq
     return launch_activation_histogram(c, seq, start, n_positions, period, reverse_complement ? 1 : 0, hist, s);
 }
 
+extern "C" int explainn_record_best(explainn_ctx* c, const uint8_t* seq, int64_t seq_len, const int64_t* rec_offsets,
+                                    int64_t n_records, int strands, const explainn_params* p, uint16_t* best_bits,
+                                    int32_t* best_site, void* stream) {
+    if (!c) { explainn_set_error("null context"); return EXPLAINN_E_ARG; }
+    if (!seq || !p || !rec_offsets || !best_bits) {
+        explainn_set_error("seq, rec_offsets, params and best_bits are required");
+        return EXPLAINN_E_ARG;
+    }
+    if (seq_len < 0 || n_records < 0 || n_records >= (int64_t)1 << 31 || (strands != 1 && strands != 2)) {
+        explainn_set_error("record_best needs seq_len >= 0, 0 <= n_records < 2^31 and strands 1 or 2 "
+                           "(seq_len %lld, n_records %lld, strands %d)", (long long)seq_len, (long long)n_records,
+                           strands);
+        return EXPLAINN_E_ARG;
+    }
+    if (c->dense) { explainn_set_error("best sites are found on base codes: not in dense input mode"); return EXPLAINN_E_UNSUPPORTED; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    drop_pending(c);
+    c->staged_B = 0;                   // nothing is staged by this call; what was staged is not kept
+    TRY(eval_tables(c, p, 1, s));
+    if (n_records == 0) return EXPLAINN_OK;
+    return launch_record_best(c, seq, seq_len, rec_offsets, n_records, strands, best_bits, best_site, s);
+}
+
 // the checks the two spacing entry points share: the unit sets' sizes and the distance
 static int check_spacing(const char* what, int A, int P, int max_distance) {
     if (A < 0 || P < 0 || A > 65535) {

@@ -253,6 +253,9 @@ int launch_call_sites(explainn_ctx* c, const uint8_t* seq, int64_t start, int64_
                       int64_t capacity, void* workspace, hipStream_t s);
 int launch_activation_histogram(explainn_ctx* c, const uint8_t* seq, int64_t start, int64_t npos, int64_t period,
                                 int rc, uint64_t* hist, hipStream_t s);
+// motif enrichment (enrich.hip): per record the best site of every unit (the test itself takes no context)
+int launch_record_best(explainn_ctx* c, const uint8_t* seq, int64_t seq_len, const int64_t* rec_offsets,
+                       int64_t n_records, int strands, uint16_t* best_bits, int32_t* best_site, hipStream_t s);
 // motif spacing (spacing.hip): distance histograms of site lists and their test; no context.  The largest
 // distance keeps a pair's 2 x (2D+1) histogram of 32-bit bins at 16 KiB of LDS.
 static_assert(EXPLAINN_SPACING_MAX_DISTANCE == 1024, "spacing.hip sizes its LDS histogram for this cap");

@@ -548,6 +548,68 @@ int explainn_spacing_test(const int64_t* hist, int A, int P, const int32_t* anch
                           int max_distance, int min_distance, int64_t min_count, int64_t* total,
                           int32_t* best_distance, int64_t* best_count, double* pvalue, void* stream);
 
+/* Motif enrichment (csrc/enrich.hip, DESIGN.md section 8, "Enrichment"): which filters' best sites score
+ * higher in a primary set of records than in a control set, and at what score threshold.
+ *
+ * explainn_record_best: seq holds device base codes as explainn_call_sites takes them; rec_offsets, device
+ * int64 [n_records + 1], cuts it into records: record r is seq[rec_offsets[r] : rec_offsets[r+1]].  For every
+ * unit u of the context (G*U on a bank context) and every record r
+ *     best_bits[u][r] (uint16) = max over the record's live starts p and the requested strands of
+ *                                bits(a16(u,p)) & 0x7FFF
+ * with a16 the value explainn_call_sites compares, bit for bit (from 0.f, taps in j order, fp32, the folded
+ * BatchNorm1 and exp, rounded to float16; N contributes 0); a start is live when its k-mer lies inside the
+ * record; strands: 1 = forward only, 2 = both, the reverse strand as in explainn_call_sites (the filter on
+ * the reverse complement of seq[p : p+k], reported at the forward start p).
+ *     best_site[u][r] (int32; may be NULL) = (p_rel << 1) | is_minus  of the maximising site, p_rel its
+ *                                forward start relative to the record
+ * Among equal maxima the lowest start wins, and at one start '+' before '-'.  A record shorter than k has no
+ * live start: bits 0, site -1.  A record whose offsets descend or leave [0, seq_len], or of 2^30 bases or
+ * more (its starts would not fit the site word), reads as having no live start and raises bit 0 of
+ * explainn_input_flags; it is never a read outside seq.  A byte above 4 inside a record reads as N and
+ * raises bit 0.  Both outputs are unit-major [units][n_records] and OVERWRITTEN.  The result is a maximum
+ * over integer keys (bits, then ~start, then strand): a function of the input alone.  EXPLAINN_E_ARG unless
+ * seq_len >= 0, 0 <= n_records < 2^31 and strands is 1 or 2; the eval-mode table handling and dense input
+ * mode (EXPLAINN_E_UNSUPPORTED) are those of explainn_call_sites.  n_records == 0 launches nothing.  No
+ * host synchronisation, no allocation, no workspace.
+ * EXPLAINN_BEST_SPAN: starts a wavefront takes per pass over its record (tests place their record lengths
+ * around it).
+ *
+ * explainn_enrichment_test: from best_bits [units][n_records] (device uint16, read & 0x7FFF) and labels
+ * (device uint8 [n_records]: 1 = primary, 0 = control, anything else leaves the record out), per unit, with
+ * Np / Nc the primary / control records and N = Np + Nc:
+ *     a_t = primary records with bits >= t,  b_t = control records with bits >= t       (t = 0 .. 32767)
+ *     the thresholds are the m patterns t that an included record holds; at each, with n = a_t + b_t,
+ *     logp(t) = 0 unless a_t N > n Np (integers), else min(0, ln P[X >= a_t]), X ~ Hypergeometric(N, Np, n):
+ *     in fp64, ln of the first term from nine lgammas, plus ln of 1 + the following terms relative to it,
+ *     each from the ratio (Np-x)(n-x) / ((x+1)(Nc-n+x+1)) of its predecessor, x = a_t upwards, until x
+ *     reaches min(Np, n) or a term no longer changes the sum (explainn_spacing_test's rule; a threshold that
+ *     is not enriched is given p = 1, not evaluated)
+ * Outputs, each [units] on the device and OVERWRITTEN:
+ *     n_thresholds (int32) m;  best_pattern (int32) the threshold of smallest logp, among equal values the
+ *     highest pattern (0 when m == 0);  tp, fp (int64) a and b at it;  log_pvalue (double) its logp;
+ *     log_padj (double) ln(1 - (1 - p)^m), computed as log(-expm1(m log1p(-p))), and as min(0, ln m +
+ *     log_pvalue) when log_pvalue < -30 -- there the two differ by (m - 1) p / 2 in ln at the most: less than
+ *     1e-13 relative to the value while m <= 50, and less than 1.6e-9 absolute (8e-11 relative) at the
+ *     largest m = 32768; 0 when m == 0;
+ *     u2 (int64) twice the Mann-Whitney U of primary over control, sum over the patterns of
+ *     primary_at(t) (2 control_below(t) + control_at(t)), an exact integer;  auroc (double) u2 / (2 Np Nc).
+ * counts: int64 [2], Np and Nc.  Np == 0 or Nc == 0: no threshold is enriched, the log values are 0, tp / fp
+ * as counted at the highest held pattern, auroc NaN.  tails: NULL, or uint32 [units][2][32768] receiving a_t
+ * and b_t.  workspace: device memory, 256-byte aligned, of explainn_enrichment_workspace_bytes(units,
+ * n_records) bytes (128 KiB per workgroup of the call, not per unit).  All counts are 32-bit integer LDS
+ * operations and every logp is computed by one lane: the result is a function of the input alone.  No
+ * context, no allocation, no host synchronisation.  units < 0 or n_records outside [0, 2^31):
+ * EXPLAINN_E_ARG (the workspace query returns 0).  units == 0 launches nothing. */
+#define EXPLAINN_BEST_SPAN 256
+int explainn_record_best(explainn_ctx* ctx, const uint8_t* seq, int64_t seq_len, const int64_t* rec_offsets,
+                         int64_t n_records, int strands, const explainn_params* p, uint16_t* best_bits,
+                         int32_t* best_site, void* stream);
+int64_t explainn_enrichment_workspace_bytes(int units, int64_t n_records);
+int explainn_enrichment_test(const uint16_t* best_bits, const uint8_t* labels, int units, int64_t n_records,
+                             int32_t* n_thresholds, int32_t* best_pattern, int64_t* tp, int64_t* fp,
+                             double* log_pvalue, double* log_padj, int64_t* u2, double* auroc, int64_t* counts,
+                             uint32_t* tails, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* The fp32 one-hot packed into the context ahead of the forward: like explainn_stage_codes, the
  * entry points then take x == NULL.  Lets the caller read explainn_input_flags BEFORE anything
  * depends on the batch -- and route a batch that is not one-hot to the dense kernels (next entry)

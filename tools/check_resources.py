@@ -72,7 +72,9 @@ MOTIFS = [r"^motif_prep_kernel", r"^motif_compare_kernel",
 ACTNULL = [r"^act_hist_kernel", r"^act_null_kernel"]
 # motif spacing (spacing.hip): the per-pair distance histogram and the binomial test
 SPACING = [r"^spacing_hist_kernel", r"^spacing_test_kernel"]
-GATED = C2_STEP + INPUT_GRAD + ISM + PATHGRAD + METRICS + SCAN + VARIANTS + HAPLOTYPES + SHUFFLE + MOTIFS + ACTNULL + SPACING
+# motif enrichment (enrich.hip): the per-record best site and the threshold test
+ENRICH = [r"^record_best_kernel<true>", r"^record_best_kernel<false>", r"^enrich_test_kernel"]
+GATED = C2_STEP + INPUT_GRAD + ISM + PATHGRAD + METRICS + SCAN + VARIANTS + HAPLOTYPES + SHUFFLE + MOTIFS + ACTNULL + SPACING + ENRICH
 
 
 # Register cliffs measured in the pipeline: 1024-thread blocks of which TWO must
