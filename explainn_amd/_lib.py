@@ -26,6 +26,8 @@ ACT_BINS = 32768         # EXPLAINN_ACT_BINS: one bin per non-negative float16 b
 ACT_SPAN = 8192          # EXPLAINN_ACT_SPAN: start positions a workgroup of explainn_activation_histogram takes at a time
 BEST_SPAN = 256          # EXPLAINN_BEST_SPAN: starts a wavefront of explainn_record_best takes per pass over its record
 SPACING_MAX_DISTANCE = 1024   # EXPLAINN_SPACING_MAX_DISTANCE: the largest max_distance of explainn_site_spacing
+CENTRALITY_MAX_THRESHOLDS = 16      # EXPLAINN_CENTRALITY_MAX_THRESHOLDS: thresholds of one explainn_site_positions call
+CENTRALITY_MAX_REGIONS = 4194304    # EXPLAINN_CENTRALITY_MAX_REGIONS: regions per unit of explainn_centrality_test
 
 _fp = C.c_void_p          # device pointers travel as integers (tensor.data_ptr())
 
@@ -151,6 +153,9 @@ SIGNATURES = {
     "explainn_enrichment_workspace_bytes": (_i64, [_i, _i64]),
     "explainn_enrichment_test": (_i, [_fp, _fp, _i, _i64, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp,
                                       _i64, _fp]),
+    "explainn_site_positions": (_i, [_fp, _fp, _fp, _fp, _i, _i64, _i, _i, _fp, _fp, _fp]),
+    "explainn_centrality_test": (_i, [_fp, _fp, _i, _i, _i, _i, _i, _i, _i64, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp,
+                                      _fp, _fp, _fp, _fp]),
     "explainn_dense_input": (_i, [_ctx, _i]),
     "explainn_pwm_scan": (_i, [_fp, _i, _i, _fp, _i, _i, _i, _fp, _fp]),
     "explainn_dinucleotide_shuffle": (_i, [_fp, _i64, _i, _i, C.c_uint64, _i64, _i, _fp, _fp, _fp]),

@@ -799,6 +799,69 @@ extern "C" int explainn_spacing_test(const int64_t* hist, int A, int P, const in
                                best_distance, best_count, pvalue, static_cast<hipStream_t>(stream));
 }
 
+// the checks the two centrality entry points share: the histogram's shape
+static int check_centrality(const char* what, int units, int T, int M) {
+    if (units < 0 || T < 1 || T > EXPLAINN_CENTRALITY_MAX_THRESHOLDS || M < 1 ||
+        (int64_t)T * 2 * M * (int64_t)sizeof(int32_t) > 64 * 1024) {
+        explainn_set_error("%s: need units >= 0, 1 <= T <= %d thresholds, M >= 1 starts and a [T][2][M] int32 "
+                           "histogram of at most 64 KiB (units=%d T=%d M=%d): split the thresholds", what,
+                           EXPLAINN_CENTRALITY_MAX_THRESHOLDS, units, T, M);
+        return EXPLAINN_E_ARG;
+    }
+    return EXPLAINN_OK;
+}
+
+extern "C" int explainn_site_positions(const uint16_t* best_bits, const int32_t* best_site, const uint8_t* labels,
+                                       const float* thresholds, int units, int64_t n_records, int T, int M,
+                                       int32_t* hist, int64_t* counts, void* stream) {
+    TRY(check_centrality("site_positions", units, T, M));
+    if (n_records < 0 || n_records >= (int64_t)1 << 31) {
+        explainn_set_error("site_positions: need 0 <= n_records < 2^31 (got %lld)", (long long)n_records);
+        return EXPLAINN_E_ARG;
+    }
+    if (!counts) { explainn_set_error("site_positions: counts must be a device pointer"); return EXPLAINN_E_ARG; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(counts, 0, 2 * sizeof(int64_t), s));
+    if (units == 0 || n_records == 0) return EXPLAINN_OK;
+    if (!best_bits || !best_site || !labels || !thresholds || !hist) {
+        explainn_set_error("site_positions: best_bits, best_site, labels, thresholds and hist must be device pointers");
+        return EXPLAINN_E_ARG;
+    }
+    return launch_site_positions(best_bits, best_site, labels, thresholds, units, n_records, T, M, hist, counts, s);
+}
+
+extern "C" int explainn_centrality_test(const int32_t* hist, const int64_t* counts, int units, int T, int M, int mode,
+                                        int min_width, int max_width, int64_t min_sites, int32_t* best_t,
+                                        int32_t* best_lo, int32_t* best_width, int64_t* sites, int64_t* count,
+                                        int64_t* n_tests, double* log_pvalue, double* log_padj, int64_t* ctrl_sites,
+                                        int64_t* ctrl_count, double* log_fisher, void* stream) {
+    TRY(check_centrality("centrality_test", units, T, M));
+    if ((mode != 0 && mode != 1) || min_width < 1 || max_width < min_width || min_sites < 0) {
+        explainn_set_error("centrality_test: need mode 0 (centred) or 1 (local), 1 <= min_width <= max_width and "
+                           "min_sites >= 0 (mode=%d min_width=%d max_width=%d min_sites=%lld)", mode, min_width,
+                           max_width, (long long)min_sites);
+        return EXPLAINN_E_ARG;
+    }
+    int j0, w0;
+    int64_t items;
+    const int64_t regions = centrality_regions(M, mode, min_width, max_width, &j0, &w0, &items);
+    if (regions > EXPLAINN_CENTRALITY_MAX_REGIONS) {
+        explainn_set_error("centrality_test: %lld regions per unit, %d at the most: narrow max_width (M=%d "
+                           "min_width=%d max_width=%d)", (long long)regions, EXPLAINN_CENTRALITY_MAX_REGIONS, M,
+                           min_width, max_width);
+        return EXPLAINN_E_ARG;
+    }
+    if (units == 0) return EXPLAINN_OK;
+    if (!hist || !counts || !best_t || !best_lo || !best_width || !sites || !count || !n_tests || !log_pvalue ||
+        !log_padj || !ctrl_sites || !ctrl_count || !log_fisher) {
+        explainn_set_error("centrality_test: hist, counts and the eleven outputs must be device pointers");
+        return EXPLAINN_E_ARG;
+    }
+    return launch_centrality_test(hist, counts, units, T, M, mode, j0, w0, items, regions, min_sites, best_t, best_lo,
+                                  best_width, sites, count, n_tests, log_pvalue, log_padj, ctrl_sites, ctrl_count,
+                                  log_fisher, static_cast<hipStream_t>(stream));
+}
+
 extern "C" int explainn_filter_act_max(explainn_ctx* c, const float* x, int B,
                                        const explainn_params* p, const uint8_t* select,
                                        float* unit_max, void* stream) {

@@ -264,6 +264,18 @@ int launch_site_spacing(const int64_t* pos, const int64_t* offsets2, int U, cons
 int launch_spacing_test(const int64_t* hist, int A, int P, const int32_t* anchors, const int32_t* partners, int D,
                         int min_distance, int64_t min_count, int64_t* total, int32_t* best_distance,
                         int64_t* best_count, double* pvalue, hipStream_t s);
+// motif centrality (central.hip): position histograms of best sites and CentriMo's test; no context.
+// centrality_regions: the admissible regions of a call (their number is returned) and how the kernel
+// enumerates them: j0 / items in centred mode, w0 / items in local mode.
+int launch_site_positions(const uint16_t* best_bits, const int32_t* best_site, const uint8_t* labels,
+                          const float* thresholds, int units, int64_t n_records, int T, int M, int32_t* hist,
+                          int64_t* counts, hipStream_t s);
+int64_t centrality_regions(int M, int mode, int min_width, int max_width, int* j0, int* w0, int64_t* items);
+int launch_centrality_test(const int32_t* hist, const int64_t* counts, int units, int T, int M, int mode, int j0,
+                           int w0, int64_t items, int64_t regions, int64_t min_sites, int32_t* best_t,
+                           int32_t* best_lo, int32_t* best_width, int64_t* sites, int64_t* count, int64_t* n_tests,
+                           double* log_pvalue, double* log_padj, int64_t* ctrl_sites, int64_t* ctrl_count,
+                           double* log_fisher, hipStream_t s);
 
 int launch_dense_moments(explainn_ctx* c, const float* x, int B, hipStream_t s);
 int launch_dense_conv_pool(explainn_ctx* c, const float* x, const explainn_params* p, int B, hipStream_t s);

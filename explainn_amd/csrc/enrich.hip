@@ -20,6 +20,7 @@
 #include <hip/hip_fp16.h>
 
 #include "common.h"
+#include "tails.h"                              // hypergeom_logsf
 
 namespace {
 
@@ -186,25 +187,6 @@ __device__ __forceinline__ void tail_scan(unsigned* h, unsigned* ws, unsigned* _
         running += total;
         __syncthreads();                       // ws is rewritten by the next chunk
     }
-}
-
-// ln P[X >= a], X ~ Hypergeometric(N, Np, n), for an enriched threshold: the first term from nine lgammas,
-// the following ones from the ratio of neighbouring terms, summed (relative to the first) until x reaches
-// min(Np, n) or a term no longer changes the sum
-__device__ __noinline__ double hypergeom_logsf(long long a, long long n, long long Np, long long Nc) {
-    const double N = (double)(Np + Nc), b = (double)(n - a);
-    const double first = lgamma((double)Np + 1.0) - lgamma((double)a + 1.0) - lgamma((double)(Np - a) + 1.0)
-                       + lgamma((double)Nc + 1.0) - lgamma(b + 1.0) - lgamma((double)Nc - b + 1.0)
-                       - lgamma(N + 1.0) + lgamma((double)n + 1.0) + lgamma(N - (double)n + 1.0);
-    const long long top = Np < n ? Np : n;
-    double sum = 1.0, term = 1.0;
-    for (long long x = a; x < top; ++x) {
-        term *= ((double)(Np - x) * (double)(n - x)) / ((double)(x + 1) * (double)(Nc - n + x + 1));
-        const double s = sum + term;
-        if (s == sum) break;
-        sum = s;
-    }
-    return fmin(0.0, first + log(sum));
 }
 
 struct EnBest { double logp; int pattern; };

@@ -16,6 +16,7 @@
 // spacing_test_kernel: one lane per (a, b, orientation): the admissible bins (folded when a == b), their
 // sum, their largest count and the Bonferroni-corrected binomial tail of it, in fp64.
 #include "common.h"
+#include "tails.h"                              // binom_logpmf
 
 namespace {
 
@@ -72,11 +73,6 @@ __global__ __launch_bounds__(SP_T) void spacing_hist_kernel(
         const unsigned v = sp_sm[b];
         if (v) atomicAdd(&row[b], (unsigned long long)v);
     }
-}
-
-// log of the Binomial(n, q) probability of x
-__device__ __forceinline__ double binom_logpmf(double n, double x, double logq, double log1mq) {
-    return lgamma(n + 1.0) - lgamma(x + 1.0) - lgamma(n - x + 1.0) + x * logq + (n - x) * log1mq;
 }
 
 __global__ __launch_bounds__(SP_T) void spacing_test_kernel(

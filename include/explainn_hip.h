@@ -610,6 +610,73 @@ int explainn_enrichment_test(const uint16_t* best_bits, const uint8_t* labels, i
                              double* log_pvalue, double* log_padj, int64_t* u2, double* auroc, int64_t* counts,
                              uint32_t* tails, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Motif centrality (csrc/central.hip, DESIGN.md section 3 item 19, section 8 "Centrality"): where in records
+ * of one length the best sites of every unit sit, and CentriMo's test of a region that holds more of them
+ * than its width explains.
+ *
+ * explainn_site_positions: best_bits (device uint16 [units][n_records], read & 0x7FFF) and best_site (device
+ * int32 [units][n_records]: (start << 1) | is_minus, negative = no site) are explainn_record_best's outputs;
+ * labels as explainn_enrichment_test takes them (1 = primary, 0 = control, anything else leaves the record
+ * out); thresholds: device float [units][T], as explainn_call_sites takes them; M: the live starts of every
+ * record, L - k + 1.  For every unit u, threshold t and included record r with a site,
+ *     a16(u,r) > thresholds[u][t]  and  0 <= start < M:   hist[u][t][set][start] += 1
+ * with a16 the float16 value of the bit pattern, compared as a float with the float threshold -- the
+ * comparison of explainn_call_sites, so the record counts where call_sites with that threshold calls its
+ * best site (a NaN pattern or a NaN threshold never counts) -- and set = 0 for primary, 1 for control.
+ * hist: device int32 [units][T][2][M], ADDED INTO: the caller zeroes it once and accumulates calls over
+ * chunks of records; a bin must stay below 2^31.  A site below 0 or a start >= M is not counted: it is never
+ * a write outside hist.  counts: device int64 [2], OVERWRITTEN with (Np, Nc), the records of this call with
+ * label 1 / 0, with or without a site (the caller adds them up over its calls).  The [T][2][M] histogram of
+ * a workgroup sits in LDS: 1 <= T <= EXPLAINN_CENTRALITY_MAX_THRESHOLDS, M >= 1 and T*2*M*4 <= 65536 bytes,
+ * else EXPLAINN_E_ARG (the caller splits the thresholds); so is units < 0 or n_records outside [0, 2^31).
+ * units == 0 or n_records == 0 launches no kernel (counts is still zeroed, by a memset on the stream).  All
+ * additions are integer: the result is a function of the input alone, whatever the slicing.  No context, no
+ * workspace, no allocation, no host synchronisation.
+ *
+ * explainn_centrality_test: reads hist and counts (the sums over the calls that filled hist).  A region is a
+ * range of starts [lo, hi] of w = hi - lo + 1 bins, w < M (the whole record has null probability 1 and is
+ * never a region):
+ *     mode 0 (centred): the regions [j, M-1-j], j >= 1;      mode 1 (local): every 0 <= lo <= hi <= M-1
+ * both restricted to min_width <= w <= max_width (max_width above M - 1 reads as M - 1).  Per unit, with
+ * n_t the sum of the primary row of threshold t: thresholds with n_t < max(min_sites, 1) are not tried.  For
+ * a tried threshold and a region, with c the primary sites inside it,
+ *     logp = 0 unless c M > n_t w (integers), else min(0, ln P[X >= c]), X ~ Binomial(n_t, q), q = w / M:
+ *     in fp64, ln of the first term as lgamma(n+1) - lgamma(c+1) - lgamma(n-c+1) + c ln q + (n-c) log1p(-q),
+ *     plus ln of 1 + the following terms relative to it, each its predecessor times
+ *     ((n-x) / (x+1)) * (q / (1-q)), x = c upwards, until x reaches n or a term no longer changes the sum
+ * (a region that is not enriched is given p = 1, not evaluated: explainn_enrichment_test's rule).  logp is a
+ * function of (n_t, c, w, M) alone, so equal counts give equal bits.  Outputs, each [units] on the device and
+ * OVERWRITTEN:
+ *     best_t, best_lo, best_width (int32): the (threshold, region) of smallest logp; among equal values the
+ *     narrower region, then the lower lo, then the lower threshold index;
+ *     sites (int64) n_t and count (int64) c there;  n_tests (int64) m = tried thresholds x admissible regions;
+ *     log_pvalue (double) its logp;  log_padj (double) ln(1 - (1 - p)^m), by the two branches of
+ *     explainn_enrichment_test with the same switch point (log_pvalue < -30: min(0, ln m + log_pvalue));
+ *     ctrl_sites, ctrl_count (int64): the sum of the control row of best_t, and its part inside the region;
+ *     log_fisher (double): with (Np, Nc) = counts, ln P[X >= count], X ~ Hypergeometric(Np + Nc, Np, count +
+ *     ctrl_count), summed as explainn_enrichment_test sums it, where count Nc > ctrl_count Np (integers) and
+ *     Nc > 0; otherwise 0 -- also where count > Np or ctrl_count > Nc, counts that do not belong to hist.  It
+ *     is evaluated at the region the binomial test chose only (CentriMo's --neg).
+ * No threshold tried, or no admissible region (M == 1, or the widths leave none): best_t = best_lo =
+ * best_width = 0, sites = count = n_tests = ctrl_sites = ctrl_count = 0 and the three log values 0.
+ * Row sums must stay below 2^31.  One lane evaluates one (threshold, region) and the best is a minimum over
+ * keys: the result is a function of the input alone.  EXPLAINN_E_ARG: the shape limits above, mode not 0 or
+ * 1, min_width < 1, max_width < min_width, min_sites < 0, and in local mode more than
+ * EXPLAINN_CENTRALITY_MAX_REGIONS admissible regions per unit (M (M+1) / 2 - 1 without a width limit:
+ * M up to 2895 fits; the caller narrows max_width) -- the bound keeps one unit's evaluation, a lane per
+ * (threshold, region), to a few milliseconds.  units == 0 launches nothing.  No context, no workspace, no
+ * allocation, no host synchronisation. */
+#define EXPLAINN_CENTRALITY_MAX_THRESHOLDS 16
+#define EXPLAINN_CENTRALITY_MAX_REGIONS 4194304
+int explainn_site_positions(const uint16_t* best_bits, const int32_t* best_site, const uint8_t* labels,
+                            const float* thresholds, int units, int64_t n_records, int T, int M, int32_t* hist,
+                            int64_t* counts, void* stream);
+int explainn_centrality_test(const int32_t* hist, const int64_t* counts, int units, int T, int M, int mode,
+                             int min_width, int max_width, int64_t min_sites, int32_t* best_t, int32_t* best_lo,
+                             int32_t* best_width, int64_t* sites, int64_t* count, int64_t* n_tests,
+                             double* log_pvalue, double* log_padj, int64_t* ctrl_sites, int64_t* ctrl_count,
+                             double* log_fisher, void* stream);
+
 /* The fp32 one-hot packed into the context ahead of the forward: like explainn_stage_codes, the
  * entry points then take x == NULL.  Lets the caller read explainn_input_flags BEFORE anything
  * depends on the batch -- and route a batch that is not one-hot to the dense kernels (next entry)

@@ -74,7 +74,9 @@ ACTNULL = [r"^act_hist_kernel", r"^act_null_kernel"]
 SPACING = [r"^spacing_hist_kernel", r"^spacing_test_kernel"]
 # motif enrichment (enrich.hip): the per-record best site and the threshold test
 ENRICH = [r"^record_best_kernel<true>", r"^record_best_kernel<false>", r"^enrich_test_kernel"]
-GATED = C2_STEP + INPUT_GRAD + ISM + PATHGRAD + METRICS + SCAN + VARIANTS + HAPLOTYPES + SHUFFLE + MOTIFS + ACTNULL + SPACING + ENRICH
+# motif centrality (central.hip): the position histogram of best sites and the region test
+CENTRAL = [r"^site_positions_kernel", r"^centrality_test_kernel"]
+GATED = C2_STEP + INPUT_GRAD + ISM + PATHGRAD + METRICS + SCAN + VARIANTS + HAPLOTYPES + SHUFFLE + MOTIFS + ACTNULL + SPACING + ENRICH + CENTRAL
 
 
 # Register cliffs measured in the pipeline: 1024-thread blocks of which TWO must
