@@ -12,8 +12,8 @@ torch = pytest.importorskip("torch")
 
 from conftest import Golden  # noqa: E402
 from oracle import explainn_oracle as orc  # noqa: E402
-from parity_util import (NEAR_NULL, ZERO_GRAD, check_grads, close as _close,  # noqa: E402
-                         model as _model, oracle_step, to_np as _np)
+from parity_util import (GRAD_TOL_ORACLE, NEAR_NULL, ZERO_GRAD, check_grads, close as _close,  # noqa: E402
+                         close_rel as _close_rel, model as _model, oracle_step, to_np as _np)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -58,6 +58,12 @@ def test_sync_bn_shapes_vs_oracle(U, k, L, T, B, R):
     for e in engines:
         names = [n for n, _ in e.model.named_parameters()]
         check_grads(list(zip(names, e.views)), grads, "sync R=%d " % R)
+        bufs = dict(e.model.named_buffers())
+        for key, v in nb.items():
+            if "tracked" in key:
+                assert int(bufs[key].item()) == int(v), key
+            else:
+                _close_rel(_np(bufs[key]), v, tol=GRAD_TOL_ORACLE, what="sync R=%d %s" % (R, key))
     assert all(torch.equal(e.flat_grad, engines[0].flat_grad) for e in engines[1:])
 
 
