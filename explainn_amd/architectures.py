@@ -798,6 +798,23 @@ class ExplaiNN(_Model):
                 self._settle(read)
         return (logits, outs) if want_outs else logits
 
+    def _codes_front(self, codes, path, verb, start=0, reverse_complement=False):
+        """Front half of the launches that read a device-resident sequence of base codes with the
+        eval-mode tables: the eval-mode check (`path` is the message's subject), the check of `codes`
+        (`verb` is what is done on them), then _front.  Returns (ctx, ps, stream, xp, dev); the caller
+        checks its other arguments and makes its call inside torch.cuda.device(dev)."""
+        if self.training:
+            raise NotImplementedError("%s an eval-mode export path; call model.eval()" % path)
+        dev = self._device()
+        if not torch.is_tensor(codes) or codes.dtype != torch.uint8 or codes.dim() != 1 or \
+                not codes.is_contiguous():
+            raise RuntimeError("%s on a contiguous 1-D uint8 tensor of base codes" % verb)
+        if codes.device != dev:
+            raise RuntimeError("input is on %s but the model is on %s" % (codes.device, dev))
+        with torch.cuda.device(dev):
+            ctx, ps, _, stream, xp, _ = self._front(SequenceWindows(codes, start, 1, 1, reverse_complement, 1), dev)
+        return ctx, ps, stream, xp, dev
+
     def _launch_call_sites(self, codes, thresholds, start=0, n_positions=None, period=0,
                            reverse_complement=False, capacity=0, pos=None, score=None):
         """Motif sites of a device-resident 1-D uint8 sequence of base codes (explainn_call_sites):
@@ -807,15 +824,9 @@ class ExplaiNN(_Model):
         (start-relative) and score fp32 hold the first `capacity` records, unit by unit in ascending
         position.  capacity 0 counts only (pos and score are None); pos / score may be given as
         buffers of at least `capacity` elements.  n_positions None: every start the sequence holds."""
-        if self.training:
-            raise NotImplementedError("calling sites is an eval-mode export path; call model.eval()")
-        dev = self._device()
+        ctx, ps, stream, xp, dev = self._codes_front(codes, "calling sites is", "sites are called", start,
+                                                     reverse_complement)
         k, U = self._options["kernel_size"], self._units()
-        if not torch.is_tensor(codes) or codes.dtype != torch.uint8 or codes.dim() != 1 or \
-                not codes.is_contiguous():
-            raise RuntimeError("sites are called on a contiguous 1-D uint8 tensor of base codes")
-        if codes.device != dev:
-            raise RuntimeError("input is on %s but the model is on %s" % (codes.device, dev))
         if not torch.is_tensor(thresholds) or tuple(thresholds.shape) != (U,) or \
                 thresholds.dtype != torch.float32 or thresholds.device != dev or not thresholds.is_contiguous():
             raise RuntimeError("thresholds must be a contiguous float32 tensor of shape (%d,) on %s" % (U, dev))
@@ -836,8 +847,6 @@ class ExplaiNN(_Model):
         else:
             pos = score = None
         with torch.cuda.device(dev):
-            win = SequenceWindows(codes, start, 1, 1, reverse_complement, 1)
-            ctx, ps, _, stream, xp, _ = self._front(win, dev)
             lib, h = ctx.lib, ctx.handle
             nbytes = int(lib.explainn_call_sites_workspace_bytes(h, int(n_positions)))
             ws = torch.empty(max(nbytes, 1), device=dev, dtype=torch.uint8)
@@ -855,15 +864,8 @@ class ExplaiNN(_Model):
         on the device, unit-major (units, n_records): bits int16, the largest float16 activation's bit
         pattern (below 0x8000) over the record's live starts (0 without one), and site int32, (start << 1) | is_minus of
         the site that holds it (-1 without one; None unless want_site)."""
-        if self.training:
-            raise NotImplementedError("the best sites are an eval-mode export path; call model.eval()")
-        dev = self._device()
+        ctx, ps, stream, xp, dev = self._codes_front(codes, "the best sites are", "best sites are found")
         U = self._units()
-        if not torch.is_tensor(codes) or codes.dtype != torch.uint8 or codes.dim() != 1 or \
-                not codes.is_contiguous():
-            raise RuntimeError("best sites are found on a contiguous 1-D uint8 tensor of base codes")
-        if codes.device != dev:
-            raise RuntimeError("input is on %s but the model is on %s" % (codes.device, dev))
         if not torch.is_tensor(rec_offsets) or rec_offsets.dtype != torch.int64 or rec_offsets.dim() != 1 or \
                 rec_offsets.numel() < 1 or rec_offsets.device != dev or not rec_offsets.is_contiguous():
             raise RuntimeError("rec_offsets must be a contiguous 1-D int64 tensor of n_records + 1 entries on %s" % dev)
@@ -873,8 +875,6 @@ class ExplaiNN(_Model):
         bits = torch.empty((U, n), device=dev, dtype=torch.int16)
         site = torch.empty((U, n), device=dev, dtype=torch.int32) if want_site else None
         with torch.cuda.device(dev):
-            win = SequenceWindows(codes, 0, 1, 1, False, 1)
-            ctx, ps, _, stream, xp, _ = self._front(win, dev)
             _lib.check(ctx.lib.explainn_record_best(
                 ctx.handle, xp, codes.numel(), rec_offsets.data_ptr(), n, int(strands), C.byref(ps),
                 bits.data_ptr(), site.data_ptr() if want_site else None, stream))
@@ -888,15 +888,9 @@ class ExplaiNN(_Model):
         device, added into.  Live as in _launch_call_sites: with a period, a start whose k-mer would
         cross a record boundary is not counted.  n_positions None: every start the sequence holds.
         Returns hist."""
-        if self.training:
-            raise NotImplementedError("the activation null is an eval-mode export path; call model.eval()")
-        dev = self._device()
+        ctx, ps, stream, xp, dev = self._codes_front(codes, "the activation null is", "activations are counted",
+                                                     start, reverse_complement)
         k, U = self._options["kernel_size"], self._units()
-        if not torch.is_tensor(codes) or codes.dtype != torch.uint8 or codes.dim() != 1 or \
-                not codes.is_contiguous():
-            raise RuntimeError("activations are counted on a contiguous 1-D uint8 tensor of base codes")
-        if codes.device != dev:
-            raise RuntimeError("input is on %s but the model is on %s" % (codes.device, dev))
         if not torch.is_tensor(hist) or tuple(hist.shape) != (U, _lib.ACT_BINS) or \
                 hist.dtype != torch.int64 or hist.device != dev or not hist.is_contiguous():
             raise RuntimeError("hist must be a contiguous int64 tensor of shape (%d, %d) on %s"
@@ -904,8 +898,6 @@ class ExplaiNN(_Model):
         if n_positions is None:
             n_positions = max(codes.numel() - int(start) - k + 1, 0)
         with torch.cuda.device(dev):
-            win = SequenceWindows(codes, start, 1, 1, reverse_complement, 1)
-            ctx, ps, _, stream, xp, _ = self._front(win, dev)
             _lib.check(ctx.lib.explainn_activation_histogram(
                 ctx.handle, xp, codes.numel(), int(start), int(n_positions), int(period),
                 int(bool(reverse_complement)), C.byref(ps), hist.data_ptr(), stream))

@@ -11,14 +11,12 @@
 // act_hist_kernel: block = (unit, slice).  The unit's spans of EXPLAINN_ACT_SPAN starts are dealt round
 // robin to its slices; a block keeps ONE 32768 x uint32 histogram in LDS (128 KiB: one block per CU, 16
 // waves to hide the LDS-atomic latency) over all its spans -- a call has fewer than 2^31 starts, so no
-// bin overflows -- and flushes the non-zero bins once, with 64-bit integer global atomics.  The sum is
-// the chain of sites_kernel (sites.hip) for one unit: from 0.f, taps in j order, fp32, qval, float16.
+// bin overflows -- and flushes the non-zero bins once, with 64-bit integer global atomics.  The pattern
+// is codescan.h's, with one unit's taps as the accumulator.
 //
 // act_null_kernel: one wavefront per unit; a sum for the total, then a reverse scan over the bins (as
 // sites_scan_tiles_kernel scans forward) for tail[b] = sum_{b' >= b} hist[b'] and the threshold.
-#include <hip/hip_fp16.h>
-
-#include "common.h"
+#include "codescan.h"
 
 namespace {
 
@@ -44,8 +42,6 @@ __global__ __launch_bounds__(AN_T) void act_hist_kernel(
     const float* src = Wt + (size_t)(u >> 2) * k * 20 + (u & 3);
     for (int i = tid; i < k * 5; i += AN_T) Wsm[i] = src[(size_t)i * 4];
     const float al = alpha[u], sh = shift[u];
-    // forward: tap j meets cs[p + j]; reverse: the filter on rc(seq[p : p + k]) meets the complement
-    // of cs[p + k - 1 - j] (complemented when it is staged)
     const int first = rc ? k - 1 : 0, step = rc ? -1 : 1;
     const bool narrow = period > 0 && period < (1ll << 30);
     int bad = 0;
@@ -55,12 +51,7 @@ __global__ __launch_bounds__(AN_T) void act_hist_kernel(
         __syncthreads();                       // the bins are zeroed / the last span's codes are read
         // the span's bases and the k-1 behind its last start: all inside [start, start + npos + k - 1),
         // which the entry point has checked against seq_len
-        const uint8_t* sp = seq + start + t0;
-        for (int i = tid; i < live_n + k - 1; i += AN_T) {
-            int v = sp[i];
-            if (v > 4) { v = 4; bad = 1; }
-            cs[i] = (uint8_t)(rc && v < 4 ? 3 - v : v);
-        }
+        bad |= stage_codes<false>(seq + start + t0, live_n + k - 1, tid, AN_T, cs, rc, nullptr);
         __syncthreads();
         const long long r0 = period > 0 ? (start + t0) % period : 0;      // the span's first start in its record
         // AN_ILP positions per thread at a time: independent chains of (code byte -> tap -> add) in flight
@@ -80,17 +71,11 @@ __global__ __launch_bounds__(AN_T) void act_hist_kernel(
                     live[i] = live[i] && r <= period - k;
                 }
                 cp[i] = cs + min(p, live_n - 1) + first;       // a dead lane reads staged codes and counts nothing
-                acc[i] = 0.f;
             }
-            for (int j = 0; j < k; ++j) {
+            tap_chain(Wsm, k, cp, step, acc);
 #pragma unroll
-                for (int i = 0; i < AN_ILP; ++i) acc[i] += Wsm[j * 5 + cp[i][j * step]];
-            }
-#pragma unroll
-            for (int i = 0; i < AN_ILP; ++i) {
-                const unsigned bits = __half_as_ushort(__float2half_rn(qval(al, acc[i], sh)));
-                if (live[i]) atomicAdd(&h[bits & (AN_BINS - 1)], 1u);
-            }
+            for (int i = 0; i < AN_ILP; ++i)
+                if (live[i]) atomicAdd(&h[act_bits(al, acc[i], sh)], 1u);
         }
     }
     if (u == 0 && bad) atomicOr(flags, 1);
@@ -100,12 +85,6 @@ __global__ __launch_bounds__(AN_T) void act_hist_kernel(
         const unsigned v = h[b];
         if (v) atomicAdd(&row[b], (unsigned long long)v);
     }
-}
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // One wavefront per unit.  Lane l of chunk c holds bin 64 c + 63 - l, so an inclusive scan up the lanes,
@@ -127,13 +106,7 @@ __global__ __launch_bounds__(64) void act_null_kernel(const unsigned long long* 
     int above = 0;                             // patterns b' in [1, 0x7C01] with tail[b'] > m
     for (int c = AN_BINS / 64 - 1; c >= 0; --c) {
         const int b = c * 64 + 63 - lane;
-        unsigned long long inc = row[b];
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned long long t = __shfl_up(inc, o, 64);
-            if (lane >= o) inc += t;
-        }
-        inc += running;
+        const unsigned long long inc = wave_scan_up(row[b], lane) + running;
         if (tail) tail[(size_t)u * AN_BINS + b] = inc;
         above += __popcll(__ballot(b >= 1 && b <= AN_INF + 1 && inc > m));
         running = __shfl(inc, 63, 64);

@@ -667,25 +667,44 @@ extern "C" int64_t explainn_call_sites_workspace_bytes(const explainn_ctx* c, in
     return sites_workspace_bytes(c, n_positions);
 }
 
+namespace {
+// The range of start positions call_sites and activation_histogram take of a raw code sequence: every
+// k-mer of [start, start + n_positions) lies inside the sequence, and a position fits an int.
+int check_code_range(const char* what, const explainn_ctx* c, int64_t seq_len, int64_t start, int64_t n_positions) {
+    if (!c) { explainn_set_error("null context"); return EXPLAINN_E_ARG; }
+    if (start < 0 || n_positions < 0 || n_positions + c->k >= (int64_t)1 << 31 ||
+        seq_len - start < n_positions + c->k - 1) {
+        explainn_set_error("%s needs 0 <= start, start + n_positions + k - 1 <= seq_len and "
+                           "n_positions + k < 2^31 (start %lld, n_positions %lld, k %d, seq_len %lld)", what,
+                           (long long)start, (long long)n_positions, c->k, (long long)seq_len);
+        return EXPLAINN_E_ARG;
+    }
+    return EXPLAINN_OK;
+}
+
+// What an entry point that reads a raw code sequence with the eval-mode tables does once its own
+// arguments have passed: `what` are done "on base codes", so not in dense input mode; nothing is staged
+// by such a call and what was staged (or pending) is not kept; the folded tables are current.
+int code_scan_begin(explainn_ctx* c, const explainn_params* p, const char* what, hipStream_t s) {
+    if (!c) { explainn_set_error("null context"); return EXPLAINN_E_ARG; }
+    if (c->dense) { explainn_set_error("%s on base codes: not in dense input mode", what); return EXPLAINN_E_UNSUPPORTED; }
+    drop_pending(c);
+    c->staged_B = 0;
+    return eval_tables(c, p, 1, s);
+}
+}  // namespace
+
 extern "C" int explainn_call_sites(explainn_ctx* c, const uint8_t* seq, int64_t seq_len, int64_t start,
                                    int64_t n_positions, int64_t period, int reverse_complement,
                                    const explainn_params* p, const float* thresholds, int64_t* offsets,
                                    int32_t* pos, float* score, int64_t capacity, void* workspace,
                                    int64_t workspace_bytes, void* stream) {
-    if (!c) { explainn_set_error("null context"); return EXPLAINN_E_ARG; }
     if (!seq || !p || !thresholds || !offsets) {
         explainn_set_error("seq, params, thresholds and offsets are required");
         return EXPLAINN_E_ARG;
     }
-    if (start < 0 || n_positions < 0 || n_positions + c->k >= (int64_t)1 << 31 ||
-        seq_len - start < n_positions + c->k - 1) {
-        explainn_set_error("call_sites needs 0 <= start, start + n_positions + k - 1 <= seq_len and "
-                           "n_positions + k < 2^31 (start %lld, n_positions %lld, k %d, seq_len %lld)",
-                           (long long)start, (long long)n_positions, c->k, (long long)seq_len);
-        return EXPLAINN_E_ARG;
-    }
+    TRY(check_code_range("call_sites", c, seq_len, start, n_positions));
     if (period < 0 || capacity < 0) { explainn_set_error("period and capacity must not be negative"); return EXPLAINN_E_ARG; }
-    if (c->dense) { explainn_set_error("sites are called on base codes: not in dense input mode"); return EXPLAINN_E_UNSUPPORTED; }
     const int64_t need = sites_workspace_bytes(c, n_positions);
     if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 255) != 0) {
         explainn_set_error("call_sites workspace of %lld bytes (256-byte aligned), %lld needed",
@@ -693,9 +712,7 @@ extern "C" int explainn_call_sites(explainn_ctx* c, const uint8_t* seq, int64_t 
         return EXPLAINN_E_ARG;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    drop_pending(c);
-    c->staged_B = 0;                   // nothing is staged by this call; what was staged is not kept
-    TRY(eval_tables(c, p, 1, s));
+    TRY(code_scan_begin(c, p, "sites are called", s));
     if (n_positions == 0) {
         HIP_TRY(hipMemsetAsync(offsets, 0, (size_t)(c->U + 1) * sizeof(int64_t), s));
         return EXPLAINN_OK;
@@ -707,21 +724,11 @@ extern "C" int explainn_call_sites(explainn_ctx* c, const uint8_t* seq, int64_t 
 extern "C" int explainn_activation_histogram(explainn_ctx* c, const uint8_t* seq, int64_t seq_len, int64_t start,
                                              int64_t n_positions, int64_t period, int reverse_complement,
                                              const explainn_params* p, uint64_t* hist, void* stream) {
-    if (!c) { explainn_set_error("null context"); return EXPLAINN_E_ARG; }
     if (!seq || !p || !hist) { explainn_set_error("seq, params and hist are required"); return EXPLAINN_E_ARG; }
-    if (start < 0 || n_positions < 0 || n_positions + c->k >= (int64_t)1 << 31 ||
-        seq_len - start < n_positions + c->k - 1) {
-        explainn_set_error("activation_histogram needs 0 <= start, start + n_positions + k - 1 <= seq_len and "
-                           "n_positions + k < 2^31 (start %lld, n_positions %lld, k %d, seq_len %lld)",
-                           (long long)start, (long long)n_positions, c->k, (long long)seq_len);
-        return EXPLAINN_E_ARG;
-    }
+    TRY(check_code_range("activation_histogram", c, seq_len, start, n_positions));
     if (period < 0) { explainn_set_error("period must not be negative"); return EXPLAINN_E_ARG; }
-    if (c->dense) { explainn_set_error("activations are counted on base codes: not in dense input mode"); return EXPLAINN_E_UNSUPPORTED; }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    drop_pending(c);
-    c->staged_B = 0;                   // nothing is staged by this call; what was staged is not kept
-    TRY(eval_tables(c, p, 1, s));
+    TRY(code_scan_begin(c, p, "activations are counted", s));
     if (n_positions == 0) return EXPLAINN_OK;
     return launch_activation_histogram(c, seq, start, n_positions, period, reverse_complement ? 1 : 0, hist, s);
 }
@@ -729,7 +736,6 @@ extern "C" int explainn_activation_histogram(explainn_ctx* c, const uint8_t* seq
 extern "C" int explainn_record_best(explainn_ctx* c, const uint8_t* seq, int64_t seq_len, const int64_t* rec_offsets,
                                     int64_t n_records, int strands, const explainn_params* p, uint16_t* best_bits,
                                     int32_t* best_site, void* stream) {
-    if (!c) { explainn_set_error("null context"); return EXPLAINN_E_ARG; }
     if (!seq || !p || !rec_offsets || !best_bits) {
         explainn_set_error("seq, rec_offsets, params and best_bits are required");
         return EXPLAINN_E_ARG;
@@ -740,11 +746,8 @@ extern "C" int explainn_record_best(explainn_ctx* c, const uint8_t* seq, int64_t
                            strands);
         return EXPLAINN_E_ARG;
     }
-    if (c->dense) { explainn_set_error("best sites are found on base codes: not in dense input mode"); return EXPLAINN_E_UNSUPPORTED; }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    drop_pending(c);
-    c->staged_B = 0;                   // nothing is staged by this call; what was staged is not kept
-    TRY(eval_tables(c, p, 1, s));
+    TRY(code_scan_begin(c, p, "best sites are found", s));
     if (n_records == 0) return EXPLAINN_OK;
     return launch_record_best(c, seq, seq_len, rec_offsets, n_records, strands, best_bits, best_site, s);
 }

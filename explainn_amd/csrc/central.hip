@@ -124,12 +124,7 @@ __global__ __launch_bounds__(CT_T) void centrality_test_kernel(
             unsigned running = 0;
             for (int b0 = 0; b0 < M; b0 += 64) {
                 const int b = b0 + lane;
-                unsigned inc = b < M ? (unsigned)row[b] : 0u;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const unsigned v = __shfl_up(inc, o, 64);
-                    if (lane >= o) inc += v;
-                }
+                const unsigned inc = wave_scan_up(b < M ? (unsigned)row[b] : 0u, lane);
                 if (b < M) pre[b] = running + inc;
                 running += __shfl(inc, 63, 64);
             }
@@ -185,11 +180,8 @@ __global__ __launch_bounds__(CT_T) void centrality_test_kernel(
                 cb += b >= blo && b < blo + bw ? v : 0;
             }
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            ca += __shfl_xor(ca, o, 64);
-            cb += __shfl_xor(cb, o, 64);
-        }
+        ca = wave_sum(ca);
+        cb = wave_sum(cb);
         if (lane == 0) { red_a[wave] = ca; red_b[wave] = cb; }
         __syncthreads();
         if (tid == 0) {

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/explainn_hip.h"
 
 #define FC_H 100          // hidden width of the per-unit FC (architectures/__init__.py:86)
@@ -440,6 +442,35 @@ __device__ __forceinline__ float wave_sum(float v) {
 __device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+// the integer forms (int, unsigned, long long, unsigned long long): sum, maximum, and the inclusive
+// scan up the lanes (lane = threadIdx.x & 63; lane 63 ends up with the wave's sum)
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+    static_assert(std::is_integral<T>::value, "floating point sums: wave_sum(float), wave_sum_d");
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+template <typename T>
+__device__ __forceinline__ T wave_max(T v) {
+    static_assert(std::is_integral<T>::value, "an integer maximum");
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const T t = __shfl_xor(v, off, 64);
+        v = t > v ? t : v;
+    }
+    return v;
+}
+template <typename T>
+__device__ __forceinline__ T wave_scan_up(T v, int lane) {
+    static_assert(std::is_integral<T>::value, "an integer scan");
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const T t = __shfl_up(v, off, 64);
+        if (lane >= off) v += t;
+    }
     return v;
 }
 

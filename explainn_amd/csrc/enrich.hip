@@ -4,8 +4,8 @@
 // record_best_kernel: block = one wavefront = (slice of records, unit quad).  The quad's taps sit in LDS as
 // float4 [k][5], as in sites_kernel; the records are dealt round robin to the slices.  A record is walked in
 // passes of EXPLAINN_BEST_SPAN starts: the pass's bases (and their complements) are staged in LDS, every
-// lane takes SPAN / 64 starts and runs both strands' chains in one tap loop -- the chain of sites_kernel:
-// from 0.f, taps in j order, fp32, qval, float16.  Every (start, strand) becomes the integer key
+// lane takes SPAN / 64 starts and runs both strands' chains in one tap loop -- codescan.h's chain and bit
+// pattern.  Every (start, strand) becomes the integer key
 //     bits << 31 | (~start & 0x3FFFFFFF) << 1 | is_plus
 // so the largest key is the largest activation, then the lowest start, then '+': a lane keeps its largest
 // key over the record's passes and one wave max per (record, unit) decides.  No atomics but the input flag.
@@ -17,10 +17,8 @@
 // 32-bit integer LDS operations (fewer than 2^31 records); the hypergeometric tail is spacing_test's rule in
 // fp64, one lane per threshold, and the best threshold is a min over (logp, -pattern) pairs: nothing depends
 // on the order in which anything arrives.
-#include <hip/hip_fp16.h>
-
-#include "common.h"
-#include "tails.h"                              // hypergeom_logsf
+#include "codescan.h"
+#include "tails.h"                             // hypergeom_logsf
 
 namespace {
 
@@ -30,22 +28,14 @@ constexpr int RB_BLOCKS = 16384;               // the records are cut into slice
 constexpr long long RB_MAX_LEN = 1ll << 30;    // a record this long has no int32 (start << 1 | strand)
 static_assert(RB_SPAN % 64 == 0 && RB_ILP >= 1, "a pass is a whole number of starts per lane");
 
-__device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long t = __shfl_xor(v, o, 64);
-        v = t > v ? t : v;
-    }
-    return v;
-}
-
 __device__ __forceinline__ unsigned long long best_key(unsigned bits, int p, int plus) {
     return ((unsigned long long)bits << 31) | ((unsigned long long)(~(unsigned)p & 0x3FFFFFFFu) << 1) |
            (unsigned long long)plus;
 }
 
+// (the second launch bound: the waves per SIMD the two forms run at)
 template <bool BOTH>
-__global__ __launch_bounds__(64) void record_best_kernel(
+__global__ __launch_bounds__(64, BOTH ? 4 : 8) void record_best_kernel(
     const uint8_t* __restrict__ seq, long long seq_len, const long long* __restrict__ off, int n_records,
     const float* __restrict__ Wt, const float* __restrict__ alpha, const float* __restrict__ shift,
     uint16_t* __restrict__ best_bits, int32_t* __restrict__ best_site, int U, int k, int* __restrict__ flags) {
@@ -77,13 +67,7 @@ __global__ __launch_bounds__(64) void record_best_kernel(
             const int live_n = min(RB_SPAN, n_starts - t0);
             __syncthreads();                   // the taps are staged / the last pass's codes are read
             // the pass's bases and the k - 1 behind its last start: inside [a, b), inside seq
-            const uint8_t* sp = seq + a + t0;
-            for (int i = lane; i < live_n + k - 1; i += 64) {
-                int v = sp[i];
-                if (v > 4) { v = 4; bad = 1; }
-                cs[i] = (uint8_t)v;
-                cc[i] = (uint8_t)(v < 4 ? 3 - v : v);
-            }
+            bad |= stage_codes<true>(seq + a + t0, live_n + k - 1, lane, 64, cs, 0, cc);
             __syncthreads();
             float4 fw[RB_ILP], rv[RB_ILP];
             const uint8_t* fp[RB_ILP];
@@ -93,22 +77,8 @@ __global__ __launch_bounds__(64) void record_best_kernel(
                 const int p = min(lane + i * 64, live_n - 1);      // a dead lane reads staged codes and keeps nothing
                 fp[i] = cs + p;
                 rp[i] = cc + p + k - 1;
-                fw[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-                rv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
             }
-            // forward: tap j meets cs[p + j]; reverse: the filter on rc(seq[p : p + k]) meets the complement
-            // of cs[p + k - 1 - j]
-            for (int j = 0; j < k; ++j) {
-#pragma unroll
-                for (int i = 0; i < RB_ILP; ++i) {
-                    const float4 v = rb_sm[j * 5 + fp[i][j]];
-                    fw[i].x += v.x; fw[i].y += v.y; fw[i].z += v.z; fw[i].w += v.w;
-                    if (BOTH) {
-                        const float4 w = rb_sm[j * 5 + rp[i][-j]];
-                        rv[i].x += w.x; rv[i].y += w.y; rv[i].z += w.z; rv[i].w += w.w;
-                    }
-                }
-            }
+            tap_chains<BOTH>(rb_sm, k, fp, 1, fw, rp, rv);
 #pragma unroll
             for (int i = 0; i < RB_ILP; ++i) {
                 if (lane + i * 64 >= live_n) continue;
@@ -117,11 +87,9 @@ __global__ __launch_bounds__(64) void record_best_kernel(
                 const float g[4] = {rv[i].x, rv[i].y, rv[i].z, rv[i].w};
 #pragma unroll
                 for (int uu = 0; uu < 4; ++uu) {
-                    const unsigned fb = __half_as_ushort(__float2half_rn(qval(al[uu], f[uu], sh[uu]))) & 0x7FFFu;
-                    unsigned long long kk = best_key(fb, p, 1);
+                    unsigned long long kk = best_key(act_bits(al[uu], f[uu], sh[uu]), p, 1);
                     if (BOTH) {
-                        const unsigned gb = __half_as_ushort(__float2half_rn(qval(al[uu], g[uu], sh[uu]))) & 0x7FFFu;
-                        const unsigned long long km = best_key(gb, p, 0);
+                        const unsigned long long km = best_key(act_bits(al[uu], g[uu], sh[uu]), p, 0);
                         kk = km > kk ? km : kk;
                     }
                     key[uu] = kk > key[uu] ? kk : key[uu];
@@ -165,12 +133,7 @@ __device__ __forceinline__ void tail_scan(unsigned* h, unsigned* ws, unsigned* _
     unsigned running = 0;
     for (int c = EN_BINS / EN_T - 1; c >= 0; --c) {
         const int b = c * EN_T + EN_T - 1 - tid;
-        unsigned inc = h[b];
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned t = __shfl_up(inc, o, 64);
-            if (lane >= o) inc += t;
-        }
+        unsigned inc = wave_scan_up(h[b], lane);
         if (lane == 63) ws[wave] = inc;
         __syncthreads();
         unsigned before = 0, total = 0;

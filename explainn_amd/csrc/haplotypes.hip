@@ -117,13 +117,7 @@ __global__ __launch_bounds__(64 * SW_WAVES) void stage_haplotypes_kernel(
                 // after = the shift behind the edit: inclusive wave prefix sum of alt_len - ref_len
                 // (0 in the lanes past the run) on top of the chunks before
                 const long long delta = (long long)al - rl;
-                long long after = delta;
-#pragma unroll
-                for (int off = 1; off < 64; off <<= 1) {
-                    const long long t = __shfl_up(after, off);
-                    if (lane >= off) after += t;
-                }
-                after = wadd(after, carry);
+                const long long after = wadd(wave_scan_up(delta, lane), carry);
                 wave_lds_order();                    // the searches of the chunk before are done
                 run_h[q][lane] = wadd(pos, wsub(after, delta));
                 run_s[q][lane] = after;

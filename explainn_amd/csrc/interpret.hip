@@ -9,18 +9,13 @@
 // materialised.  Block = (sequence, unit quad), threads over start positions, so the in-sequence
 // order of sites is the thread order and a site's global rank is
 //     offset[unit][sequence] (exclusive scan of per-sequence counts) + rank inside the sequence.
-#include <hip/hip_fp16.h>
-
-#include "common.h"
+#include "codescan.h"
 
 namespace {
 
 constexpr int SITE_T = 256;
 
 enum { SITE_MAX = 0, SITE_COUNT = 1, SITE_ACCUM = 2 };
-
-// float32 activation -> the float16 value numpy stores (round-to-nearest-even, overflow -> inf)
-__device__ __forceinline__ float as_f16(float a) { return __half2float(__float2half_rn(a)); }
 
 template <int MODE>
 __global__ __launch_bounds__(SITE_T) void site_kernel(
@@ -61,50 +56,37 @@ __global__ __launch_bounds__(SITE_T) void site_kernel(
     for (int p0 = 0; p0 < Lo; p0 += SITE_T) {
         const int p = p0 + tid;
         const bool live = p < Lo;
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (live)
-            for (int j = 0; j < k; ++j) {
-                const float4 v = Wsm[j * 5 + cs[p + j]];
-                acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-            }
-        const float av[4] = {acc.x, acc.y, acc.z, acc.w};
+        float a16[4] = {0.f, 0.f, 0.f, 0.f};
+        if (live) {
+            const uint8_t* const cp[1] = {cs + p};
+            float4 acc[1];
+            tap_chain(Wsm, k, cp, 1, acc);
+            const float av[4] = {acc[0].x, acc[0].y, acc[0].z, acc[0].w};
+#pragma unroll
+            for (int uu = 0; uu < 4; ++uu) a16[uu] = act_value(al[uu], av[uu], sh[uu]);
+        }
+        if (MODE == SITE_MAX) {
+#pragma unroll
+            for (int uu = 0; uu < 4; ++uu) mx[uu] = fmaxf(mx[uu], a16[uu]);
+            continue;
+        }
         bool hit[4];
-        int pre[4];
+#pragma unroll
+        for (int uu = 0; uu < 4; ++uu) hit[uu] = live && a16[uu] > th[uu];
+        int pre[4], total[4];
+        block_hit_ranks<SITE_T>(hit, wtot, pre, total);
 #pragma unroll
         for (int uu = 0; uu < 4; ++uu) {
-            const float a16 = live ? as_f16(qval(al[uu], av[uu], sh[uu])) : 0.f;
-            if (MODE == SITE_MAX) {
-                mx[uu] = fmaxf(mx[uu], a16);
-            } else {
-                hit[uu] = live && a16 > th[uu];
-                const unsigned long long bal = __ballot(hit[uu]);
-                pre[uu] = __popcll(bal & ((1ull << lane) - 1ull));
-                if (lane == 0) wtot[uu][wave] = __popcll(bal);
+            if (MODE == SITE_ACCUM && hit[uu]) {
+                // rank of this site among all sites of the unit (interpret.py:398-425 order)
+                const long long rank = (long long)base[uu] + run[uu] + pre[uu];
+                if (rank < cap)
+                    for (int t = 0; t < k; ++t) {
+                        const int cd = cs[p + t];
+                        if (cd < 4) atomicAdd(&hist[(uu * k + t) * 4 + cd], 1);
+                    }
             }
-        }
-        if (MODE != SITE_MAX) {
-            __syncthreads();
-#pragma unroll
-            for (int uu = 0; uu < 4; ++uu) {
-                int before = 0, total = 0;
-#pragma unroll
-                for (int w = 0; w < SITE_T / 64; ++w) {
-                    const int t = wtot[uu][w];
-                    before += w < wave ? t : 0;
-                    total += t;
-                }
-                if (MODE == SITE_ACCUM && hit[uu]) {
-                    // rank of this site among all sites of the unit (interpret.py:398-425 order)
-                    const long long rank = (long long)base[uu] + run[uu] + before + pre[uu];
-                    if (rank < cap)
-                        for (int t = 0; t < k; ++t) {
-                            const int cd = cs[p + t];
-                            if (cd < 4) atomicAdd(&hist[(uu * k + t) * 4 + cd], 1);
-                        }
-                }
-                run[uu] += total;
-            }
-            __syncthreads();                   // wtot is rewritten by the next chunk
+            run[uu] += total[uu];
         }
     }
     if (MODE == SITE_MAX) {
@@ -146,12 +128,7 @@ __global__ __launch_bounds__(64) void site_scan_kernel(const int* __restrict__ c
     for (int b0 = 0; b0 < B; b0 += 64) {
         const int b = b0 + lane;
         const int v = b < B ? cnt[(size_t)u * Bs + b] : 0;
-        int inc = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(inc, o, 64);
-            if (lane >= o) inc += t;
-        }
+        const int inc = wave_scan_up(v, lane);
         if (b < B) {
             const long long o64 = running + (inc - v);
             off[(size_t)u * Bs + b] = (int)(o64 < cap ? o64 : cap);

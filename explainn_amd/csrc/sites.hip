@@ -5,9 +5,8 @@
 //
 // In eval mode BatchNorm1 is folded, so a unit's activation at a position depends only on the k bases
 // under it: one gather pass over the codes, tile by tile, lists the hits of every unit without a
-// window ever being cut.  The sum is the chain of conv_act_kernel (convpool.hip) and site_kernel
-// (interpret.hip) -- from 0.f, taps in j order, fp32 -- which is what makes a site here a position
-// where float16(linears[:3]) > threshold, bit for bit.
+// window ever being cut.  The activation is the one definition of codescan.h, which is what makes a
+// site here a position where float16(linears[:3]) > threshold, bit for bit.
 //
 // Block = (tile of SITES_TILE positions, unit quad).  Two passes of the same kernel recompute the
 // activations instead of storing them:
@@ -17,9 +16,7 @@
 //   EMIT   rank = offsets[u] + cnt[u][tile] + rank inside the tile (ballots and popcounts in thread =
 //          position order); records with rank >= capacity are dropped
 // so per unit the sites ascend in position and no rank depends on the order atomics arrive in.
-#include <hip/hip_fp16.h>
-
-#include "common.h"
+#include "codescan.h"
 
 namespace {
 
@@ -27,9 +24,6 @@ constexpr int SITES_T = 256;
 static_assert(EXPLAINN_SITES_TILE % SITES_T == 0, "a tile is a whole number of position chunks");
 
 enum { SITES_COUNT = 0, SITES_EMIT = 1 };
-
-// float32 activation -> the float16 value numpy stores (as interpret.hip)
-__device__ __forceinline__ float as_f16(float a) { return __half2float(__float2half_rn(a)); }
 
 template <int MODE>
 __global__ __launch_bounds__(SITES_T) void sites_kernel(
@@ -42,20 +36,13 @@ __global__ __launch_bounds__(SITES_T) void sites_kernel(
     uint8_t* cs = reinterpret_cast<uint8_t*>(Wsm + k * 5);
     __shared__ int wtot[4][SITES_T / 64];
     const int tile = blockIdx.x, quad = blockIdx.y, tid = threadIdx.x;
-    const int wave = tid >> 6, lane = tid & 63;
     const int t0 = tile * EXPLAINN_SITES_TILE;              // < npos < 2^31
     const int live_n = min(EXPLAINN_SITES_TILE, npos - t0); // start positions of this tile
     const float4* src = reinterpret_cast<const float4*>(Wt) + (size_t)quad * k * 5;
     for (int i = tid; i < k * 5; i += SITES_T) Wsm[i] = src[i];
     // the tile's bases and the k-1 behind its last start: all inside [start, start + npos + k - 1),
     // which the entry point has checked against seq_len.  The reverse strand reads the complement.
-    int bad = 0;
-    const uint8_t* sp = seq + start + t0;
-    for (int i = tid; i < live_n + k - 1; i += SITES_T) {
-        int v = sp[i];
-        if (v > 4) { v = 4; bad = 1; }
-        cs[i] = (uint8_t)(rc && v < 4 ? 3 - v : v);
-    }
+    const int bad = stage_codes<false>(seq + start + t0, live_n + k - 1, tid, SITES_T, cs, rc, nullptr);
     if (MODE == SITES_COUNT && quad == 0 && bad) atomicOr(flags, 1);
     float al[4], sh[4], th[4];
     long long base[4];
@@ -68,55 +55,38 @@ __global__ __launch_bounds__(SITES_T) void sites_kernel(
         base[uu] = MODE == SITES_EMIT ? offsets[u] + cnt[(size_t)u * ntiles + tile] : 0;
     }
     __syncthreads();
-    // forward: tap j meets cs[p + j]; reverse: the filter on rc(seq[p : p + k]) meets the
-    // complement of cs[p + k - 1 - j] (already complemented above)
-    const int first = rc ? k - 1 : 0, step = rc ? -1 : 1;
+    const int first = rc ? k - 1 : 0, step = rc ? -1 : 1;      // (the codes are complemented already)
     int run[4] = {0, 0, 0, 0};                 // sites of this tile in earlier position chunks
     for (int p0 = 0; p0 < live_n; p0 += SITES_T) {
         const int p = p0 + tid;
         bool live = p < live_n;
         // a start whose k-mer would cross the end of its record is never a site
         if (period > 0 && (start + t0 + p) % period > period - k) live = false;
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        float a16[4] = {0.f, 0.f, 0.f, 0.f};
         if (live) {
-            const uint8_t* cp = cs + p + first;
-            for (int j = 0; j < k; ++j) {
-                const float4 v = Wsm[j * 5 + cp[j * step]];
-                acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-            }
+            const uint8_t* const cp[1] = {cs + p + first};
+            float4 acc[1];
+            tap_chain(Wsm, k, cp, step, acc);
+            const float av[4] = {acc[0].x, acc[0].y, acc[0].z, acc[0].w};
+#pragma unroll
+            for (int uu = 0; uu < 4; ++uu) a16[uu] = act_value(al[uu], av[uu], sh[uu]);
         }
-        const float av[4] = {acc.x, acc.y, acc.z, acc.w};
-        float a16[4];
         bool hit[4];
-        int pre[4];
+#pragma unroll
+        for (int uu = 0; uu < 4; ++uu) hit[uu] = live && a16[uu] > th[uu];
+        int pre[4], total[4];
+        block_hit_ranks<SITES_T>(hit, wtot, pre, total);
 #pragma unroll
         for (int uu = 0; uu < 4; ++uu) {
-            a16[uu] = live ? as_f16(qval(al[uu], av[uu], sh[uu])) : 0.f;
-            hit[uu] = live && a16[uu] > th[uu];
-            const unsigned long long bal = __ballot(hit[uu]);
-            pre[uu] = __popcll(bal & ((1ull << lane) - 1ull));
-            if (lane == 0) wtot[uu][wave] = __popcll(bal);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int uu = 0; uu < 4; ++uu) {
-            int before = 0, total = 0;
-#pragma unroll
-            for (int w = 0; w < SITES_T / 64; ++w) {
-                const int t = wtot[uu][w];
-                before += w < wave ? t : 0;
-                total += t;
-            }
             if (MODE == SITES_EMIT && hit[uu] && quad * 4 + uu < U) {
-                const long long rank = base[uu] + run[uu] + before + pre[uu];
+                const long long rank = base[uu] + run[uu] + pre[uu];
                 if (rank < capacity) {
                     pos[rank] = t0 + p;
                     if (score) score[rank] = a16[uu];
                 }
             }
-            run[uu] += total;
+            run[uu] += total[uu];
         }
-        __syncthreads();                       // wtot is rewritten by the next chunk
     }
     if (MODE == SITES_COUNT && tid < 4 && quad * 4 + tid < U)
         cnt[(size_t)(quad * 4 + tid) * ntiles + tile] = run[tid];
@@ -132,12 +102,7 @@ __global__ __launch_bounds__(64) void sites_scan_tiles_kernel(int* __restrict__ 
     for (int b0 = 0; b0 < ntiles; b0 += 64) {
         const int b = b0 + lane;
         const int v = b < ntiles ? row[b] : 0;
-        int inc = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(inc, o, 64);
-            if (lane >= o) inc += t;
-        }
+        const int inc = wave_scan_up(v, lane);
         if (b < ntiles) row[b] = running + (inc - v);
         running += __shfl(inc, 63, 64);
     }
@@ -152,12 +117,7 @@ __global__ __launch_bounds__(64) void sites_scan_units_kernel(const long long* _
     for (int u0 = 0; u0 < U; u0 += 64) {
         const int u = u0 + lane;
         const long long v = u < U ? tot[u] : 0;
-        long long inc = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const long long t = __shfl_up(inc, o, 64);
-            if (lane >= o) inc += t;
-        }
+        const long long inc = wave_scan_up(v, lane);
         if (u < U) offsets[u] = running + (inc - v);
         running += __shfl(inc, 63, 64);
     }

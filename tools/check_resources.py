@@ -76,7 +76,12 @@ SPACING = [r"^spacing_hist_kernel", r"^spacing_test_kernel"]
 ENRICH = [r"^record_best_kernel<true>", r"^record_best_kernel<false>", r"^enrich_test_kernel"]
 # motif centrality (central.hip): the position histogram of best sites and the region test
 CENTRAL = [r"^site_positions_kernel", r"^centrality_test_kernel"]
-GATED = C2_STEP + INPUT_GRAD + ISM + PATHGRAD + METRICS + SCAN + VARIANTS + HAPLOTYPES + SHUFFLE + MOTIFS + ACTNULL + SPACING + ENRICH + CENTRAL
+# the site callers (sites.hip: count / emit and the two scans; interpret.hip: maximum / count / accumulate
+# of the filter -> PWM export and its scan)
+SITES = [r"^sites_kernel<0>", r"^sites_kernel<1>", r"^sites_scan_tiles_kernel", r"^sites_scan_units_kernel",
+         r"^site_kernel<0>", r"^site_kernel<1>", r"^site_kernel<2>", r"^site_scan_kernel"]
+GATED = (C2_STEP + INPUT_GRAD + ISM + PATHGRAD + METRICS + SCAN + VARIANTS + HAPLOTYPES + SHUFFLE + MOTIFS + ACTNULL +
+         SPACING + ENRICH + CENTRAL + SITES)
 
 
 # Register cliffs measured in the pipeline: 1024-thread blocks of which TWO must
