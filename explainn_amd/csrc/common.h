@@ -316,6 +316,41 @@ extern __device__ unsigned long long g_stamps[];
 // Pattern: issue all loads into an array, KEEP() each element in a second loop, then compute.
 #define KEEP(x) asm volatile("" : "+v"(x))
 
+// The sub-batch of an entry point that works through a batch in pieces of one workspace (ISM, IG): the
+// sequences that fit cap_bytes at per_sequence_bytes each, in whole steps (a wave: lane = sequence), at
+// least one step, no more than the batch rounded up to a step.
+#define SUB_BATCH_STEP 64
+__host__ inline int sub_batch_of(int64_t cap_bytes, int64_t per_sequence_bytes, int B) {
+    int64_t s = cap_bytes / per_sequence_bytes / SUB_BATCH_STEP * SUB_BATCH_STEP;
+    if (s < SUB_BATCH_STEP) s = SUB_BATCH_STEP;
+    const int64_t bb = ((int64_t)B + SUB_BATCH_STEP - 1) / SUB_BATCH_STEP * SUB_BATCH_STEP;
+    return (int)(s < bb ? s : bb);
+}
+
+// acc += w s, one FMA per base (the transposed convolutions of inputgrad.hip and pathgrad.hip)
+__device__ __forceinline__ void fma4(float4& acc, const float4& w, float s) {
+    acc.x = fmaf(w.x, s, acc.x); acc.y = fmaf(w.y, s, acc.y);
+    acc.z = fmaf(w.z, s, acc.z); acc.w = fmaf(w.w, s, acc.w);
+}
+
+// The filters of units u0 .. u0 + UT - 1 as float4 over the bases, Ws[uu * MAX_K + t] (zeros past U), by
+// all nthreads threads of the block between two barriers of the caller; SCALED: times the unit's alpha.
+template <bool SCALED, int UT>
+__device__ __forceinline__ void stage_filters4(const float* __restrict__ W, const float* __restrict__ alpha,
+                                               int u0, int U, int k, int tid, int nthreads, float4* Ws) {
+    for (int i = tid; i < UT * k; i += nthreads) {
+        const int uu = i / k, t = i - uu * k, u = u0 + uu;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (u < U) {
+            const float a = SCALED ? alpha[u] : 1.f;
+            const float* wr = W + (size_t)u * 4 * k + t;
+            v = SCALED ? make_float4(a * wr[0], a * wr[k], a * wr[2 * k], a * wr[3 * k])
+                       : make_float4(wr[0], wr[k], wr[2 * k], wr[3 * k]);
+        }
+        Ws[uu * MAX_K + t] = v;
+    }
+}
+
 // The filter bank as a GEMM (convpool.hip) on v_mfma_f32_32x32x16_bf16: k-steps of 16 (4 taps x 4
 // bases), 32-unit tiles, two tiles per wave while their fragments and three operand buffers fit
 __host__ __device__ inline int conv_ksteps(int k) { return (k + 3) / 4; }

@@ -15,6 +15,7 @@
 // and identifies the pair, so it indexes the 2k-1 distinct tables (the interior class is k-1).
 // Every sum is in a fixed order; no float atomics.
 #include "common.h"
+#include "unit_eval.h"
 
 #define IG_POS 8             // positions per input_grad workgroup
 #define IG_UT 64             // units whose filters one LDS pass stages (16 per wave)
@@ -29,7 +30,7 @@ __device__ __forceinline__ int ig_class(int p, int k, int Lo) {
 // sequence.  y2 = A2 q + sh2 is recomputed here (the forward keeps no ReLU bits in eval mode): the
 // unit's A2 is staged in LDS (rows padded to whole chunks of 16 pooled positions, zeros past n) and
 // read at wave-uniform addresses; each thread's 100 channels live in an LDS column, the pooled
-// positions go by in register chunks of 16.
+// positions go by in register chunks of 16 -- another layout of unit_eval.h's algebra.
 #define IG_WC 16
 #define IG_DY_THREADS 128
 __host__ __device__ inline int ig_nsp(int n) { return (n + IG_WC - 1) / IG_WC * IG_WC; }
@@ -73,10 +74,8 @@ __global__ __launch_bounds__(IG_DY_THREADS) void ig_eval_dy_kernel(
         }
     }
     // dz = (dl . Wf[:,u]) [y3 > 0] gamma3 / sqrt(rv3 + eps); y3 > 0 exactly where the stored o is
-    float dout = 0.f;
-    if (live)
-        for (int t = 0; t < T; ++t) dout = fmaf(dl[(size_t)b * T + t], final_w[(size_t)t * U + u], dout);
-    const float inv3 = g3[u] / sqrtf(rv3[u] + (float)BN_EPS_D);
+    const float dout = live ? unit_dout(dl, final_w, b, T, U, u) : 0.f;
+    const float inv3 = unit_inv3(g3, rv3, u);
     const float dz = (live && o[(size_t)u * Bs + bl] > 0.f) ? dout * inv3 : 0.f;
     for (int r = 0; r < FC_H; ++r) {
         const float y = ys[r * IG_DY_THREADS + tid];
@@ -227,16 +226,7 @@ __global__ __launch_bounds__(256) void input_grad_kernel(
     const int whi = min(n - 1, (P0 + IG_POS - 1) / POOLW);
     for (int u0 = 0; u0 < U; u0 += IG_UT) {
         __syncthreads();
-        for (int i = tid; i < IG_UT * k; i += 256) {
-            const int uu = i / k, t = i - uu * k, u = u0 + uu;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (u < U) {
-                const float a = alpha[u];
-                const float* wr = W + (size_t)u * 4 * k + t;
-                v = make_float4(a * wr[0], a * wr[k], a * wr[2 * k], a * wr[3 * k]);
-            }
-            Ws[uu * MAX_K + t] = v;
-        }
+        stage_filters4<true, IG_UT>(W, alpha, u0, U, k, tid, 256, Ws);
         __syncthreads();
         const int ub = u0 + (IG_UT / 4) * wave, ue = min(ub + IG_UT / 4, U);
         if (ub >= ue) continue;                               // wave-uniform
@@ -254,11 +244,7 @@ __global__ __launch_bounds__(256) void input_grad_kernel(
 #pragma unroll
                 for (int i = 0; i < IG_POS; ++i) {
                     const int t = P0 + i - ps;
-                    if ((unsigned)t < (unsigned)k) {
-                        const float4 wv = wu[t];
-                        acc[i].x = fmaf(d, wv.x, acc[i].x); acc[i].y = fmaf(d, wv.y, acc[i].y);
-                        acc[i].z = fmaf(d, wv.z, acc[i].z); acc[i].w = fmaf(d, wv.w, acc[i].w);
-                    }
+                    if ((unsigned)t < (unsigned)k) fma4(acc[i], wu[t], d);
                 }
             }
 #pragma unroll
@@ -300,9 +286,7 @@ __global__ __launch_bounds__(256) void input_grad_kernel(
 #pragma unroll
                     for (int a2 = 0; a2 < 4; ++a2) {
                         const float xv = live ? xb[(size_t)a2 * L + q] : 0.f;
-                        const float4 hv = hrow[d * 4 + a2];
-                        t.x = fmaf(hv.x, xv, t.x); t.y = fmaf(hv.y, xv, t.y);
-                        t.z = fmaf(hv.z, xv, t.z); t.w = fmaf(hv.w, xv, t.w);
+                        fma4(t, hrow[d * 4 + a2], xv);
                     }
                 } else {
                     const int sc = cs[(q - q0) * 64 + lane];

@@ -7,6 +7,7 @@
 //   dq_w = qval(alpha, ext over the window of g + d, shift) - q_w
 //   y2' = y2 + sum_w A2[:,w] dq_w,  z' = fc2_w . relu(y2') ,  o' = relu(BN3_eval(z' + fc2_b))
 //   delta[b,t,a,p] = sum_u final_w[t,u] (o'_u - o_u)       (units in order)
+// The unit itself (window sums, FC1, FC2, BatchNorm3, the LDS tables) is unit_eval.h's.
 // ism_units: workgroup = (256 sequences, unit), lane = sequence.  Each lane rebuilds its own g, y2
 // and o from the codes with the same code that evaluates the substitutions, so a substitution that
 // changes no pooled extreme gives exactly 0.  Lanes iterate over a = (s + d) & 3, d = 1..3 (an N
@@ -16,6 +17,7 @@
 // ism_sum: delta = sum_u final_w[t,u] dout[u][d][p][b], one owner per element, units in order;
 // reference rows and positions whose windows MaxPool1d drops are written as 0.  No float atomics.
 #include "common.h"
+#include "unit_eval.h"
 
 #define ISM_WAVES 4
 #define ISM_RING 64                // per-lane code ring (positions mod 64), >= k + 13
@@ -26,22 +28,7 @@
 __host__ __device__ inline int ism_nw(int k) { return (k + 5) / 7 + 1; }   // ceil((k-1)/7) + 1
 __host__ __device__ inline int ism_pend(int k, int n, int L) { return min(L, POOLW * n + k - 1); }
 
-// g of window w (7 positions) from the code ring: g[e] = sum_(t ascending) W[u, code(7w+e+t), t]
-__device__ __forceinline__ void ism_window(const uint8_t* __restrict__ rg, const float* __restrict__ Wl,
-                                           int w, int k, int lane, float* g) {
-    const int q0 = POOLW * w;
-#pragma unroll
-    for (int e = 0; e < POOLW; ++e) g[e] = 0.f;
-    for (int q = 0; q < k + POOLW - 1; ++q) {
-        const int c = rg[((q0 + q) & (ISM_RING - 1)) * 64 + lane];
-#pragma unroll
-        for (int e = 0; e < POOLW; ++e) {
-            const int t = q - e;
-            if ((unsigned)t < (unsigned)k) g[e] += Wl[t * 8 + c];
-        }
-    }
-}
-
+// The pooled extreme as MaxPool1d folds it (fmaxf; pathgrad.hip's pg_pool needs the index and compares)
 __device__ __forceinline__ float ism_ext(const float* g, float sg) {
     float m = sg * g[0];
 #pragma unroll
@@ -56,11 +43,7 @@ __device__ __forceinline__ void ism_fc(const float (&y2)[FC_H], const float* __r
                                        float (&z)[ND]) {
 #pragma unroll
     for (int d = 0; d < ND; ++d) z[d] = 0.f;
-    // an offset the compiler cannot see through, on every LDS read below: otherwise it hoists the 25
-    // loop-invariant fc2 reads out of the position loop, and reuses the A2 reads of the d = 1..3 call
-    // in the N pass, keeping up to 100 (NW + 1) more registers live (spills)
-    int fo = 0;
-    asm volatile("" : "+v"(fo));
+    const int fo = unit_opaque_zero();             // on every LDS read below (unit_eval.h)
 #pragma unroll
     for (int r4 = 0; r4 < FC_H / 4; ++r4) {
         float y[ND][4];
@@ -93,8 +76,8 @@ __device__ __forceinline__ void ism_fc(const float (&y2)[FC_H], const float* __r
 template <int NW>
 __device__ __forceinline__ void ism_dq(const float (&G)[NW][POOLW], const float (&q0)[NW],
                                        const float (&ws)[NW][POOLW], const float* __restrict__ Wl,
-                                       int wb, int p, int k, int a, unsigned vmask, float al, float sh,
-                                       float sg, float (&dq)[NW]) {
+                                       int wb, int p, int k, int a, unsigned vmask, const unit_consts& uc,
+                                       float (&dq)[NW]) {
 #pragma unroll
     for (int i = 0; i < NW; ++i) {
         dq[i] = 0.f;
@@ -106,7 +89,7 @@ __device__ __forceinline__ void ism_dq(const float (&G)[NW][POOLW], const float 
                 g[e] = G[i][e];
                 if ((unsigned)t < (unsigned)k) g[e] = G[i][e] + (Wl[t * 8 + a] - ws[i][e]);
             }
-            dq[i] = qval(al, ism_ext(g, sg), sh) - q0[i];
+            dq[i] = qval(uc.al, ism_ext(g, uc.sg), uc.sh) - q0[i];
         }
     }
 }
@@ -125,15 +108,7 @@ __global__ __launch_bounds__(64 * ISM_WAVES) void ism_units_kernel(
     int u, chunk;
     if (!unit_chunk_of_block(U, u, chunk)) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int i = tid; i < n * FC_H; i += 64 * ISM_WAVES) {
-        const int w = i / FC_H, r = i - w * FC_H;
-        ism_sm[i] = A2[((size_t)u * FC_H + r) * NS + w];
-    }
-    for (int i = tid; i < k * 8; i += 64 * ISM_WAVES) {
-        const int t = i >> 3, a = i & 7;
-        Wl[i] = a < 4 ? conv_w[((size_t)u * 4 + a) * k + t] : 0.f;
-    }
-    for (int i = tid; i < FC_H; i += 64 * ISM_WAVES) fcs[i] = fc2_w[(size_t)u * FC_H + i];
+    unit_stage<false>(A2, conv_w, fc2_w, u, k, n, NS, tid, 64 * ISM_WAVES, ism_sm, Wl, fcs);
     __syncthreads();
     const int bw = chunk * 64 * ISM_WAVES + wave * 64;
     if (bw >= Bsub) return;                        // wave-uniform; no barrier below
@@ -142,9 +117,8 @@ __global__ __launch_bounds__(64 * ISM_WAVES) void ism_units_kernel(
     const uint8_t* __restrict__ col = codesT + b0 + min(bi, Bsub - 1);
     uint8_t* rg = ring[wave];
     const float* A2T = ism_sm;
-    const float al = alpha[u], sh = shift[u], sg = al < 0.f ? -1.f : 1.f;
-    const float inv3 = g3[u] / sqrtf(rv3[u] + (float)BN_EPS_D);
-    const float c2 = fc2_b[u], m3 = rm3[u], be3 = b3[u];
+    const unit_consts uc = unit_load(alpha, shift, fc2_b, g3, b3, rm3, rv3, u);
+    const auto code = [&](int q) -> int { return rg[(q & (ISM_RING - 1)) * 64 + lane]; };
 
     // code ring: positions [0, k+6) first; window w > 0 adds [7w+k-1, 7w+k+6) from pf (loaded one
     // window ahead).  Only this lane's column is touched: no barrier.
@@ -175,21 +149,15 @@ __global__ __launch_bounds__(64 * ISM_WAVES) void ism_units_kernel(
     for (int w = 0; w < n; ++w) {
         if (w > 0) ring_advance(w);
         float g[POOLW];
-        ism_window(rg, Wl, w, k, lane, g);
-        const float q = qval(al, ism_ext(g, sg), sh);
-        const float4* __restrict__ a4 = reinterpret_cast<const float4*>(A2T + w * FC_H);
-#pragma unroll
-        for (int r4 = 0; r4 < FC_H / 4; ++r4) {
-            const float4 a = a4[r4];
-            y2[4 * r4] = fmaf(a.x, q, y2[4 * r4]); y2[4 * r4 + 1] = fmaf(a.y, q, y2[4 * r4 + 1]);
-            y2[4 * r4 + 2] = fmaf(a.z, q, y2[4 * r4 + 2]); y2[4 * r4 + 3] = fmaf(a.w, q, y2[4 * r4 + 3]);
-        }
+        unit_window(code, Wl, w, k, g);
+        const float q = qval(uc.al, ism_ext(g, uc.sg), uc.sh);
+        UNIT_FC1_ADD(y2, reinterpret_cast<const float4*>(A2T + w * FC_H), q);
     }
-    // z by the chain of ism_fc (with every dq = 0 that gives these values: fmaf(a, 0, y) = y)
-    float z0 = 0.f;
-#pragma unroll
-    for (int r = 0; r < FC_H; ++r) z0 = fmaf(fcs[r], fmaxf(y2[r], 0.f), z0);
-    const float o0 = fmaxf(fmaf(inv3, z0 + c2 - m3, be3), 0.f);
+    // z by the chain of ism_fc, channels ascending (with every dq = 0 that gives these values:
+    // fmaf(a, 0, y) = y)
+    float z0;
+    UNIT_FC2(z0, y2, fcs);
+    const float o0 = fmaxf(unit_bn3(uc, z0), 0.f);
 
     // ---- the substitutions, position by position ----
     // G[i] = g of window wt - (NW-1) + i (wt = the newest window entered); every window a
@@ -212,7 +180,7 @@ __global__ __launch_bounds__(64 * ISM_WAVES) void ism_units_kernel(
             for (int i = 0; i + 1 < NW; ++i)
 #pragma unroll
                 for (int e = 0; e < POOLW; ++e) G[i][e] = G[i + 1][e];
-            ism_window(rg, Wl, wt, k, lane, G[NW - 1]);
+            unit_window(code, Wl, wt, k, G[NW - 1]);
         }
         const int wb = wt - (NW - 1);
         const int wlo = p - k + 1 <= 0 ? 0 : (p - k + 1) / POOLW;
@@ -228,7 +196,7 @@ __global__ __launch_bounds__(64 * ISM_WAVES) void ism_units_kernel(
 #pragma unroll
             for (int e = 0; e < POOLW; ++e) ws[i][e] = 0.f;
             if (vmask & (1u << i)) {
-                q0[i] = qval(al, ism_ext(G[i], sg), sh);
+                q0[i] = qval(uc.al, ism_ext(G[i], uc.sg), uc.sh);
 #pragma unroll
                 for (int e = 0; e < POOLW; ++e) {
                     const int t = p - (POOLW * (wb + i) + e);
@@ -238,7 +206,7 @@ __global__ __launch_bounds__(64 * ISM_WAVES) void ism_units_kernel(
         }
         float dq[3][NW];
 #pragma unroll
-        for (int d = 0; d < 3; ++d) ism_dq<NW>(G, q0, ws, Wl, wb, p, k, (sa + d + 1) & 3, vmask, al, sh, sg, dq[d]);
+        for (int d = 0; d < 3; ++d) ism_dq<NW>(G, q0, ws, Wl, wb, p, k, (sa + d + 1) & 3, vmask, uc, dq[d]);
         bool moved = false;                        // some extreme of this lane moved
 #pragma unroll
         for (int i = 0; i < NW; ++i) moved = moved || dq[0][i] != 0.f || dq[1][i] != 0.f || dq[2][i] != 0.f;
@@ -247,7 +215,7 @@ __global__ __launch_bounds__(64 * ISM_WAVES) void ism_units_kernel(
             float z[3];
             ism_fc<3, NW>(y2, A2T, fcs, dq, wb, z);
 #pragma unroll
-            for (int d = 0; d < 3; ++d) o3[d] = fmaxf(fmaf(inv3, z[d] + c2 - m3, be3), 0.f) - o0;
+            for (int d = 0; d < 3; ++d) o3[d] = fmaxf(unit_bn3(uc, z[d]), 0.f) - o0;
         }
         if (live) {
 #pragma unroll
@@ -256,7 +224,7 @@ __global__ __launch_bounds__(64 * ISM_WAVES) void ism_units_kernel(
         // a = 0 where the reference is N (the passes above covered a = 1, 2, 3 there)
         if (__any(live && s >= 4)) {
             float dn[1][NW];
-            ism_dq<NW>(G, q0, ws, Wl, wb, p, k, 0, vmask, al, sh, sg, dn[0]);
+            ism_dq<NW>(G, q0, ws, Wl, wb, p, k, 0, vmask, uc, dn[0]);
             bool nmoved = false;
 #pragma unroll
             for (int i = 0; i < NW; ++i) nmoved = nmoved || dn[0][i] != 0.f;
@@ -264,7 +232,7 @@ __global__ __launch_bounds__(64 * ISM_WAVES) void ism_units_kernel(
             if (__any(live && s >= 4 && nmoved)) {
                 float z[1];
                 ism_fc<1, NW>(y2, A2T, fcs, dn, wb, z);
-                on = fmaxf(fmaf(inv3, z[0] + c2 - m3, be3), 0.f) - o0;
+                on = fmaxf(unit_bn3(uc, z[0]), 0.f) - o0;
             }
             if (live && s >= 4) du[(size_t)p * S] = on;
         }
@@ -326,7 +294,9 @@ __global__ __launch_bounds__(64 * ISM_SUM_P) void ism_sum_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------
-// sub-batch: a multiple of 64 sequences whose dout stays near ISM_WS_CAP (at least 64)
+// sub-batch: a multiple of 64 sequences whose dout stays near ISM_WS_CAP (at least 64): sub_batch_of's
+// rule, in the text tests/dispatch_model.py reads the step and the cap from
+static_assert(SUB_BATCH_STEP == 64, "ism_sub_batch spells the step of sub_batch_of out");
 int ism_sub_batch(const explainn_ctx* c, int B) {
     const int64_t per = (int64_t)c->U * 4 * c->L * (int64_t)sizeof(float);
     int64_t s = ISM_WS_CAP / per / 64 * 64;

@@ -10,21 +10,21 @@
 // index on a tie, sign-aware for a negative BatchNorm1 scale) and F = sum_t dl[b,t] logit_t,
 //   G[b,u,j]  = (1/S) sum_s D_(a_s)[b,u,j]                                       (s ascending)
 //   IG[b,a,p] = (x - x')[b,a,p] sum_u sum_(t: 0 <= p-t < 7n) W[u,a,t] G[b,u,p-t]  (u, t ascending)
-// pg_path: workgroup = (256 sequences, unit), lane = sequence; the unit's A2 (as [w][100]) and fc2
-// row sit in LDS and are read at wave-uniform addresses.  A lane first writes g and g' of its
-// sequence (taps ascending, the same code for both ends) into its own columns of the workspace and
+// The unit itself (window sums, FC1, FC2, BatchNorm3, the LDS tables, the baseline codes) is
+// unit_eval.h's.  pg_path: workgroup = (256 sequences, unit), lane = sequence; the unit's A2 (as
+// [w][100]) and fc2 row sit in LDS and are read at wave-uniform addresses.  A lane first writes g and
+// g' of its sequence (taps ascending, the same code for both ends) into its own columns of the workspace and
 // zeroes its column of G, then walks the two ends (forward only: the unit outputs behind the endpoint
 // logits) and the S nodes (forward, backward to the pooled values, G += alpha dy / S at the argmax:
 // lane-exclusive addresses, plain read-modify-write).  pg_gather: the transposed convolution, one
 // owner per output element.  pg_logits: the two ends' logits, units in order.  No float atomics.
 #include "common.h"
+#include "unit_eval.h"
 
 #define PG_WAVES 4
 #define PG_POS 8                   // positions per pg_gather wave
 #define PG_UT 64                   // units whose filters one LDS pass of pg_gather stages
 #define PG_WS_CAP (1LL << 30)      // workspace bytes the sub-batch size aims at
-#define PG_CODE_ZERO 4             // baseline code: an all-zero column (N)
-#define PG_CODE_UNIFORM 5          // baseline code: 0.25 in all four rows
 
 // ---- workspace of a sub-batch of S sequences (S a multiple of 64), J = 7n covered conv positions:
 //   G, GX, GB  [U][J][S] fp32      the path-averaged gradient, g of x, g of x'
@@ -36,10 +36,7 @@ static int64_t pg_per_sequence_bytes(const explainn_ctx* c) {
 }
 
 int pathgrad_sub_batch(const explainn_ctx* c, int B) {
-    int64_t s = PG_WS_CAP / pg_per_sequence_bytes(c) / 64 * 64;
-    if (s < 64) s = 64;
-    const int64_t bb = ((int64_t)B + 63) / 64 * 64;
-    return (int)(s < bb ? s : bb);
+    return sub_batch_of(PG_WS_CAP, pg_per_sequence_bytes(c), B);
 }
 
 int64_t pathgrad_workspace_bytes(const explainn_ctx* c, int B) {
@@ -61,23 +58,6 @@ __global__ __launch_bounds__(256) void pg_base_kernel(const uint8_t* __restrict_
     BT[(size_t)p * S + bi] = v;
 }
 
-// g of window w (7 positions) of one end: g[e] = sum_(t ascending) W[u, code(7w+e+t), t]; col points
-// at the lane's code of position 0, cs is the stride of a position.  7w + e + t <= 7n + k - 2 < L.
-__device__ __forceinline__ void pg_window(const uint8_t* __restrict__ col, size_t cs,
-                                          const float* __restrict__ Wl, int w, int k, float* g) {
-    const int q0 = POOLW * w;
-#pragma unroll
-    for (int e = 0; e < POOLW; ++e) g[e] = 0.f;
-    for (int q = 0; q < k + POOLW - 1; ++q) {
-        const int c = col[(size_t)(q0 + q) * cs];
-#pragma unroll
-        for (int e = 0; e < POOLW; ++e) {
-            const int t = q - e;
-            if ((unsigned)t < (unsigned)k) g[e] += Wl[t * 8 + c];
-        }
-    }
-}
-
 // Window w's conv sums of both ends, from the lane's columns.
 __device__ __forceinline__ void pg_load(const float* __restrict__ gx, const float* __restrict__ gb, size_t rs,
                                         float* vx, float* vb) {
@@ -86,7 +66,8 @@ __device__ __forceinline__ void pg_load(const float* __restrict__ gx, const floa
 }
 
 // The pooled extreme of a window at path position a and its offset: first index on an exact tie,
-// the minimum where BatchNorm1's scale is negative.  mode 0: the node a; 1: the end x; 2: the end x'.
+// the minimum where BatchNorm1's scale is negative (a compare, for the index; ism.hip's ism_ext folds
+// with fmaxf).  mode 0: the node a; 1: the end x; 2: the end x'.
 __device__ __forceinline__ float pg_pool(const float* vx, const float* vb, float a, int mode, float sg,
                                          int& idx) {
     float m = 0.f;
@@ -115,19 +96,7 @@ __global__ __launch_bounds__(64 * PG_WAVES) void pg_path_kernel(
     int u, chunk;
     if (!unit_chunk_of_block(U, u, chunk)) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int i = tid; i < n * FC_H; i += 64 * PG_WAVES) {
-        const int w = i / FC_H, r = i - w * FC_H;
-        pg_sm[i] = A2[((size_t)u * FC_H + r) * NS + w];
-    }
-    for (int i = tid; i < k * 8; i += 64 * PG_WAVES) {
-        const int t = i >> 3, a = i & 7;
-        const float* wr = conv_w + (size_t)u * 4 * k + t;
-        float v = 0.f;
-        if (a < 4) v = wr[a * k];
-        else if (a == PG_CODE_UNIFORM) v = 0.25f * (((wr[0] + wr[k]) + wr[2 * k]) + wr[3 * k]);
-        Wl[i] = v;
-    }
-    for (int i = tid; i < FC_H; i += 64 * PG_WAVES) fcs[i] = fc2_w[(size_t)u * FC_H + i];
+    unit_stage<true>(A2, conv_w, fc2_w, u, k, n, NS, tid, 64 * PG_WAVES, pg_sm, Wl, fcs);
     __syncthreads();
     const int bw = chunk * 64 * PG_WAVES + wave * 64;
     if (bw >= Bsub) return;                        // wave-uniform; no barrier below
@@ -135,9 +104,7 @@ __global__ __launch_bounds__(64 * PG_WAVES) void pg_path_kernel(
     const bool live = bi < Bsub;
     const int bic = min(bi, Bsub - 1);             // a dead lane repeats the last sequence and stores nothing
     const float* A2T = pg_sm;
-    const float al = alpha[u], sh = shift[u], sg = al < 0.f ? -1.f : 1.f;
-    const float inv3 = g3[u] / sqrtf(rv3[u] + (float)BN_EPS_D);
-    const float c2 = fc2_b[u], m3 = rm3[u], be3 = b3[u];
+    const unit_consts uc = unit_load(alpha, shift, fc2_b, g3, b3, rm3, rv3, u);
     const int J = POOLW * n;
     const size_t rs = (size_t)S;
     const size_t ub = (size_t)u * J * rs + bic;
@@ -151,8 +118,8 @@ __global__ __launch_bounds__(64 * PG_WAVES) void pg_path_kernel(
         const uint8_t* __restrict__ cb = BT + bic;
         for (int w = 0; w < n; ++w) {
             float g[POOLW], h[POOLW];
-            pg_window(cx, (size_t)Bs, Wl, w, k, g);
-            pg_window(cb, rs, Wl, w, k, h);
+            unit_window([&](int q) -> int { return cx[(size_t)q * Bs]; }, Wl, w, k, g);
+            unit_window([&](int q) -> int { return cb[(size_t)q * rs]; }, Wl, w, k, h);
             if (live) {
 #pragma unroll
                 for (int e = 0; e < POOLW; ++e) {
@@ -162,19 +129,14 @@ __global__ __launch_bounds__(64 * PG_WAVES) void pg_path_kernel(
             }
         }
     }
-    float dout = 0.f;                              // dF / d(unit output)
-    for (int t = 0; t < T; ++t)
-        dout = fmaf(dl[(size_t)(b0 + bic) * T + t], final_w[(size_t)t * U + u], dout);
+    const float dout = unit_dout(dl, final_w, b0 + bic, T, U, u);     // dF / d(unit output)
     const float invS = 1.f / (float)steps;
 
     // ---- the two ends (s = -2: x, s = -1: x'), then the nodes ----
     for (int s = -2; s < steps; ++s) {
         const int mode = s == -2 ? 1 : (s == -1 ? 2 : 0);
         const float a = ((float)s + 0.5f) * invS;
-        // an offset the compiler cannot see through, on the LDS reads of this node: otherwise it
-        // hoists the loop-invariant fc2 reads out of the node loop (100 more registers live)
-        int fo = 0;
-        asm volatile("" : "+v"(fo));
+        const int fo = unit_opaque_zero();         // on the LDS reads of this node (unit_eval.h)
         float y2[FC_H];
 #pragma unroll
         for (int r = 0; r < FC_H; ++r) y2[r] = sh2[(size_t)u * FC_H + r];
@@ -185,30 +147,19 @@ __global__ __launch_bounds__(64 * PG_WAVES) void pg_path_kernel(
             const size_t on = (size_t)(POOLW * min(w + 1, n - 1)) * rs;
             pg_load(gxu + on, gbu + on, rs, nx, nb);
             int idx;
-            const float q = qval(al, pg_pool(vx, vb, a, mode, sg, idx), sh);
-            const float4* __restrict__ a4 = reinterpret_cast<const float4*>(A2T + fo + w * FC_H);
-#pragma unroll
-            for (int r4 = 0; r4 < FC_H / 4; ++r4) {
-                const float4 av = a4[r4];
-                y2[4 * r4] = fmaf(av.x, q, y2[4 * r4]); y2[4 * r4 + 1] = fmaf(av.y, q, y2[4 * r4 + 1]);
-                y2[4 * r4 + 2] = fmaf(av.z, q, y2[4 * r4 + 2]); y2[4 * r4 + 3] = fmaf(av.w, q, y2[4 * r4 + 3]);
-            }
+            const float q = qval(uc.al, pg_pool(vx, vb, a, mode, uc.sg, idx), uc.sh);
+            UNIT_FC1_ADD(y2, reinterpret_cast<const float4*>(A2T + fo + w * FC_H), q);
 #pragma unroll
             for (int e = 0; e < POOLW; ++e) { vx[e] = nx[e]; vb[e] = nb[e]; }
         }
-        float z = 0.f;
-#pragma unroll
-        for (int r4 = 0; r4 < FC_H / 4; ++r4) {
-            const float4 f = *reinterpret_cast<const float4*>(fcs + fo + 4 * r4);
-            z = fmaf(f.x, fmaxf(y2[4 * r4], 0.f), z); z = fmaf(f.y, fmaxf(y2[4 * r4 + 1], 0.f), z);
-            z = fmaf(f.z, fmaxf(y2[4 * r4 + 2], 0.f), z); z = fmaf(f.w, fmaxf(y2[4 * r4 + 3], 0.f), z);
-        }
-        const float y3 = fmaf(inv3, z + c2 - m3, be3);
+        float z;
+        UNIT_FC2(z, y2, fcs + fo);
+        const float y3 = unit_bn3(uc, z);
         if (mode != 0) {
             if (live) O[((size_t)(mode - 1) * U + u) * rs + bi] = fmaxf(y3, 0.f);
             continue;
         }
-        const float dz = y3 > 0.f ? dout * inv3 : 0.f;
+        const float dz = y3 > 0.f ? dout * uc.inv3 : 0.f;
         if (!__any(live && dz != 0.f)) continue;   // wave-uniform: every lane's unit is closed here
         // e[r] = dF/dy2[r], in y2's registers
 #pragma unroll
@@ -230,11 +181,11 @@ __global__ __launch_bounds__(64 * PG_WAVES) void pg_path_kernel(
                 dq = fmaf(av.z, y2[4 * r4 + 2], dq); dq = fmaf(av.w, y2[4 * r4 + 3], dq);
             }
             int idx;
-            const float q = qval(al, pg_pool(vx, vb, a, 0, sg, idx), sh);
+            const float q = qval(uc.al, pg_pool(vx, vb, a, 0, uc.sg, idx), uc.sh);
             // dF/dg at the argmax = alpha q dq (BatchNorm1 scale, exp', FC1), averaged over the nodes
             if (live) {
                 float* gp = Gu + (size_t)(POOLW * w + idx) * rs;
-                *gp = fmaf(al * (dq * q), invS, *gp);
+                *gp = fmaf(uc.al * (dq * q), invS, *gp);
             }
 #pragma unroll
             for (int e = 0; e < POOLW; ++e) { vx[e] = nx[e]; vb[e] = nb[e]; }
@@ -277,15 +228,7 @@ __global__ __launch_bounds__(256) void pg_gather_kernel(
     for (int i = 0; i < PG_POS; ++i) acc[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int u0 = 0; u0 < U; u0 += PG_UT) {
         __syncthreads();
-        for (int i = tid; i < PG_UT * k; i += 256) {
-            const int uu = i / k, t = i - uu * k, u = u0 + uu;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (u < U) {
-                const float* wr = W + (size_t)u * 4 * k + t;
-                v = make_float4(wr[0], wr[k], wr[2 * k], wr[3 * k]);
-            }
-            Ws[uu * MAX_K + t] = v;
-        }
+        stage_filters4<false, PG_UT>(W, nullptr, u0, U, k, tid, 256, Ws);
         __syncthreads();
         if (P0 >= L) continue;                                   // wave-uniform; the barriers are above
         const int ue = min(u0 + PG_UT, U);
@@ -308,11 +251,7 @@ __global__ __launch_bounds__(256) void pg_gather_kernel(
 #pragma unroll
                     for (int i = 0; i < PG_POS; ++i) {
                         const int t = 8 * c + r + i - 7;
-                        if ((unsigned)t < (unsigned)k) {
-                            const float4 wv = wu[t];
-                            acc[i].x = fmaf(wv.x, g, acc[i].x); acc[i].y = fmaf(wv.y, g, acc[i].y);
-                            acc[i].z = fmaf(wv.z, g, acc[i].z); acc[i].w = fmaf(wv.w, g, acc[i].w);
-                        }
+                        if ((unsigned)t < (unsigned)k) fma4(acc[i], wu[t], g);
                     }
                 }
             }
@@ -340,16 +279,14 @@ __global__ __launch_bounds__(256) void pg_gather_kernel(
 int launch_pathgrad(explainn_ctx* c, const explainn_params* p, int B, int kind, const uint8_t* base_codes,
                     int rc, const float* dlogits, int steps, float* ig, float* logits_x, float* logits_base,
                     void* ws, int64_t ws_bytes, hipStream_t s) {
-    // the sub-batch the caller's workspace holds: a multiple of 64, no more than the batch needs
-    int64_t S64 = ws_bytes / pg_per_sequence_bytes(c) / 64 * 64;
-    const int64_t bb = ((int64_t)B + 63) / 64 * 64;
-    if (S64 > bb) S64 = bb;
-    if (S64 < 64) {
+    // the sub-batch the caller's workspace holds: the rule of pathgrad_sub_batch on ws_bytes
+    const int64_t least = SUB_BATCH_STEP * pg_per_sequence_bytes(c);
+    if (ws_bytes < least) {
         explainn_set_error("integrated-gradients workspace of %lld bytes holds no 64-sequence sub-batch "
-                           "(%lld needed)", (long long)ws_bytes, (long long)(64 * pg_per_sequence_bytes(c)));
+                           "(%lld needed)", (long long)ws_bytes, (long long)least);
         return EXPLAINN_E_ARG;
     }
-    const int S = (int)S64, J = POOLW * c->n;
+    const int S = sub_batch_of(ws_bytes, pg_per_sequence_bytes(c), B), J = POOLW * c->n;
     const size_t plane = (size_t)c->U * J * S;
     float* G = static_cast<float*>(ws);
     float* GX = G + plane;
