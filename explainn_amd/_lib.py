@@ -22,6 +22,7 @@ MOTIF_MAX_WIDTH = 64      # EXPLAINN_MOTIF_MAX_WIDTH: columns per motif of expla
 MOTIF_MAX_BINS = 128      # EXPLAINN_MOTIF_MAX_BINS: score bins per column of explainn_motif_significance
 MOTIF_NO_SCORE = 255      # EXPLAINN_MOTIF_NO_SCORE: a colscore entry without a column
 SITES_TILE = 1024        # EXPLAINN_SITES_TILE: start positions per workgroup of explainn_call_sites
+PWM_GROUP = 16           # EXPLAINN_PWM_GROUP: motifs per workgroup of explainn_pwm_sites
 ACT_BINS = 32768         # EXPLAINN_ACT_BINS: one bin per non-negative float16 bit pattern
 ACT_SPAN = 8192          # EXPLAINN_ACT_SPAN: start positions a workgroup of explainn_activation_histogram takes at a time
 BEST_SPAN = 256          # EXPLAINN_BEST_SPAN: starts a wavefront of explainn_record_best takes per pass over its record
@@ -165,6 +166,11 @@ SIGNATURES = {
     "explainn_motif_significance_workspace_bytes": (_i64, [_i, _i, _i, _i, _i]),
     "explainn_motif_significance": (_i, [_fp, _fp, _i, _fp, _fp, _i, _i, C.c_float, _i, _i, _i, _fp, _fp, _fp, _fp,
                                          _fp, _fp, _i64, _fp]),
+    "explainn_pwm_null": (_i, [_fp, _fp, _i, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _fp,
+                               _fp, _fp]),
+    "explainn_pwm_sites_workspace_bytes": (_i64, [_i, _i64]),
+    "explainn_pwm_sites": (_i, [_fp, _i64, _i64, _i64, _i64, _i, _fp, _fp, _i, _i, _fp, _fp, _i, _fp, _fp, _fp, _fp,
+                                _i64, _fp, _i64, _fp]),
     "explainn_adam_step": (_i, [_i, C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp),
                                 C.POINTER(_i64), _i64, C.c_double, C.c_double, C.c_double, C.c_double,
                                 _fp]),

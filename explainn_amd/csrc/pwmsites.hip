@@ -1,0 +1,344 @@
+// Known-motif sites ("Known-motif sites"): where do the motifs of a database occur in
+// a device-resident sequence of base codes -- what FIMO lists, and what the reference vendors PWMScan for.
+//
+// A motif is an integer score table S[w][4], 0 <= S <= bins (the host quantises its log-odds,
+// explainn_amd/pwmsites.py), so a site's score is an integer <= w * bins <= 8192 and everything below is exact
+// integer work except the null, which is fp64 sums of positive terms in a fixed order:
+//
+//   explainn_pwm_null   per motif the distribution of the score of a random w-mer drawn iid from the
+//                       background, column by column (a gather: one lane per score value, the four bases in
+//                       order, no atomics), its tail, and the smallest score whose tail is <= pcut
+//   explainn_pwm_sites  every (motif, strand, start) with score >= the motif's threshold, as a compacted
+//                       list: the COUNT / scan / EMIT scheme of sites.hip with one row per (motif, strand)
+//
+// Scan geometry (a first choice): a workgroup is a tile of EXPLAINN_SITES_TILE starts x a group of
+// EXPLAINN_PWM_GROUP motifs.  The tile's codes and the group's tables sit in LDS; a table entry (column j,
+// code c) is one 32-bit word holding two int16: the forward score S[j][c] and the score the reverse strand
+// takes at the same base, S[w-1-j][3-c] -- so one pass over the window's codes, in forward order, scores both
+// strands.  Code 4 (N) holds a sentinel so negative in both halves that no sum reaches a threshold >= 0.
+#include <limits.h>
+
+#include <algorithm>
+
+#include "codescan.h"
+#include "sitescan.h"
+
+namespace {
+
+constexpr int PS_T = 256;                       // one lane per start, four position chunks per tile
+constexpr int PS_CHUNKS = EXPLAINN_SITES_TILE / PS_T;
+constexpr int PS_G = EXPLAINN_PWM_GROUP;
+constexpr int PS_N = -16384;                    // 64 of them stay inside int32; one outweighs 63 x 128
+static_assert(EXPLAINN_SITES_TILE % PS_T == 0, "a tile is a whole number of position chunks");
+static_assert(PS_G % 2 == 0, "block_hit_ranks ranks four rows = two motifs x two strands at a time");
+static_assert(EXPLAINN_MOTIF_MAX_WIDTH * EXPLAINN_MOTIF_MAX_BINS + PS_N < 0, "an N outweighs the rest of a window");
+
+enum { PS_COUNT = 0, PS_EMIT = 1 };
+
+// the only way a width is read: outside [1, wmax] the motif is empty
+__device__ __forceinline__ int motif_width(const int* __restrict__ widths, int m, int wmax) {
+    const int w = widths[m];
+    return (w >= 1 && w <= wmax) ? w : 0;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(PS_T) void pwm_sites_kernel(
+    const uint8_t* __restrict__ seq, long long start, int npos, int span, long long period, int both,
+    const int16_t* __restrict__ S, const int* __restrict__ widths, const int* __restrict__ thr,
+    const double* __restrict__ tail, int tail_stride, int* __restrict__ cnt,
+    const long long* __restrict__ offsets, int* __restrict__ pos, int* __restrict__ score,
+    double* __restrict__ pvalue, long long capacity, int M, int wmax, int ntiles) {
+    extern __shared__ int tab[];               // [PS_G][wmax][8] | codes [SITES_TILE + wmax - 1] bytes
+    uint8_t* cs = reinterpret_cast<uint8_t*>(tab + PS_G * wmax * 8);
+    __shared__ int wtot[4][PS_T / 64];
+    const int tile = blockIdx.x, tid = threadIdx.x, m0 = blockIdx.y * PS_G;
+    const int t0 = tile * EXPLAINN_SITES_TILE;              // < npos < 2^31
+    const int live_n = min(EXPLAINN_SITES_TILE, npos - t0); // start positions of this tile
+    // the tile's bases and the wmax-1 behind its last start, as far as the sequence goes: span = the bases
+    // from `start` to the end of what the call may read, >= npos (the entry point has checked it)
+    const int nstage = min(live_n + wmax - 1, span - t0);
+    stage_codes<false>(seq + start + t0, nstage, tid, PS_T, cs, 0, nullptr);
+    for (int i = tid; i < PS_G * wmax * 8; i += PS_T) {
+        const int g = i / (wmax * 8), r = i - g * wmax * 8, j = r >> 3, c = r & 7, m = m0 + g;
+        unsigned word = 0;
+        const int w = m < M ? motif_width(widths, m, wmax) : 0;
+        if (j < w) {
+            const int16_t* row = S + (size_t)m * wmax * 4;
+            word = c < 4 ? (unsigned)(uint16_t)row[j * 4 + c] | ((unsigned)(uint16_t)row[(w - 1 - j) * 4 + 3 - c] << 16)
+                         : (unsigned)(uint16_t)PS_N | ((unsigned)(uint16_t)PS_N << 16);
+        }
+        tab[i] = (int)word;
+    }
+    // per position chunk: the widest motif that may start at this lane's position -- it ends inside the
+    // staged bases and, with a period, inside its record; 0 past the tile's starts
+    int lim[PS_CHUNKS];
+#pragma unroll
+    for (int c = 0; c < PS_CHUNKS; ++c) {
+        const int p = c * PS_T + tid;
+        int l = p < live_n ? nstage - p : 0;
+        if (period > 0 && l > 0) l = (int)min((long long)l, period - (start + t0 + p) % period);
+        lim[c] = l;
+    }
+    __syncthreads();
+    for (int q = 0; q < PS_G / 2; ++q) {
+        const int ma = m0 + 2 * q;             // motifs ma, ma + 1: rows 2 ma .. 2 ma + 3
+        if (ma >= M) break;                    // (the same in every thread)
+        int w[2], th[2];
+        long long base[4];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const bool ok = ma + i < M;
+            w[i] = ok ? motif_width(widths, ma + i, wmax) : 0;
+            th[i] = ok ? thr[ma + i] : INT_MAX;
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = 2 * ma + r;
+            base[r] = (MODE == PS_EMIT && row < 2 * M) ? offsets[row] + cnt[(size_t)row * ntiles + tile] : 0;
+        }
+        int run[4] = {0, 0, 0, 0};             // sites of this tile in earlier position chunks
+#pragma unroll
+        for (int c = 0; c < PS_CHUNKS; ++c) {
+            if (c * PS_T >= live_n) break;
+            const int p = c * PS_T + tid;
+            // the two motifs walk the window together: one code read serves both, and the two table reads
+            // are independent chains; the wider one goes on alone.  wl = 0 where the start is not live.
+            const bool live[2] = {w[0] >= 1 && w[0] <= lim[c], w[1] >= 1 && w[1] <= lim[c]};
+            const int wl[2] = {live[0] ? w[0] : 0, live[1] ? w[1] : 0};
+            const int* tb0 = tab + 2 * q * wmax * 8;
+            const int* tb1 = tb0 + wmax * 8;
+            const uint8_t* cp = cs + p;            // cp[j] is read for j < max(wl) <= lim[c] only
+            int sc[4] = {0, 0, 0, 0};
+            int j = 0;
+            for (const int wb = min(wl[0], wl[1]); j < wb; ++j) {
+                const int code = cp[j], v0 = tb0[j * 8 + code], v1 = tb1[j * 8 + code];
+                sc[0] += (int)(short)(v0 & 0xFFFF);
+                sc[1] += v0 >> 16;
+                sc[2] += (int)(short)(v1 & 0xFFFF);
+                sc[3] += v1 >> 16;
+            }
+            const bool first = wl[0] > wl[1];
+            const int* tbw = first ? tb0 : tb1;
+            int fw = 0, rw = 0;
+            for (const int wa = max(wl[0], wl[1]); j < wa; ++j) {
+                const int v = tbw[j * 8 + cp[j]];
+                fw += (int)(short)(v & 0xFFFF);
+                rw += v >> 16;
+            }
+            sc[0] += first ? fw : 0;
+            sc[1] += first ? rw : 0;
+            sc[2] += first ? 0 : fw;
+            sc[3] += first ? 0 : rw;
+            bool hit[4];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                hit[2 * i] = live[i] && sc[2 * i] >= th[i];
+                hit[2 * i + 1] = live[i] && both && sc[2 * i + 1] >= th[i];
+            }
+            int pre[4], total[4];
+            block_hit_ranks<PS_T>(hit, wtot, pre, total);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if (MODE == PS_EMIT && hit[r]) {
+                    const long long rank = base[r] + run[r] + pre[r];
+                    if (rank < capacity) {
+                        pos[rank] = t0 + p;
+                        if (score) score[rank] = sc[r];
+                        if (pvalue)
+                            pvalue[rank] = (unsigned)sc[r] < (unsigned)tail_stride
+                                               ? tail[(size_t)(ma + (r >> 1)) * tail_stride + sc[r]] : 0.0;
+                    }
+                }
+                run[r] += total[r];
+            }
+        }
+        if (MODE == PS_COUNT && tid < 4 && 2 * ma + tid < 2 * M)
+            cnt[(size_t)(2 * ma + tid) * ntiles + tile] = tid == 0 ? run[0] : tid == 1 ? run[1] : tid == 2 ? run[2] : run[3];
+    }
+}
+
+// ---- the null ----------------------------------------------------------------------------------------
+constexpr int PN_T = 256;
+
+// One workgroup per motif.  The score of a random w-mer: pdf after column j lives on [0, (j+1) bins];
+// pdf_new[s] = sum_a bg[a] pdf_old[s - S[j][a]], a = 0..3 in order, one lane per s.  Then the tail: every
+// thread sums its run of scores from the top down, thread 0 chains the runs from the top down, and
+// tail[s] = (sum inside the run from its top to s) + (the runs above): sums of non-negative terms, so the
+// tail never rises with s and "the smallest s with tail[s] <= pcut" is the number of s with tail[s] > pcut.
+__global__ __launch_bounds__(PN_T) void pwm_null_kernel(const int16_t* __restrict__ S, const int* __restrict__ widths,
+                                                        int wmax, int bins, double bg0, double bg1, double bg2,
+                                                        double bg3, double pcut, double* __restrict__ tail,
+                                                        int* __restrict__ thr) {
+    extern __shared__ double pn_lds[];         // two buffers [wmax bins + 1] | the threads' run sums [PN_T]
+    __shared__ int above;
+    const int m = blockIdx.x, tid = threadIdx.x;
+    const int cap = wmax * bins + 1, stride = cap + 1;
+    double* cur = pn_lds;
+    double* nxt = pn_lds + cap;
+    double* part = pn_lds + 2 * cap;
+    double* trow = tail ? tail + (size_t)m * stride : nullptr;
+    const int w = motif_width(widths, m, wmax);
+    if (w == 0) {                              // an empty motif: no distribution, the out-of-range threshold
+        if (trow) for (int s = tid; s < stride; s += PN_T) trow[s] = 0.0;
+        if (tid == 0) thr[m] = 1;
+        return;
+    }
+    const int n = w * bins + 1;                // scores 0 .. w bins
+    for (int s = tid; s < n; s += PN_T) cur[s] = s == 0 ? 1.0 : 0.0;
+    if (tid == 0) above = 0;
+    __syncthreads();
+    const double bg[4] = {bg0, bg1, bg2, bg3};
+    for (int j = 0; j < w; ++j) {
+        const int16_t* col = S + ((size_t)m * wmax + j) * 4;
+        const int sa[4] = {col[0], col[1], col[2], col[3]};
+        const int top_old = j * bins, top_new = top_old + bins;
+        for (int s = tid; s <= top_new; s += PN_T) {
+            double acc = 0.0;
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                const int idx = s - sa[a];
+                if (idx >= 0 && idx <= top_old) acc += bg[a] * cur[idx];
+            }
+            nxt[s] = acc;
+        }
+        __syncthreads();
+        double* t = cur; cur = nxt; nxt = t;
+    }
+    const int per = (n + PN_T - 1) / PN_T;
+    const int lo = min(tid * per, n), hi = min(lo + per, n);
+    double run = 0.0;
+    for (int s = hi - 1; s >= lo; --s) run += cur[s];
+    part[tid] = run;
+    __syncthreads();
+    if (tid == 0) {
+        double after = 0.0;                    // the runs above thread t's
+        for (int t = PN_T - 1; t >= 0; --t) {
+            const double v = part[t];
+            part[t] = after;
+            after += v;
+        }
+    }
+    __syncthreads();
+    const double after = part[tid];
+    int mine = 0;
+    run = 0.0;
+    for (int s = hi - 1; s >= lo; --s) {
+        run += cur[s];
+        const double v = run + after;
+        nxt[s] = v;
+        mine += v > pcut ? 1 : 0;
+    }
+    if (mine) atomicAdd(&above, mine);         // an integer sum: the order does not matter
+    __syncthreads();
+    if (trow) for (int s = tid; s < stride; s += PN_T) trow[s] = s < n ? nxt[s] : 0.0;
+    if (tid == 0) thr[m] = above;              // n = w bins + 1 when no tail is <= pcut
+}
+
+int64_t align256(int64_t v) { return (v + 255) & ~int64_t(255); }
+int64_t sites_tiles(int64_t npos) { return (npos + EXPLAINN_SITES_TILE - 1) / EXPLAINN_SITES_TILE; }
+int64_t pwm_cnt_bytes(int M, int64_t npos) { return align256(2 * (int64_t)M * sites_tiles(npos) * (int64_t)sizeof(int)); }
+
+bool pwm_geometry_ok(const char* who, int M, int wmax, int bins) {
+    if (M < 0 || M > 65535 * PS_G || wmax < 1 || wmax > EXPLAINN_MOTIF_MAX_WIDTH || bins < 1 ||
+        bins > EXPLAINN_MOTIF_MAX_BINS) {
+        explainn_set_error("%s: need 0 <= M <= %d, 1 <= wmax <= %d and 1 <= bins <= %d (M=%d wmax=%d bins=%d)", who,
+                           65535 * PS_G, EXPLAINN_MOTIF_MAX_WIDTH, EXPLAINN_MOTIF_MAX_BINS, M, wmax, bins);
+        return false;
+    }
+    return true;
+}
+
+}  // namespace
+
+extern "C" int explainn_pwm_null(const int16_t* scores, const int32_t* widths, int M, int wmax, int bins, double bg_a,
+                                 double bg_c, double bg_g, double bg_t, double pcut, double* tail,
+                                 int32_t* thresholds, void* stream) {
+    if (!pwm_geometry_ok("pwm_null", M, wmax, bins)) return EXPLAINN_E_ARG;
+    if (!(pcut >= 0.0 && pcut <= 1.0)) {
+        explainn_set_error("pwm_null: pcut must be in [0, 1] (got %g)", pcut);
+        return EXPLAINN_E_ARG;
+    }
+    const double bg[4] = {bg_a, bg_c, bg_g, bg_t};
+    for (int a = 0; a < 4; ++a)
+        if (!(bg[a] > 0.0 && bg[a] <= 1.0)) {
+            explainn_set_error("pwm_null: every background frequency must be in (0, 1] (got %g)", bg[a]);
+            return EXPLAINN_E_ARG;
+        }
+    if (M == 0) return EXPLAINN_OK;
+    if (!scores || !widths || !thresholds) {
+        explainn_set_error("pwm_null: scores, widths and thresholds must be device pointers");
+        return EXPLAINN_E_ARG;
+    }
+    const size_t sm = ((size_t)2 * (wmax * bins + 1) + PN_T) * sizeof(double);      // <= 133136 bytes
+    if (sm > 64 * 1024)
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&pwm_null_kernel),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
+    hipLaunchKernelGGL(pwm_null_kernel, dim3(M), dim3(PN_T), sm, static_cast<hipStream_t>(stream), scores, widths,
+                       wmax, bins, bg_a, bg_c, bg_g, bg_t, pcut, tail, thresholds);
+    LAUNCH_CHECK();
+    return EXPLAINN_OK;
+}
+
+// the caller's workspace: cnt int [2M][tiles] | tot int64 [2M]
+extern "C" int64_t explainn_pwm_sites_workspace_bytes(int M, int64_t n_positions) {
+    if (M < 0 || n_positions < 0) return 0;
+    return pwm_cnt_bytes(M, n_positions) + align256(2 * (int64_t)M * (int64_t)sizeof(long long));
+}
+
+extern "C" int explainn_pwm_sites(const uint8_t* seq, int64_t seq_len, int64_t start, int64_t n_positions,
+                                  int64_t period, int both_strands, const int16_t* scores, const int32_t* widths,
+                                  int M, int wmax, const int32_t* thresholds, const double* tail, int bins,
+                                  int64_t* offsets, int32_t* pos, int32_t* score, double* pvalue, int64_t capacity,
+                                  void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!pwm_geometry_ok("pwm_sites", M, wmax, bins)) return EXPLAINN_E_ARG;
+    if (start < 0 || n_positions < 0 || start + n_positions > seq_len || n_positions + wmax >= (int64_t)INT_MAX) {
+        explainn_set_error("pwm_sites: need 0 <= start, start + n_positions <= seq_len and n_positions + wmax < 2^31 "
+                           "(start=%lld n_positions=%lld seq_len=%lld)", (long long)start, (long long)n_positions,
+                           (long long)seq_len);
+        return EXPLAINN_E_ARG;
+    }
+    if (period < 0 || capacity < 0) {
+        explainn_set_error("pwm_sites: period and capacity must not be negative");
+        return EXPLAINN_E_ARG;
+    }
+    if (!offsets) { explainn_set_error("pwm_sites: offsets is required"); return EXPLAINN_E_ARG; }
+    if (pvalue && !tail) { explainn_set_error("pwm_sites: pvalue needs tail"); return EXPLAINN_E_ARG; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (M == 0 || n_positions == 0) {
+        HIP_TRY(hipMemsetAsync(offsets, 0, (size_t)(2 * (int64_t)M + 1) * sizeof(int64_t), s));
+        return EXPLAINN_OK;
+    }
+    if (!seq || !scores || !widths || !thresholds) {
+        explainn_set_error("pwm_sites: seq, scores, widths and thresholds must be device pointers");
+        return EXPLAINN_E_ARG;
+    }
+    const int64_t need = explainn_pwm_sites_workspace_bytes(M, n_positions);
+    if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 255) != 0) {
+        explainn_set_error("pwm_sites workspace of %lld bytes (256-byte aligned), %lld needed",
+                           (long long)workspace_bytes, (long long)need);
+        return EXPLAINN_E_ARG;
+    }
+    const int ntiles = (int)sites_tiles(n_positions), rows = 2 * M;
+    int* cnt = static_cast<int*>(workspace);
+    long long* tot = reinterpret_cast<long long*>(static_cast<char*>(workspace) + pwm_cnt_bytes(M, n_positions));
+    long long* off = reinterpret_cast<long long*>(offsets);
+    // the bases the call may read from `start` on: n_positions + wmax - 1, clipped to the sequence
+    const int span = (int)std::min<int64_t>(n_positions + wmax - 1, seq_len - start);
+    const size_t sm = (size_t)PS_G * wmax * 8 * sizeof(int) + ((EXPLAINN_SITES_TILE + wmax - 1 + 15) & ~15);
+    const dim3 grid(ntiles, (M + PS_G - 1) / PS_G);
+    const int both = both_strands ? 1 : 0, stride = wmax * bins + 2;
+    hipLaunchKernelGGL(pwm_sites_kernel<PS_COUNT>, grid, dim3(PS_T), sm, s, seq, (long long)start, (int)n_positions,
+                       span, (long long)period, both, scores, widths, thresholds, (const double*)nullptr, stride, cnt,
+                       (const long long*)nullptr, (int*)nullptr, (int*)nullptr, (double*)nullptr, 0ll, M, wmax, ntiles);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(sites_scan_tiles_kernel, dim3(rows), dim3(64), 0, s, cnt, tot, ntiles);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(sites_scan_units_kernel, dim3(1), dim3(64), 0, s, tot, off, rows);
+    LAUNCH_CHECK();
+    if (pos == nullptr || capacity <= 0) return EXPLAINN_OK;
+    hipLaunchKernelGGL(pwm_sites_kernel<PS_EMIT>, grid, dim3(PS_T), sm, s, seq, (long long)start, (int)n_positions,
+                       span, (long long)period, both, scores, widths, thresholds, tail, stride, cnt, off, pos, score,
+                       pvalue, (long long)capacity, M, wmax, ntiles);
+    LAUNCH_CHECK();
+    return EXPLAINN_OK;
+}

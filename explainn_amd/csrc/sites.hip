@@ -17,6 +17,7 @@
 //          position order); records with rank >= capacity are dropped
 // so per unit the sites ascend in position and no rank depends on the order atomics arrive in.
 #include "codescan.h"
+#include "sitescan.h"
 
 namespace {
 
@@ -90,38 +91,6 @@ __global__ __launch_bounds__(SITES_T) void sites_kernel(
     }
     if (MODE == SITES_COUNT && tid < 4 && quad * 4 + tid < U)
         cnt[(size_t)(quad * 4 + tid) * ntiles + tile] = run[tid];
-}
-
-// One wavefront per unit: cnt[u][.] <- its exclusive scan over the tiles, tot[u] <- the unit's sites.
-// A unit has fewer than 2^31 sites (one per position at most), so the in-unit prefix stays int.
-__global__ __launch_bounds__(64) void sites_scan_tiles_kernel(int* __restrict__ cnt,
-                                                              long long* __restrict__ tot, int ntiles) {
-    const int u = blockIdx.x, lane = threadIdx.x;
-    int* row = cnt + (size_t)u * ntiles;
-    int running = 0;
-    for (int b0 = 0; b0 < ntiles; b0 += 64) {
-        const int b = b0 + lane;
-        const int v = b < ntiles ? row[b] : 0;
-        const int inc = wave_scan_up(v, lane);
-        if (b < ntiles) row[b] = running + (inc - v);
-        running += __shfl(inc, 63, 64);
-    }
-    if (lane == 0) tot[u] = running;
-}
-
-// One wavefront: offsets[0 .. U] <- exclusive scan of the units' totals.
-__global__ __launch_bounds__(64) void sites_scan_units_kernel(const long long* __restrict__ tot,
-                                                              long long* __restrict__ offsets, int U) {
-    const int lane = threadIdx.x;
-    long long running = 0;
-    for (int u0 = 0; u0 < U; u0 += 64) {
-        const int u = u0 + lane;
-        const long long v = u < U ? tot[u] : 0;
-        const long long inc = wave_scan_up(v, lane);
-        if (u < U) offsets[u] = running + (inc - v);
-        running += __shfl(inc, 63, 64);
-    }
-    if (lane == 0) offsets[U] = running;
 }
 
 int64_t align256(int64_t v) { return (v + 255) & ~int64_t(255); }

@@ -1,0 +1,354 @@
+"""Where do the known motifs occur?  PWM hits of a sequence at an exact p-value cutoff, on the device.
+
+`sites.call_sites` lists the sites of the model's own filters; this module lists those of motifs that come
+from a database (JASPAR, a MEME file, `motifs.write_meme` output) -- what FIMO does, and what the reference
+vendors PWMScan for -- so that filter sites can be annotated by the sites of known motifs and not only by
+the shape of their matrices (`spacing.spacing(sites.concat_units(filter_calls, pwm_calls), ...)`).
+
+    calls = scan_motifs(read_motifs("JASPAR.meme"), codes, pvalue=1e-4)      # both strands
+    start, strand, score = calls.unit(3)                # '+' sites ascending, then '-' sites ascending
+    calls.pvalue, calls.iscore, calls.widths, calls.names
+
+A motif's log-odds against the background are rescaled to integers 0..bins per cell (`quantise`: FIMO's
+per-motif rescaling; the pseudocount rule is this project's), so a site's score is an
+integer and its null -- the score of a random w-mer drawn iid from the background -- is an exact
+column-by-column convolution (explainn_pwm_null, fp64, on the device); the threshold of a motif is the
+smallest integer score whose tail is <= pvalue.  The scan (explainn_pwm_sites, csrc/pwmsites.hip) lists every
+(motif, strand, start) at or above it with the count / scan / emit scheme of call_sites.
+
+`python -m explainn_amd.pwmsites MOTIFS FASTA -o OUT.bed` writes `SeqId start end name score strand pvalue`.
+There is no CPU path.
+"""
+import argparse
+import ctypes as C
+import sys
+
+import numpy as np
+
+from . import motifs as _motifs
+from . import sites as _sites
+from .sites import SiteCalls
+
+WORKSPACE_BYTES = 256 << 20      # device scratch of one scan call; the chunk of start positions is sized to it
+
+
+# ---------------------------------------------------------------- the score tables (host, fp64)
+def _background(bg):
+    """(4,) float64, all > 0, summing to 1; None: uniform."""
+    if bg is None:
+        return np.full(4, 0.25)
+    b = np.zeros(0) if isinstance(bg, str) else np.asarray(bg, dtype=np.float64)
+    if b.shape != (4,) or not np.all(np.isfinite(b)) or np.any(b <= 0) or abs(b.sum() - 1.0) > 1e-6:
+        raise ValueError("bg must hold four positive frequencies (A, C, G, T) that sum to 1 (got %r)" % (bg,))
+    return b / b.sum()
+
+
+def _check_table_args(pseudocount, bins):
+    if not (np.isfinite(pseudocount) and float(pseudocount) >= 0):
+        raise ValueError("pseudocount must not be negative (got %r)" % (pseudocount,))
+    if int(bins) != bins or not 1 <= int(bins) <= _motifs.MAX_BINS:
+        raise ValueError("bins must be an integer in [1, %d] (got %r)" % (_motifs.MAX_BINS, bins))
+
+
+def motif_list(motifs):
+    """(names, [(w,4) float64]) of [(id, name, matrix)] or of anything motifs._as_set accepts; motifs without
+    an identifier are called motif<i>."""
+    if isinstance(motifs, (list, tuple)) and all(isinstance(m, tuple) and len(m) == 3 for m in motifs):
+        return [str(m[0]) for m in motifs], [np.asarray(m[2], dtype=np.float64).reshape(-1, 4) for m in motifs]
+    x, widths = _motifs._as_set(motifs, "cpu")
+    x, widths = x.numpy().astype(np.float64), widths.numpy()
+    if np.any(widths < 0) or np.any(widths > x.shape[1]):
+        raise ValueError("a motif's width lies outside [0, %d]" % x.shape[1])
+    return ["motif%d" % i for i in range(len(x))], [x[i, :widths[i]] for i in range(len(x))]
+
+
+def quantise(motifs, bg=None, pseudocount=0.1, bins=100):
+    """Integer score tables of [(w,4)] count or probability matrices (or [(id, name, matrix)]):
+
+        p'[j][a] = (P[j][a] + pc bg[a]) / (1 + pc)          P = the column divided by its sum (0.25 where 0)
+        l[j][a]  = log2(p'[j][a] / bg[a]);   lo, hi = min, max of l over the motif;   scale = bins / (hi - lo)
+        S[j][a]  = rint((l[j][a] - lo) scale)                in [0, bins]; the real score of a site of
+                                                            integer score s is s / scale + w lo
+
+    Returns (S int16 (M,wmax,4) zero padded, widths int32 (M,), scale float64 (M,), lo float64 (M,)).  A motif of
+    width 0, or one whose log-odds are all equal (hi == lo), is EMPTY: scale 0, lo 0, an all-zero table."""
+    _check_table_args(pseudocount, bins)
+    b = _background(bg)
+    mats = [np.asarray(m[2] if isinstance(m, tuple) else m, dtype=np.float64).reshape(-1, 4) for m in motifs]
+    M = len(mats)
+    wmax = max([len(m) for m in mats] + [1])
+    if wmax > _motifs.MAX_WIDTH:
+        raise ValueError("motifs wider than %d columns are not supported (got %d)" % (_motifs.MAX_WIDTH, wmax))
+    widths = np.array([len(m) for m in mats], dtype=np.int32).reshape(M)
+    x = np.zeros((M, wmax, 4))                             # all motifs at once: a database holds thousands
+    for i, m in enumerate(mats):
+        x[i, :len(m)] = m
+    bad = ~np.isfinite(x) | (x < 0)
+    if bad.any():
+        raise ValueError("motif %d holds a negative or non-finite entry" % int(np.nonzero(bad)[0][0]))
+    inside = np.arange(wmax)[None, :, None] < widths[:, None, None]
+    pc = float(pseudocount)
+    tot = x.sum(axis=2, keepdims=True)
+    p = np.where(tot > 0, x / np.where(tot > 0, tot, 1.0), 0.25)
+    with np.errstate(divide="ignore"):
+        l = np.log2((p + pc * b) / (1.0 + pc) / b)          # -inf where pc == 0 meets a zero probability
+    bad = inside & ~np.isfinite(l)
+    if bad.any():
+        raise ValueError("motif %d has a zero probability and pseudocount is 0: its log-odds are not finite"
+                         % int(np.nonzero(bad)[0][0]))
+    a = np.where(inside, l, np.inf).min(axis=(1, 2))
+    z = np.where(inside, l, -np.inf).max(axis=(1, 2))
+    live = (widths > 0) & (z > a)
+    scale = np.where(live, int(bins) / np.where(live, z - a, 1.0), 0.0)
+    lo = np.where(live, a, 0.0)
+    S = np.where(inside & live[:, None, None], np.rint((l - lo[:, None, None]) * scale[:, None, None]), 0.0).astype(np.int16)
+    return S, widths, scale, lo
+
+
+# ---------------------------------------------------------------- the device calls
+def _device_for(device, codes, what):
+    import torch
+    if device is None and torch.is_tensor(codes) and codes.device.type == "cuda":
+        device = codes.device
+    if device is None:
+        if not torch.cuda.is_available():
+            raise RuntimeError("pwmsites.%s runs only on a HIP device (there is no CPU fallback)" % what)
+        device = torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("pwmsites.%s runs only on a HIP device (there is no CPU fallback)" % what)
+    return device
+
+
+class PwmNull:
+    """The exact null of a set of quantised motifs, on the device: `tail` float64 (M, wmax bins + 2),
+    tail[m][s] = P(score of a random w-mer >= s) (zero past w bins, all zero for an empty motif) and
+    `thresholds` int32 (M,), the smallest s with tail[m][s] <= pvalue (w bins + 1: no score reaches it; an
+    empty motif: 1).  `scores` (int16 (M,wmax,4)) and `widths` (int32, 0 for an empty motif) are the tables
+    as the device calls take them; scale, lo (host float64) map integer scores back to log-odds."""
+
+    def __init__(self, tail, thresholds, scores, widths, scale, lo, bins, bg, pvalue):
+        self.tail, self.thresholds, self.scores, self.widths = tail, thresholds, scores, widths
+        self.scale, self.lo, self.bins, self.bg, self.pvalue = scale, lo, int(bins), bg, float(pvalue)
+
+    @property
+    def wmax(self):
+        return self.scores.shape[1]
+
+
+def _null(S, live_widths, scale, lo, bins, bg, pvalue, device):
+    import torch
+
+    from . import _lib
+    M, wmax = S.shape[0], S.shape[1]
+    scores = torch.from_numpy(S).to(device).contiguous()
+    widths = torch.from_numpy(live_widths).to(device)
+    tail = torch.empty((M, wmax * int(bins) + 2), dtype=torch.float64, device=device)     # every entry is overwritten
+    thr = torch.empty((M,), dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        _lib.check(_lib.load().explainn_pwm_null(
+            scores.data_ptr(), widths.data_ptr(), M, wmax, int(bins), float(bg[0]), float(bg[1]), float(bg[2]),
+            float(bg[3]), float(pvalue), tail.data_ptr(), thr.data_ptr(),
+            C.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+    return PwmNull(tail, thr, scores, widths, scale, lo, bins, bg, pvalue)
+
+
+def _check_pvalue(pvalue):
+    if not 0.0 <= float(pvalue) <= 1.0:
+        raise ValueError("pvalue must be in [0, 1] (got %r)" % (pvalue,))
+
+
+def score_null(motifs, pvalue=1e-4, bg=None, pseudocount=0.1, bins=100, device=None):
+    """quantise() and the exact null of every motif (explainn_pwm_null): a PwmNull.  Enqueued on the current
+    stream; no host synchronisation."""
+    _check_pvalue(pvalue)
+    _, mats = motif_list(motifs)
+    b = _background(bg)
+    S, widths, scale, lo = quantise(mats, b, pseudocount, bins)
+    device = _device_for(device, None, "score_null")
+    return _null(S, np.where(scale > 0, widths, 0).astype(np.int32), scale, lo, bins, b, pvalue, device)
+
+
+class PwmCalls(SiteCalls):
+    """SiteCalls of known motifs: unit m = motif m, per motif '+' sites in ascending start, then '-' sites.
+    `score` is the real log-odds (float32, bits), `iscore` the integer score (int32) the threshold and the
+    p-value are functions of, `pvalue` float64; `widths` (int32, per motif) and `names` are carried, and
+    kernel_size is the largest width."""
+
+    def __init__(self, offsets, start, strand, score, widths, names, iscore, pvalue):
+        self.widths = np.asarray(widths, dtype=np.int32)
+        self.names = list(names)
+        super().__init__(offsets, start, strand, score, int(self.widths.max()) if len(self.widths) else 0, pvalue)
+        self.iscore = np.asarray(iscore, dtype=np.int32)
+        if self.pvalue is None or self.iscore.shape != self.pvalue.shape:
+            raise ValueError("iscore and pvalue must hold one value per record")
+        if len(self.widths) != self.units or len(self.names) != self.units:
+            raise ValueError("widths and names must hold one entry per motif")
+
+
+def sequence_background(codes, strands="both"):
+    """The ACGT frequencies of 1-D base codes (N left out), both strands pooled when strands == "both"
+    (freq[A] == freq[T], freq[C] == freq[G])."""
+    import torch
+    if torch.is_tensor(codes):
+        n = torch.bincount(codes.reshape(-1).to(torch.int64), minlength=256)[:4].cpu().numpy().astype(np.float64)
+    else:
+        n = np.bincount(np.asarray(codes).reshape(-1), minlength=256)[:4].astype(np.float64)
+    if strands == "both":
+        n = n + n[::-1]
+    if np.any(n <= 0):
+        raise ValueError("bg='sequence' needs every base A, C, G, T to occur in codes")
+    return n / n.sum()
+
+
+def _chunk_for(M, chunk_positions):
+    """Start positions per call: what was asked for, else as many whole tiles as keep the workspace (one int
+    per (motif, strand, tile)) under WORKSPACE_BYTES, 2^24 at the most."""
+    from . import _lib
+    if chunk_positions is not None:
+        return int(chunk_positions)
+    tiles = max(WORKSPACE_BYTES // (8 * max(M, 1)), 1)
+    return int(min(_sites.CHUNK_POSITIONS, tiles * _lib.SITES_TILE))
+
+
+def _assemble(blocks, M, widths, names, scale, lo):
+    """PwmCalls from per-chunk blocks [(first position, offsets (2M+1), pos, iscore, pvalue)] in ascending
+    order: a stable sort by row keeps ascending starts inside every (motif, strand)."""
+    if not blocks:
+        z = np.zeros(0)
+        return PwmCalls(np.zeros(M + 1, np.int64), z, z, z, widths, names, z, z)
+    row = np.concatenate([np.repeat(np.arange(2 * M, dtype=np.int64), np.diff(o)) for _, o, _, _, _ in blocks])
+    start = np.concatenate([np.asarray(p, dtype=np.int64) + p0 for p0, _, p, _, _ in blocks])
+    iscore = np.concatenate([b[3] for b in blocks])
+    pvalue = np.concatenate([b[4] for b in blocks])
+    order = np.argsort(row, kind="stable")
+    row, start, iscore, pvalue = row[order], start[order], iscore[order], pvalue[order]
+    unit = row >> 1
+    offsets = np.zeros(M + 1, dtype=np.int64)
+    np.cumsum(np.bincount(unit, minlength=M), out=offsets[1:])
+    score = iscore / scale[unit] + widths[unit] * lo[unit]          # a record's motif is never empty: scale > 0
+    return PwmCalls(offsets, start, 1 - 2 * (row & 1), score, widths, names, iscore, pvalue)
+
+
+def scan_motifs(motifs, codes, pvalue=1e-4, bg=None, pseudocount=0.1, bins=100, strands="both", period=0,
+                chunk_positions=None, max_sites=_sites.MAX_SITES, device=None):
+    """Every site of every motif in `codes` at p-value <= pvalue: a PwmCalls.
+
+    motifs: [(id, name, (w,4) matrix)] as read_meme / read_jaspar / read_motifs give them, or anything
+    motifs.compare accepts (counts or probabilities).  codes: 1-D uint8 base codes (0..3 = A,C,G,T, 4 and above
+    = N), numpy array or tensor, host or device.  bg: None = uniform, "sequence" = the ACGT frequencies of
+    `codes` (both strands pooled when strands == "both"), or four frequencies.  (m, '+', p) is a site when
+    the integer score of codes[p : p + w_m] under quantise()'s table reaches the motif's threshold (the
+    smallest score with exact null tail <= pvalue); (m, '-', p) when that of its reverse complement does;
+    a window that holds an N, or with period > 0 crosses a record boundary, is none.  The sequence goes to the
+    device in chunks of start positions that overlap by wmax - 1 bases, sized so that the call's workspace
+    stays under WORKSPACE_BYTES (or chunk_positions starts); each chunk takes a count call, one read of the
+    total, and an emit call into buffers of exactly that size; the result does not depend on the chunking.
+    More than max_sites records raise ValueError."""
+    import torch
+
+    from . import _lib
+    _sites._check_args(strands, chunk_positions, max_sites, period)
+    _check_pvalue(pvalue)
+    names, mats = motif_list(motifs)
+    data = codes if torch.is_tensor(codes) else torch.as_tensor(np.ascontiguousarray(codes))
+    if data.dtype != torch.uint8 or data.dim() != 1:
+        raise ValueError("codes must be a 1-D uint8 array of base codes")
+    b = sequence_background(data, strands) if isinstance(bg, str) and bg == "sequence" else _background(bg)
+    S, widths, scale, lo = quantise(mats, b, pseudocount, bins)
+    device = _device_for(device, data, "scan_motifs")
+    M, wmax, n = len(mats), S.shape[1], int(data.shape[0])
+    blocks = []
+    if M and n:
+        lib = _lib.load()
+        null = _null(S, np.where(scale > 0, widths, 0).astype(np.int32), scale, lo, bins, b, pvalue, device)
+        chunks = _sites.position_chunks(n, _chunk_for(M, chunk_positions), period)
+        nbytes = int(lib.explainn_pwm_sites_workspace_bytes(M, max(c for _, c in chunks)))
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=device)
+        offsets = torch.empty((2 * M + 1,), dtype=torch.int64, device=device)
+        both, counts = int(strands == "both"), np.zeros(M, dtype=np.int64)
+        with torch.cuda.device(device):
+            stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+            def call(piece, cnt, pos, score, pv, capacity):
+                _lib.check(lib.explainn_pwm_sites(
+                    piece.data_ptr(), piece.shape[0], 0, cnt, int(period), both, null.scores.data_ptr(),
+                    null.widths.data_ptr(), M, wmax, null.thresholds.data_ptr(), null.tail.data_ptr(), int(bins),
+                    offsets.data_ptr(), pos, score, pv, capacity, ws.data_ptr(), nbytes, stream))
+
+            for p0, cnt in chunks:
+                piece = data[p0:p0 + cnt + wmax - 1].to(device).contiguous()
+                call(piece, cnt, None, None, None, 0)
+                offs = offsets.cpu().numpy()                                  # the one read of the totals
+                counts += np.diff(offs).reshape(M, 2).sum(axis=1)
+                if int(counts.sum()) > max_sites:
+                    raise ValueError("more than max_sites = %d sites (%d so far): lower pvalue, or raise max_sites"
+                                     % (max_sites, int(counts.sum())))
+                total = int(offs[-1])
+                if total == 0:
+                    continue
+                pos = torch.empty((total,), dtype=torch.int32, device=device)
+                isc = torch.empty((total,), dtype=torch.int32, device=device)
+                pv = torch.empty((total,), dtype=torch.float64, device=device)
+                call(piece, cnt, pos.data_ptr(), isc.data_ptr(), pv.data_ptr(), total)
+                blocks.append((p0, offs, pos.cpu().numpy(), isc.cpu().numpy(), pv.cpu().numpy()))
+    return _assemble(blocks, M, widths, names, scale, lo)
+
+
+# ---------------------------------------------------------------- command line
+def bed_rows(seq_id, calls):
+    """Lines `SeqId start end name score strand pvalue` of one record's PwmCalls: 0-based half-open, end =
+    start + the motif's width, sorted by (start, motif, strand) with '+' before '-'."""
+    unit = calls.unit_ids()
+    order = np.lexsort((-calls.strand, unit, calls.start))
+    return ["%s\t%d\t%d\t%s\t%.6g\t%s\t%.6g\n" % (
+        seq_id, calls.start[i], calls.start[i] + calls.widths[unit[i]], calls.names[unit[i]], calls.score[i],
+        "+" if calls.strand[i] > 0 else "-", calls.pvalue[i]) for i in order]
+
+
+def _bg_arg(text):
+    if text in ("uniform", "sequence"):
+        return None if text == "uniform" else text
+    try:
+        vals = [float(v) for v in text.split(",")]
+    except ValueError:
+        vals = []
+    if len(vals) != 4:
+        raise argparse.ArgumentTypeError("--bg takes uniform, sequence or four frequencies a,c,g,t")
+    return vals
+
+
+def _parser():
+    ap = argparse.ArgumentParser(prog="python -m explainn_amd.pwmsites", description=main.__doc__)
+    ap.add_argument("motifs", help="a MEME file, a JASPAR file or a directory of filter*.jaspar")
+    ap.add_argument("fasta_file")
+    ap.add_argument("-o", "--output-file")
+    ap.add_argument("--pvalue", type=float, default=1e-4)
+    ap.add_argument("--bg", type=_bg_arg, default=None, help="uniform (default), sequence, or a,c,g,t")
+    ap.add_argument("--pseudocount", type=float, default=0.1)
+    ap.add_argument("--bins", type=int, default=100)
+    ap.add_argument("--strands", choices=("both", "fwd"), default="both")
+    return ap
+
+
+def main(argv=None):
+    """FASTA records of any length -> `SeqId start end name score strand pvalue`: one row per site of a known
+    motif at p-value <= --pvalue, 0-based half-open, sorted by (start, motif, strand) within a record.  With
+    --bg sequence every record is scored against its own base frequencies."""
+    args = _parser().parse_args(argv)
+    from .loader import read_fasta_records
+    motifs = _motifs.read_motifs(args.motifs)
+    records = read_fasta_records(args.fasta_file)
+    fh = open(args.output_file, "w") if args.output_file else sys.stdout
+    try:
+        for rid, codes in records:
+            fh.writelines(bed_rows(rid, scan_motifs(motifs, codes, pvalue=args.pvalue, bg=args.bg,
+                                                    pseudocount=args.pseudocount, bins=args.bins,
+                                                    strands=args.strands)))
+    finally:
+        if fh is not sys.stdout:
+            fh.close()
+
+
+if __name__ == "__main__":
+    main()

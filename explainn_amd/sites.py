@@ -120,6 +120,16 @@ def assemble(blocks, units, kernel_size):
     return SiteCalls(offsets, start[order], strand[order], score[order], kernel_size)
 
 
+def concat_units(a, b):
+    """A SiteCalls whose units are a's followed by b's (two calls over the same coordinates: a model's filters
+    and known motifs, say); kernel_size is the larger of the two, and pvalue is kept only if both carry one.
+    spacing.spacing() of it counts filter-versus-filter, filter-versus-motif and motif-versus-motif pairs."""
+    pvalue = None if a.pvalue is None or b.pvalue is None else np.concatenate([a.pvalue, b.pvalue])
+    return SiteCalls(np.concatenate([a.offsets, b.offsets[1:] + a.offsets[-1]]), np.concatenate([a.start, b.start]),
+                     np.concatenate([a.strand, b.strand]), np.concatenate([a.score, b.score]),
+                     max(a.kernel_size, b.kernel_size), pvalue)
+
+
 def call_sites(model, codes, thresholds, strands="both", chunk_positions=None, max_sites=MAX_SITES, period=0,
                null=None):
     """Every site of every unit of `model` (an ExplaiNN, or an ExplaiNNBank: global unit indices) in

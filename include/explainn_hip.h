@@ -776,6 +776,54 @@ int explainn_motif_significance(const float* q, const int32_t* q_widths, int Q, 
                                 uint8_t* colscore, int32_t* hist, void* workspace, int64_t workspace_bytes,
                                 void* stream);
 
+/* Known-motif sites (csrc/pwmsites.hip, DESIGN.md section 8, "Known-motif sites"): where the motifs of a
+ * database occur in a sequence, at an exact p-value cutoff -- what FIMO lists.  A motif is an integer score
+ * table: scores, device int16 (M,wmax,4), rows A,C,G,T per column, every entry in [0, bins], and int32
+ * widths[M]; a width outside [1, wmax] is found on the device and makes the motif EMPTY (no sites).  The host
+ * quantises log-odds to these integers (explainn_amd/pwmsites.py); 1 <= wmax <= EXPLAINN_MOTIF_MAX_WIDTH and
+ * 1 <= bins <= EXPLAINN_MOTIF_MAX_BINS, so a site's score is at most 8192.
+ *
+ * explainn_pwm_null: per motif m of width w, the distribution of the score of a random w-mer drawn iid from
+ * the background (bg_a .. bg_t, each in (0,1]; the caller makes them sum to 1), column by column in fp64:
+ *     pdf_0 = [1];   pdf_{j+1}[s] = sum_{a = A,C,G,T in this order} bg[a] pdf_j[s - scores[m][j][a]]
+ *     tail[m][s] = sum_{s' >= s} pdf_w[s']            for 0 <= s <= w bins, 0 beyond
+ *     thresholds[m] = the smallest s with tail[m][s] <= pcut;  w bins + 1 if there is none
+ * All terms are non-negative and every sum has a fixed order (no atomics on floats): the same input gives the
+ * same bits.  An empty motif has an all-zero tail row and thresholds[m] = 1 (0 bins + 1).  tail: device double
+ * [M][wmax bins + 2], may be NULL; thresholds: device int32 [M].  pcut outside [0,1] (or NaN), a background
+ * frequency outside (0,1], M < 0 or wmax / bins outside their ranges: EXPLAINN_E_ARG.  M == 0 launches nothing.
+ *
+ * explainn_pwm_sites: seq, seq_len, start, n_positions and period as explainn_call_sites takes them, except
+ * that the call may end at the sequence's end: it needs start + n_positions <= seq_len only, and reads the
+ * bases [start, min(start + n_positions + wmax - 1, seq_len)).  Codes 0..3 = ACGT; 4 and every byte above it = N.
+ * Rows r = 2m + (strand is '-'):
+ *     row 2m    at start p scores  sum_{j<w} scores[m][j][seq[p+j]]
+ *     row 2m+1  at start p scores  sum_{j<w} scores[m][j][3 - seq[p+w-1-j]]    (the reverse complement of
+ *               seq[p : p+w]; the same forward coordinate p); empty when both_strands == 0
+ * A start is not live for motif m when its w bases run past the bases the call reads, when its window holds
+ * an N, or, with period > 0, when p mod period > period - w (the rule of explainn_call_sites with the
+ * motif's own width).  A live start with score >= thresholds[m] is a site.
+ * offsets: int64 [2M+1], device, always written: the exclusive scan of the FULL per-row counts -- the
+ * offsets2 layout explainn_site_spacing reads.  pos (int32, start-relative), score (int32, may be NULL) and
+ * pvalue (double, may be NULL, needs tail: tail[m][score] of explainn_pwm_null's table with the same wmax and
+ * bins): record offsets[r] + i is the i-th site of row r in ascending position; records with index >= capacity
+ * are not written.  pos == NULL: count only.  Order and bits are a function of the input alone (counts, scans
+ * and ballots in position order).  workspace: device memory, 256-byte aligned, of
+ * explainn_pwm_sites_workspace_bytes(M, n_positions) bytes.  No context, no allocation, no host
+ * synchronisation.  EXPLAINN_E_ARG unless 0 <= start, start + n_positions <= seq_len, n_positions + wmax < 2^31,
+ * period >= 0, capacity >= 0 and 0 <= M <= 65535 EXPLAINN_PWM_GROUP.  M == 0 or n_positions == 0 zeroes offsets.
+ * EXPLAINN_PWM_GROUP: motifs per workgroup (tests place their motif counts around it). */
+#define EXPLAINN_PWM_GROUP 16
+int explainn_pwm_null(const int16_t* scores, const int32_t* widths, int M, int wmax, int bins, double bg_a,
+                      double bg_c, double bg_g, double bg_t, double pcut, double* tail, int32_t* thresholds,
+                      void* stream);
+int64_t explainn_pwm_sites_workspace_bytes(int M, int64_t n_positions);
+int explainn_pwm_sites(const uint8_t* seq, int64_t seq_len, int64_t start, int64_t n_positions, int64_t period,
+                       int both_strands, const int16_t* scores, const int32_t* widths, int M, int wmax,
+                       const int32_t* thresholds, const double* tail, int bins, int64_t* offsets, int32_t* pos,
+                       int32_t* score, double* pvalue, int64_t capacity, void* workspace, int64_t workspace_bytes,
+                       void* stream);
+
 /* One Adam step over n_tensors parameter tensors in a single launch -- torch.optim.Adam(params, lr)
  * with its defaults, the optimiser the reference builds (architectures/__init__.py:463-464) and
  * steps at selene/__init__.py:291.  params/grads/exp_avg/exp_avg_sq: HOST arrays of n_tensors

@@ -80,8 +80,10 @@ CENTRAL = [r"^site_positions_kernel", r"^centrality_test_kernel"]
 # of the filter -> PWM export and its scan)
 SITES = [r"^sites_kernel<0>", r"^sites_kernel<1>", r"^sites_scan_tiles_kernel", r"^sites_scan_units_kernel",
          r"^site_kernel<0>", r"^site_kernel<1>", r"^site_kernel<2>", r"^site_scan_kernel"]
+# known-motif sites (pwmsites.hip): the exact null and the count / emit scan (its two scans are SITES')
+PWMSITES = [r"^pwm_null_kernel", r"^pwm_sites_kernel<0>", r"^pwm_sites_kernel<1>"]
 GATED = (C2_STEP + INPUT_GRAD + ISM + PATHGRAD + METRICS + SCAN + VARIANTS + HAPLOTYPES + SHUFFLE + MOTIFS + ACTNULL +
-         SPACING + ENRICH + CENTRAL + SITES)
+         SPACING + ENRICH + CENTRAL + SITES + PWMSITES)
 
 
 # Register cliffs measured in the pipeline: 1024-thread blocks of which TWO must
