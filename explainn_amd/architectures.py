@@ -139,40 +139,21 @@ class BaseCodes:
         return self.codes.shape
 
 
-class SequenceWindows:
-    """The windows codes[start + i*stride : ... + L], i < n_windows, of ONE device-resident sequence
-    of base codes (1-D uint8), as ExplaiNN._launch_scan takes them: the context cuts them out of the
-    sequence itself (explainn_scan), `sub_batch` of them per device pass."""
+def _check_codes(codes, dev, subject):
+    """A device-resident sequence of base codes as the context reads it; `subject` opens the message."""
+    if not torch.is_tensor(codes) or codes.dtype != torch.uint8 or codes.dim() != 1 or not codes.is_contiguous():
+        raise RuntimeError("%s a contiguous 1-D uint8 tensor of base codes" % subject)
+    if codes.device != dev:
+        raise RuntimeError("input is on %s but the model is on %s" % (codes.device, dev))
 
-    def __init__(self, codes, start, n_windows, stride, reverse_complement=False, sub_batch=4096):
-        self.codes, self.start, self.n_windows, self.stride = codes, int(start), int(n_windows), int(stride)
+
+class _SequenceRows:
+    """A batch whose rows the context cuts out of ONE device-resident sequence of base codes (1-D uint8)
+    itself, `sub_batch` of them per device pass."""
+
+    def __init__(self, codes, n_rows, reverse_complement, sub_batch):
+        self.codes, self.n_rows = codes, int(n_rows)
         self.reverse_complement = bool(reverse_complement)
-        self.sub_batch = max(1, min(int(sub_batch), self.n_windows))
-
-    @property
-    def shape(self):
-        """(sequences per device pass, L): what _front sizes the context by."""
-        return (self.sub_batch, None)
-
-
-class EditedWindows:
-    """Windows of ONE device-resident sequence of base codes (1-D uint8) at arbitrary starts, each with
-    at most one edit spliced in, as ExplaiNN._launch_score_edits takes them (explainn_score_edits,
-    include/explainn_hip.h has the row definition).  All tables are contiguous tensors on the codes'
-    device: row_start int64 (rows,), row_edit int32 (rows,) with -1 = no edit; pos int64, ref_len /
-    alt_len / alt_off int32 (edits,); alt uint8, the pool of alt base codes.  `sub_batch` rows run per
-    device pass."""
-
-    _TABLES = (("row_start", torch.int64), ("row_edit", torch.int32), ("pos", torch.int64),
-               ("ref_len", torch.int32), ("alt_len", torch.int32), ("alt_off", torch.int32), ("alt", torch.uint8))
-
-    def __init__(self, codes, row_start, row_edit, pos, ref_len, alt_len, alt_off, alt,
-                 reverse_complement=False, sub_batch=4096):
-        self.codes = codes
-        self.row_start, self.row_edit = row_start, row_edit
-        self.pos, self.ref_len, self.alt_len, self.alt_off, self.alt = pos, ref_len, alt_len, alt_off, alt
-        self.reverse_complement = bool(reverse_complement)
-        self.n_rows = int(row_start.numel())
         self.sub_batch = max(1, min(int(sub_batch), self.n_rows))
 
     @property
@@ -180,70 +161,82 @@ class EditedWindows:
         """(sequences per device pass, L): what _front sizes the context by."""
         return (self.sub_batch, None)
 
-    def _check_tensors(self, dev):
-        c = self.codes
-        if not torch.is_tensor(c) or c.dtype != torch.uint8 or c.dim() != 1 or not c.is_contiguous():
-            raise RuntimeError("edited windows take a contiguous 1-D uint8 tensor of base codes")
-        if c.device != dev:
-            raise RuntimeError("input is on %s but the model is on %s" % (c.device, dev))
+
+class SequenceWindows(_SequenceRows):
+    """The windows codes[start + i*stride : ... + L], i < n_windows, as ExplaiNN._launch_scan takes them
+    (explainn_scan)."""
+
+    def __init__(self, codes, start, n_windows, stride, reverse_complement=False, sub_batch=4096):
+        super().__init__(codes, n_windows, reverse_complement, sub_batch)
+        self.start, self.n_windows, self.stride = int(start), self.n_rows, int(stride)
+
+    def check(self, dev):
+        _check_codes(self.codes, dev, "a scan takes")
+
+
+class EditedWindows(_SequenceRows):
+    """Windows at arbitrary starts, each with at most one edit spliced in, as ExplaiNN._launch_score_edits
+    takes them (explainn_score_edits, include/explainn_hip.h has the row definition).  All tables are
+    contiguous tensors on the codes' device: row_start int64 (rows,), row_edit int32 (rows,) with -1 = no
+    edit; pos int64, ref_len / alt_len / alt_off int32 (edits,); alt uint8, the pool of alt base codes."""
+
+    _TABLES = (("row_start", torch.int64), ("row_edit", torch.int32), ("pos", torch.int64),
+               ("ref_len", torch.int32), ("alt_len", torch.int32), ("alt_off", torch.int32), ("alt", torch.uint8))
+    # the struct of these tables, its count fields (each the length of a table), the tables with one entry per row
+    _STRUCT = (_lib.Edits, (("n_edits", "pos"), ("alt_bytes", "alt")), ("row_start", "row_edit"))
+
+    def __init__(self, codes, row_start, row_edit, pos, ref_len, alt_len, alt_off, alt,
+                 reverse_complement=False, sub_batch=4096):
+        self._init_tables(codes, (row_start, row_edit, pos, ref_len, alt_len, alt_off, alt), reverse_complement,
+                          sub_batch)
+
+    def _init_tables(self, codes, tables, reverse_complement, sub_batch):
+        for (name, _), t in zip(self._TABLES, tables):
+            setattr(self, name, t)
+        _SequenceRows.__init__(self, codes, tables[0].numel(), reverse_complement, sub_batch)
+
+    def check(self, dev):
+        _check_codes(self.codes, dev, "edited windows take")
         for name, dt in self._TABLES:
             t = getattr(self, name)
             if not torch.is_tensor(t) or t.dtype != dt or t.dim() != 1 or not t.is_contiguous() or t.device != dev:
                 raise RuntimeError("%s must be a contiguous 1-D %s tensor on %s" % (name, dt, dev))
-
-    def check(self, dev):
-        self._check_tensors(dev)
-        if self.row_edit.numel() != self.n_rows:
-            raise RuntimeError("row_start and row_edit must have one entry per row")
+        per_row = self._STRUCT[2]
+        if any(getattr(self, name).numel() != self.n_rows for name in per_row):
+            raise RuntimeError("%s and %s must have one entry per row" % (", ".join(per_row[:-1]), per_row[-1]))
         if not self.pos.numel() == self.ref_len.numel() == self.alt_len.numel() == self.alt_off.numel():
             raise RuntimeError("pos, ref_len, alt_len and alt_off must have one entry per edit")
 
     def struct(self):
-        """The explainn_edits of these tables (valid while this object lives)."""
-        ed = _lib.Edits()
+        """The explainn_edits / explainn_haplotypes of these tables (valid while this object lives)."""
+        cls, counts, _ = self._STRUCT
+        st = cls()
         for name, _ in self._TABLES:
             t = getattr(self, name)
-            setattr(ed, name, t.data_ptr() if t.numel() else None)
-        ed.n_edits, ed.alt_bytes = self.pos.numel(), self.alt.numel()
-        return ed
+            setattr(st, name, t.data_ptr() if t.numel() else None)
+        for field, name in counts:
+            setattr(st, field, getattr(self, name).numel())
+        return st
 
 
 class HaplotypeWindows(EditedWindows):
-    """Windows of ONE device-resident sequence of base codes at arbitrary starts, each carrying a RUN of
-    edits, as ExplaiNN._launch_score_haplotypes takes them (explainn_score_haplotypes,
-    include/explainn_hip.h has the run algebra and the ordering rule).  Contiguous tensors on the codes'
-    device: row_start int64, row_first int64, row_count int32 (rows,); edit_index int32, the rows' runs
-    as indices into the edit table; pos int64, ref_len / alt_len / alt_off int32 (edits,); alt uint8.
-    Row b carries the edits edit_index[row_first[b] : row_first[b] + row_count[b]]."""
+    """Windows at arbitrary starts, each carrying a RUN of edits, as ExplaiNN._launch_score_haplotypes
+    takes them (explainn_score_haplotypes, include/explainn_hip.h has the run algebra and the ordering
+    rule).  Contiguous tensors on the codes' device: row_start int64, row_first int64, row_count int32
+    (rows,); edit_index int32, the rows' runs as indices into the edit table; pos int64, ref_len / alt_len /
+    alt_off int32 (edits,); alt uint8.  Row b carries the edits
+    edit_index[row_first[b] : row_first[b] + row_count[b]]."""
 
     _TABLES = (("row_start", torch.int64), ("row_first", torch.int64), ("row_count", torch.int32),
                ("edit_index", torch.int32), ("pos", torch.int64), ("ref_len", torch.int32),
                ("alt_len", torch.int32), ("alt_off", torch.int32), ("alt", torch.uint8))
+    _STRUCT = (_lib.Haplotypes, (("n_index", "edit_index"), ("n_edits", "pos"), ("alt_bytes", "alt")),
+               ("row_start", "row_first", "row_count"))
 
     def __init__(self, codes, row_start, row_first, row_count, edit_index, pos, ref_len, alt_len, alt_off, alt,
                  reverse_complement=False, sub_batch=4096):
-        self.codes = codes
-        self.row_start, self.row_first, self.row_count, self.edit_index = row_start, row_first, row_count, edit_index
-        self.pos, self.ref_len, self.alt_len, self.alt_off, self.alt = pos, ref_len, alt_len, alt_off, alt
-        self.reverse_complement = bool(reverse_complement)
-        self.n_rows = int(row_start.numel())
-        self.sub_batch = max(1, min(int(sub_batch), self.n_rows))
-
-    def check(self, dev):
-        self._check_tensors(dev)
-        if self.row_first.numel() != self.n_rows or self.row_count.numel() != self.n_rows:
-            raise RuntimeError("row_start, row_first and row_count must have one entry per row")
-        if not self.pos.numel() == self.ref_len.numel() == self.alt_len.numel() == self.alt_off.numel():
-            raise RuntimeError("pos, ref_len, alt_len and alt_off must have one entry per edit")
-
-    def struct(self):
-        """The explainn_haplotypes of these tables (valid while this object lives)."""
-        hp = _lib.Haplotypes()
-        for name, _ in self._TABLES:
-            t = getattr(self, name)
-            setattr(hp, name, t.data_ptr() if t.numel() else None)
-        hp.n_index, hp.n_edits, hp.alt_bytes = self.edit_index.numel(), self.pos.numel(), self.alt.numel()
-        return hp
+        self._init_tables(codes, (row_start, row_first, row_count, edit_index, pos, ref_len, alt_len, alt_off, alt),
+                          reverse_complement, sub_batch)
 
 
 VALIDATE_EVERY = 64      # deferred input validation: the sticky device flag is read every this many calls
@@ -619,7 +612,7 @@ class ExplaiNN(_Model):
           VALIDATE_FIRST  always validated as above;
           ONEHOT_ONLY     staged and validated; dense_input or a batch that is not one-hot raises."""
         lib, h = ctx.lib, ctx.handle
-        if isinstance(x, (SequenceWindows, EditedWindows)):
+        if isinstance(x, _SequenceRows):
             # base codes that the entry point stages itself, sub-batch by sub-batch: the flag stays
             # sticky for _settle, as for BaseCodes
             self._rt.calls += 1
@@ -688,11 +681,11 @@ class ExplaiNN(_Model):
     def _stream(self, dev):
         return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
-    def check_input(self):
+    def check_input(self, also=0):
         """Read (one host sync) and clear the sticky validation flag; raise if any batch since the
         last read was not one-hot.  predict(), Trainer validation passes and the filter export call
-        it after their loops."""
-        if self.input_flags() & 1:
+        it after their loops.  also: the flags already read of another context (the replica's)."""
+        if (self.input_flags() | also) & 1:
             raise ValueError(
                 "input is not one-hot: base codes must be 0..4, and every column of an fp32 x must "
                 "be one-hot (A,C,G,T) or all-zero (N) as sequence.one_hot_encode produces.  A batch "
@@ -738,11 +731,7 @@ class ExplaiNN(_Model):
         if self.training:
             raise RuntimeError("a scan is an eval-mode path; call model.eval()")
         dev = self._device()
-        c = win.codes
-        if not torch.is_tensor(c) or c.dtype != torch.uint8 or c.dim() != 1 or not c.is_contiguous():
-            raise RuntimeError("a scan takes a contiguous 1-D uint8 tensor of base codes")
-        if c.device != dev:
-            raise RuntimeError("input is on %s but the model is on %s" % (c.device, dev))
+        win.check(dev)
         logits = self._logits_empty(win.n_windows, dev)
         if win.n_windows == 0:
             return logits
@@ -752,51 +741,39 @@ class ExplaiNN(_Model):
             nbytes = int(lib.explainn_scan_workspace_bytes(h, win.n_windows, win.stride, mode))
             _lib.check(min(nbytes, 0))
             ws = torch.empty(max(nbytes, 1), device=dev, dtype=torch.uint8)
-            _lib.check(lib.explainn_scan(h, xp, c.numel(), win.start, win.n_windows, win.stride,
+            _lib.check(lib.explainn_scan(h, xp, win.codes.numel(), win.start, win.n_windows, win.stride,
                                          int(win.reverse_complement), C.byref(ps), logits.data_ptr(), mode,
                                          ws.data_ptr(), nbytes, stream))
             self._settle(read)
         return logits
 
-    def _launch_score_edits(self, ew, want_outs=False):
-        """Eval-mode logits of the rows of an EditedWindows (explainn_score_edits): (rows, T) --
-        (rows, G, T) on a bank -- fp32 on the device; with want_outs also the per-unit outputs
-        (rows, units), units = G*U on a bank, from the same pass: returns (logits, outs)."""
+    def _launch_score_rows(self, rows, symbol, noun, want_outs):
+        """Eval-mode logits of the rows of an EditedWindows / HaplotypeWindows through the entry point
+        `symbol`: (rows, T) -- (rows, G, T) on a bank -- fp32 on the device; with want_outs also the
+        per-unit outputs (rows, units), units = G*U on a bank, from the same pass: returns (logits, outs)."""
         if self.training:
-            raise RuntimeError("scoring edits is an eval-mode path; call model.eval()")
+            raise RuntimeError("scoring %s is an eval-mode path; call model.eval()" % noun)
         dev = self._device()
-        ew.check(dev)
-        logits = self._logits_empty(ew.n_rows, dev)
-        outs = torch.empty(ew.n_rows, self._units(), device=dev, dtype=torch.float32) if want_outs else None
-        if ew.n_rows > 0:
+        rows.check(dev)
+        logits = self._logits_empty(rows.n_rows, dev)
+        outs = torch.empty(rows.n_rows, self._units(), device=dev, dtype=torch.float32) if want_outs else None
+        if rows.n_rows > 0:
             with torch.cuda.device(dev):
-                ctx, ps, _, stream, xp, read = self._front(ew, dev)
-                ed = ew.struct()
-                _lib.check(ctx.lib.explainn_score_edits(
-                    ctx.handle, xp, ew.codes.numel(), C.byref(ed), ew.n_rows, int(ew.reverse_complement),
+                ctx, ps, _, stream, xp, read = self._front(rows, dev)
+                st = rows.struct()
+                _lib.check(getattr(ctx.lib, symbol)(
+                    ctx.handle, xp, rows.codes.numel(), C.byref(st), rows.n_rows, int(rows.reverse_complement),
                     C.byref(ps), logits.data_ptr(), outs.data_ptr() if want_outs else None, stream))
                 self._settle(read)
         return (logits, outs) if want_outs else logits
 
+    def _launch_score_edits(self, ew, want_outs=False):
+        """_launch_score_rows of an EditedWindows (explainn_score_edits)."""
+        return self._launch_score_rows(ew, "explainn_score_edits", "edits", want_outs)
+
     def _launch_score_haplotypes(self, hw, want_outs=False):
-        """Eval-mode logits of the rows of a HaplotypeWindows (explainn_score_haplotypes): (rows, T) --
-        (rows, G, T) on a bank -- fp32 on the device; with want_outs also the per-unit outputs
-        (rows, units), units = G*U on a bank, from the same pass: returns (logits, outs)."""
-        if self.training:
-            raise RuntimeError("scoring haplotypes is an eval-mode path; call model.eval()")
-        dev = self._device()
-        hw.check(dev)
-        logits = self._logits_empty(hw.n_rows, dev)
-        outs = torch.empty(hw.n_rows, self._units(), device=dev, dtype=torch.float32) if want_outs else None
-        if hw.n_rows > 0:
-            with torch.cuda.device(dev):
-                ctx, ps, _, stream, xp, read = self._front(hw, dev)
-                hp = hw.struct()
-                _lib.check(ctx.lib.explainn_score_haplotypes(
-                    ctx.handle, xp, hw.codes.numel(), C.byref(hp), hw.n_rows, int(hw.reverse_complement),
-                    C.byref(ps), logits.data_ptr(), outs.data_ptr() if want_outs else None, stream))
-                self._settle(read)
-        return (logits, outs) if want_outs else logits
+        """_launch_score_rows of a HaplotypeWindows (explainn_score_haplotypes)."""
+        return self._launch_score_rows(hw, "explainn_score_haplotypes", "haplotypes", want_outs)
 
     def _codes_front(self, codes, path, verb, start=0, reverse_complement=False):
         """Front half of the launches that read a device-resident sequence of base codes with the
@@ -806,11 +783,7 @@ class ExplaiNN(_Model):
         if self.training:
             raise NotImplementedError("%s an eval-mode export path; call model.eval()" % path)
         dev = self._device()
-        if not torch.is_tensor(codes) or codes.dtype != torch.uint8 or codes.dim() != 1 or \
-                not codes.is_contiguous():
-            raise RuntimeError("%s on a contiguous 1-D uint8 tensor of base codes" % verb)
-        if codes.device != dev:
-            raise RuntimeError("input is on %s but the model is on %s" % (codes.device, dev))
+        _check_codes(codes, dev, verb + " on")
         with torch.cuda.device(dev):
             ctx, ps, _, stream, xp, _ = self._front(SequenceWindows(codes, start, 1, 1, reverse_complement, 1), dev)
         return ctx, ps, stream, xp, dev

@@ -418,22 +418,28 @@ extern "C" int explainn_unit_activations(explainn_ctx* c, const float* x, int B,
     return EXPLAINN_OK;
 }
 
+namespace {
+// What every explainn_stage_* entry point does once its own arguments have passed: the packed codes of
+// a pending backward are overwritten, and the staged batch is of this strand (returned as 0 / 1).
+int stage_begin(explainn_ctx* c, int reverse_complement) {
+    drop_pending(c);
+    c->staged_rc = reverse_complement ? 1 : 0;
+    return c->staged_rc;
+}
+}  // namespace
+
 extern "C" int explainn_stage_codes(explainn_ctx* c, const uint8_t* codes, int B,
                                     int reverse_complement, void* stream) {
     TRY(check_batch(c, B));
     if (!codes) { explainn_set_error("codes is null"); return EXPLAINN_E_ARG; }
-    drop_pending(c);                   // the packed codes of a pending backward are overwritten
-    c->staged_rc = reverse_complement ? 1 : 0;
-    return launch_pack_codes(c, codes, B, c->staged_rc, static_cast<hipStream_t>(stream));
+    return launch_pack_codes(c, codes, B, stage_begin(c, reverse_complement), static_cast<hipStream_t>(stream));
 }
 
 extern "C" int explainn_stage_windows(explainn_ctx* c, const uint8_t* seq, int64_t seq_len, int64_t start0,
                                       int64_t step, int B, int reverse_complement, void* stream) {
     TRY(check_batch(c, B));
     if (!seq || seq_len < 0) { explainn_set_error("seq is null or seq_len negative"); return EXPLAINN_E_ARG; }
-    drop_pending(c);                   // the packed codes of a pending backward are overwritten
-    c->staged_rc = reverse_complement ? 1 : 0;
-    return launch_stage_windows(c, seq, seq_len, start0, step, B, reverse_complement ? 1 : 0,
+    return launch_stage_windows(c, seq, seq_len, start0, step, B, stage_begin(c, reverse_complement),
                                 static_cast<hipStream_t>(stream));
 }
 
@@ -479,6 +485,23 @@ int64_t scan_shared_bytes(const explainn_ctx* c, int64_t n_windows, int64_t stri
     const int64_t J = scan_tiles(c, n_windows, (int)(stride / POOLW));
     return (J + c->maxB - 1) / c->maxB * scan_track_block_elems(c) * (int64_t)sizeof(float);
 }
+
+// Rows the context stages itself, max_batch at a time: stage(i0, Bw) stages rows [i0, i0 + Bw), and
+// their logits (n_rows, [G,] T) and unit outputs (n_rows, units), either may be null, land behind
+// those of the rows before.  Nothing stays staged.
+template <class Stage>
+int score_rows(explainn_ctx* c, int64_t n_rows, const explainn_params* p, float* logits, float* outs,
+               hipStream_t s, Stage stage) {
+    const int64_t row = (int64_t)c->Gm * c->T;
+    for (int64_t i0 = 0; i0 < n_rows; i0 += c->maxB) {
+        const int Bw = (int)(n_rows - i0 < c->maxB ? n_rows - i0 : c->maxB);
+        TRY(stage(i0, Bw));
+        TRY(eval_forward(c, nullptr, Bw, p, false, logits ? logits + i0 * row : nullptr,
+                         outs ? outs + i0 * c->U : nullptr, s));
+    }
+    c->staged_B = 0;
+    return EXPLAINN_OK;
+}
 }  // namespace
 
 extern "C" int64_t explainn_scan_workspace_bytes(const explainn_ctx* c, int64_t n_windows, int64_t stride,
@@ -503,15 +526,10 @@ extern "C" int explainn_scan(explainn_ctx* c, const uint8_t* seq, int64_t seq_le
     const int rc = reverse_complement ? 1 : 0;
     const int64_t row = (int64_t)c->Gm * c->T;       // logits are (n_windows, [G,] T)
     drop_pending(c);
-    if (md == EXPLAINN_SCAN_WINDOWS) {
-        for (int64_t i0 = 0; i0 < n_windows; i0 += c->maxB) {
-            const int Bw = (int)(n_windows - i0 < c->maxB ? n_windows - i0 : c->maxB);
-            TRY(launch_stage_windows(c, seq, seq_len, start + i0 * stride, stride, Bw, rc, s));
-            TRY(eval_forward(c, nullptr, Bw, p, false, logits + i0 * row, nullptr, s));
-        }
-        c->staged_B = 0;
-        return EXPLAINN_OK;
-    }
+    if (md == EXPLAINN_SCAN_WINDOWS)
+        return score_rows(c, n_windows, p, logits, nullptr, s, [&](int64_t i0, int Bw) {
+            return launch_stage_windows(c, seq, seq_len, start + i0 * stride, stride, Bw, rc, s);
+        });
     const int64_t need = scan_shared_bytes(c, n_windows, stride);
     if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 255) != 0) {
         explainn_set_error("scan workspace of %lld bytes (256-byte aligned), %lld needed", (long long)workspace_bytes,
@@ -549,7 +567,19 @@ extern "C" int explainn_scan(explainn_ctx* c, const uint8_t* seq, int64_t seq_le
 }
 
 namespace {
-// what can be checked of an edit table without reading it (its arrays live on the device)
+// What can be checked of these tables without reading them (their arrays live on the device).  The
+// edit-table half, which explainn_edits and explainn_haplotypes share field by field, once the counts
+// have passed:
+template <class Tables>
+int check_edit_table(const Tables* t) {
+    if (t->n_edits > 0 && (!t->pos || !t->ref_len || !t->alt_len || !t->alt_off)) {
+        explainn_set_error("an edit table of %lld edits needs pos, ref_len, alt_len and alt_off", (long long)t->n_edits);
+        return EXPLAINN_E_ARG;
+    }
+    if (t->alt_bytes > 0 && !t->alt) { explainn_set_error("alt is null but alt_bytes is %lld", (long long)t->alt_bytes); return EXPLAINN_E_ARG; }
+    return EXPLAINN_OK;
+}
+
 int check_edits(const uint8_t* seq, int64_t seq_len, const explainn_edits* ed, int64_t row0) {
     if (!seq || seq_len < 0) { explainn_set_error("seq is null or seq_len negative"); return EXPLAINN_E_ARG; }
     if (!ed || !ed->row_start || !ed->row_edit || row0 < 0) {
@@ -561,50 +591,9 @@ int check_edits(const uint8_t* seq, int64_t seq_len, const explainn_edits* ed, i
                            (long long)ed->n_edits, (long long)ed->alt_bytes);
         return EXPLAINN_E_ARG;
     }
-    if (ed->n_edits > 0 && (!ed->pos || !ed->ref_len || !ed->alt_len || !ed->alt_off)) {
-        explainn_set_error("an edit table of %lld edits needs pos, ref_len, alt_len and alt_off", (long long)ed->n_edits);
-        return EXPLAINN_E_ARG;
-    }
-    if (ed->alt_bytes > 0 && !ed->alt) { explainn_set_error("alt is null but alt_bytes is %lld", (long long)ed->alt_bytes); return EXPLAINN_E_ARG; }
-    return EXPLAINN_OK;
-}
-}  // namespace
-
-extern "C" int explainn_stage_edited_windows(explainn_ctx* c, const uint8_t* seq, int64_t seq_len,
-                                             const explainn_edits* edits, int64_t row0, int B,
-                                             int reverse_complement, void* stream) {
-    TRY(check_batch(c, B));
-    TRY(check_edits(seq, seq_len, edits, row0));
-    drop_pending(c);                   // the packed codes of a pending backward are overwritten
-    c->staged_rc = reverse_complement ? 1 : 0;
-    return launch_stage_edits(c, seq, seq_len, edits, row0, B, reverse_complement ? 1 : 0,
-                              static_cast<hipStream_t>(stream));
+    return check_edit_table(ed);
 }
 
-extern "C" int explainn_score_edits(explainn_ctx* c, const uint8_t* seq, int64_t seq_len,
-                                    const explainn_edits* edits, int64_t n_rows, int reverse_complement,
-                                    const explainn_params* p, float* logits, float* outs, void* stream) {
-    if (!c) { explainn_set_error("null context"); return EXPLAINN_E_ARG; }
-    if (n_rows < 1 || !p) { explainn_set_error("score_edits needs n_rows >= 1 and params"); return EXPLAINN_E_ARG; }
-    if (!logits && !outs) { explainn_set_error("score_edits needs logits or outs (both are null)"); return EXPLAINN_E_ARG; }
-    TRY(check_edits(seq, seq_len, edits, 0));
-    if (c->dense) { explainn_set_error("edits are scored on base codes: not in dense input mode"); return EXPLAINN_E_UNSUPPORTED; }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int rc = reverse_complement ? 1 : 0;
-    const int64_t row = (int64_t)c->Gm * c->T;       // logits are (n_rows, [G,] T), outs (n_rows, units)
-    drop_pending(c);
-    for (int64_t i0 = 0; i0 < n_rows; i0 += c->maxB) {
-        const int Bw = (int)(n_rows - i0 < c->maxB ? n_rows - i0 : c->maxB);
-        TRY(launch_stage_edits(c, seq, seq_len, edits, i0, Bw, rc, s));
-        TRY(eval_forward(c, nullptr, Bw, p, false, logits ? logits + i0 * row : nullptr,
-                         outs ? outs + i0 * c->U : nullptr, s));
-    }
-    c->staged_B = 0;
-    return EXPLAINN_OK;
-}
-
-namespace {
-// what can be checked of haplotype tables without reading them (their arrays live on the device)
 int check_haplotypes(const uint8_t* seq, int64_t seq_len, const explainn_haplotypes* hp, int64_t row0) {
     if (!seq || seq_len < 0) { explainn_set_error("seq is null or seq_len negative"); return EXPLAINN_E_ARG; }
     if (!hp || !hp->row_start || !hp->row_first || !hp->row_count || row0 < 0) {
@@ -620,46 +609,62 @@ int check_haplotypes(const uint8_t* seq, int64_t seq_len, const explainn_haploty
         explainn_set_error("edit_index is null but n_index is %lld", (long long)hp->n_index);
         return EXPLAINN_E_ARG;
     }
-    if (hp->n_edits > 0 && (!hp->pos || !hp->ref_len || !hp->alt_len || !hp->alt_off)) {
-        explainn_set_error("an edit table of %lld edits needs pos, ref_len, alt_len and alt_off", (long long)hp->n_edits);
-        return EXPLAINN_E_ARG;
-    }
-    if (hp->alt_bytes > 0 && !hp->alt) { explainn_set_error("alt is null but alt_bytes is %lld", (long long)hp->alt_bytes); return EXPLAINN_E_ARG; }
+    return check_edit_table(hp);
+}
+
+// The front of explainn_score_edits / explainn_score_haplotypes (`name`), whose rows are `scored`
+// on base codes; check() is check_edits / check_haplotypes of the call's tables.
+template <class Check>
+int score_rows_begin(explainn_ctx* c, const char* name, const char* scored, int64_t n_rows,
+                     const explainn_params* p, const float* logits, const float* outs, Check check) {
+    if (!c) { explainn_set_error("null context"); return EXPLAINN_E_ARG; }
+    if (n_rows < 1 || !p) { explainn_set_error("%s needs n_rows >= 1 and params", name); return EXPLAINN_E_ARG; }
+    if (!logits && !outs) { explainn_set_error("%s needs logits or outs (both are null)", name); return EXPLAINN_E_ARG; }
+    TRY(check());
+    if (c->dense) { explainn_set_error("%s are scored on base codes: not in dense input mode", scored); return EXPLAINN_E_UNSUPPORTED; }
+    drop_pending(c);
     return EXPLAINN_OK;
 }
 }  // namespace
+
+extern "C" int explainn_stage_edited_windows(explainn_ctx* c, const uint8_t* seq, int64_t seq_len,
+                                             const explainn_edits* edits, int64_t row0, int B,
+                                             int reverse_complement, void* stream) {
+    TRY(check_batch(c, B));
+    TRY(check_edits(seq, seq_len, edits, row0));
+    return launch_stage_edits(c, seq, seq_len, edits, row0, B, stage_begin(c, reverse_complement),
+                              static_cast<hipStream_t>(stream));
+}
+
+extern "C" int explainn_score_edits(explainn_ctx* c, const uint8_t* seq, int64_t seq_len,
+                                    const explainn_edits* edits, int64_t n_rows, int reverse_complement,
+                                    const explainn_params* p, float* logits, float* outs, void* stream) {
+    TRY(score_rows_begin(c, "score_edits", "edits", n_rows, p, logits, outs,
+                         [&] { return check_edits(seq, seq_len, edits, 0); }));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return score_rows(c, n_rows, p, logits, outs, s, [&](int64_t i0, int Bw) {
+        return launch_stage_edits(c, seq, seq_len, edits, i0, Bw, reverse_complement ? 1 : 0, s);
+    });
+}
 
 extern "C" int explainn_stage_haplotype_windows(explainn_ctx* c, const uint8_t* seq, int64_t seq_len,
                                                 const explainn_haplotypes* haps, int64_t row0, int B,
                                                 int reverse_complement, void* stream) {
     TRY(check_batch(c, B));
     TRY(check_haplotypes(seq, seq_len, haps, row0));
-    drop_pending(c);                   // the packed codes of a pending backward are overwritten
-    c->staged_rc = reverse_complement ? 1 : 0;
-    return launch_stage_haplotypes(c, seq, seq_len, haps, row0, B, reverse_complement ? 1 : 0,
+    return launch_stage_haplotypes(c, seq, seq_len, haps, row0, B, stage_begin(c, reverse_complement),
                                    static_cast<hipStream_t>(stream));
 }
 
 extern "C" int explainn_score_haplotypes(explainn_ctx* c, const uint8_t* seq, int64_t seq_len,
                                          const explainn_haplotypes* haps, int64_t n_rows, int reverse_complement,
                                          const explainn_params* p, float* logits, float* outs, void* stream) {
-    if (!c) { explainn_set_error("null context"); return EXPLAINN_E_ARG; }
-    if (n_rows < 1 || !p) { explainn_set_error("score_haplotypes needs n_rows >= 1 and params"); return EXPLAINN_E_ARG; }
-    if (!logits && !outs) { explainn_set_error("score_haplotypes needs logits or outs (both are null)"); return EXPLAINN_E_ARG; }
-    TRY(check_haplotypes(seq, seq_len, haps, 0));
-    if (c->dense) { explainn_set_error("haplotypes are scored on base codes: not in dense input mode"); return EXPLAINN_E_UNSUPPORTED; }
+    TRY(score_rows_begin(c, "score_haplotypes", "haplotypes", n_rows, p, logits, outs,
+                         [&] { return check_haplotypes(seq, seq_len, haps, 0); }));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int rc = reverse_complement ? 1 : 0;
-    const int64_t row = (int64_t)c->Gm * c->T;       // logits are (n_rows, [G,] T), outs (n_rows, units)
-    drop_pending(c);
-    for (int64_t i0 = 0; i0 < n_rows; i0 += c->maxB) {
-        const int Bw = (int)(n_rows - i0 < c->maxB ? n_rows - i0 : c->maxB);
-        TRY(launch_stage_haplotypes(c, seq, seq_len, haps, i0, Bw, rc, s));
-        TRY(eval_forward(c, nullptr, Bw, p, false, logits ? logits + i0 * row : nullptr,
-                         outs ? outs + i0 * c->U : nullptr, s));
-    }
-    c->staged_B = 0;
-    return EXPLAINN_OK;
+    return score_rows(c, n_rows, p, logits, outs, s, [&](int64_t i0, int Bw) {
+        return launch_stage_haplotypes(c, seq, seq_len, haps, i0, Bw, reverse_complement ? 1 : 0, s);
+    });
 }
 
 extern "C" int64_t explainn_call_sites_workspace_bytes(const explainn_ctx* c, int64_t n_positions) {

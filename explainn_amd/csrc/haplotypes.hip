@@ -14,7 +14,7 @@
 //     seq[g]                           g < hstart_0
 //     alt[alt_off_i + g - hstart_i]    hstart_i <= g < hstart_i + alt_len_i
 //     seq[g - after_i]                 otherwise, i the last edit with hstart_i <= g
-// which for a run of one edit is stage_edits_kernel's expression (variants.hip), term for term.
+// which is edit_source (stage_tile.h); stage_edits_kernel (variants.hip) calls it with its one edit.
 #include "common.h"
 #include "stage_tile.h"
 
@@ -27,12 +27,6 @@ __device__ __forceinline__ void wave_lds_order() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-__device__ __forceinline__ long long wadd(long long a, long long b) {      // wrapping, never undefined
-    return (long long)((unsigned long long)a + (unsigned long long)b);
-}
-__device__ __forceinline__ long long wsub(long long a, long long b) {
-    return (long long)((unsigned long long)a - (unsigned long long)b);
-}
 __device__ __forceinline__ long long lane_i64(long long v, int l) {         // lane l's value, wave-uniform
     const unsigned lo = __builtin_amdgcn_readlane((int)(unsigned)((unsigned long long)v & 0xffffffffu), l);
     const unsigned hi = __builtin_amdgcn_readlane((int)(unsigned)((unsigned long long)v >> 32), l);
@@ -53,19 +47,14 @@ __global__ __launch_bounds__(64 * SW_WAVES) void stage_haplotypes_kernel(
     const uint8_t* __restrict__ seq, long long seq_len, explainn_haplotypes hp, long long row0, int rc,
     uint8_t* __restrict__ codesT, uint32_t* __restrict__ pk2, uint32_t* __restrict__ nmask, int B, int L,
     int Bs, int PW, int NW, int* __restrict__ flags, unsigned long long* __restrict__ bm, int Lp) {
-    constexpr int ROWS = 64 / SW_WAVES;
+    constexpr int ROWS = SW_ROWS;
     __shared__ uint8_t tile[64][68];
     __shared__ long long run_h[SW_WAVES][64];        // hstart of the chunk's edits
     __shared__ long long run_s[SW_WAVES][64];        // the shift behind each of them
     __shared__ int run_al[SW_WAVES][64];
     __shared__ int run_ao[SW_WAVES][64];
-    const int bx = blockIdx.x, by = blockIdx.y;
-    const int b0 = bx * 64, p0 = by * 64;
-    const int lane = threadIdx.x & 63;
-    const int q = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // the row tables are read once per wave
-    const int p = p0 + lane;
-    // haplotype offset of output position p inside its row: the reverse complement reads the row backwards
-    const long long hq = rc ? (long long)L - 1 - p : (long long)p;
+    const stage_front f = stage_front_of(rc, L);
+    const int b0 = f.b0, lane = f.lane, q = f.q;
     int bad = 0;
     // the tables of the wave's 8 rows in one load: lane r holds row r's, read back lane by lane below
     long long start_v = 0, first_v = 0;
@@ -85,7 +74,7 @@ __global__ __launch_bounds__(64 * SW_WAVES) void stage_haplotypes_kernel(
         // a table the host never saw: nothing of it becomes an address before it is range-checked, and
         // whatever fails makes the whole row N and raises the flag.  The run must lie inside edit_index
         bool ok = cnt >= 0 && fst >= 0 && cnt <= hp.n_index && fst <= hp.n_index - cnt;
-        const long long g = wadd(lane_i64(start_v, r), hq);
+        const long long g = wadd(lane_i64(start_v, r), f.hq);
         bool have = false;                           // an edit with hstart <= g exists: the last such is
         long long sel_h = 0, sel_s = 0;              // ... at sel_h, with shift sel_s behind it,
         int sel_al = 0, sel_ao = 0;                  // ... and these alt bases
@@ -96,15 +85,7 @@ __global__ __launch_bounds__(64 * SW_WAVES) void stage_haplotypes_kernel(
                 const int n = cnt - c0 < 64 ? (int)(cnt - c0) : 64;
                 long long pos = 0;
                 int rl = 0, al = 0, ao = 0;
-                if (lane < n) {
-                    const int e = hp.edit_index[fst + c0 + lane];
-                    bool eok = e >= 0 && e < hp.n_edits;
-                    if (eok) {
-                        pos = hp.pos[e]; rl = hp.ref_len[e]; al = hp.alt_len[e]; ao = hp.alt_off[e];
-                        eok = rl >= 0 && al >= 0 && ao >= 0 && (long long)ao + al <= hp.alt_bytes;
-                    }
-                    if (!eok) { ok = false; pos = 0; rl = 0; al = 0; ao = 0; }
-                }
+                if (lane < n && !load_edit(hp, hp.edit_index[fst + c0 + lane], pos, rl, al, ao)) ok = false;
                 // ordered and non-overlapping: the edit before (the neighbouring lane's, or the last of
                 // the chunk before) ends at or before this one's pos.  prev <= pos makes the difference
                 // exact as an unsigned number, whatever the positions are
@@ -138,45 +119,19 @@ __global__ __launch_bounds__(64 * SW_WAVES) void stage_haplotypes_kernel(
             }
         }
         const bool row_ok = !__any(!ok);            // (voted by the whole wave, outside the p < L branch)
-        if (p < L) {
-            if (!row_ok) {
-                bad = 1;
-            } else {
-                // every index is range-checked before it is used
-                const long long d = wsub(g, sel_h);
-                if (have && d >= 0 && d < sel_al) {
-                    src[r] = hp.alt + sel_ao + d;
-                } else {
-                    const long long t = have ? wsub(g, sel_s) : g;
-                    if (t >= 0 && t < seq_len) src[r] = seq + t;    // outside the sequence: N, not flagged
-                }
-            }
+        if (f.p < L) {
+            if (!row_ok) bad = 1;
+            else src[r] = edit_source(seq, seq_len, hp.alt, g, have, sel_h, sel_s, sel_al, sel_ao);
         }
     }
     int v[ROWS];
 #pragma unroll
     for (int r = 0; r < ROWS; ++r) v[r] = src[r] ? *src[r] : 4;
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-        const int i = q + SW_WAVES * r, b = b0 + i;
-        uint8_t code = 0;                            // padding lanes / past the end: 'A', as pack_tile
-        if (b < B && p < L) {
-            if (v[r] < 4) code = rc ? 3 - v[r] : v[r];
-            else { code = 4; if (v[r] != 4) bad = 1; }
-        }
-        tile[i][lane] = code;
-    }
-    __syncthreads();
-    stage_tile_store(tile, lane, q, bx, b0, p0, codesT, pk2, nmask, B, L, Bs, PW, NW, bm, Lp);
-    if (bad) atomicOr(flags, 1);
+    stage_rows_codes(tile, f, v, rc, B, L, bad);
+    stage_tile_finish(tile, f, bad, codesT, pk2, nmask, B, L, Bs, PW, NW, flags, bm, Lp);
 }
 
 int launch_stage_haplotypes(explainn_ctx* c, const uint8_t* seq, int64_t seq_len, const explainn_haplotypes* hp,
                             int64_t row0, int B, int rc, hipStream_t s) {
-    hipLaunchKernelGGL(stage_haplotypes_kernel, dim3((B + 63) / 64, (c->NW * 32 + 63) / 64),
-                       dim3(64 * SW_WAVES), 0, s, seq, (long long)seq_len, *hp, (long long)row0, rc, c->codesT,
-                       c->pk2, c->nmask, B, c->L, c->Bs, c->PW, c->NW, c->flags, c->bm, c->Lp);
-    LAUNCH_CHECK();
-    c->staged_B = B;
-    return EXPLAINN_OK;
+    return launch_stage_rows(c, stage_haplotypes_kernel, B, s, seq, (long long)seq_len, *hp, (long long)row0, rc);
 }

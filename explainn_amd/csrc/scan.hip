@@ -20,27 +20,23 @@
 // 64-byte runs are disjoint: each wave reads its rows' runs directly (64 contiguous bytes per load).
 #define SW_SEG 4096
 
-// Must write exactly what pack_tile<true> (pack.hip) writes for the materialised matrix: codesT, pk2,
-// nmask, bm and the flag; the second half (stage_tile.h) is that function's, on the same 64 x 64 tile.
+// The middle is arithmetic: byte hq of row b is seq[start0 + b*step + hq] (stage_tile.h has both ends).
 __global__ __launch_bounds__(64 * SW_WAVES) void stage_windows_kernel(
     const uint8_t* __restrict__ seq, long long seq_len, long long start0, long long step, int rc,
     uint8_t* __restrict__ codesT, uint32_t* __restrict__ pk2, uint32_t* __restrict__ nmask, int B, int L,
     int Bs, int PW, int NW, int* __restrict__ flags, unsigned long long* __restrict__ bm, int Lp) {
     __shared__ uint8_t tile[64][68];
     __shared__ uint8_t seg[SW_SEG];
-    const int bx = blockIdx.x, by = blockIdx.y;
-    const int b0 = bx * 64, p0 = by * 64;
-    const int lane = threadIdx.x & 63, q = threadIdx.x >> 6;
+    const stage_front f = stage_front_of(rc, L);
     int bad = 0;
-    const int p = p0 + lane;
-    // source offset of output position p inside its row's window; the block's 64 positions are the
-    // run [off0, off0 + 64) of every row, ascending (rc = 0) or descending (rc = 1) in the lane
-    const long long off0 = rc ? (long long)L - 64 - p0 : (long long)p0;
-    const int lo_lane = rc ? 63 - lane : lane;
     const long long astep = step < 0 ? -step : step;
     if (astep < 64) {
-        const int rows = min(64, B - b0);
-        const long long first = start0 + (long long)b0 * step, last = first + (long long)(rows - 1) * step;
+        // the block's 64 positions are the run [off0, off0 + 64) of every row's window, ascending
+        // (rc = 0) or descending (rc = 1) in the lane: f.hq = off0 + lo_lane
+        const long long off0 = rc ? (long long)L - 64 - f.p0 : (long long)f.p0;
+        const int lo_lane = rc ? 63 - f.lane : f.lane;
+        const int rows = min(64, B - f.b0);
+        const long long first = start0 + (long long)f.b0 * step, last = first + (long long)(rows - 1) * step;
         const long long lo = (first < last ? first : last) + off0;
         const int span = (int)((rows - 1) * astep) + 64;
         for (int t = threadIdx.x; t < span; t += 64 * SW_WAVES) {
@@ -48,48 +44,29 @@ __global__ __launch_bounds__(64 * SW_WAVES) void stage_windows_kernel(
             seg[t] = (g >= 0 && g < seq_len) ? seq[g] : (uint8_t)4;     // outside the sequence: N, not flagged
         }
         __syncthreads();
-        for (int i = q; i < 64; i += SW_WAVES) {
-            const int b = b0 + i;
+        for (int i = f.q; i < 64; i += SW_WAVES) {
             uint8_t code = 0;                           // padding lanes / past the end: 'A', as pack_tile
-            if (b < B && p < L) {
-                const int v = seg[(int)(first + (long long)i * step + off0 - lo) + lo_lane];
-                if (v < 4) code = rc ? 3 - v : v;
-                else { code = 4; if (v != 4) bad = 1; }
-            }
-            tile[i][lane] = code;
+            if (f.b0 + i < B && f.p < L)
+                code = stage_code(seg[(int)(first + (long long)i * step + off0 - lo) + lo_lane], rc, bad);
+            tile[i][f.lane] = code;
         }
     } else {
-        int v[64 / SW_WAVES];
+        int v[SW_ROWS];
 #pragma unroll
-        for (int r = 0; r < 64 / SW_WAVES; ++r) {
-            const int b = b0 + q + SW_WAVES * r;
-            const long long g = start0 + (long long)b * step + off0 + lo_lane;
-            v[r] = (b < B && p < L && g >= 0 && g < seq_len) ? seq[g] : 4;
+        for (int r = 0; r < SW_ROWS; ++r) {
+            const int b = f.b0 + f.q + SW_WAVES * r;
+            const long long g = start0 + (long long)b * step + f.hq;
+            v[r] = (b < B && f.p < L && g >= 0 && g < seq_len) ? seq[g] : 4;
         }
-#pragma unroll
-        for (int r = 0; r < 64 / SW_WAVES; ++r) {
-            const int i = q + SW_WAVES * r, b = b0 + i;
-            uint8_t code = 0;
-            if (b < B && p < L) {
-                if (v[r] < 4) code = rc ? 3 - v[r] : v[r];
-                else { code = 4; if (v[r] != 4) bad = 1; }
-            }
-            tile[i][lane] = code;
-        }
+        stage_rows_codes(tile, f, v, rc, B, L, bad);
     }
-    __syncthreads();
-    stage_tile_store(tile, lane, q, bx, b0, p0, codesT, pk2, nmask, B, L, Bs, PW, NW, bm, Lp);
-    if (bad) atomicOr(flags, 1);
+    stage_tile_finish(tile, f, bad, codesT, pk2, nmask, B, L, Bs, PW, NW, flags, bm, Lp);
 }
 
 int launch_stage_windows(explainn_ctx* c, const uint8_t* seq, int64_t seq_len, int64_t start0, int64_t step,
                          int B, int rc, hipStream_t s) {
-    hipLaunchKernelGGL(stage_windows_kernel, dim3((B + 63) / 64, (c->NW * 32 + 63) / 64), dim3(64 * SW_WAVES),
-                       0, s, seq, (long long)seq_len, (long long)start0, (long long)step, rc, c->codesT, c->pk2,
-                       c->nmask, B, c->L, c->Bs, c->PW, c->NW, c->flags, c->bm, c->Lp);
-    LAUNCH_CHECK();
-    c->staged_B = B;
-    return EXPLAINN_OK;
+    return launch_stage_rows(c, stage_windows_kernel, B, s, seq, (long long)seq_len, (long long)start0,
+                             (long long)step, rc);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -26,6 +26,8 @@ import argparse
 import numpy as np
 import torch
 
+from .strands import check_strands
+
 CHUNK_BASES = 1 << 26        # bases per device call of best_sites
 COLUMNS = ("Filter", "Threshold", "TP", "TPpct", "FP", "FPpct", "Enrichment", "LogPvalue", "LogPadj", "Evalue",
            "Qvalue", "AUROC")
@@ -34,8 +36,7 @@ _FIELDS = ("n_thresholds", "best_pattern", "tp", "fp", "log_pvalue", "log_padj",
 
 
 def _strands(strands):
-    if strands not in ("both", "fwd"):
-        raise ValueError("strands must be 'both' or 'fwd' (got %r)" % (strands,))
+    check_strands(strands)
     return 2 if strands == "both" else 1
 
 

@@ -248,12 +248,11 @@ def scan_motifs(motifs, codes, pvalue=1e-4, bg=None, pseudocount=0.1, bins=100, 
     import torch
 
     from . import _lib
+    from .strands import as_codes_1d
     _sites._check_args(strands, chunk_positions, max_sites, period)
     _check_pvalue(pvalue)
     names, mats = motif_list(motifs)
-    data = codes if torch.is_tensor(codes) else torch.as_tensor(np.ascontiguousarray(codes))
-    if data.dtype != torch.uint8 or data.dim() != 1:
-        raise ValueError("codes must be a 1-D uint8 array of base codes")
+    data = as_codes_1d(codes)
     b = sequence_background(data, strands) if isinstance(bg, str) and bg == "sequence" else _background(bg)
     S, widths, scale, lo = quantise(mats, b, pseudocount, bins)
     device = _device_for(device, data, "scan_motifs")

@@ -12,7 +12,6 @@ run once over the sequence instead of once per window (mode "shared", DESIGN.md 
 `python -m explainn_amd.scan MODEL FASTA` writes the windows of every FASTA record as TSV.
 """
 import argparse
-import contextlib
 import sys
 
 import numpy as np
@@ -20,6 +19,7 @@ import torch
 
 from . import _lib
 from .architectures import SequenceWindows
+from .strands import TwoStrands, as_codes_1d, check_strands, stack_strands
 
 MODES = {"auto": _lib.SCAN_AUTO, "windows": _lib.SCAN_WINDOWS, "shared": _lib.SCAN_SHARED}
 _POOL = 7                    # MaxPool1d(7,7): the strides whose windows share one pooling grid
@@ -64,8 +64,7 @@ def chunks(n_windows, limit):
 def _check_args(stride, strands, mode):
     if stride < 1:
         raise ValueError("stride must be at least 1 (got %d)" % stride)
-    if strands not in ("both", "fwd"):
-        raise ValueError("strands must be 'both' or 'fwd' (got %r)" % (strands,))
+    check_strands(strands)
     if mode not in MODES:
         raise ValueError("mode must be one of %s (got %r)" % (", ".join(MODES), mode))
     if mode == "shared" and stride % _POOL:
@@ -92,9 +91,7 @@ def scan(model, codes, stride=7, strands="both", mode="auto", batch_size=4096, a
     L, k = o["sequence_length"], o["kernel_size"]
     batch_size = max(1, int(batch_size))
     device = model.final.weight.device
-    data = codes if torch.is_tensor(codes) else torch.as_tensor(np.ascontiguousarray(codes))
-    if data.dtype != torch.uint8 or data.dim() != 1:
-        raise ValueError("codes must be a 1-D uint8 array of base codes")
+    data = as_codes_1d(codes)
     starts = window_starts(data.shape[0], L, stride)
     W = len(starts)
     shape = tuple(model._logits_empty(0, torch.device("cpu")).shape[1:])
@@ -102,34 +99,15 @@ def scan(model, codes, stride=7, strands="both", mode="auto", batch_size=4096, a
     if W == 0:
         return starts, out
     limit = int(chunk_windows) if chunk_windows is not None else chunk_limit(L, k, stride, batch_size)
-    both = strands == "both"
-    cur = torch.cuda.current_stream(device)
-    rep = side = None
-    if both:
-        rep = model.eval_replica()
-        if model._rt.side_stream is None:
-            model._rt.side_stream = torch.cuda.Stream(device)
-        side = model._rt.side_stream
-    with torch.no_grad(), model.eval_cache(), (rep.eval_cache() if both else contextlib.nullcontext()):
+    with TwoStrands(model, strands == "both") as ts:
         for w0, cnt in chunks(W, limit):
             piece = data[w0 * stride:(w0 + cnt - 1) * stride + L].to(device).contiguous()
-            if both:
-                side.wait_stream(cur)                           # the chunk is on the device
-                with torch.cuda.stream(side):
-                    rev = rep._launch_scan(SequenceWindows(piece, 0, cnt, stride, True, batch_size), MODES[mode])
-                    piece.record_stream(side)
-            fwd = model._launch_scan(SequenceWindows(piece, 0, cnt, stride, False, batch_size), MODES[mode])
-            if both:
-                cur.wait_stream(side)
-                rev.record_stream(cur)
-                res = torch.stack((fwd, rev, (fwd + rev) / 2, torch.maximum(fwd, rev)), dim=-1)
-                out[w0:w0 + cnt] = res.cpu().numpy()
+            fwd, rev = ts.run(lambda m, rc: m._launch_scan(
+                SequenceWindows(piece, 0, cnt, stride, rc, batch_size), MODES[mode]), held=(piece,))
+            if rev is not None:
+                out[w0:w0 + cnt] = stack_strands(fwd, rev).cpu().numpy()
             else:
                 out[w0:w0 + cnt, ..., 0] = fwd.cpu().numpy()
-    if model.validate_input:
-        if both:
-            rep.check_input()
-        model.check_input()
     if apply_sigmoid:
         out = torch.sigmoid(torch.Tensor(out)).numpy()
     return starts, out

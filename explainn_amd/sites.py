@@ -23,11 +23,12 @@ The float16 activation is never negative, so its 32768 bit patterns sort like th
 thresholds and p-values are exact functions of integers.  `--null NULL.npz` adds the p-value column.
 """
 import argparse
-import contextlib
 import sys
 
 import numpy as np
 import torch
+
+from .strands import TwoStrands, as_codes_1d, check_strands
 
 CHUNK_POSITIONS = 1 << 24    # start positions per device call
 MAX_SITES = 50000000         # records a call_sites() result may hold (17 bytes each on the host)
@@ -86,8 +87,7 @@ def position_chunks(n_positions, chunk, period=0):
 
 
 def _check_args(strands, chunk_positions, max_sites, period):
-    if strands not in ("both", "fwd"):
-        raise ValueError("strands must be 'both' or 'fwd' (got %r)" % (strands,))
+    check_strands(strands)
     if chunk_positions is not None and int(chunk_positions) < 1:
         raise ValueError("chunk_positions must be at least 1 (got %r)" % (chunk_positions,))
     if int(max_sites) < 0:
@@ -149,9 +149,7 @@ def call_sites(model, codes, thresholds, strands="both", chunk_positions=None, m
     if null is not None and (null.units, null.kernel_size) != (units, k):
         raise ValueError("the null is of %d units of kernel size %d, the model of %d of %d" % (
             null.units, null.kernel_size, units, k))
-    data = codes if torch.is_tensor(codes) else torch.as_tensor(np.ascontiguousarray(codes))
-    if data.dtype != torch.uint8 or data.dim() != 1:
-        raise ValueError("codes must be a 1-D uint8 array of base codes")
+    data = as_codes_1d(codes)
     thr = torch.as_tensor(np.asarray(thresholds.detach().cpu() if torch.is_tensor(thresholds) else thresholds,
                                      dtype=np.float32))
     if tuple(thr.shape) != (units,):
@@ -165,16 +163,11 @@ def call_sites(model, codes, thresholds, strands="both", chunk_positions=None, m
     counts = np.zeros(units, dtype=np.int64)
     if n_positions > 0:
         thr = thr.to(device)
-        cur = torch.cuda.current_stream(device)
-        rep = side = None
-        if both:
-            rep = model.eval_replica()
-            if model._rt.side_stream is None:
-                model._rt.side_stream = torch.cuda.Stream(device)
-            side = model._rt.side_stream
         chunk = int(chunk_positions) if chunk_positions is not None else CHUNK_POSITIONS
-        legs = [(1, model, cur)] + ([(-1, rep, side)] if both else [])
-        with torch.no_grad(), model.eval_cache(), (rep.eval_cache() if both else contextlib.nullcontext()):
+        # count and emit of the two strands interleave, so the legs are driven here, not by ts.run
+        with TwoStrands(model, both) as ts:
+            cur, rep, side = ts.cur, ts.rep, ts.side
+            legs = [(1, model, cur)] + ([(-1, rep, side)] if both else [])
             for p0, cnt in position_chunks(n_positions, chunk, period):
                 piece = data[p0:p0 + cnt + k - 1].to(device).contiguous()
                 if both:
@@ -205,10 +198,6 @@ def call_sites(model, codes, thresholds, strands="both", chunk_positions=None, m
                         blocks[s].append((s, p0, offs[s].numpy(), out[s][0].numpy(), out[s][1].numpy()))
                 if both:
                     cur.wait_stream(side)
-        if model.validate_input:
-            if both:
-                rep.check_input()
-            model.check_input()
     calls = assemble(blocks[1] + blocks[-1], units, k)
     if null is not None:
         calls.pvalue = null.pvalue(calls.unit_ids(), calls.score)

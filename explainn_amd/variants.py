@@ -27,7 +27,6 @@ haplotype a list of the variants it carries (explainn_score_haplotypes).
 `--haplotypes --regions BED` one row per region, sample, haplotype and class from the VCF's genotypes.
 """
 import argparse
-import contextlib
 import sys
 from collections import namedtuple
 
@@ -35,6 +34,7 @@ import numpy as np
 import torch
 
 from .architectures import EditedWindows, HaplotypeWindows
+from .strands import TwoStrands, as_codes_1d, check_strands, stack_strands
 
 _CHUNK_PASSES = 32           # rows per device call, at most: this many sub-batches of `batch_size` rows
 _MAX_POOL = (1 << 31) - 1    # bytes the alt pool may hold (explainn_edits.alt_bytes < 2^31)
@@ -113,34 +113,70 @@ def _final_rows(model):
     return w if w.dim() == 2 else w.permute(1, 0, 2).reshape(w.shape[1], -1)
 
 
-def _strand_handles(model, both):
-    """(current stream, eval replica, side stream) of the two-stream strand handling; the last two None
-    for the forward strand alone."""
+def _begin(model, codes, strands, batch_size):
+    """What both scorers open with: (codes as a 1-D tensor, L, batch_size, the shape of a row of logits,
+    units)."""
+    check_strands(strands)
+    batch_size = max(1, int(batch_size))
+    data = as_codes_1d(codes)
+    shape = tuple(model._logits_empty(0, torch.device("cpu")).shape[1:])
+    return data, model._options["sequence_length"], batch_size, shape, model._units()
+
+
+def _check_inside(tab, length):
+    """Every variant of the edit table lies inside the sequence of `length` bases."""
+    if len(tab["pos"]) and (tab["pos"].min() < 0 or (tab["pos"] + tab["ref_len"]).max() > length):
+        bad = np.flatnonzero((tab["pos"] < 0) | (tab["pos"] + tab["ref_len"] > length))
+        raise ValueError("%d variant(s) outside the sequence of %d bases (0 <= pos, pos + ref_len <= length); "
+                         "the first: #%d at %d" % (bad.size, length, bad[0], tab["pos"][bad[0]]))
+
+
+def _score_spans(model, data, tab, names, spans, rows_of, launch, both, check_ref, unit_effects):
+    """The sequence and the tables `names` of tab go to the device once (check_ref is settled there); then
+    the rows [r0, r1) of every span are scored, on both strands at once (strands.TwoStrands):
+    rows_of(seq_d, tables, r0, r1, reverse_complement) makes the span's rows, the model's method `launch`
+    scores them.  Yields (r0, r1, fwd, rev, ofwd, orev) per span: logits and, with unit_effects, unit
+    outputs of the two strands, on the device; rev and the outputs are None where not asked for.  Input
+    validation is settled behind the last span."""
+    if not spans:
+        return
     device = model.final.weight.device
-    cur = torch.cuda.current_stream(device)
-    if not both:
-        return cur, None, None
-    rep = model.eval_replica()
-    if model._rt.side_stream is None:
-        model._rt.side_stream = torch.cuda.Stream(device)
-    return cur, rep, model._rt.side_stream
+    ts = TwoStrands(model, both)
+    seq_d = data.to(device).contiguous()
+    if check_ref is not None:
+        _check_ref_alleles(seq_d, tab["pos"], tab["ref_len"].astype(np.int64), check_ref)
+    dt = {k: torch.from_numpy(tab[k]).to(device) for k in names}
+    with ts:
+        for r0, r1 in spans:
+            fwd, rev = ts.run(lambda m, rc: getattr(m, launch)(rows_of(seq_d, dt, r0, r1, rc), unit_effects))
+            ofwd = orev = None
+            if unit_effects:
+                (fwd, ofwd), (rev, orev) = fwd, (rev if both else (None, None))
+            yield r0, r1, fwd, rev, ofwd, orev
 
 
-def _launch_strands(model, handles, launch, unit_effects):
-    """launch(m, reverse_complement) on the model and, when both strands are asked for, on its replica
-    on the side stream at the same time: (fwd, rev), rev None for the forward strand alone."""
-    cur, rep, side = handles
-    rev = None
-    if rep is not None:
-        side.wait_stream(cur)                           # the tables are on the device
-        with torch.cuda.stream(side):
-            rev = launch(rep, True)
-    fwd = launch(model, False)
-    if rep is not None:
-        cur.wait_stream(side)
-        for t in (rev if unit_effects else (rev,)):
-            t.record_stream(cur)
-    return fwd, rev
+def _strand_mean(fwd, rev):
+    return fwd if rev is None else (fwd + rev) / 2
+
+
+def _unit_effects(d, wrows):
+    """(rows, units) differences of unit outputs -> (rows, units, T) on the host: each times its unit's
+    final.weight row."""
+    return (d[:, :, None] * wrows.t()[None, :, :]).cpu().numpy()
+
+
+def _columns(fwd, rev):
+    """Logits of the two strands -> predict()'s columns (rows, ..., 4) on the host; NaN in columns 1..3
+    for the forward strand alone."""
+    if rev is not None:
+        return stack_strands(fwd, rev).cpu().numpy()
+    out = np.full(tuple(fwd.shape) + (4,), np.nan)
+    out[..., 0] = fwd.cpu().numpy()
+    return out
+
+
+def _sigmoid(scores):
+    return torch.sigmoid(torch.from_numpy(scores)).numpy()
 
 
 def score_variants(model, codes, pos, ref_len, alts, shifts=(0,), strands="both", batch_size=4096,
@@ -164,23 +200,11 @@ def score_variants(model, codes, pos, ref_len, alts, shifts=(0,), strands="both"
     check_ref: the VCF REF alleles as code arrays; a mismatch with the sequence raises ValueError.
     The two strands run on the model and its eval_replica() on two streams, as in scan(); the rows go
     to the device in chunks of at most 32 * batch_size rows (chunk_rows overrides it)."""
-    if strands not in ("both", "fwd"):
-        raise ValueError("strands must be 'both' or 'fwd' (got %r)" % (strands,))
-    L = model._options["sequence_length"]
-    batch_size = max(1, int(batch_size))
-    device = model.final.weight.device
-    data = codes if torch.is_tensor(codes) else torch.as_tensor(np.ascontiguousarray(codes))
-    if data.dtype != torch.uint8 or data.dim() != 1:
-        raise ValueError("codes must be a 1-D uint8 array of base codes")
+    data, L, batch_size, shape, units = _begin(model, codes, strands, batch_size)
     shifts = tuple(int(s) for s in shifts)
     tab = build_tables(pos, ref_len, alts, L, shifts)
     V, S = len(tab["pos"]), len(shifts)
-    if V and (tab["pos"].min() < 0 or (tab["pos"] + tab["ref_len"]).max() > data.shape[0]):
-        bad = np.flatnonzero((tab["pos"] < 0) | (tab["pos"] + tab["ref_len"] > data.shape[0]))
-        raise ValueError("%d variant(s) outside the sequence of %d bases (0 <= pos, pos + ref_len <= length); "
-                         "the first: #%d at %d" % (bad.size, data.shape[0], bad[0], tab["pos"][bad[0]]))
-    shape = tuple(model._logits_empty(0, torch.device("cpu")).shape[1:])
-    units = model._units()
+    _check_inside(tab, data.shape[0])
     res = {"ref": np.full((V, S) + shape + (4,), np.nan), "alt": np.full((V, S) + shape + (4,), np.nan),
            "delta": np.zeros((V,) + shape)}
     if unit_effects:
@@ -188,47 +212,25 @@ def score_variants(model, codes, pos, ref_len, alts, shifts=(0,), strands="both"
     if V == 0:
         return res
     both = strands == "both"
-    handles = _strand_handles(model, both)
-    rep = handles[1]
-    seq_d = data.to(device).contiguous()
-    if check_ref is not None:
-        _check_ref_alleles(seq_d, tab["pos"], tab["ref_len"].astype(np.int64), check_ref)
-    dt = {k: torch.from_numpy(v).to(device) for k, v in tab.items()}
     wrows = _final_rows(model) if unit_effects else None
     limit = int(chunk_rows) if chunk_rows is not None else _CHUNK_PASSES * batch_size
-    with torch.no_grad(), model.eval_cache(), (rep.eval_cache() if both else contextlib.nullcontext()):
-        for v0, cnt in chunks(V, S, limit):
-            r0, r1 = 2 * S * v0, 2 * S * (v0 + cnt)
+    spans = [(2 * S * v0, 2 * S * (v0 + cnt)) for v0, cnt in chunks(V, S, limit)]
 
-            def launch(m, rc):
-                return m._launch_score_edits(
-                    EditedWindows(seq_d, dt["row_start"][r0:r1], dt["row_edit"][r0:r1], dt["pos"], dt["ref_len"],
-                                  dt["alt_len"], dt["alt_off"], dt["alt"], rc, batch_size), unit_effects)
+    def rows_of(seq_d, dt, r0, r1, rc):
+        return EditedWindows(seq_d, dt["row_start"][r0:r1], dt["row_edit"][r0:r1], dt["pos"], dt["ref_len"],
+                             dt["alt_len"], dt["alt_off"], dt["alt"], rc, batch_size)
 
-            fwd, rev = _launch_strands(model, handles, launch, unit_effects)
-            if unit_effects:
-                (fwd, ofwd), orev = fwd, None
-                if both:
-                    rev, orev = rev
-                d = ofwd[1::2] - ofwd[0::2]                     # (cnt*S, units): alt - ref
-                if both:
-                    d = (d + (orev[1::2] - orev[0::2])) / 2
-                d = d.reshape(cnt, S, units).mean(dim=1)
-                res["units"][v0:v0 + cnt] = (d[:, :, None] * wrows.t()[None, :, :]).cpu().numpy()
-            if both:
-                full = torch.stack((fwd, rev, (fwd + rev) / 2, torch.maximum(fwd, rev)), dim=-1)
-                full = full.reshape((cnt, S, 2) + shape + (4,)).cpu().numpy()
-                res["ref"][v0:v0 + cnt], res["alt"][v0:v0 + cnt] = full[:, :, 0], full[:, :, 1]
-            else:
-                one = fwd.reshape((cnt, S, 2) + shape).cpu().numpy()
-                res["ref"][v0:v0 + cnt, ..., 0], res["alt"][v0:v0 + cnt, ..., 0] = one[:, :, 0], one[:, :, 1]
-    if model.validate_input:
-        if both:
-            rep.check_input()
-        model.check_input()
+    for r0, r1, fwd, rev, ofwd, orev in _score_spans(model, data, tab, tuple(tab), spans, rows_of,
+                                                     "_launch_score_edits", both, check_ref, unit_effects):
+        v0, v1 = r0 // (2 * S), r1 // (2 * S)
+        if unit_effects:
+            # (rows / 2, units): alt - ref
+            d = _strand_mean(ofwd[1::2] - ofwd[0::2], orev[1::2] - orev[0::2] if both else None)
+            res["units"][v0:v1] = _unit_effects(d.reshape(v1 - v0, S, units).mean(dim=1), wrows)
+        full = _columns(fwd, rev).reshape((v1 - v0, S, 2) + shape + (4,))
+        res["ref"][v0:v1], res["alt"][v0:v1] = full[:, :, 0], full[:, :, 1]
     if apply_sigmoid:
-        for key in ("ref", "alt"):
-            res[key] = torch.sigmoid(torch.from_numpy(res[key])).numpy()
+        res["ref"], res["alt"] = _sigmoid(res["ref"]), _sigmoid(res["alt"])
     col = 2 if both else 0
     res["delta"] = (res["alt"][..., col] - res["ref"][..., col]).mean(axis=1)
     return res
@@ -309,86 +311,52 @@ def score_haplotypes(model, codes, pos, ref_len, alts, haplotypes, starts, stran
                   the bank layout).
     Strands, streams and chunking are score_variants': the rows go to the device in chunks of at most
     32 * batch_size rows (chunk_rows overrides it), the reference windows first."""
-    if strands not in ("both", "fwd"):
-        raise ValueError("strands must be 'both' or 'fwd' (got %r)" % (strands,))
-    L = model._options["sequence_length"]
-    batch_size = max(1, int(batch_size))
-    device = model.final.weight.device
-    data = codes if torch.is_tensor(codes) else torch.as_tensor(np.ascontiguousarray(codes))
-    if data.dtype != torch.uint8 or data.dim() != 1:
-        raise ValueError("codes must be a 1-D uint8 array of base codes")
+    data, L, batch_size, shape, units = _begin(model, codes, strands, batch_size)
     tab = build_haplotype_tables(pos, ref_len, alts, haplotypes, starts, L)
-    V, H = len(tab["pos"]), len(haplotypes)
+    H = len(haplotypes)
     R = len(tab["row_start"]) // H if H else len(np.asarray(starts).reshape(-1))
-    if V and (tab["pos"].min() < 0 or (tab["pos"] + tab["ref_len"]).max() > data.shape[0]):
-        bad = np.flatnonzero((tab["pos"] < 0) | (tab["pos"] + tab["ref_len"] > data.shape[0]))
-        raise ValueError("%d variant(s) outside the sequence of %d bases (0 <= pos, pos + ref_len <= length); "
-                         "the first: #%d at %d" % (bad.size, data.shape[0], bad[0], tab["pos"][bad[0]]))
+    _check_inside(tab, data.shape[0])
     # the reference windows are rows of their own, without a run, ahead of the haplotypes' rows
     ref_start = np.asarray(starts, dtype=np.int64).reshape(-1)
     tab["row_start"] = np.concatenate((ref_start, tab["row_start"]))
     tab["row_first"] = np.concatenate((np.zeros(R, np.int64), tab["row_first"]))
     tab["row_count"] = np.concatenate((np.zeros(R, np.int32), tab["row_count"]))
-    shape = tuple(model._logits_empty(0, torch.device("cpu")).shape[1:])
-    units = model._units()
     rows = R + H * R
     scores = np.full((rows,) + shape + (4,), np.nan)
     res = {"straddling": tab["straddling"]}
     if unit_effects:
         res["units"] = np.zeros((H * R, units, shape[-1]), dtype=np.float32)
-    if rows:
-        both = strands == "both"
-        handles = _strand_handles(model, both)
-        rep = handles[1]
-        seq_d = data.to(device).contiguous()
-        if check_ref is not None:
-            _check_ref_alleles(seq_d, tab["pos"], tab["ref_len"].astype(np.int64), check_ref)
-        dt = {k: torch.from_numpy(tab[k]).to(device) for k in _HAP_TABLES}
-        wrows = _final_rows(model) if unit_effects else None
-        limit = max(1, int(chunk_rows) if chunk_rows is not None else _CHUNK_PASSES * batch_size)
-        # the reference rows in chunks of their own, so that a chunk of haplotype rows finds them all
-        spans = [(r0, min(r0 + limit, R)) for r0 in range(0, R, limit)]
-        spans += [(r0, min(r0 + limit, rows)) for r0 in range(R, rows, limit)]
-        ref_parts, ref_outs = ([], []), None
-        with torch.no_grad(), model.eval_cache(), (rep.eval_cache() if both else contextlib.nullcontext()):
-            for r0, r1 in spans:
+    both = strands == "both"
+    wrows = _final_rows(model) if unit_effects else None
+    limit = max(1, int(chunk_rows) if chunk_rows is not None else _CHUNK_PASSES * batch_size)
+    # the reference rows in chunks of their own, so that a chunk of haplotype rows finds them all
+    spans = [(r0, min(r0 + limit, R)) for r0 in range(0, R, limit)]
+    spans += [(r0, min(r0 + limit, rows)) for r0 in range(R, rows, limit)]
 
-                def launch(m, rc):
-                    return m._launch_score_haplotypes(
-                        HaplotypeWindows(seq_d, dt["row_start"][r0:r1], dt["row_first"][r0:r1],
-                                         dt["row_count"][r0:r1], dt["edit_index"], dt["pos"], dt["ref_len"],
-                                         dt["alt_len"], dt["alt_off"], dt["alt"], rc, batch_size), unit_effects)
+    def rows_of(seq_d, dt, r0, r1, rc):
+        return HaplotypeWindows(seq_d, dt["row_start"][r0:r1], dt["row_first"][r0:r1], dt["row_count"][r0:r1],
+                                dt["edit_index"], dt["pos"], dt["ref_len"], dt["alt_len"], dt["alt_off"],
+                                dt["alt"], rc, batch_size)
 
-                fwd, rev = _launch_strands(model, handles, launch, unit_effects)
-                if unit_effects:
-                    (fwd, ofwd), orev = fwd, None
-                    if both:
-                        rev, orev = rev
-                    if r0 < R:
-                        ref_parts[0].append(ofwd)
-                        ref_parts[1].append(orev)
-                    else:
-                        if ref_outs is None:
-                            ref_outs = (torch.cat(ref_parts[0]), torch.cat(ref_parts[1]) if both else None)
-                        window = torch.arange(r0 - R, r1 - R, device=device) % R
-                        d = ofwd - ref_outs[0][window]                  # (rows, units): hap - ref
-                        if both:
-                            d = (d + (orev - ref_outs[1][window])) / 2
-                        res["units"][r0 - R:r1 - R] = (d[:, :, None] * wrows.t()[None, :, :]).cpu().numpy()
-                if both:
-                    full = torch.stack((fwd, rev, (fwd + rev) / 2, torch.maximum(fwd, rev)), dim=-1)
-                    scores[r0:r1] = full.cpu().numpy()
-                else:
-                    scores[r0:r1, ..., 0] = fwd.cpu().numpy()
-        if model.validate_input:
-            if both:
-                rep.check_input()
-            model.check_input()
+    ref_parts, ref_outs = ([], []), None
+    for r0, r1, fwd, rev, ofwd, orev in _score_spans(model, data, tab, _HAP_TABLES, spans, rows_of,
+                                                     "_launch_score_haplotypes", both, check_ref, unit_effects):
+        if unit_effects and r0 < R:
+            ref_parts[0].append(ofwd)
+            ref_parts[1].append(orev)
+        elif unit_effects:
+            if ref_outs is None:
+                ref_outs = (torch.cat(ref_parts[0]), torch.cat(ref_parts[1]) if both else None)
+            window = torch.arange(r0 - R, r1 - R, device=ofwd.device) % R
+            # (rows, units): hap - ref
+            d = _strand_mean(ofwd - ref_outs[0][window], orev - ref_outs[1][window] if both else None)
+            res["units"][r0 - R:r1 - R] = _unit_effects(d, wrows)
+        scores[r0:r1] = _columns(fwd, rev)
     if apply_sigmoid:
-        scores = torch.sigmoid(torch.from_numpy(scores)).numpy()
+        scores = _sigmoid(scores)
     res["ref"] = scores[:R]
     res["hap"] = scores[R:].reshape((H, R) + shape + (4,))
-    col = 2 if strands == "both" else 0
+    col = 2 if both else 0
     res["delta"] = res["hap"][..., col] - res["ref"][None, ..., col]
     if unit_effects:
         res["units"] = res["units"].reshape(H, R, units, shape[-1])

@@ -357,3 +357,25 @@ def test_scan_state_and_errors():
     L_.check(lib.explainn_forward_eval(h, x.data_ptr(), B, C.byref(ps), logits.data_ptr(), stream))
     torch.cuda.synchronize()
     assert torch.isfinite(logits).all()
+
+
+def test_scan_bad_byte_raises_once_and_leaves_no_flag_behind():
+    """A byte that is no base code is seen by both strands, so both contexts raise their sticky flag.
+    scan() settles them behind its loop: it must raise the one ValueError, and it must read (and so
+    clear) BOTH flags before it does -- the next scan(), on clean codes, must not raise for the last
+    one's byte.  The first two launches of a handle validate inside the launch itself; three clean
+    scans put the model and its replica past that, on the deferred schedule this test is about."""
+    from explainn_amd.scan import scan
+    sd = _sd(8, K0, L0, 1, seed=4)
+    m = model(sd, 8, K0, L0, 1).eval()
+    assert m.validate_input is True
+    clean = sm.random_codes(400, seed=2)
+    bad = clean.copy()
+    bad[250] = 7
+    first = scan(m, clean, stride=7, strands="both", mode="windows")[1]
+    for _ in range(2):
+        scan(m, clean, stride=7, strands="both", mode="windows")
+    with pytest.raises(ValueError, match="input is not one-hot: base codes must be 0..4"):
+        scan(m, bad, stride=7, strands="both", mode="windows")
+    again = scan(m, clean, stride=7, strands="both", mode="windows")[1]
+    assert np.array_equal(first, again)
