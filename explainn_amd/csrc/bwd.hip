@@ -22,31 +22,61 @@ typedef float f32x4b __attribute__((ext_vector_type(4)));
 // check -Rpass-analysis=kernel-resource-usage after touching it.)
 // n <= 72: one 1024-thread block per unit with V1, A2, EQ and M
 // staged in LDS, so every inner loop reads LDS instead of chasing dependent global loads.
-__global__ __launch_bounds__(1024) void mid_fused_kernel(
+// One instantiation per pooled-length bucket: the row strides, the tile counts and the bounds of the
+// loops over w are compile-time (nq_lower(NQ) < n <= NQ), so those loops unroll with their LDS reads
+// ahead of the fp64 chains, and every index below is a shift, a mask or a constant multiple.
+constexpr int mid_log2c(int NQ) { int l = 0; while ((1 << l) < NQ) ++l; return l; }
+template <int NQ>
+__host__ __device__ constexpr size_t mid_fused_lds() {
+    // doubles: qbar [NQ] and the five row factors of dV1 [100].  floats: V1, A2, EQ, V1.C [100][NQ+1];
+    // M [NQ][NQ]; se, md2, cf, V2 [100]; NQ more behind V1.C, the last table: the dV1 grid reads (and
+    // drops) up to the next power of two of every row
+    return ((size_t)NQ + 5 * FC_H) * sizeof(double) +
+           ((size_t)4 * FC_H * (NQ + 1) + (size_t)NQ * NQ + 4 * FC_H + NQ) * sizeof(float);
+}
+// (eight waves per SIMD -- 64 registers -- wherever the LDS lets two blocks share a CU)
+template <int NQ>
+__global__ __launch_bounds__(1024, (mid_fused_lds<NQ>() <= 80 * 1024 ? 8 : 4)) void mid_fused_kernel(
     const float* __restrict__ EQp, const float* __restrict__ Sep, const float* __restrict__ A2,
     const float* __restrict__ sh2, const float* __restrict__ sig2, const float* __restrict__ fc1_w,
     const float* __restrict__ fc2_w, const float* __restrict__ g2, const double* __restrict__ qbar,
     const float* __restrict__ VC, float* __restrict__ Ttf,
     float* __restrict__ Mff, float* __restrict__ k0p, float* __restrict__ g_fc2_w, float* __restrict__ g_bn2_w,
     float* __restrict__ g_bn2_b, float* __restrict__ g_fc1_b, float* __restrict__ g_fc1_w, int n,
-    int NS, int NW16, int B, int ACH, float scale) {
-    extern __shared__ float fsm[];
-    const int ld = n + 1;
-    float* V1s = fsm;                        // [100][ld]
+    int B, int ACH, float scale) {
+    constexpr int NS = ns_stride(NQ), NW16 = fc_nw16(NQ), NQLO = nq_lower(NQ);
+    // (the doubles first, and no pointer through an integer: a cast to size_t and back made every read
+    // of them a flat load)
+    extern __shared__ double dsm[];
+    constexpr int ld = NQ + 1;
+    double* qbd = dsm;                       // [NQ]  qbar
+    // dV1's per-channel factors, as the doubles its expression multiplies by (each computed once, by
+    // the channel's thread of the second phase): scale * V2, gamma2 / sigma2, md2 * B, md2h, B / sigma2
+    double* svd = qbd + NQ;                  // [100]
+    double* gsd = svd + FC_H;                // [100]
+    double* mBd = gsd + FC_H;                // [100]
+    double* mhd = mBd + FC_H;                // [100]
+    double* sgd = mhd + FC_H;                // [100]
+    float* V1s = reinterpret_cast<float*>(sgd + FC_H);   // [100][ld]
     float* A2s = V1s + FC_H * ld;            // [100][ld]
     float* EQl = A2s + FC_H * ld;            // [100][ld]
-    float* Ms = EQl + FC_H * ld;             // [n][n]
-    float* qb = Ms + n * n;                  // [n]
-    float* se = qb + n;                      // [100]
+    float* Ms = EQl + FC_H * ld;             // [NQ][NQ]
+    float* se = Ms + NQ * NQ;                // [100]
     float* md2s = se + FC_H;                 // [100]
     float* cfs = md2s + FC_H;                // [100]  md2h / sig2
-    float* md2hs = cfs + FC_H;               // [100]
-    float* VCl = md2hs + FC_H;               // [100][ld]  (V1.C), read once here: the dV1 loop below
-    float* svl = VCl + FC_H * ld;            // [100]      then runs on LDS alone (its five global
-    float* gsl = svl + FC_H;                 // [100]      loads per element made it a latency chain:
-    float* sgl = gsl + FC_H;                 // [100]      12 K of the block's 31 K cycles)
+    float* v2s = cfs + FC_H;                 // [100]  V2
+    float* VCl = v2s + FC_H;                 // [100][ld]  (V1.C), read once here: the dV1 loop below
+                                             // then runs on LDS alone (its five global loads per element
+                                             // made it a latency chain: 12 K of the block's 31 K cycles)
     const int u = blockIdx.x, tid = threadIdx.x;
     STAMP(0);
+    // the per-channel scalars of the second phase, in flight with the first phase's loads (issued in
+    // that phase, in the middle of its chain, they were a memory round trip 14 waves waited for)
+    float v2f = 0.f, sg2f = 1.f, sh2f = 0.f, g2f = 0.f;
+    if (tid < FC_H) {
+        const size_t ch = (size_t)u * FC_H + tid;
+        v2f = fc2_w[ch]; sg2f = sig2[ch]; sh2f = sh2[ch]; g2f = g2[ch];
+    }
     {
         // (all the loads of the block's three passes over [100][n] in flight before the first LDS store:
         // as a loop with a run-time trip count every pass was its own memory round trip)
@@ -103,8 +133,7 @@ __global__ __launch_bounds__(1024) void mid_fused_kernel(
             if (e < FC_H * n) EQl[(e % FC_H) * ld + e / FC_H] = (float)eq[it];
         }
     }
-    double* qbd = reinterpret_cast<double*>((reinterpret_cast<size_t>(sgl + FC_H) + 7) & ~size_t(7));   // [n] doubles
-    for (int w = tid; w < n; w += 1024) { const double v = qbar[(size_t)u * NS + w]; qb[w] = (float)v; qbd[w] = v; }
+    for (int w = tid; w < n; w += 1024) qbd[w] = qbar[(size_t)u * NS + w];
     for (int r = tid; r < FC_H; r += 1024) {
         double s = 0;
         for (int c0 = 0; c0 < ACH; c0 += 4) {          // four partials in flight (was one round trip each)
@@ -118,6 +147,8 @@ __global__ __launch_bounds__(1024) void mid_fused_kernel(
         }
         se[r] = (float)s;
     }
+    KEEP(v2f); KEEP(sg2f); KEEP(sh2f); KEEP(g2f);
+    if (tid < FC_H) v2s[tid] = v2f;
     __syncthreads();
     STAMP(1);
     const double sc = (double)scale;
@@ -126,21 +157,90 @@ __global__ __launch_bounds__(1024) void mid_fused_kernel(
         const size_t ch = (size_t)u * FC_H + r;
         double sAE = 0, sVE = 0;
         const double ser = (double)se[r];
-        for (int w = 0; w < n; ++w) {
-            const double eq = (double)EQl[r * ld + w];
-            sAE = fma((double)A2s[r * ld + w], eq, sAE);
-            sVE = fma((double)V1s[r * ld + w], eq - ser * qbd[w], sVE);
+        // (as `for (w = 0; w < n; ++w)` every trip was three exposed LDS reads in front of the two
+        // dependent FMAs, with 14 of the 16 waves at the barrier.  Eight trips' operands are read
+        // ahead; the chain and its order are the same; the trips past n -- only those above the bucket
+        // below can be -- keep the sums as they are)
+        constexpr int WB = 8;
+#pragma unroll
+        for (int w0 = 0; w0 < NQ; w0 += WB) {
+            float av[WB], vv[WB], ev[WB];
+            double qv[WB];
+#pragma unroll
+            for (int i = 0; i < WB; ++i) {
+                const int w = w0 + i < NQ ? w0 + i : NQ - 1;
+                av[i] = A2s[r * ld + w]; vv[i] = V1s[r * ld + w]; ev[i] = EQl[r * ld + w]; qv[i] = qbd[w];
+            }
+#pragma unroll
+            for (int i = 0; i < WB; ++i) {
+                const int w = w0 + i;
+                if (w >= NQ) continue;
+                const double eq = (double)ev[i];
+                const double nAE = fma((double)av[i], eq, sAE);
+                const double nVE = fma((double)vv[i], eq - ser * qv[i], sVE);
+                const bool on = w < NQLO || w < n;
+                sAE = on ? nAE : sAE;
+                sVE = on ? nVE : sVE;
+            }
         }
-        const double v2 = (double)fc2_w[ch], sg = (double)sig2[ch];
-        g_fc2_w[ch] = (float)(sc * (sAE + (double)sh2[ch] * ser));
+        const double v2 = (double)v2f, sg = (double)sg2f;
+        g_fc2_w[ch] = (float)(sc * (sAE + (double)sh2f * ser));
         const double db2 = sc * v2 * ser, dg2 = sc * v2 / sg * sVE;
         g_bn2_b[ch] = (float)db2;
         g_bn2_w[ch] = (float)dg2;
         g_fc1_b[ch] = 0.f;
-        md2s[r] = (float)(db2 / (double)B);
-        md2hs[r] = (float)(dg2 / (double)B);
+        const float md2 = (float)(db2 / (double)B);
+        md2s[r] = md2;
         cfs[r] = (float)((dg2 / (double)B) / sg);
-        svl[r] = (float)v2; gsl[r] = (float)((double)g2[ch] / sg); sgl[r] = (float)((double)B / sg);
+        // (every factor rounded to fp32 first, as when they were kept as floats and converted per
+        // element; md2h and B / sigma2 stay apart: their product is not a factor of the expression)
+        svd[r] = sc * (double)(float)v2;
+        gsd[r] = (double)(float)((double)g2f / sg);
+        mBd[r] = (double)md2 * (double)B;
+        mhd[r] = (double)(float)(dg2 / (double)B);
+        sgd[r] = (double)(float)((double)B / sg);
+    }
+    // T[r][w] = scale * V2[r] * A2[r][w] needs nothing of the chain above: eight of the waves that
+    // would wait at the barrier for it emit T meanwhile (every other pair of waves: by the usual
+    // placement not the SIMDs of waves 0 and 1).  T goes out as three bf16 pieces (hi + mid + lo = tv
+    // exactly) in the A-fragment order of v_mfma_f32_16x16x32_bf16: lane 16((r>>3)&3) + (w&15),
+    // element r&7 of k-step r>>5.  By destination: a thread owns the 16-byte row (w tile, k-step,
+    // lane) of each piece, computes its eight values and stores three rows whole -- 2-byte stores
+    // 16 bytes apart made this a third of the block.  Rows of r >= 100 or w >= n are zeros.
+    if (((tid >> 6) & 3) >= 2) {
+        constexpr int NTT = 512;
+        const int t = (((tid >> 8) * 2 + ((tid >> 6) & 1)) << 6) + (tid & 63);
+#pragma unroll
+        for (int f0 = 0; f0 < NW16 * 256; f0 += NTT) {
+            const int f = f0 + t;
+            if (f0 + NTT <= NW16 * 256 || f < NW16 * 256) {
+                const int lane = f & 63, ks = (f >> 6) & 3, wt = f >> 8;
+                const int w = 16 * wt + (lane & 15), r0 = 32 * ks + 8 * (lane >> 4);
+                const bool won = w < n;
+                const int wc = won ? w : 0;
+                uint32_t ph[4], pm[4], pl[4];
+#pragma unroll
+                for (int el = 0; el < 8; ++el) {
+                    const int r = r0 + el;
+                    const bool ron = r < FC_H;
+                    const int rc = ron ? r : 0;
+                    const double sv = sc * (double)v2s[rc];
+                    const float tq = (float)(sv * (double)A2s[rc * ld + wc]);
+                    const float tv = won && ron ? tq : 0.f;
+                    const uint32_t hb = __float_as_uint(tv) & 0xffff0000u;
+                    const float r1 = tv - __uint_as_float(hb);
+                    const uint32_t mb = __float_as_uint(r1) & 0xffff0000u;
+                    const float r2 = r1 - __uint_as_float(mb);
+                    const uint32_t lb = __float_as_uint(r2) & 0xffff0000u;
+                    if (el & 1) { ph[el >> 1] |= hb; pm[el >> 1] |= mb; pl[el >> 1] |= lb; }
+                    else { ph[el >> 1] = hb >> 16; pm[el >> 1] = mb >> 16; pl[el >> 1] = lb >> 16; }
+                }
+                uint4* tb = reinterpret_cast<uint4*>(Ttf) + (((size_t)u * NW16 + wt) * (3 * 4) + ks) * 64 + lane;
+                tb[0] = make_uint4(ph[0], ph[1], ph[2], ph[3]);
+                tb[4 * 64] = make_uint4(pm[0], pm[1], pm[2], pm[3]);
+                tb[8 * 64] = make_uint4(pl[0], pl[1], pl[2], pl[3]);
+            }
+        }
     }
     __syncthreads();
     STAMP(2);
@@ -149,8 +249,7 @@ __global__ __launch_bounds__(1024) void mid_fused_kernel(
     // steps with all operands read ahead.  (One 32x32x2 tile on ONE wave -- 50 dependent 64-cycle
     // steps plus a 16-value scattered epilogue -- was the block's critical path: every other wave sat
     // at the barrier below for 12 K of the block's 34 K cycles.  As an fp64 VALU loop: worse still.)
-    const int NT2 = NW16;
-    const int ntile_m = NT2 * NT2;
+    constexpr int NT2 = NW16, ntile_m = NT2 * NT2;
     {
         const int wave = tid >> 6, lane = tid & 63, c = lane & 15, gq = lane >> 4;
         for (int tile = wave; tile < ntile_m; tile += 16) {
@@ -179,43 +278,34 @@ __global__ __launch_bounds__(1024) void mid_fused_kernel(
             for (int i = 0; i < 4; ++i) {
                 const int v = 16 * vt + 4 * gq + i;
                 Mff[(((size_t)u * NW16 + wt) * (4 * NW16) + 4 * vt + i) * 64 + 16 * gq + c] = acc[i];
-                if (v < n && wb < n) Ms[v * n + wb] = acc[i];
+                if (v < n && wb < n) Ms[v * NQ + wb] = acc[i];
             }
         }
     }
     STAMP(3);
-    // dV1 and T do not need M: the waves that had no M tile above do this loop while the tile waves
+    // dV1 does not need M: the waves that had no M tile above do this loop while the tile waves
     // are still in their MFMA chains (with everybody taking an equal share the block waited for
     // wave 0 to finish its tile AND its share)
-    const int busy = min(ntile_m, 8) * 64;             // threads of the tile waves
-    for (int e = tid - busy; e < FC_H * NS; e += 1024 - busy) {
-        if (e < 0) break;                              // tile waves skip
-        const int r = e / NS, w = e % NS;
-        const size_t ch = (size_t)u * FC_H + r;
-        const double sv = sc * (double)svl[r];
-        float tv = 0.f;
-        if (w < n) {
-            tv = (float)(sv * (double)A2s[r * ld + w]);
+    // (As one loop over e = r * NS + w that also emitted T the body was ~145 instructions per element
+    // -- a run-time division, four 64-bit addresses, ten conversions, three 2-byte stores -- and the
+    // phase was a third of the block, bound by vector issue, not by memory.)
+    constexpr int busy = (ntile_m < 8 ? ntile_m : 8) * 64, NTH = 1024 - busy;   // threads of the tile waves; the rest
+    const int t = tid - busy;
+    if (t >= 0) {                                      // tile waves skip
+        // dV1 on a [100][CP] grid of the free threads, CP the power of two above the bucket: row and
+        // column are a shift and a mask.  Rows read past w = n hold whatever LDS holds (in bounds:
+        // the next table) and are not stored.
+        constexpr int LOGC = mid_log2c(NQ), CP = 1 << LOGC;
+        float* gw = g_fc1_w + (size_t)u * FC_H * n;    // this unit's [100][n]
+#pragma unroll
+        for (int e0 = 0; e0 < FC_H * CP; e0 += NTH) {
+            const int e = e0 + t, w = e & (CP - 1);
+            const bool rin = e0 + NTH <= FC_H * CP || (e >> LOGC) < FC_H;
+            const int r = rin ? e >> LOGC : 0;
             // (V1.C)[r][w], computed once by prep2, times B / sigma2 (per-channel, from LDS)
-            const double hq = (double)VCl[r * ld + w] * (double)sgl[r];
-            const double val = (double)gsl[r] *
-                               (sv * (double)EQl[r * ld + w] -
-                                (double)md2s[r] * (double)B * qbd[w] -
-                                (double)md2hs[r] * hq);
-            g_fc1_w[ch * n + w] = (float)val;
-        }
-        {
-            // T[r][w] as three bf16 pieces (hi + mid + lo = tv exactly) in the A-fragment order of
-            // v_mfma_f32_16x16x32_bf16: lane 16((r>>3)&3) + (w&15), element r&7 of k-step r>>5
-            const uint32_t hb = __float_as_uint(tv) & 0xffff0000u;
-            const float r1 = tv - __uint_as_float(hb);
-            const uint32_t mb = __float_as_uint(r1) & 0xffff0000u;
-            const float r2 = r1 - __uint_as_float(mb);
-            uint16_t* tb = reinterpret_cast<uint16_t*>(Ttf) + ((size_t)u * NW16 + (w >> 4)) * (3 * 4 * 512) +
-                           ((size_t)(r >> 5) * 64 + 16 * ((r >> 3) & 3) + (w & 15)) * 8 + (r & 7);
-            tb[0] = (uint16_t)(hb >> 16);
-            tb[4 * 512] = (uint16_t)(mb >> 16);
-            tb[8 * 512] = (uint16_t)(__float_as_uint(r2) >> 16);
+            const double hq = (double)VCl[r * ld + w] * sgd[r];
+            const double val = gsd[r] * (svd[r] * (double)EQl[r * ld + w] - mBd[r] * qbd[w] - mhd[r] * hq);
+            if (rin && w < n) gw[r * n + w] = (float)val;
         }
     }
     __syncthreads();
@@ -224,7 +314,12 @@ __global__ __launch_bounds__(1024) void mid_fused_kernel(
         double k0 = 0;
         if (w < n) {
             for (int r = 0; r < FC_H; ++r) k0 = fma((double)A2s[r * ld + w], (double)md2s[r], k0);
-            for (int v = 0; v < n; ++v) k0 -= qbd[v] * (double)Ms[v * n + w];
+            // (compile-time bound; the trips past n keep k0)
+#pragma unroll 8
+            for (int v = 0; v < NQ; ++v) {
+                const double nk = k0 - qbd[v] * (double)Ms[v * NQ + w];
+                k0 = (v < NQLO || v < n) ? nk : k0;
+            }
         }
         k0p[(size_t)u * NS + w] = (float)k0;
     }
@@ -396,18 +491,20 @@ static size_t mid_big_lds(int n) {
     return ((size_t)2 * FC_H * (n + 1) + n + 5 * FC_H) * sizeof(float);
 }
 
-static size_t mid_fused_lds(int n) {
-    return ((size_t)4 * FC_H * (n + 1) + (size_t)n * n + n + 7 * FC_H + 2) * sizeof(float) + (size_t)n * sizeof(double);
-}
+#define MID_FUSED_MAX_NQ 72                 /* the largest bucket mid_fused is instantiated for */
 
 int launch_mid_bwd(explainn_ctx* c, const explainn_params* p, const explainn_grads* g, int B,
                    hipStream_t s) {
     if (c->n <= 72) {
-        hipLaunchKernelGGL(mid_fused_kernel, dim3(c->U), dim3(1024), mid_fused_lds(c->n), s, c->EQp,
-                           c->Sep, c->A2, c->sh2, c->sig2, p->fc1_w, p->fc2_w, p->bn2_w, c->qbar,
-                           c->VC, c->Ttf, c->Mff, c->k0p, g->fc2_w, g->bn2_w, g->bn2_b,
-                           g->fc1_b, g->fc1_w, c->n, c->NS, fc_nw16(c->NQ), B, c->ACH,
-                           c->fwd_scale);
+#define CALL(N)                                                                                   \
+        if constexpr ((N) <= MID_FUSED_MAX_NQ)   /* (the buckets above go to mid_big) */           \
+            hipLaunchKernelGGL(mid_fused_kernel<N>, dim3(c->U), dim3(1024), mid_fused_lds<N>(), s, \
+                               c->EQp, c->Sep, c->A2, c->sh2, c->sig2, p->fc1_w, p->fc2_w,        \
+                               p->bn2_w, c->qbar, c->VC, c->Ttf, c->Mff, c->k0p, g->fc2_w,        \
+                               g->bn2_w, g->bn2_b, g->fc1_b, g->fc1_w, c->n, B, c->ACH,           \
+                               c->fwd_scale)
+        NQ_DISPATCH(c->NQ, CALL);
+#undef CALL
         LAUNCH_CHECK();
         return EXPLAINN_OK;
     }
@@ -827,9 +924,14 @@ int bwd_configure(explainn_ctx* c) {
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mid_big_kernel),
                                     hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)mid_big_lds(c->n)));
-    if (c->n <= 72 && mid_fused_lds(c->n) > 48 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mid_fused_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)mid_fused_lds(c->n)));
+    if (c->n <= 72) {
+#define CALL(N)                                                                                   \
+        if constexpr ((N) <= MID_FUSED_MAX_NQ && mid_fused_lds<N>() > 48 * 1024)                  \
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&mid_fused_kernel<N>),      \
+                                        hipFuncAttributeMaxDynamicSharedMemorySize,               \
+                                        (int)mid_fused_lds<N>()))
+        NQ_DISPATCH(c->NQ, CALL);
+#undef CALL
+    }
     return EXPLAINN_OK;
 }

@@ -89,7 +89,8 @@ GATED = (C2_STEP + INPUT_GRAD + ISM + PATHGRAD + METRICS + SCAN + VARIANTS + HAP
 # Register cliffs measured in the pipeline: 1024-thread blocks of which TWO must
 # share a CU (300 units on 256 CUs take two rounds otherwise) -- 64 registers, not one more.
 # passA: three waves per SIMD (512 registers / 3, in allocation units of 8).
-VGPR_CAP = {r"^mid_fused_kernel": 64, r"^prep2_kernel<true>": 64,
+# (mid_fused: the buckets up to 40, whose LDS lets two blocks share a CU; above, one block has the CU)
+VGPR_CAP = {r"^mid_fused_kernel<([1-9]|[1-3]\d|40)>": 64, r"^prep2_kernel<true>": 64,
             r"^passA_kernel<26, 0>": 168, r"^passA_kernel<26, 2>": 168}
 
 
