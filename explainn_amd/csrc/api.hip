@@ -252,6 +252,11 @@ static int create_ctx(explainn_ctx** out, int groups, int units_per_member, int 
         // tuning overrides (experiments only; defaults above are what is tested and benchmarked)
         if (const char* e = getenv("EXPLAINN_ACH")) { const int v = atoi(e); if (v >= 1 && v <= 16) c->ACH = v; }
         if (const char* e = getenv("EXPLAINN_QCH")) { const int v = atoi(e); if (v >= 1 && v <= cap && v <= 8) c->QCH = v; }
+        // blocks per 64 sequences of the head sums' combiner launch (head.hip, launch_head_fwd_sums): 1 = one
+        // block that does everything, R = the storing block and R - 1 unit groups; the launch clamps
+        // it to [1, U + 1]
+        c->head_groups = HEAD_GROUPS_DEFAULT;
+        if (const char* e = getenv("EXPLAINN_HEAD_GROUPS")) c->head_groups = atoi(e);
     }
     Carver dry;
     carve(c, dry);

@@ -12,6 +12,7 @@
 #define FC_H 100          // hidden width of the per-unit FC (architectures/__init__.py:86)
 #define HEAD_RB 8            // head kernels keep up to HEAD_RB*256 sequences per unit in registers
 #define HEAD_GEMM_MIN_T 8   // more tasks than this: combiner forward/backward as MFMA GEMMs (head.hip)
+#define HEAD_GROUPS_DEFAULT 4   // blocks per sequence block of the head sums' combiner launch (EXPLAINN_HEAD_GROUPS)
 // d Wf = dl^T o^T has K = batch and only ceil(T/32) x ceil((U+1)/32) output tiles (20 at C3): the batch is
 // cut into chunks of >= 128 sequences, one workgroup per (tile, chunk), summed per unit in head_bwd
 #define HEAD_GW_MAXCH 32
@@ -33,6 +34,7 @@ struct explainn_ctx {
     int K4;               // 4*k
     int QCH;              // b-chunks of the q-moment kernel
     int ACH;              // b-chunks of passA
+    int head_groups;      // blocks per sequence block of the combiner launch that carries the head sums
     // per-stage timing (explainn_stage_timing): events bracketing every stage of the training step
     bool timing; unsigned timed;
     hipEvent_t ev0[16], ev1[16];

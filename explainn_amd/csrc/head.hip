@@ -242,8 +242,9 @@ __global__ __launch_bounds__(1024) void logits_kernel(const float* __restrict__ 
 // block (0, 0) of each member its running statistics, member 0's the shared num_batches_tracked.
 // (The member offsets are block-uniform: they cost scalar registers, none of the kernel's 128 vector ones.)
 //
-// TT > 0 is the form of the training step with few tasks and more than 512 sequences (G = 1, grid.y =
-// 1): the block sums all TT tasks of its 64 sequences (TT weight rows in LDS, the sums of task t in
+// TT > 0 is the form of the training step with few tasks and more than 512 sequences (G = 1; grid.y
+// counts the unit groups of head_sums below, and every group does all of this paragraph for its 64
+// sequences): the block sums all TT tasks of its 64 sequences (TT weight rows in LDS, the sums of task t in
 // the order the block of task t has above, so the logits keep their bits), and with the logits of
 // its sequences in hand goes on to the loss gradient and its share of the head backward's batch sums
 // (head_sums below): the per-unit head backward launch that re-read all of this disappears.
@@ -256,16 +257,47 @@ struct head_sums_args {
 // The block's part of the head backward, entered with the logits s[t] of sequence b in wave 0.
 // Wave 0: dl = loss_grad for its 64 sequences (0 for the dead ones), to memory and through LDS to
 // everybody; the block's sums of dl and of the loss terms to hb.  Then every thread takes (unit, eight
-// sequences): zhat back from memory (this block stored it; two 16-byte loads per unit, three units in
-// flight), o by the forward's own expression, and in fp64, sequence order
+// sequences): z from memory (the previous launch's output: two 16-byte loads per unit, PC units in
+// flight), zhat and o by the forward's own expressions, and in fp64, sequence order
 //   s1 = sum d3,  s2 = sum d3 zhat,  gw[t] = sum dl[b][t] o     d3 = o > 0 ? sum_t dl[b][t] Wf[t][u] : 0
 // the eight threads of a unit are adjacent lanes: three butterfly steps, one store of 2 + T doubles
 // per (unit, block).  Plain stores: passA, the next launch but one, adds the blocks up.
+//
+// Unit groups (gridDim.y = R > 1): the R blocks of a sequence block all hold the same logits (phase 1
+// is run by each of them in full).  Group 0 is the one that stores -- zhat, o, logits, dl, hb -- and so
+// carries wave 0's whole stretch; it takes no units.  Groups 1 .. R-1 form dl for LDS alone and share
+// the units: group r takes [(r - 1) U / (R - 1), r U / (R - 1)), never empty because R - 1 <= U.  (With
+// an even share for group 0 as well it finished 2.5 K cycles behind the others: phase 1 and wave 0's
+// stretch are what bounds the launch, profiles/r29_head_groups_stamps.txt.)  Nothing here reads what
+// another block of the launch stored -- that is why z and not the stored zhat is read.  Every row of
+// hp is still written exactly once.  R = 1: the one block does all of it.
+
+// units per thread and round trip: with three and four tasks more than one spilled, and with unit
+// groups one is all a thread has up to 128 units per group
+template <int T> struct head_sums_pc { static constexpr int value = T <= 2 ? 3 : 1; };
+
+// the z values of this thread's (unit c0 + 128 q, eight sequences from b0): loads only, nothing waits
+template <int PC>
+__device__ __forceinline__ void head_sums_load(const float* __restrict__ z, int c0, int uhi, int Bs, int b0,
+                                               float (&zv)[PC][8]) {
+#pragma unroll
+    for (int q = 0; q < PC; ++q) {
+        const float4* src = reinterpret_cast<const float4*>(z + (size_t)min(c0 + 128 * q, uhi - 1) * Bs + b0);
+        const float4 v0 = src[0], v1 = src[1];
+        zv[q][0] = v0.x; zv[q][1] = v0.y; zv[q][2] = v0.z; zv[q][3] = v0.w;
+        zv[q][4] = v1.x; zv[q][5] = v1.y; zv[q][6] = v1.z; zv[q][7] = v1.w;
+    }
+}
+
+// zv: the loads of the first trip (c0 = ulo + tid / 8), issued by the caller in front of its barrier
 template <int T>
 __device__ __forceinline__ void head_sums(const head_sums_args& hs, const float (&s)[T], float4* st4,
-                                          const float* wl, const float* zhat, int U, int Bs, int B) {
+                                          const float* wl, const float* __restrict__ z,
+                                          float (&zv)[head_sums_pc<T>::value][8], int U, int ulo, int uhi,
+                                          int Bs, int B) {
     __shared__ float dls[T][64];
     const int tid = threadIdx.x, lane = tid & 63, blk = blockIdx.x;
+    const bool first = blockIdx.y == 0;                // the group that stores dl and hb (block-uniform)
     STAMP(2);
     if (tid < 64) {                                    // wave 0
         const int b = blk * 64 + lane;
@@ -277,29 +309,29 @@ __device__ __forceinline__ void head_sums(const head_sums_args& hs, const float 
             if (b < B) {
                 const float yv = hs.y[b * T + t];
                 d = loss_grad(hs.kind, s[t], yv, invN);
-                lacc += (double)loss_value(hs.kind, s[t], yv);
-                hs.dl[b * T + t] = d;
+                if (first) {
+                    lacc += (double)loss_value(hs.kind, s[t], yv);
+                    hs.dl[b * T + t] = d;
+                }
             }
             dls[t][lane] = d;
-            const double sd = wave_sum_d((double)d);
-            if (lane == 0) hs.hb[blk * (T + 1) + t] = sd;
+            if (first) {
+                const double sd = wave_sum_d((double)d);
+                if (lane == 0) hs.hb[blk * (T + 1) + t] = sd;
+            }
         }
-        const double sl = wave_sum_d(lacc);
-        if (lane == 0) hs.hb[blk * (T + 1) + T] = sl;
+        if (first) {
+            const double sl = wave_sum_d(lacc);
+            if (lane == 0) hs.hb[blk * (T + 1) + T] = sl;
+        }
     }
     __syncthreads();
     STAMP(3);
-    constexpr int PC = T <= 2 ? 3 : 2;                 // units per thread and round trip (three with four tasks spilled)
+    constexpr int PC = head_sums_pc<T>::value;
     const int seg = tid & 7, b0 = blk * 64 + 8 * seg, nb = gridDim.x;
-    for (int c0 = tid >> 3; c0 < U; c0 += 128 * PC) {
-        float zv[PC][8];
-#pragma unroll
-        for (int q = 0; q < PC; ++q) {
-            const float4* src = reinterpret_cast<const float4*>(zhat + (size_t)min(c0 + 128 * q, U - 1) * Bs + b0);
-            const float4 v0 = src[0], v1 = src[1];
-            zv[q][0] = v0.x; zv[q][1] = v0.y; zv[q][2] = v0.z; zv[q][3] = v0.w;
-            zv[q][4] = v1.x; zv[q][5] = v1.y; zv[q][6] = v1.z; zv[q][7] = v1.w;
-        }
+    const int cf = ulo + (tid >> 3);
+    for (int c0 = cf; c0 < uhi; c0 += 128 * PC) {
+        if (c0 != cf) head_sums_load<PC>(z, c0, uhi, Bs, b0, zv);
 #pragma unroll
         for (int q = 0; q < PC; ++q)
 #pragma unroll
@@ -307,19 +339,20 @@ __device__ __forceinline__ void head_sums(const head_sums_args& hs, const float 
         STAMP_AFTER_LOADS(4);
 #pragma unroll
         for (int q = 0; q < PC; ++q) {
-            const int u = c0 + 128 * q, uc = min(u, U - 1);
-            const float4 sv = st4[uc];
+            const int u = c0 + 128 * q;
+            if (u >= uhi) continue;                    // (the eight lanes of a unit agree; whole waves skip)
+            const float4 sv = st4[u];
             float wf[T];
 #pragma unroll
-            for (int t = 0; t < T; ++t) wf[t] = wl[t * U + uc];
+            for (int t = 0; t < T; ++t) wf[t] = wl[t * U + u];
             double s1 = 0, s2 = 0, gw[T];
 #pragma unroll
             for (int t = 0; t < T; ++t) gw[t] = 0;
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                // (a dead sequence's zhat was never stored: whatever the memory holds is masked here.
-                // Its dl is 0, so its finite o and d3 = 0 add nothing: one select per element, not three)
-                const float zh = b0 + i < B ? zv[q][i] : 0.f;
+                // (a dead sequence's z is whatever the memory holds: masked here.  Its dl is 0, so its
+                // finite o and d3 = 0 add nothing: one select per element, not three)
+                const float zh = b0 + i < B ? (zv[q][i] - sv.x) * sv.y : 0.f;
                 const float ov = fmaxf(fmaf(sv.z, zh, sv.w), 0.f);
                 float dob = 0.f;
 #pragma unroll
@@ -339,7 +372,7 @@ __device__ __forceinline__ void head_sums(const head_sums_args& hs, const float 
 #pragma unroll
                 for (int t = 0; t < T; ++t) gw[t] += __shfl_xor(gw[t], off, 64);
             }
-            if (seg == 0 && u < U) {
+            if (seg == 0) {
                 double* dst = hs.hp + ((size_t)u * nb + blk) * (2 + T);
                 dst[0] = s1; dst[1] = s2;
 #pragma unroll
@@ -404,7 +437,9 @@ __global__ __launch_bounds__(1024) void logits_bn_kernel(
         }
     }
     __syncthreads();
-    const bool store = t == 0 && b < B;
+    // (TT > 0: gridDim.y unit groups repeat this phase on the same 64 sequences; group 0 stores)
+    const bool first = TT == 0 || blockIdx.y == 0;
+    const bool store = t == 0 && b < B && first;
     float acc[NT];
 #pragma unroll
     for (int tt = 0; tt < NT; ++tt) acc[tt] = 0.f;
@@ -441,6 +476,20 @@ __global__ __launch_bounds__(1024) void logits_bn_kernel(
             }
         }
     }
+    // head_sums' first trip of z loads depends on nothing here: requested in front of the barrier, with
+    // the registers of the z batch above free again, so that the round trip hides behind the logits' sum
+    // (units [ulo, uhi) of this block: all of them in a grid of one group; otherwise none in group 0 and
+    // an even share of them in each of the other gridDim.y - 1)
+    int ulo = 0, uhi = U;
+    if constexpr (TT > 0) {
+        const int ng = (int)gridDim.y - 1, r = (int)blockIdx.y - 1;
+        if (ng > 0) { ulo = r < 0 ? 0 : r * U / ng; uhi = r < 0 ? 0 : (r + 1) * U / ng; }
+    }
+    float zv[head_sums_pc<NT>::value][8];
+    if constexpr (TT > 0)
+        if (ulo < uhi)                                 // (block-uniform)
+            head_sums_load<head_sums_pc<NT>::value>(z, ulo + ((int)threadIdx.x >> 3), uhi, Bs,
+                                                    (int)blockIdx.x * 64 + 8 * ((int)threadIdx.x & 7), zv);
 #pragma unroll
     for (int tt = 0; tt < NT; ++tt) part[tt][wv][lane] = acc[tt];
     __syncthreads();
@@ -454,12 +503,12 @@ __global__ __launch_bounds__(1024) void logits_bn_kernel(
             float s = bf[t + tt];
 #pragma unroll
             for (int i = 0; i < 16; ++i) s += part[tt][i][lane];
-            logits[(size_t)b * ldl + t + tt] = s;
+            if (first) logits[(size_t)b * ldl + t + tt] = s;
             sum[tt] = s;
         }
     }
     if constexpr (TT > 0) {
-        head_sums<NT>(hs, sum, st4, wl, zhat, U, Bs, B);
+        head_sums<NT>(hs, sum, st4, wl, z, zv, U, ulo, uhi, Bs, B);
         STAMP(5);
     }
 }
@@ -529,8 +578,12 @@ int launch_head_fwd_sums(explainn_ctx* c, const explainn_params* p, int B, float
     const int U = c->U, T = c->T;
     const head_sums_args hs = {y, kind, c->dlogits, c->hp, c->hb};
     const size_t lds = (size_t)U * (sizeof(float4) + T * sizeof(float));
+    // R blocks per sequence block (head_sums; c->head_groups: EXPLAINN_HEAD_GROUPS or the default): 1 is
+    // the grid of one block that does everything; otherwise the storing group and R - 1 unit groups,
+    // never more of those than there are units
+    const int R = min(max(c->head_groups, 1), U + 1);
 #define CALL(TT)                                                                                      \
-    hipLaunchKernelGGL(logits_bn_kernel<TT>, dim3((B + 63) / 64), dim3(1024), lds, s, c->z, c->z12p,   \
+    hipLaunchKernelGGL(logits_bn_kernel<TT>, dim3((B + 63) / 64, R), dim3(1024), lds, s, c->z, c->z12p, \
                        fc_fwd_blocks(B, c->NQ), p->fc2_b, p->bn3_w, p->bn3_b, p->bn3_rm, p->bn3_rv,    \
                        p->bn3_nbt, c->zhat, c->o, c->sig3, p->final_w, p->final_b, logits, U, T, c->Bs, \
                        B, 1, hs)

@@ -78,9 +78,10 @@ static void clear_stamps() {
     CK(hipMemset(p, 0, sizeof(unsigned long long) << 20));
 }
 
-static void report(const char* name, int waves, int nst, float ms) {
+// (first: the first wave of the report -- the waves of unit group r of logits_bn start at r * waves)
+static void report(const char* name, int waves, int nst, float ms, int first = 0) {
     std::vector<unsigned long long> h((size_t)waves * 8);
-    CK(hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(g_stamps), h.size() * 8));
+    CK(hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(g_stamps), h.size() * 8, (size_t)first * 64));
 #ifdef BALANCE
     balance(name, h, waves, nst);
 #endif
@@ -149,6 +150,19 @@ int main() {
             hipLaunchKernelGGL(logits_bn_kernel<1>, dim3((B + 63) / 64), dim3(1024), (size_t)U * 20, 0, z, z12p, 4, fz300, g3one, fz300, hst, hst + U, (int64_t*)nullptr, zhat, o, hst + 2 * U, g3one, fz300, hlog, U, 1, Bs, B, 1, hs);
             CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1)); CK(hipEventElapsedTime(&ms, e0, e1));
             if (rep) report("logits_bn<1>", (B + 63) / 64 * 16, 6, ms);
+            // the same with R blocks per sequence block (EXPLAINN_HEAD_GROUPS): group 0, which stores and
+            // takes no units (it leaves no stamps 4 and 5), apart from the last group, which only sums
+            for (int R = 2; R <= 8; R *= 2) {
+                clear_stamps();
+                CK(hipEventRecord(e0));
+                hipLaunchKernelGGL(logits_bn_kernel<1>, dim3((B + 63) / 64, R), dim3(1024), (size_t)U * 20, 0, z, z12p, 4, fz300, g3one, fz300, hst, hst + U, (int64_t*)nullptr, zhat, o, hst + 2 * U, g3one, fz300, hlog, U, 1, Bs, B, 1, hs);
+                CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1)); CK(hipEventElapsedTime(&ms, e0, e1));
+                char nm[32];
+                snprintf(nm, sizeof nm, "lbn<1> R%d g0", R);
+                if (rep) report(nm, (B + 63) / 64 * 16, 6, ms);
+                snprintf(nm, sizeof nm, "lbn<1> R%d g%d", R, R - 1);
+                if (rep) report(nm, (B + 63) / 64 * 16, 6, ms, (R - 1) * ((B + 63) / 64 * 16));
+            }
             const pa_sums_args ps = {zhat, hdl, dz, g3one, g3one, fz300, g3one, 1, (B + 63) / 64, hp, hb, hout, hout + U, hout + 2 * U, hout + 3 * U, hout + 4 * U, hout + 5 * U};
             clear_stamps();
             CK(hipEventRecord(e0));
