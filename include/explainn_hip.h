@@ -824,6 +824,37 @@ int explainn_pwm_sites(const uint8_t* seq, int64_t seq_len, int64_t start, int64
                        int32_t* score, double* pvalue, int64_t capacity, void* workspace, int64_t workspace_bytes,
                        void* stream);
 
+/* Known-motif enrichment and centrality (csrc/pwmbest.hip, DESIGN.md section 3 item 21, section 8 "Known-motif
+ * enrichment"): explainn_record_best for the score tables of explainn_pwm_sites in place of a model's filters.
+ *
+ * explainn_pwm_record_best: seq, seq_len, rec_offsets and n_records as explainn_record_best takes them (device
+ * base codes; device int64 [n_records + 1]; record r is seq[rec_offsets[r] : rec_offsets[r+1]]); scores, widths, M
+ * and wmax as explainn_pwm_sites takes them (int16 (M,wmax,4), entries in [0, bins]; a width outside [1, wmax]
+ * makes the motif EMPTY).  Codes 0..3 = ACGT; 4 and every byte above it = N.  For motif m of width w, record r
+ * and a start p relative to the record:
+ *     '+' scores  sum_{j<w} scores[m][j][seq[p+j]]
+ *     '-' scores  sum_{j<w} scores[m][j][3 - seq[p+w-1-j]]     (row 2m+1 of explainn_pwm_sites: the reverse
+ *                 complement of the same w bases, reported at the same forward p); not taken when both_strands == 0
+ * A start is live when its w bases lie inside the record and hold no N.
+ *     best_bits[m][r] (uint16) = the largest score over the record's live starts and the requested strands
+ *     best_site[m][r] (int32; may be NULL) = (p << 1) | is_minus of the maximum
+ * Among equal maxima the lowest start wins, and at one start '+' before '-' (explainn_record_best's key: score,
+ * then ~start, then is_plus).  No live start -- a record shorter than w, a record with an N in every window, an
+ * empty motif --: bits 0, site -1.  A record whose offsets descend or leave [0, seq_len], or of 2^30 bases or more,
+ * reads as having no live start for every motif and ORs bit 0 into *flags (device int32, may be NULL; never
+ * cleared here); the check is a compare before any read of seq.  Both outputs are unit-major [M][n_records] and
+ * OVERWRITTEN: the layout explainn_enrichment_test and explainn_site_positions read (a score is at most 8192: a
+ * 15-bit pattern that sorts like the score).  The result is a maximum over integer keys: a function of the
+ * input alone.  EXPLAINN_E_ARG unless seq_len >= 0, 0 <= n_records < 2^31, 0 <= M <= 65535 EXPLAINN_PWM_GROUP and
+ * 1 <= wmax <= EXPLAINN_MOTIF_MAX_WIDTH.  M == 0 or n_records == 0 launches nothing.  No context, no workspace,
+ * no allocation, no host synchronisation.
+ * EXPLAINN_PWM_BEST_SPAN: starts a wavefront takes per pass over its record (tests place their record lengths
+ * around it). */
+#define EXPLAINN_PWM_BEST_SPAN 256
+int explainn_pwm_record_best(const uint8_t* seq, int64_t seq_len, const int64_t* rec_offsets, int64_t n_records,
+                             int both_strands, const int16_t* scores, const int32_t* widths, int M, int wmax,
+                             uint16_t* best_bits, int32_t* best_site, int32_t* flags, void* stream);
+
 /* One Adam step over n_tensors parameter tensors in a single launch -- torch.optim.Adam(params, lr)
  * with its defaults, the optimiser the reference builds (architectures/__init__.py:463-464) and
  * steps at selene/__init__.py:291.  params/grads/exp_avg/exp_avg_sq: HOST arrays of n_tensors

@@ -82,8 +82,10 @@ SITES = [r"^sites_kernel<0>", r"^sites_kernel<1>", r"^sites_scan_tiles_kernel", 
          r"^site_kernel<0>", r"^site_kernel<1>", r"^site_kernel<2>", r"^site_scan_kernel"]
 # known-motif sites (pwmsites.hip): the exact null and the count / emit scan (its two scans are SITES')
 PWMSITES = [r"^pwm_null_kernel", r"^pwm_sites_kernel<0>", r"^pwm_sites_kernel<1>"]
+# known-motif enrichment (pwmbest.hip): the per-record best PWM site
+PWMBEST = [r"^pwm_best_kernel"]
 GATED = (C2_STEP + INPUT_GRAD + ISM + PATHGRAD + METRICS + SCAN + VARIANTS + HAPLOTYPES + SHUFFLE + MOTIFS + ACTNULL +
-         SPACING + ENRICH + CENTRAL + SITES + PWMSITES)
+         SPACING + ENRICH + CENTRAL + SITES + PWMSITES + PWMBEST)
 
 
 # Register cliffs measured in the pipeline: 1024-thread blocks of which TWO must
