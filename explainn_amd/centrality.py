@@ -2,7 +2,7 @@
 
 The question CentriMo of the MEME suite answers for PWMs: a motif that belongs to the assayed factor sits
 where the ChIP-/ATAC-seq signal peaks, a co-factor's or a compositional one does not.  Two device passes
-(csrc/central.hip) behind the best sites of explainn_amd.enrichment:
+(csrc/central.hip) behind the best sites of explainn_amd.records; `pwmenrich` shares centred_records:
 
     pos = site_positions(model, peaks, thresholds)            # where every record's best site sits
     res = centrality(model, peaks, thresholds, control=None)  # or test_positions(pos)
@@ -39,7 +39,9 @@ import argparse
 import numpy as np
 import torch
 
-from .enrichment import (RecordBest, _device_best, _strands, benjamini_hochberg, record_codes, record_labels)
+from .enrichment import _strands, benjamini_hochberg
+from .records import (FilterScorer, RecordBest, best_over_records, pack_site, record_codes, record_labels,
+                      table_order)
 
 COLUMNS = ("Filter", "Threshold", "Sites", "RegionStart", "RegionEnd", "Width", "Center", "Count", "Expected",
            "LogPvalue", "LogPadj", "Evalue", "Qvalue")
@@ -49,6 +51,12 @@ HIST_BYTES = 64 * 1024       # the [T][2][M] int32 histogram of one device call
 _FIELDS = ("best_t", "best_lo", "best_width", "sites", "count", "n_tests", "log_pvalue", "log_padj", "ctrl_sites",
            "ctrl_count", "log_fisher")
 _INT32, _FLOAT = ("best_t", "best_lo", "best_width"), ("log_pvalue", "log_padj", "log_fisher")
+STAT_FORMAT = "%.6g\t%d\t%d\t%d\t%d\t%.1f\t%d\t%.4g\t%.6g\t%.6g\t%.4g\t%.4g"      # COLUMNS from Threshold on
+
+
+def field_dtype(field, ns=np):
+    """The dtype of one of _FIELDS in numpy (or, ns=torch, in torch)."""
+    return ns.int32 if field in _INT32 else ns.float64 if field in _FLOAT else ns.int64
 
 
 def check_thresholds(thresholds, units):
@@ -204,8 +212,7 @@ def test_device(hist, counts, local=False, min_width=1, max_width=None, min_site
         raise ValueError("%d thresholds of %d starts: one test takes at most %d thresholds and %d bytes of "
                          "[T][2][M] counts; test fewer thresholds at once" % (T, M, MAX_THRESHOLDS, HIST_BYTES))
     hi = max(M, lo) if hi is None else hi
-    out = {f: torch.empty(units, device=dev, dtype=torch.int32 if f in _INT32 else
-                          torch.float64 if f in _FLOAT else torch.int64) for f in _FIELDS}
+    out = {f: torch.empty(units, device=dev, dtype=field_dtype(f, torch)) for f in _FIELDS}
     with torch.cuda.device(dev):
         _lib.check(_lib.load().explainn_centrality_test(
             hist.data_ptr(), counts.data_ptr(), units, T, M, 1 if local else 0, lo, hi, need,
@@ -229,10 +236,9 @@ class Centrality:
 
     def __init__(self, best_t, best_lo, best_width, sites, count, n_tests, log_pvalue, log_padj, ctrl_sites, ctrl_count,
                  log_fisher, counts, thresholds, kernel_size, length, local=False, strands="both"):
-        given = dict(zip(_FIELDS, (best_t, best_lo, best_width, sites, count, n_tests, log_pvalue, log_padj,
-                                   ctrl_sites, ctrl_count, log_fisher)))
-        for f, x in given.items():
-            setattr(self, f, np.asarray(x, dtype=np.int32 if f in _INT32 else np.float64 if f in _FLOAT else np.int64))
+        for f, x in zip(_FIELDS, (best_t, best_lo, best_width, sites, count, n_tests, log_pvalue, log_padj,
+                                  ctrl_sites, ctrl_count, log_fisher)):
+            setattr(self, f, np.asarray(x, dtype=field_dtype(f)))
         self.counts = np.asarray(counts, dtype=np.int64)
         self.kernel_size, self.length, self.local, self.strands = int(kernel_size), int(length), bool(local), str(strands)
         units = len(self.best_t)
@@ -269,27 +275,31 @@ class Centrality:
                        bool(z["local"]), str(z["strands"]))
 
 
-def _device_positions(model, records, thresholds, control, strands, chunk_bases, out):
-    """The device half of site_positions: (hist, counts) on the device, thresholds (units, T), k, L."""
-    n_strands = _strands(strands)
+def centred_records(records, control, need):
+    """The front of both centrality paths: (code arrays of the primary records followed by the control's,
+    their labels -- uint8, numpy, records shorter than `need` left out --, the one length L of the others)."""
     _, prim = record_codes(records)
     _, ctrl = record_codes(control) if control is not None else ([], [])
     if not prim:
         raise ValueError("no primary record")
-    k, units = model._options["kernel_size"], model._units()
+    L = common_length([len(c) for c in prim + ctrl], need)
+    return prim + ctrl, record_labels([len(c) for c in prim], [len(c) for c in ctrl], need), L
+
+
+def _device_positions(model, records, thresholds, control, strands, chunk_bases, out):
+    """The device half of site_positions: (hist, counts) on the device, thresholds (units, T), k, L."""
+    scorer = FilterScorer(model, _strands(strands))
+    k, units = scorer.need, scorer.units
+    codes, labels, L = centred_records(records, control, k)
     thr = check_thresholds(thresholds, units)
-    lengths = [len(c) for c in prim + ctrl]
-    L = common_length(lengths, k)
     M = L - k + 1
     if 2 * M * 4 > HIST_BYTES:
         raise ValueError("records of %d starts: the histogram of one threshold must fit %d bytes" % (M, HIST_BYTES))
     if out is not None and (not isinstance(out, SitePositions) or (out.units, out.kernel_size, out.length) != (units, k, L)
                             or not np.array_equal(out.thresholds, thr) or out.strands != strands):
         raise ValueError("out must be a SitePositions of this model, these thresholds, strands and record length")
-    labels = record_labels([len(c) for c in prim], [len(c) for c in ctrl], k)
-    bits, site = _device_best(model, prim + ctrl, n_strands, chunk_bases, True)
-    if model.validate_input:
-        model.check_input()
+    bits, site = best_over_records(scorer, codes, chunk_bases, True)
+    scorer.finish()
     dev = bits.device
     hist = None if out is None else torch.from_numpy(out.hist).to(dev)
     hist, counts = positions_device(bits, site, torch.from_numpy(labels).to(dev), torch.from_numpy(thr).to(dev), M, hist)
@@ -314,12 +324,6 @@ def site_positions(model, records, thresholds, control=None, strands="both", chu
     return out
 
 
-def _best_to_device(best, device):
-    none = best.start < 0
-    site = np.where(none, -1, (best.start.astype(np.int64) << 1) | (best.strand < 0)).astype(np.int32)
-    return torch.from_numpy(best.bits.view(np.int16).copy()).to(device), torch.from_numpy(site).to(device)
-
-
 def positions_from_best(best, thresholds, control_best=None, device="cuda"):
     """site_positions from saved best sites (RecordBest: best_sites(), `enrichment --save-best`) of the primary
     and, optionally, the control records, uploaded once."""
@@ -333,9 +337,9 @@ def positions_from_best(best, thresholds, control_best=None, device="cuda"):
     ctrl_lengths = control_best.lengths if control_best is not None else np.zeros(0, np.int64)
     L = common_length(list(best.lengths) + list(ctrl_lengths), k)
     labels = record_labels(best.lengths, ctrl_lengths, k)
-    parts = [_best_to_device(b, device) for b in ([best] if control_best is None else [best, control_best])]
-    bits = torch.cat([p[0] for p in parts], dim=1).contiguous()
-    site = torch.cat([p[1] for p in parts], dim=1).contiguous()
+    parts = [best] if control_best is None else [best, control_best]
+    bits = torch.from_numpy(np.concatenate([b.bits.view(np.int16) for b in parts], axis=1)).to(device)
+    site = torch.from_numpy(np.concatenate([pack_site(b.start, b.strand) for b in parts], axis=1)).to(device)
     hist, counts = positions_device(bits, site, torch.from_numpy(labels).to(bits.device),
                                     torch.from_numpy(thr).to(bits.device), L - k + 1)
     return SitePositions(hist.cpu().numpy(), counts.cpu().numpy(), thr, k, L)
@@ -370,17 +374,17 @@ def centrality(model, records, thresholds, control=None, local=False, min_width=
     return _result(test_device(hist, counts, local, min_width, max_width, min_sites), counts, thr, k, L, local, strands)
 
 
-def table_rows(result, max_evalue=None, control=None):
+def table_rows(result, max_evalue=None, control=None, lead=None, keep=None):
     """The rows of the CLI's table: (filter, threshold, sites, region_start, region_end, width, center, count,
     expected, log_pvalue, log_padj, evalue, qvalue) and, with control (None: when the result has control
-    records), (ctrl_sites, ctrl_count, log_fisher), of the units with evalue <= max_evalue (None: all), by
-    ascending log_pvalue, ties by filter."""
+    records), (ctrl_sites, ctrl_count, log_fisher), of the units -- of `keep`, if given -- with evalue <=
+    max_evalue (None: all), by ascending log_pvalue, ties by filter.  lead: a function of the unit whose tuple
+    stands in place of (filter,)."""
     control = bool(result.counts[1] > 0) if control is None else bool(control)
-    keep = np.arange(result.units) if max_evalue is None else np.flatnonzero(result.evalue <= max_evalue)
-    order = keep[np.lexsort((keep, result.log_pvalue[keep]))]
+    lead = lead or (lambda u: (int(u),))
     rows = []
-    for u in order:
-        row = (int(u), float(result.threshold[u]), int(result.sites[u]), int(result.region_start[u]),
+    for u in table_order(result, max_evalue, keep):
+        row = lead(u) + (float(result.threshold[u]), int(result.sites[u]), int(result.region_start[u]),
                int(result.region_end[u]), int(result.best_width[u]), float(result.center[u]), int(result.count[u]),
                float(result.expected[u]), float(result.log_pvalue[u]), float(result.log_padj[u]),
                float(result.evalue[u]), float(result.qvalue[u]))
@@ -390,13 +394,14 @@ def table_rows(result, max_evalue=None, control=None):
     return rows
 
 
-def write_table(fh, rows, control=None):
-    control = (bool(rows) and len(rows[0]) > len(COLUMNS)) if control is None else bool(control)
-    fh.write("\t".join(COLUMNS + (CONTROL_COLUMNS if control else ())) + "\n")
+def write_table(fh, rows, control=None, columns=COLUMNS, lead="filter%d"):
+    """The rows as TSV: `lead` formats what table_rows' lead gave, STAT_FORMAT the rest."""
+    control = (bool(rows) and len(rows[0]) > len(columns)) if control is None else bool(control)
+    fh.write("\t".join(columns + (CONTROL_COLUMNS if control else ())) + "\n")
     for row in rows:
-        line = "filter%d\t%.6g\t%d\t%d\t%d\t%d\t%.1f\t%d\t%.4g\t%.6g\t%.6g\t%.4g\t%.4g" % row[:len(COLUMNS)]
+        line = (lead + "\t" + STAT_FORMAT) % row[:len(columns)]
         if control:
-            line += "\t%d\t%d\t%.6g" % row[len(COLUMNS):]
+            line += "\t%d\t%d\t%.6g" % row[len(columns):]
         fh.write(line + "\n")
 
 

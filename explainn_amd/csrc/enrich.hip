@@ -5,10 +5,8 @@
 // float4 [k][5], as in sites_kernel; the records are dealt round robin to the slices.  A record is walked in
 // passes of EXPLAINN_BEST_SPAN starts: the pass's bases (and their complements) are staged in LDS, every
 // lane takes SPAN / 64 starts and runs both strands' chains in one tap loop -- codescan.h's chain and bit
-// pattern.  Every (start, strand) becomes the integer key
-//     bits << 31 | (~start & 0x3FFFFFFF) << 1 | is_plus
-// so the largest key is the largest activation, then the lowest start, then '+': a lane keeps its largest
-// key over the record's passes and one wave max per (record, unit) decides.  No atomics but the input flag.
+// pattern.  Every (start, strand) becomes bestsite.h's integer key: a lane keeps its largest key over the
+// record's passes and one wave max per (record, unit) decides.  No atomics but the input flag.
 //
 // enrich_test_kernel: a workgroup loops over units.  It counts the unit's primary records into a 32768-bin
 // LDS histogram, turns it in place into the tail a_t (a block-wide scan from the top pattern down) and parks
@@ -17,6 +15,7 @@
 // 32-bit integer LDS operations (fewer than 2^31 records); the hypergeometric tail is spacing_test's rule in
 // fp64, one lane per threshold, and the best threshold is a min over (logp, -pattern) pairs: nothing depends
 // on the order in which anything arrives.
+#include "bestsite.h"
 #include "codescan.h"
 #include "tails.h"                             // hypergeom_logsf
 
@@ -25,13 +24,7 @@ namespace {
 constexpr int RB_SPAN = EXPLAINN_BEST_SPAN;
 constexpr int RB_ILP = RB_SPAN / 64;           // starts a lane takes per pass
 constexpr int RB_BLOCKS = 16384;               // the records are cut into slices until a call has about this many blocks
-constexpr long long RB_MAX_LEN = 1ll << 30;    // a record this long has no int32 (start << 1 | strand)
 static_assert(RB_SPAN % 64 == 0 && RB_ILP >= 1, "a pass is a whole number of starts per lane");
-
-__device__ __forceinline__ unsigned long long best_key(unsigned bits, int p, int plus) {
-    return ((unsigned long long)bits << 31) | ((unsigned long long)(~(unsigned)p & 0x3FFFFFFFu) << 1) |
-           (unsigned long long)plus;
-}
 
 // (the second launch bound: the waves per SIMD the two forms run at)
 template <bool BOTH>
@@ -55,8 +48,7 @@ __global__ __launch_bounds__(64, BOTH ? 4 : 8) void record_best_kernel(
     int bad = 0;
     for (long long r = blockIdx.x; r < n_records; r += gridDim.x) {
         const long long a = off[r], b = off[r + 1];
-        // offsets that descend or leave [0, seq_len], or a record too long for the site word: no live start
-        const bool ok = a >= 0 && b >= a && b <= seq_len && b - a < RB_MAX_LEN;
+        const bool ok = BEST_RECORD_OK(a, b, seq_len);
         if (!ok) bad = 1;
         const int len = ok ? (int)(b - a) : 0;
         const int n_starts = len - k + 1;      // <= 0: the record is shorter than the kernel
@@ -102,11 +94,8 @@ __global__ __launch_bounds__(64, BOTH ? 4 : 8) void record_best_kernel(
             const int u = quad * 4 + uu;
             if (lane == 0 && u < U) {
                 const size_t o = (size_t)u * n_records + r;
-                best_bits[o] = (uint16_t)(kk >> 31);
-                if (best_site) {
-                    const unsigned low = (unsigned)kk & 0x7FFFFFFFu;           // ~start << 1 | is_plus
-                    best_site[o] = kk == 0 ? -1 : (int32_t)((((~(low >> 1)) & 0x3FFFFFFFu) << 1) | ((low & 1u) ^ 1u));
-                }
+                best_bits[o] = best_key_bits(kk);
+                if (best_site) best_site[o] = best_key_site(kk);
             }
         }
     }

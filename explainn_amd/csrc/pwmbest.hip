@@ -21,17 +21,16 @@
 // 64 i, and walks them TOGETHER with the two motifs: up to four independent (code read, table read)
 // chains in flight -- the walk is LDS-latency bound otherwise.  A lane's starts ascend, so it keeps
 // (score, site) of the first strictly larger score -- per start the larger strand, '+' on a tie -- and
-// only its final best becomes enrich.hip's key
-//     score << 31 | (~start & 0x3FFFFFFF) << 1 | is_plus
-// for the one wave maximum per (record, motif).  With one pass (records up to SPAN bases) the codes are
-// staged once per record; a longer record restages its passes per motif pair (320 bytes a pass, from
-// L2).  The records are cut into slices until the call has about PB_BLOCKS workgroups: several rounds of
+// only its final best becomes bestsite.h's key for the one wave maximum per (record, motif).  With one
+// pass (records up to SPAN bases) the codes are staged once per record; a longer record restages its
+// passes per motif pair (320 bytes a pass, from L2).  The records are cut into slices until the call has about PB_BLOCKS workgroups: several rounds of
 // the device, so that a last, part-filled round costs little.  No atomics but the input flag; no
 // block-wide barrier after the tables are staged.
 #include <limits.h>
 
 #include <algorithm>
 
+#include "bestsite.h"
 #include "common.h"
 
 namespace {
@@ -42,16 +41,9 @@ constexpr int PB_SPAN = EXPLAINN_PWM_BEST_SPAN;
 constexpr int PB_ILP = PB_SPAN / 64;           // starts a lane takes per pass
 constexpr int PB_G = EXPLAINN_PWM_GROUP;
 constexpr int PB_BLOCKS = 16384;               // the records are cut into slices until a call has about this many blocks
-constexpr long long PB_MAX_LEN = 1ll << 30;    // a record this long has no int32 (start << 1 | strand)
 static_assert(PB_SPAN % 64 == 0 && PB_ILP == 4, "pb_walk is instantiated for one to four starts per lane");
 static_assert(PB_G % 2 == 0, "the motifs of a group are walked in pairs");
 static_assert(EXPLAINN_MOTIF_MAX_WIDTH * EXPLAINN_MOTIF_MAX_BINS < 65536, "two sums share a word without a carry");
-
-// enrich.hip's best_key
-__device__ __forceinline__ unsigned long long pb_key(unsigned bits, int p, int plus) {
-    return ((unsigned long long)bits << 31) | ((unsigned long long)(~(unsigned)p & 0x3FFFFFFFu) << 1) |
-           (unsigned long long)plus;
-}
 
 // the only way a width is read: outside [1, wmax] the motif is empty
 __device__ __forceinline__ int pb_width(const int* __restrict__ widths, int m, int M, int wmax) {
@@ -152,9 +144,7 @@ __global__ __launch_bounds__(PB_T) void pwm_best_kernel(
     int bad = 0;
     for (long long r = (long long)blockIdx.x * PB_WAVES + wave; r < n_records; r += (long long)gridDim.x * PB_WAVES) {
         const long long a = off[r], b = off[r + 1];
-        // offsets that descend or leave [0, seq_len], or a record too long for the site word: no live start.
-        // A compare, before any read of seq.
-        const bool ok = a >= 0 && b >= a && b <= seq_len && b - a < PB_MAX_LEN;
+        const bool ok = BEST_RECORD_OK(a, b, seq_len);            // before any read of seq
         if (!ok) bad = 1;
         const int len = ok ? (int)(b - a) : 0;
         const uint8_t* rec = seq + (ok ? a : 0);
@@ -192,16 +182,13 @@ __global__ __launch_bounds__(PB_T) void pwm_best_kernel(
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 // a live start's key is never 0
-                const unsigned long long mine = bs[i] < 0 ? 0ull : pb_key((unsigned)bs[i], bw[i] >> 1, (bw[i] & 1) ^ 1);
+                const unsigned long long mine = bs[i] < 0 ? 0ull : best_key((unsigned)bs[i], bw[i] >> 1, (bw[i] & 1) ^ 1);
                 const unsigned long long kk = wave_max(mine);
                 const int m = ma + i;
                 if (lane == 0 && m < M) {
                     const size_t o = (size_t)m * n_records + r;
-                    best_bits[o] = (uint16_t)(kk >> 31);
-                    if (best_site) {
-                        const unsigned low = (unsigned)kk & 0x7FFFFFFFu;           // ~start << 1 | is_plus
-                        best_site[o] = kk == 0 ? -1 : (int32_t)((((~(low >> 1)) & 0x3FFFFFFFu) << 1) | ((low & 1u) ^ 1u));
-                    }
+                    best_bits[o] = best_key_bits(kk);
+                    if (best_site) best_site[o] = best_key_site(kk);
                 }
             }
         }

@@ -19,6 +19,8 @@ reported with its multiple-testing correction over the thresholds tried.  Unlike
 filter's own activation, not a PWM log-odds, and a threshold at which the primary set is not enriched is
 given p = 1 without being evaluated.
 
+The host path from records to that matrix is explainn_amd.records, shared with `centrality` and `pwmenrich`.
+
 `python -m explainn_amd.enrichment MODEL PRIMARY.fa [--control C.fa | --shuffles R --seed S] -o OUT.tsv`
 """
 import argparse
@@ -26,12 +28,14 @@ import argparse
 import numpy as np
 import torch
 
+from .records import (CHUNK_BASES, LABEL_CONTROL, LABEL_EXCLUDED, LABEL_PRIMARY, FilterScorer,  # noqa: F401
+                      RecordBest, best_over_records, enrichment_bits, record_chunks, record_codes, record_labels,
+                      table_order)
 from .strands import check_strands
 
-CHUNK_BASES = 1 << 26        # bases per device call of best_sites
 COLUMNS = ("Filter", "Threshold", "TP", "TPpct", "FP", "FPpct", "Enrichment", "LogPvalue", "LogPadj", "Evalue",
            "Qvalue", "AUROC")
-LABEL_PRIMARY, LABEL_CONTROL, LABEL_EXCLUDED = 1, 0, 2
+STAT_FORMAT = "%d\t%.2f\t%d\t%.2f\t%.4g\t%.6g\t%.6g\t%.4g\t%.4g\t%.4f"        # COLUMNS from TP on
 _FIELDS = ("n_thresholds", "best_pattern", "tp", "fp", "log_pvalue", "log_padj", "u2", "auroc")
 
 
@@ -40,109 +44,9 @@ def _strands(strands):
     return 2 if strands == "both" else 1
 
 
-def record_codes(records):
-    """(ids, [1-D uint8 arrays]) of a list of (id, codes) pairs or of code arrays."""
-    ids, codes = [], []
-    for i, rec in enumerate(records):
-        rid, c = rec if isinstance(rec, tuple) else (str(i), rec)
-        c = c.cpu().numpy() if torch.is_tensor(c) else np.asarray(c)
-        if c.dtype != np.uint8 or c.ndim != 1:
-            raise ValueError("record %s: base codes must be a 1-D uint8 array" % (rid,))
-        ids.append(rid)
-        codes.append(c)
-    return ids, codes
-
-
-def record_chunks(lengths, chunk_bases):
-    """[(first record, one past the last), ...]: runs of whole records of at most chunk_bases bases each (a
-    record longer than that is a run of its own)."""
-    chunk_bases = int(chunk_bases)
-    if chunk_bases < 1:
-        raise ValueError("chunk_bases must be at least 1 (got %d)" % chunk_bases)
-    out, first, held = [], 0, 0
-    for i, n in enumerate(lengths):
-        if i > first and held + int(n) > chunk_bases:
-            out.append((first, i))
-            first, held = i, 0
-        held += int(n)
-    if len(lengths) > first:
-        out.append((first, len(lengths)))
-    return out
-
-
-def record_labels(primary_lengths, control_lengths, kernel_size):
-    """uint8 labels of the primary records followed by the control records: 1 / 0, and 2 (left out of the
-    test) for a record shorter than the kernel, which has no site."""
-    lab = np.concatenate([np.full(len(primary_lengths), LABEL_PRIMARY, np.uint8),
-                          np.full(len(control_lengths), LABEL_CONTROL, np.uint8)])
-    short = np.concatenate([np.asarray(primary_lengths, np.int64), np.asarray(control_lengths, np.int64)]) < kernel_size
-    lab[short] = LABEL_EXCLUDED
-    return lab
-
-
-class RecordBest:
-    """The best site of every unit in every record: `score` float16 (units, N), the largest activation over
-    the record's live starts (0 where the record is shorter than the kernel); `start` int32 (units, N), the
-    0-based forward start of the k-mer that holds it (-1 without one) -- the lowest among equal maxima;
-    `strand` int8 (units, N), +1 / -1 ('+' wins a tie at one start; 0 without a site); `lengths` int64 (N,)."""
-
-    def __init__(self, score, start, strand, lengths, kernel_size, ids=None):
-        self.score = np.asarray(score, dtype=np.float16)
-        self.start = np.asarray(start, dtype=np.int32)
-        self.strand = np.asarray(strand, dtype=np.int8)
-        self.lengths = np.asarray(lengths, dtype=np.int64)
-        self.kernel_size = int(kernel_size)
-        self.ids = None if ids is None else [str(i) for i in ids]
-        if self.score.ndim != 2 or self.score.shape != self.start.shape or self.score.shape != self.strand.shape or \
-                self.lengths.shape != (self.score.shape[1],):
-            raise ValueError("score, start and strand must be (units, N) and lengths (N,)")
-
-    @property
-    def bits(self):
-        """uint16 (units, N): the scores' bit patterns, which sort like the scores."""
-        return self.score.view(np.uint16)
-
-    @classmethod
-    def from_device(cls, bits, site, lengths, kernel_size, ids=None):
-        site = np.asarray(site, dtype=np.int32)
-        none = site < 0
-        return cls(np.ascontiguousarray(bits).view(np.float16), np.where(none, -1, site >> 1),
-                   np.where(none, 0, 1 - 2 * (site & 1)), lengths, kernel_size, ids)
-
-    def save(self, path):
-        with open(path, "wb") as fh:
-            np.savez(fh, bits=self.bits, start=self.start, strand=self.strand, lengths=self.lengths,
-                     k=np.int64(self.kernel_size), ids=np.array(self.ids if self.ids is not None else [], dtype=np.str_))
-
-    @classmethod
-    def load(cls, path):
-        with np.load(path) as z:
-            ids = [str(i) for i in z["ids"]] if len(z["ids"]) == len(z["lengths"]) else None
-            return cls(z["bits"].view(np.float16), z["start"], z["strand"], z["lengths"], int(z["k"]), ids)
-
-
-def _device_best(model, codes, strands, chunk_bases, want_site):
-    """(bits int16 -- the patterns are below 0x8000 --, site int32 or None), each (units, len(codes)) on the
-    model's device: the records go over concatenated, in runs of whole records; every run is one
-    explainn_record_best call."""
-    if model.training:
-        raise NotImplementedError("the best sites are an eval-mode export path; call model.eval()")
-    device = model._device()
-    lengths = np.array([len(c) for c in codes], dtype=np.int64)
-    bits = torch.empty((model._units(), len(codes)), device=device, dtype=torch.int16)
-    site = torch.empty((model._units(), len(codes)), device=device, dtype=torch.int32) if want_site else None
-    chunk = CHUNK_BASES if chunk_bases is None else chunk_bases
-    with torch.no_grad(), model.eval_cache():
-        for r0, r1 in record_chunks(lengths, chunk):
-            flat = np.concatenate(codes[r0:r1] + [np.full(1, 4, np.uint8)])      # never an empty tensor
-            off = np.zeros(r1 - r0 + 1, dtype=np.int64)
-            np.cumsum(lengths[r0:r1], out=off[1:])
-            b, s = model._launch_record_best(torch.from_numpy(flat).to(device), torch.from_numpy(off).to(device),
-                                             strands, want_site)
-            bits[:, r0:r1] = b
-            if want_site:
-                site[:, r0:r1] = s
-    return bits, site
+def _device_best(model, codes, n_strands, chunk_bases, want_site):
+    """records.best_over_records for a model's filters, under the name and signature callers know."""
+    return best_over_records(FilterScorer(model, n_strands), codes, chunk_bases, want_site)
 
 
 def best_sites(model, records, strands="both", chunk_bases=None):
@@ -151,13 +55,11 @@ def best_sites(model, records, strands="both", chunk_bases=None):
     any lengths.  strands="both" also takes the filter on the reverse complement of every k-mer.  The records
     go to the device concatenated, in chunks of at most chunk_bases bases (default 2^26) cut at record
     boundaries; the result does not depend on the chunking.  Eval mode only.  Returns a RecordBest."""
-    n_strands = _strands(strands)
+    scorer = FilterScorer(model, _strands(strands))
     ids, codes = record_codes(records)
-    bits, site = _device_best(model, codes, n_strands, chunk_bases, True)
-    if model.validate_input:
-        model.check_input()
-    return RecordBest.from_device(bits.cpu().numpy(), site.cpu().numpy(), [len(c) for c in codes],
-                                  model._options["kernel_size"], ids)
+    bits, site = best_over_records(scorer, codes, chunk_bases, True)
+    scorer.finish()
+    return RecordBest.from_device(bits.cpu().numpy(), site.cpu().numpy(), [len(c) for c in codes], scorer.need, ids)
 
 
 def enrichment_test(bits, labels, want_tails=False):
@@ -250,24 +152,6 @@ class Enrichment:
                        int(z["seed"]))
 
 
-def _shuffled_control(model, codes, shuffles, seed, n_strands, chunk_bases):
-    """Device bits (units, N x shuffles) of `shuffles` dinucleotide-preserving shuffles of every record (all
-    of one length L), drawn on the device chunk by chunk: column r * shuffles + s is shuffle s of record r."""
-    from .sequence import dinucleotide_shuffle_device
-    device = model._device()
-    L = len(codes[0])
-    rows = torch.from_numpy(np.stack(codes))
-    per = max((CHUNK_BASES if chunk_bases is None else int(chunk_bases)) // max(L * shuffles, 1), 1)
-    out = torch.empty((model._units(), len(codes) * shuffles), device=device, dtype=torch.int16)
-    with torch.no_grad(), model.eval_cache():
-        for r0 in range(0, len(codes), per):
-            shuf = dinucleotide_shuffle_device(rows[r0:r0 + per].to(device), shuffles, seed, row0=r0).reshape(-1)
-            n = shuf.numel() // L
-            off = torch.arange(n + 1, device=device, dtype=torch.int64) * L
-            out[:, r0 * shuffles:r0 * shuffles + n] = model._launch_record_best(shuf.contiguous(), off, n_strands, False)[0]
-    return out
-
-
 def enrichment(model, primary, control=None, shuffles=1, seed=0, strands="both", chunk_bases=None):
     """Enrichment of every filter of `model` (an ExplaiNN or an ExplaiNNBank) in the `primary` records against
     the `control` records (lists as best_sites takes them).  control=None: the control set is `shuffles`
@@ -275,55 +159,31 @@ def enrichment(model, primary, control=None, shuffles=1, seed=0, strands="both",
     (sequence.dinucleotide_shuffle_device with `seed`: a pure function of (seed, record, shuffle)); this
     needs primary records of one length (ValueError otherwise).  Records shorter than the kernel are left out
     of the test.  Returns an Enrichment."""
-    n_strands = _strands(strands)
-    _, prim = record_codes(primary)
-    if not prim:
-        raise ValueError("no primary record")
-    k = model._options["kernel_size"]
-    if control is None:
-        if int(shuffles) < 1:
-            raise ValueError("shuffles must be at least 1 without a control set")
-        if len({len(c) for c in prim}) != 1:
-            raise ValueError("a shuffled control needs primary records of one length; pass control= for records "
-                             "of unequal lengths")
-        if len(prim[0]) == 0:
-            raise ValueError("the primary records are empty")
-        ctrl_lengths = np.repeat([len(c) for c in prim], int(shuffles))
-    else:
-        _, ctrl = record_codes(control)
-        ctrl_lengths = [len(c) for c in ctrl]
-        shuffles = 0
-    labels = record_labels([len(c) for c in prim], ctrl_lengths, k)
-    pbits, _ = _device_best(model, prim, n_strands, chunk_bases, False)
-    if control is None:
-        cbits = _shuffled_control(model, prim, int(shuffles), seed, n_strands, chunk_bases)
-    else:
-        cbits, _ = _device_best(model, ctrl, n_strands, chunk_bases, False)
-    if model.validate_input:
-        model.check_input()
-    out = enrichment_test(torch.cat([pbits, cbits], dim=1).contiguous(), torch.from_numpy(labels).to(pbits.device))
-    return Enrichment(*(out[f].cpu().numpy() for f in _FIELDS), out["counts"].cpu().numpy(), k, strands, shuffles, seed)
+    scorer = FilterScorer(model, _strands(strands))
+    bits, labels, shuffles = enrichment_bits(scorer, primary, control, shuffles, seed, chunk_bases)
+    out = enrichment_test(bits, torch.from_numpy(labels).to(bits.device))
+    return Enrichment(*(out[f].cpu().numpy() for f in _FIELDS), out["counts"].cpu().numpy(), scorer.need, strands,
+                      shuffles, seed)
 
 
-def table_rows(result, max_evalue=None):
+def table_rows(result, max_evalue=None, lead=None):
     """The rows of the CLI's table: (filter, threshold, tp, tp %, fp, fp %, enrichment, log_pvalue, log_padj,
     evalue, qvalue, auroc) of the units with evalue <= max_evalue (None: all), by ascending log_pvalue, ties
-    by filter."""
+    by filter.  lead: a function of the unit whose tuple stands in place of (filter, threshold)."""
+    lead = lead or (lambda u: (int(u), float(result.threshold[u])))
     Np, Nc = (float(c) for c in result.counts)
-    keep = np.arange(result.units) if max_evalue is None else np.flatnonzero(result.evalue <= max_evalue)
-    order = keep[np.lexsort((keep, result.log_pvalue[keep]))]
     pct = lambda x, n: 100.0 * float(x) / n if n > 0 else float("nan")
-    return [(int(u), float(result.threshold[u]), int(result.tp[u]), pct(result.tp[u], Np), int(result.fp[u]),
-             pct(result.fp[u], Nc), float(result.enrichment[u]), float(result.log_pvalue[u]),
-             float(result.log_padj[u]), float(result.evalue[u]), float(result.qvalue[u]), float(result.auroc[u]))
-            for u in order]
+    return [lead(u) + (int(result.tp[u]), pct(result.tp[u], Np), int(result.fp[u]), pct(result.fp[u], Nc),
+                       float(result.enrichment[u]), float(result.log_pvalue[u]), float(result.log_padj[u]),
+                       float(result.evalue[u]), float(result.qvalue[u]), float(result.auroc[u]))
+            for u in table_order(result, max_evalue)]
 
 
-def write_table(fh, rows):
-    fh.write("\t".join(COLUMNS) + "\n")
-    for u, thr, tp, tpp, fp, fpp, enr, lp, la, ev, q, auc in rows:
-        fh.write("filter%d\t%.6g\t%d\t%.2f\t%d\t%.2f\t%.4g\t%.6g\t%.6g\t%.4g\t%.4g\t%.4f\n" % (
-            u, thr, tp, tpp, fp, fpp, enr, lp, la, ev, q, auc))
+def write_table(fh, rows, columns=COLUMNS, lead="filter%d\t%.6g"):
+    """The rows as TSV: `lead` formats what table_rows' lead gave, STAT_FORMAT the rest."""
+    fh.write("\t".join(columns) + "\n")
+    for row in rows:
+        fh.write((lead + "\t" + STAT_FORMAT + "\n") % tuple(row))
 
 
 def _parser():

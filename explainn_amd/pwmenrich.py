@@ -4,7 +4,8 @@ centrality for PWMs -- what SEA / AME and CentriMo of the MEME suite answer -- o
 `enrichment` and `centrality` ask these questions of a model's own filters; this module asks them of motifs
 that come from a database (JASPAR, a MEME file, `motifs.write_meme` output), so that a filter's enrichment can
 be set beside that of the motif `motifs.annotate` matched it to.  One device pass is new
-(explainn_pwm_record_best, csrc/pwmbest.hip); the two tests are the existing ones.
+(explainn_pwm_record_best, csrc/pwmbest.hip), wrapped as a MotifScorer; the host path from records to the
+best-site matrix is explainn_amd.records, shared with the filters, and the two tests are the existing ones.
 
     best = best_motif_sites(read_motifs("JASPAR.meme"), peaks)        # per record the best site of every motif
     res = motif_enrichment(motifs, peaks, control)                    # or control=None: dinucleotide shuffles
@@ -29,6 +30,7 @@ every 0 <= t <= 8193.  explainn_enrichment_test takes the raw integers.
 There is no CPU path.
 """
 import argparse
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -37,11 +39,12 @@ import torch
 from . import centrality as _cen
 from . import enrichment as _enr
 from . import pwmsites as _pwm
-from .enrichment import Enrichment, RecordBest, benjamini_hochberg, record_chunks, record_codes, record_labels
+from .enrichment import Enrichment, benjamini_hochberg
+from .records import (LABEL_EXCLUDED, BestSites, RecordBest, best_over_records, enrichment_bits, record_codes,
+                      record_labels, unpack_site)
 
 BRIDGE = 0x400               # added to an integer score: the pattern of the smallest normal float16
-ENRICHMENT_COLUMNS = ("Motif", "Name", "Threshold", "ThresholdPvalue", "TP", "TPpct", "FP", "FPpct", "Enrichment",
-                      "LogPvalue", "LogPadj", "Evalue", "Qvalue", "AUROC")
+ENRICHMENT_COLUMNS = ("Motif", "Name", "Threshold", "ThresholdPvalue") + _enr.COLUMNS[2:]
 CENTRALITY_COLUMNS = ("Motif", "Name") + _cen.COLUMNS[1:]
 _EFIELDS, _CFIELDS = _enr._FIELDS, _cen._FIELDS
 
@@ -88,10 +91,6 @@ class _Tables:
         return np.where(ok, x / np.where(ok, self.scale.reshape(shape), 1.0) + (self.widths * self.lo).reshape(shape), np.nan)
 
 
-def _device(device, what):
-    return _pwm._device_for(device, None, what)
-
-
 def record_best_device(scores, widths, seq, offsets, both=True, want_site=True, flags=None):
     """explainn_pwm_record_best on device tensors: scores int16 (M,wmax,4), widths int32 (M,), seq uint8 (n,),
     offsets int64 (R+1,).  Returns (bits int16 (M,R), site int32 (M,R) or None) on the device; `flags`: an int32
@@ -117,31 +116,25 @@ def record_best_device(scores, widths, seq, offsets, both=True, want_site=True, 
     return bits, site
 
 
-def _device_best(tab, scores, widths, codes, both, chunk_bases, want_site, device):
-    """(bits int16, site int32 or None), each (M, len(codes)) on the device: the records go over concatenated,
-    in runs of whole records; every run is one explainn_pwm_record_best call."""
-    lengths = np.array([len(c) for c in codes], dtype=np.int64)
-    bits = torch.empty((tab.M, len(codes)), device=device, dtype=torch.int16)
-    site = torch.empty((tab.M, len(codes)), device=device, dtype=torch.int32) if want_site else None
-    chunk = _enr.CHUNK_BASES if chunk_bases is None else chunk_bases
-    for r0, r1 in record_chunks(lengths, chunk):
-        flat = np.concatenate(codes[r0:r1] + [np.full(1, 4, np.uint8)])      # never an empty tensor
-        off = np.zeros(r1 - r0 + 1, dtype=np.int64)
-        np.cumsum(lengths[r0:r1], out=off[1:])
-        b, s = record_best_device(scores, widths, torch.from_numpy(flat).to(device), torch.from_numpy(off).to(device),
-                                  both, want_site)
-        bits[:, r0:r1] = b
-        if want_site:
-            site[:, r0:r1] = s
-    return bits, site
+class MotifScorer:
+    """The motifs of a _Tables, uploaded to `device` once, on one or both strands: explainn_pwm_record_best."""
 
+    def __init__(self, tab, both, device):
+        self.both, self.device, self.units, self.need = both, device, tab.M, tab.widest
+        self.scores = torch.from_numpy(tab.S).to(device).contiguous()
+        self.widths = torch.from_numpy(tab.live).to(device)
 
-def _upload(tab, device):
-    return torch.from_numpy(tab.S).to(device).contiguous(), torch.from_numpy(tab.live).to(device)
+    def best(self, seq, offsets, want_site):
+        return record_best_device(self.scores, self.widths, seq, offsets, self.both, want_site)
+
+    span = staticmethod(contextlib.nullcontext)
+
+    def finish(self):
+        pass
 
 
 # ---------------------------------------------------------------- best sites
-class MotifBest:
+class MotifBest(BestSites):
     """The best site of every motif in every record: `iscore` int16 (M, N), the largest integer score over the
     record's live starts (0 without one); `start` int32 (M, N), the 0-based forward start of the w-mer that holds
     it (-1 without one) -- the lowest among equal maxima; `strand` int8 (M, N), +1 / -1 ('+' wins a tie at one
@@ -151,17 +144,11 @@ class MotifBest:
 
     def __init__(self, iscore, start, strand, lengths, widths, names, scale, lo, ids=None):
         self.iscore = np.asarray(iscore, dtype=np.int16)
-        self.start = np.asarray(start, dtype=np.int32)
-        self.strand = np.asarray(strand, dtype=np.int8)
-        self.lengths = np.asarray(lengths, dtype=np.int64)
         self.widths = np.asarray(widths, dtype=np.int32)
         self.names = [str(n) for n in names]
         self.scale, self.lo = np.asarray(scale, dtype=np.float64), np.asarray(lo, dtype=np.float64)
-        self.ids = None if ids is None else [str(i) for i in ids]
         M = len(self.names)
-        if self.iscore.ndim != 2 or self.iscore.shape != self.start.shape or self.iscore.shape != self.strand.shape or \
-                self.iscore.shape[0] != M or self.lengths.shape != (self.iscore.shape[1],):
-            raise ValueError("iscore, start and strand must be (M, N) and lengths (N,)")
+        self._set_sites(self.iscore, start, strand, lengths, ids, ("iscore", "M"), M)
         if self.widths.shape != (M,) or self.scale.shape != (M,) or self.lo.shape != (M,):
             raise ValueError("widths, scale and lo must hold one entry per motif")
 
@@ -186,23 +173,19 @@ class MotifBest:
 
     @classmethod
     def from_device(cls, bits, site, lengths, widths, names, scale, lo, ids=None):
-        site = np.asarray(site, dtype=np.int32)
-        none = site < 0
-        return cls(bits, np.where(none, -1, site >> 1), np.where(none, 0, 1 - 2 * (site & 1)), lengths, widths, names,
-                   scale, lo, ids)
+        return cls(bits, *unpack_site(site), lengths, widths, names, scale, lo, ids)
 
     def save(self, path):
         with open(path, "wb") as fh:
             np.savez(fh, iscore=self.iscore, start=self.start, strand=self.strand, lengths=self.lengths,
                      widths=self.widths, names=np.array(self.names, dtype=np.str_), scale=self.scale, lo=self.lo,
-                     ids=np.array(self.ids if self.ids is not None else [], dtype=np.str_))
+                     ids=self._ids_array())
 
     @classmethod
     def load(cls, path):
         with np.load(path) as z:
-            ids = [str(i) for i in z["ids"]] if len(z["ids"]) == len(z["lengths"]) else None
             return cls(z["iscore"], z["start"], z["strand"], z["lengths"], z["widths"], [str(n) for n in z["names"]],
-                       z["scale"], z["lo"], ids)
+                       z["scale"], z["lo"], cls._ids_of(z))
 
 
 def best_motif_sites(motifs, records, bg=None, pseudocount=0.1, bins=100, strands="both", chunk_bases=None,
@@ -216,9 +199,8 @@ def best_motif_sites(motifs, records, bg=None, pseudocount=0.1, bins=100, strand
     both = _enr._strands(strands) == 2
     tab = _Tables(motifs, bg, pseudocount, bins)
     ids, codes = record_codes(records)
-    device = _device(device, "best_motif_sites")
-    scores, widths = _upload(tab, device)
-    bits, site = _device_best(tab, scores, widths, codes, both, chunk_bases, True, device)
+    scorer = MotifScorer(tab, both, _pwm._device_for(device, None, "best_motif_sites"))
+    bits, site = best_over_records(scorer, codes, chunk_bases, True)
     return MotifBest.from_device(bits.cpu().numpy(), site.cpu().numpy(), [len(c) for c in codes], tab.widths, tab.ids,
                                  tab.scale, tab.lo, ids)
 
@@ -260,22 +242,6 @@ class MotifEnrichment(Enrichment):
                        int(z["k"]), str(z["strands"]), int(z["shuffles"]), int(z["seed"]))
 
 
-def _shuffled_control(tab, scores, widths, codes, shuffles, seed, both, chunk_bases, device):
-    """Device bits (M, N x shuffles) of `shuffles` dinucleotide-preserving shuffles of every record (all of one
-    length L), drawn on the device chunk by chunk: column r * shuffles + s is shuffle s of record r."""
-    from .sequence import dinucleotide_shuffle_device
-    L = len(codes[0])
-    rows = torch.from_numpy(np.stack(codes))
-    per = max((_enr.CHUNK_BASES if chunk_bases is None else int(chunk_bases)) // max(L * shuffles, 1), 1)
-    out = torch.empty((tab.M, len(codes) * shuffles), device=device, dtype=torch.int16)
-    for r0 in range(0, len(codes), per):
-        shuf = dinucleotide_shuffle_device(rows[r0:r0 + per].to(device), shuffles, seed, row0=r0).reshape(-1)
-        n = shuf.numel() // L
-        off = torch.arange(n + 1, device=device, dtype=torch.int64) * L
-        out[:, r0 * shuffles:r0 * shuffles + n] = record_best_device(scores, widths, shuf.contiguous(), off, both, False)[0]
-    return out
-
-
 def motif_enrichment(motifs, primary, control=None, shuffles=1, seed=0, bg=None, pseudocount=0.1, bins=100,
                      strands="both", chunk_bases=None, device=None):
     """Enrichment of every motif in the `primary` records against the `control` records (lists as
@@ -287,39 +253,17 @@ def motif_enrichment(motifs, primary, control=None, shuffles=1, seed=0, bg=None,
     the call; `excluded` counts them).  Returns a MotifEnrichment."""
     both = _enr._strands(strands) == 2
     tab = _Tables(motifs, bg, pseudocount, bins)
-    _, prim = record_codes(primary)
-    if not prim:
-        raise ValueError("no primary record")
-    if control is None:
-        if int(shuffles) < 1:
-            raise ValueError("shuffles must be at least 1 without a control set")
-        if len({len(c) for c in prim}) != 1:
-            raise ValueError("a shuffled control needs primary records of one length; pass control= for records "
-                             "of unequal lengths")
-        if len(prim[0]) == 0:
-            raise ValueError("the primary records are empty")
-        ctrl_lengths = np.repeat([len(c) for c in prim], int(shuffles))
-    else:
-        _, ctrl = record_codes(control)
-        ctrl_lengths = [len(c) for c in ctrl]
-        shuffles = 0
-    device = _device(device, "motif_enrichment")
-    labels = record_labels([len(c) for c in prim], ctrl_lengths, tab.widest)
-    scores, widths = _upload(tab, device)
-    pbits, _ = _device_best(tab, scores, widths, prim, both, chunk_bases, False, device)
-    if control is None:
-        cbits = _shuffled_control(tab, scores, widths, prim, int(shuffles), seed, both, chunk_bases, device)
-    else:
-        cbits, _ = _device_best(tab, scores, widths, ctrl, both, chunk_bases, False, device)
-    out = _enr.enrichment_test(torch.cat([pbits, cbits], dim=1).contiguous(), torch.from_numpy(labels).to(device))
+    scorer = MotifScorer(tab, both, _pwm._device_for(device, None, "motif_enrichment"))
+    bits, labels, shuffles = enrichment_bits(scorer, primary, control, shuffles, seed, chunk_bases)
+    out = _enr.enrichment_test(bits, torch.from_numpy(labels).to(scorer.device))
     if tab.M:
-        null = _pwm._null(tab.S, tab.live, tab.scale, tab.lo, tab.bins, tab.bg, 1.0, device)
+        null = _pwm._null(tab.S, tab.live, tab.scale, tab.lo, tab.bins, tab.bg, 1.0, scorer.device)
         at = out["best_pattern"].to(torch.int64).clamp_(0, null.tail.shape[1] - 1)
         tpv = null.tail.gather(1, at[:, None])[:, 0].cpu().numpy()          # on the device: bit-equal to the table
     else:
         tpv = np.zeros(0)
     return enrichment_result([out[f].cpu().numpy() for f in _EFIELDS], out["counts"].cpu().numpy(), tab, tpv,
-                             int(np.sum(labels == _enr.LABEL_EXCLUDED)), strands, shuffles, seed)
+                             int(np.sum(labels == LABEL_EXCLUDED)), strands, shuffles, seed)
 
 
 def enrichment_result(fields, counts, tab, threshold_pvalue, excluded, strands="both", shuffles=0, seed=0):
@@ -335,20 +279,12 @@ def enrichment_rows(result, max_evalue=None):
     """The rows of the CLI's table: (id, name, threshold, threshold_pvalue, tp, tp %, fp, fp %, enrichment,
     log_pvalue, log_padj, evalue, qvalue, auroc) of the motifs with evalue <= max_evalue (None: all), by ascending
     log_pvalue, ties by motif order."""
-    Np, Nc = (float(c) for c in result.counts)
-    keep = np.arange(result.units) if max_evalue is None else np.flatnonzero(result.evalue <= max_evalue)
-    order = keep[np.lexsort((keep, result.log_pvalue[keep]))]
-    pct = lambda x, n: 100.0 * float(x) / n if n > 0 else float("nan")
-    return [(result.ids[u], result.names[u], float(result.threshold[u]), float(result.threshold_pvalue[u]),
-             int(result.tp[u]), pct(result.tp[u], Np), int(result.fp[u]), pct(result.fp[u], Nc),
-             float(result.enrichment[u]), float(result.log_pvalue[u]), float(result.log_padj[u]),
-             float(result.evalue[u]), float(result.qvalue[u]), float(result.auroc[u])) for u in order]
+    return _enr.table_rows(result, max_evalue, lambda u: (result.ids[u], result.names[u], float(result.threshold[u]),
+                                                          float(result.threshold_pvalue[u])))
 
 
 def write_enrichment_table(fh, rows):
-    fh.write("\t".join(ENRICHMENT_COLUMNS) + "\n")
-    for row in rows:
-        fh.write("%s\t%s\t%.6g\t%.4g\t%d\t%.2f\t%d\t%.2f\t%.4g\t%.6g\t%.6g\t%.4g\t%.4g\t%.4f\n" % row)
+    _enr.write_table(fh, rows, ENRICHMENT_COLUMNS, "%s\t%s\t%.6g\t%.4g")
 
 
 # ---------------------------------------------------------------- filters and motifs in one table
@@ -371,7 +307,7 @@ def filters_and_motifs(filter_primary, motif_primary, filter_control, motif_cont
     mp = motif_primary
     need = max([filter_primary.kernel_size] + [int(w) for w in mp.live_widths])
     labels = record_labels(filter_primary.lengths, filter_control.lengths, need)
-    device = _device(device, "filters_and_motifs")
+    device = _pwm._device_for(device, None, "filters_and_motifs")
     bits = torch.from_numpy(np.ascontiguousarray(np.concatenate(sets, axis=1)).view(np.int16)).to(device)
     out = _enr.enrichment_test(bits, torch.from_numpy(labels).to(device))
     res = Enrichment(*(out[f].cpu().numpy() for f in _EFIELDS), out["counts"].cpu().numpy(), need)
@@ -404,8 +340,7 @@ class MotifCentrality:
 
     def __init__(self, fields, counts, pvalues, iscore_thresholds, tab, length, excluded=0, local=False, strands="both"):
         for f, x in zip(_CFIELDS, fields):
-            setattr(self, f, np.asarray(x, dtype=np.int32 if f in _cen._INT32 else np.float64 if f in _cen._FLOAT
-                                        else np.int64))
+            setattr(self, f, np.asarray(x, dtype=_cen.field_dtype(f)))
         M = len(tab.ids)
         self.counts = np.asarray(counts, dtype=np.int64)
         self.pvalues = np.asarray(pvalues, dtype=np.float64).reshape(-1)
@@ -458,24 +393,18 @@ def motif_centrality(motifs, records, pvalues=(1e-4,), control=None, local=False
     both = _enr._strands(strands) == 2
     pv = _check_pvalues(pvalues)
     tab = _Tables(motifs, bg, pseudocount, bins)
-    _, prim = record_codes(records)
-    _, ctrl = record_codes(control) if control is not None else ([], [])
-    if not prim:
-        raise ValueError("no primary record")
     if tab.widest == 0:
         raise ValueError("no motif is live (every motif is empty)")
-    L = _cen.common_length([len(c) for c in prim + ctrl], tab.widest)
-    device = _device(device, "motif_centrality")
-    labels_np = record_labels([len(c) for c in prim], [len(c) for c in ctrl], tab.widest)
+    codes, labels_np, L = _cen.centred_records(records, control, tab.widest)
+    device = _pwm._device_for(device, None, "motif_centrality")
     labels = torch.from_numpy(labels_np).to(device)
-    scores, widths = _upload(tab, device)
+    scorer = MotifScorer(tab, both, device)
     thr = np.stack([_pwm._null(tab.S, tab.live, tab.scale, tab.lo, tab.bins, tab.bg, p, device).thresholds.cpu().numpy()
                     for p in pv], axis=1).astype(np.int32)                               # (M, T)
-    bits, site = _device_best(tab, scores, widths, prim + ctrl, both, chunk_bases, True, device)
+    bits, site = best_over_records(scorer, codes, chunk_bases, True)
     pattern = bits + BRIDGE                                                              # normal halves, on the device
     fthr = torch.from_numpy(bridge_thresholds(thr)).to(device)
-    full = {f: torch.zeros(tab.M, device=device, dtype=torch.int32 if f in _cen._INT32 else
-                           torch.float64 if f in _cen._FLOAT else torch.int64) for f in _CFIELDS}
+    full = {f: torch.zeros(tab.M, device=device, dtype=_cen.field_dtype(f, torch)) for f in _CFIELDS}
     counts = torch.from_numpy(np.array([np.sum(labels_np == 1), np.sum(labels_np == 0)], dtype=np.int64)).to(device)
     for w, idx in width_groups(tab.live):
         sel = torch.from_numpy(idx).to(device)
@@ -485,52 +414,21 @@ def motif_centrality(motifs, records, pvalues=(1e-4,), control=None, local=False
         for f in _CFIELDS:
             full[f][sel] = out[f]
     return MotifCentrality([full[f].cpu().numpy() for f in _CFIELDS], counts.cpu().numpy(), pv, thr, tab, L,
-                           int(np.sum(labels_np == _enr.LABEL_EXCLUDED)), local, strands)
+                           int(np.sum(labels_np == LABEL_EXCLUDED)), local, strands)
 
 
 def centrality_rows(result, max_evalue=None, control=None):
     """The rows of the CLI's table: (id, name) and centrality.table_rows' columns after the filter, of the LIVE
     motifs with evalue <= max_evalue (None: all), by ascending log_pvalue, ties by motif order."""
-    control = bool(result.counts[1] > 0) if control is None else bool(control)
-    keep = np.flatnonzero(result.live_widths > 0)
-    if max_evalue is not None:
-        keep = keep[result.evalue[keep] <= max_evalue]
-    order = keep[np.lexsort((keep, result.log_pvalue[keep]))]
-    rows = []
-    for u in order:
-        row = (result.ids[u], result.names[u], float(result.threshold[u]), int(result.sites[u]),
-               int(result.region_start[u]), int(result.region_end[u]), int(result.best_width[u]),
-               float(result.center[u]), int(result.count[u]), float(result.expected[u]), float(result.log_pvalue[u]),
-               float(result.log_padj[u]), float(result.evalue[u]), float(result.qvalue[u]))
-        if control:
-            row += (int(result.ctrl_sites[u]), int(result.ctrl_count[u]), float(result.log_fisher[u]))
-        rows.append(row)
-    return rows
+    return _cen.table_rows(result, max_evalue, control, lambda u: (result.ids[u], result.names[u]),
+                           np.flatnonzero(result.live_widths > 0))
 
 
 def write_centrality_table(fh, rows, control=None):
-    control = (bool(rows) and len(rows[0]) > len(CENTRALITY_COLUMNS)) if control is None else bool(control)
-    fh.write("\t".join(CENTRALITY_COLUMNS + (_cen.CONTROL_COLUMNS if control else ())) + "\n")
-    for row in rows:
-        line = "%s\t%s\t%.6g\t%d\t%d\t%d\t%d\t%.1f\t%d\t%.4g\t%.6g\t%.6g\t%.4g\t%.4g" % row[:len(CENTRALITY_COLUMNS)]
-        if control:
-            line += "\t%d\t%d\t%.6g" % row[len(CENTRALITY_COLUMNS):]
-        fh.write(line + "\n")
+    _cen.write_table(fh, rows, control, CENTRALITY_COLUMNS, "%s\t%s")
 
 
 # ---------------------------------------------------------------- command line
-def _bg_arg(text):
-    if text == "uniform":
-        return None
-    try:
-        vals = [float(v) for v in text.split(",")]
-    except ValueError:
-        vals = []
-    if len(vals) != 4:
-        raise argparse.ArgumentTypeError("--bg takes uniform or four frequencies a,c,g,t")
-    return vals
-
-
 def _parser():
     ap = argparse.ArgumentParser(prog="python -m explainn_amd.pwmenrich", description=main.__doc__)
     sub = ap.add_subparsers(dest="command", required=True)
@@ -540,7 +438,8 @@ def _parser():
         p.add_argument("fasta_file", help="the primary records / the summit-centred peaks")
         p.add_argument("-o", "--output-file", required=True)
         p.add_argument("--control", help="control FASTA")
-        p.add_argument("--bg", type=_bg_arg, default=None, help="uniform (default) or a,c,g,t")
+        p.add_argument("--bg", type=lambda text: _pwm._bg_arg(text, sequence=False), default=None,
+                       help="uniform (default) or a,c,g,t")
         p.add_argument("--pseudocount", type=float, default=0.1)
         p.add_argument("--bins", type=int, default=100)
         p.add_argument("--strands", choices=("both", "fwd"), default="both")

@@ -305,15 +305,19 @@ def bed_rows(seq_id, calls):
         "+" if calls.strand[i] > 0 else "-", calls.pvalue[i]) for i in order]
 
 
-def _bg_arg(text):
-    if text in ("uniform", "sequence"):
-        return None if text == "uniform" else text
+def _bg_arg(text, sequence=True):
+    """--bg: None for uniform, four frequencies, or -- where `sequence` says the tool takes it -- "sequence"."""
+    if text == "uniform":
+        return None
+    if sequence and text == "sequence":
+        return text
     try:
         vals = [float(v) for v in text.split(",")]
     except ValueError:
         vals = []
     if len(vals) != 4:
-        raise argparse.ArgumentTypeError("--bg takes uniform, sequence or four frequencies a,c,g,t")
+        raise argparse.ArgumentTypeError(
+            "--bg takes uniform%s or four frequencies a,c,g,t" % (", sequence" if sequence else ""))
     return vals
 
 
