@@ -630,23 +630,36 @@ __device__ __forceinline__ void fin_unit(const fin_args& f, const float* __restr
 typedef __attribute__((ext_vector_type(8))) __bf16 cb_bf16x8;
 typedef uint32_t cb_u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned short cb_u16x2 __attribute__((ext_vector_type(2)));
+typedef short cb_s16x2 __attribute__((ext_vector_type(2)));
 #define CBM_CHUNK 14                  // pooling windows per LDS image of the expanded masks (even: parity)
 #define CBM_WAVES 4                   // wavefronts per workgroup (one per SIMD): they take the windows of a chunk in turn
 #ifndef CBM_PF
 #define CBM_PF 1                      // windows of dy / idx a wave keeps in flight (2 and 3 measured slower)
 #endif
+// the sign of each 16-bit half over the whole half (the left shift that brings a bit there is made on
+// UNSIGNED halves: on signed ones it may not overflow, and the compiler folds `x << 15 >> 15` to x)
+__device__ __forceinline__ uint32_t cbm_spread(uint32_t x) {
+    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(cb_s16x2, x) >> 15);
+}
 __host__ __device__ constexpr int cbm_tiles(int K) { return (K + 3) / 4; }   // 16-column tiles = 4 taps x 4 bases
-// waves per SIMD the register budget is held to: accumulators and B fragments grow with the tile count
-__host__ __device__ constexpr int cbm_occ(int K) { return cbm_tiles(K) <= 5 ? 4 : (cbm_tiles(K) <= 6 ? 3 : 2); }
+// waves per SIMD the register budget is held to: accumulators and B fragments grow with the tile count.
+// Up to five tiles (k <= 20) that is FIVE: 96 registers (512 / 5 in allocation units of 8), so that with
+// four-wave workgroups five are resident per CU and the C2 grid (1216 on 256 CUs) starts in one round.
+__host__ __device__ constexpr int cbm_occ(int K) { return cbm_tiles(K) <= 5 ? 5 : (cbm_tiles(K) <= 6 ? 3 : 2); }
 
 // Geometry: workgroup = (block of 32 sequences, tile of 16 units, half of the pooling windows), four
-// wavefronts = one per SIMD, so a CU's SIMDs always hold equal shares.  At C2 that is 1216 workgroups
-// of 28 KB of LDS; the kernel is held to 128 registers so that four are resident per CU (4 waves per
-// SIMD) and the dispatcher hands the remaining ones to whichever CU finishes first.  What the stamps
-// showed about the alternatives (tools/stampbench, profiles/r03): the main loop saturates the matrix
-// pipe, so the time is set by the SIMD with the most waves -- 608 four-wave workgroups over all
-// windows (three per CU at 51 KB) and 1216 two-wave ones (2-3 waves per SIMD) both left SIMDs with
-// 3 x 10.9 K cycles of MFMA work where the average is 2.4 x.
+// wavefronts = one per SIMD, so a CU's SIMDs always hold equal shares (the dispatcher starts each
+// workgroup on the next SIMD, so the wavefronts with the extra window do not pile up on one:
+// profiles/r31_cbm_balance.txt).  At C2 that is 1216 workgroups of 28 KB of LDS; the kernel is held to
+// 96 registers so that five are resident per CU (5 waves per SIMD) and every workgroup starts at once.
+// At 128 registers four were resident, and the other 192 workgroups waited for a first-round one to
+// end and then paid mask expansion, main loop and reduction again on a fifth of the chip, at one wave
+// per SIMD.  What fits the main loop into 96 registers: see boff0 / boffl, live4, lo, te and the
+// place of the prefetch below -- none of them changes a sum.  What the stamps showed about the
+// alternatives (tools/stampbench, profiles/r03): the main loop saturates the matrix pipe, so the time is
+// set by the SIMD with the most waves -- 608 four-wave workgroups over all windows (three per CU at
+// 51 KB) and 1216 two-wave ones (2-3 waves per SIMD) both left SIMDs with 3 x 10.9 K cycles of MFMA
+// work where the average is 2.4 x.
 template <int K>
 __global__ __launch_bounds__(64 * CBM_WAVES, cbm_occ(K)) void conv_bwd_mm_kernel(
     const float* __restrict__ dy, const uint8_t* __restrict__ idx,
@@ -655,34 +668,38 @@ __global__ __launch_bounds__(64 * CBM_WAVES, cbm_occ(K)) void conv_bwd_mm_kernel
     constexpr int K4 = 4 * K, NTL = cbm_tiles(K), NTH = 64 * CBM_WAVES;
     extern __shared__ __attribute__((aligned(16))) unsigned char cbsm[];
     cb_u32x4* X = reinterpret_cast<cb_u32x4*>(cbsm);           // [positions][4 bases][4 slots] x 16 bytes
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 15, g = lane >> 4;
+    const int tid = threadIdx.x, lane = tid & 63, c = lane & 15, g = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // (scalar: window index and LDS base stay in SGPRs)
     const int b0 = blockIdx.x * 32, u0 = blockIdx.y * 16;
     const int wlo = blockIdx.z * wper, whi = min(n, wlo + wper);   // this workgroup's windows
     const int tile64 = b0 >> 6, half = (b0 >> 5) & 1;
     const int ua = min(u0 + c, U - 1);                          // the unit this lane feeds as an A row
     // sequences past the batch: their idx bytes are forced to 7, which no position matches
-    uint32_t dead0 = 0u, dead1 = 0u;
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-        if (b0 + 8 * g + j >= B) { if (j < 4) dead0 |= 7u << (8 * j); else dead1 |= 7u << (8 * (j - 4)); }
+    // (kept as one register: four times the number of this lane's sequences inside the batch, 0..32; the
+    // two mask words are 0x07 in every byte from that sequence on -- the shift is made in two halves
+    // because a 64-bit shift by 64 is a shift by 0)
+    const uint32_t live4 = 4u * (uint32_t)min(max(B - (b0 + 8 * g), 0), 8);
     // Column order inside the matrix-core tiles: n = 4 j + a (tap-major), so the 16 columns of tile t
     // are taps 4t .. 4t+3 x the four bases.  X holds one 256-byte row per position q, [base][slot]
     // with slot = g ^ 2 (q & 1): with that swizzle the 16 lanes of every ds_read_b128 lane group hit
     // 16 distinct 16-byte bank slots whatever q is (searched exhaustively; the plain [a][q][g]
     // image was 2.6-way conflicted).  Byte offset of this lane's fragment for column tile t at an
     // EVEN relative position; an odd one flips bit 5 (slot ^ 2).
+    // Tile t sits 1024 t bytes behind tile 0 (four taps on: the parity of j, hence the swizzle, is the
+    // same), which the LDS read takes as an immediate; only the last tile's taps past the filter, which
+    // read the last tap instead, need an offset of their own.
     const int ca = c & 3;
-    uint32_t boff[NTL];
-#pragma unroll
-    for (int t = 0; t < NTL; ++t) {
+    const auto cbm_boff = [&](int t) {
         const int j = min(4 * t + (c >> 2), K - 1);
-        boff[t] = (uint32_t)(j * 256 + ca * 64 + ((g ^ ((j & 1) << 1)) * 16));
-    }
+        return (uint32_t)(j * 256 + ca * 64 + ((g ^ ((j & 1) << 1)) * 16));
+    };
+    const uint32_t boff0 = cbm_boff(0), boffl = cbm_boff(NTL - 1) - (uint32_t)(1024 * (NTL - 1));
     f32x4b acc[NTL];
 #pragma unroll
     for (int t = 0; t < NTL; ++t) acc[t] = f32x4b{0.f, 0.f, 0.f, 0.f};
-    const float* __restrict__ dyu = dy + (size_t)ua * n * Bs + b0 + 8 * g;
-    const uint8_t* __restrict__ ixu = idx + (size_t)ua * n * Bs + b0 + 8 * g;
+    // this lane's 8 sequences of unit ua: one element offset serves dy and idx; the window's row is
+    // added to the (scalar) array base
+    const size_t lo = (size_t)ua * n * Bs + b0 + 8 * g;
     typedef __attribute__((address_space(3))) cb_u32x4 lds_u32x4;
     typedef __attribute__((address_space(3))) unsigned char lds_uchar;
     const uint32_t xlds = (uint32_t)(size_t)(const lds_uchar*)cbsm;
@@ -695,36 +712,55 @@ __global__ __launch_bounds__(64 * CBM_WAVES, cbm_occ(K)) void conv_bwd_mm_kernel
         int w = wc + wave;
         float4 qd0[CBM_PF], qd1[CBM_PF];
         uint2 qiw[CBM_PF];
+        size_t lc = lo;
+        asm volatile("" : "+v"(lc));                            // (addresses formed here, as te below)
 #pragma unroll
         for (int f = 0; f < CBM_PF; ++f) {
             const int wf = min(w + f * CBM_WAVES, wc + nwin - 1);
-            qd0[f] = *reinterpret_cast<const float4*>(dyu + (size_t)wf * Bs);
-            qd1[f] = *reinterpret_cast<const float4*>(dyu + (size_t)wf * Bs + 4);
-            qiw[f] = *reinterpret_cast<const uint2*>(ixu + (size_t)wf * Bs);
+            size_t row = (size_t)wf * Bs;
+            asm volatile("" : "+s"(row));                       // (one scalar product for both arrays)
+            const float* dyw = dy + row;
+            const uint8_t* ixw = idx + row;
+            qd0[f] = *reinterpret_cast<const float4*>(dyw + lc);
+            qd1[f] = *reinterpret_cast<const float4*>(dyw + lc + 4);
+            qiw[f] = *reinterpret_cast<const uint2*>(ixw + lc);
         }
         __syncthreads();                                        // the previous chunk's X is dead
         // (every mask word of this thread is requested before the first is expanded: one load per
         // loop turn exposed a memory round trip each, 8 K of the kernel's 43 K cycles per wave)
         constexpr int XIT = (4 * (POOLW * CBM_CHUNK + K - 1) + NTH - 1) / NTH;
+        // (te: the thread index as a value the compiler cannot trace back, so that the element numbers and
+        // store addresses of the expansion are formed here and die with it, instead of riding through
+        // the main loop in registers it has no room for)
+        int te = tid;
+        asm volatile("" : "+v"(te));
+        // mask word of (base a, position q): bm[(a * NT64 + tile64) * Lp + q], the scalar part first
+        const unsigned long long* __restrict__ bmt = bm + (size_t)tile64 * Lp + q0;
+        const size_t plane = (size_t)NT64 * Lp;
         unsigned long long mw[XIT];
 #pragma unroll
         for (int it = 0; it < XIT; ++it) {
-            const int e = min(tid + it * NTH, 4 * nq - 1);
-            mw[it] = bm[((size_t)(e & 3) * NT64 + tile64) * Lp + q0 + (e >> 2)];
+            const int e = min(te + it * NTH, 4 * nq - 1);
+            mw[it] = bmt[(size_t)(e & 3) * plane + (e >> 2)];
         }
 #pragma unroll
         for (int it = 0; it < XIT; ++it) {
-            const int e = tid + it * NTH;
+            const int e = te + it * NTH;
             if (e < 4 * nq) {
                 const int q = e >> 2, a = e & 3;                 // (position, base): 64 contiguous bytes each
                 const uint32_t bits32 = half ? (uint32_t)(mw[it] >> 32) : (uint32_t)mw[it];
+                // 16 sequences and, OR-ed in, the same 15 bits up (a sum would carry where the copies meet,
+                // at bit 15): sequence 2p sits at bit 2p and sequence 2p + 1 at bit 16 + 2p, so a shift by 2p
+                // and one AND leave the pair as the low bits of the two halves, and 0x10001 x 0x3f80 =
+                // 1.0 | 1.0 (three instructions per pair of bf16, not four)
+                const uint32_t s0 = bits32 & 0xffffu, s1 = bits32 >> 16;
+                const uint32_t sp[2] = {s0 | (s0 << 15), s1 | (s1 << 15)};
 #pragma unroll
                 for (int gg = 0; gg < 4; ++gg) {
-                    const uint32_t by = (bits32 >> (8 * gg)) & 0xffu;
                     cb_u32x4 v;
 #pragma unroll
                     for (int d = 0; d < 4; ++d)
-                        v[d] = ((by >> (2 * d)) & 1u) * 0x00003f80u + ((by >> (2 * d + 1)) & 1u) * 0x3f800000u;
+                        v[d] = (uint32_t)__umul24((sp[gg >> 1] >> (8 * (gg & 1) + 2 * d)) & 0x00010001u, 0x3f80u);
                     X[(q * 4 + a) * 4 + (gg ^ ((q & 1) << 1))] = v;
                 }
             }
@@ -756,24 +792,21 @@ __global__ __launch_bounds__(64 * CBM_WAVES, cbm_occ(K)) void conv_bwd_mm_kernel
             }
             // one-hot of the argmax offset per sequence, as 16-bit pairs in the order of the packed
             // pieces: bit r of a half says "this sequence's gradient sits at position 7w + r"
-            const uint32_t i0 = iw.x | dead0, i1 = iw.y | dead1;
+            uint32_t l4 = live4;
+            asm volatile("" : "+v"(l4));                        // (formed per window, as te below)
+            const unsigned long long dead = (0x0707070707070707ull << l4) << l4;
+            const uint32_t i0 = iw.x | (uint32_t)dead, i1 = iw.y | (uint32_t)(dead >> 32);
             uint32_t ip[4];
             ip[0] = (1u << (i0 & 0xffu)) | (0x10000u << ((i0 >> 8) & 0xffu));
             ip[1] = (1u << ((i0 >> 16) & 0xffu)) | (0x10000u << (i0 >> 24));
             ip[2] = (1u << (i1 & 0xffu)) | (0x10000u << ((i1 >> 8) & 0xffu));
             ip[3] = (1u << ((i1 >> 16) & 0xffu)) | (0x10000u << (i1 >> 24));
-            // the queue moves up one and the window CBM_PF turns ahead is requested
-#pragma unroll
-            for (int f = 0; f + 1 < CBM_PF; ++f) { qd0[f] = qd0[f + 1]; qd1[f] = qd1[f + 1]; qiw[f] = qiw[f + 1]; }
-            {
-                const int wn = min(w + CBM_PF * CBM_WAVES, wc + nwin - 1);
-                qd0[CBM_PF - 1] = *reinterpret_cast<const float4*>(dyu + (size_t)wn * Bs);
-                qd1[CBM_PF - 1] = *reinterpret_cast<const float4*>(dyu + (size_t)wn * Bs + 4);
-                qiw[CBM_PF - 1] = *reinterpret_cast<const uint2*>(ixu + (size_t)wn * Bs);
-            }
             // parity of this window's first position (the chunk starts on an even one: 7 * 14 windows)
             const uint32_t xbase = xlds + (uint32_t)(POOLW * (w - wc) * 256);
             const uint32_t wpar = (uint32_t)((w - wc) & 1) << 5;
+            // this lane's fragment addresses at the window's even and odd positions: tile 0, last tile
+            const uint32_t xa0 = xbase + (boff0 ^ wpar), xa1 = xbase + (boff0 ^ wpar ^ 32u);
+            const uint32_t xl0 = xbase + (boffl ^ wpar), xl1 = xbase + (boffl ^ wpar ^ 32u);
             // A fragments of position r: the pieces where the offset equals r (0xffff per half whose
             // bit r is set).  The fragments of position r + 1 are built IN PLACE while the MFMAs of
             // position r run, each piece as soon as the matrix instructions that read it have issued
@@ -784,30 +817,49 @@ __global__ __launch_bounds__(64 * CBM_WAVES, cbm_occ(K)) void conv_bwd_mm_kernel
             cb_u32x4 ah, am, al;
 #pragma unroll
             for (int d = 0; d < 4; ++d) {
-                const uint32_t mk = __umul24(ip[d] & 0x00010001u, 0xffffu);
+                const uint32_t mk = cbm_spread(__builtin_bit_cast(uint32_t, __builtin_bit_cast(cb_u16x2, ip[d]) << 15));
                 ah[d] = ph[d] & mk; am[d] = pm[d] & mk; al[d] = pl[d] & mk;
             }
 #pragma unroll
             for (int r = 0; r < POOLW; ++r) {
+                if (r == POOLW - 1) {
+                    // the queue moves up one and the window CBM_PF turns ahead is requested -- here, at the
+                    // window's last position, where the pieces and the offsets of this window are dead and
+                    // their registers take the load (asked for at the window's start, the ten registers in
+                    // flight sat on top of the whole live set of the main loop)
+#pragma unroll
+                    for (int f = 0; f + 1 < CBM_PF; ++f) { qd0[f] = qd0[f + 1]; qd1[f] = qd1[f + 1]; qiw[f] = qiw[f + 1]; }
+                    int wn = min(w + CBM_PF * CBM_WAVES, wc + nwin - 1);
+                    size_t ln = lo;
+                    asm volatile("" : "+s"(wn), "+v"(ln));      // (the addresses are formed here, from the one
+                                                                // offset, not kept as two pointers per lane)
+                    size_t row = (size_t)wn * Bs;
+                    asm volatile("" : "+s"(row));
+                    const float* dyw = dy + row;
+                    const uint8_t* ixw = idx + row;
+                    qd0[CBM_PF - 1] = *reinterpret_cast<const float4*>(dyw + ln);
+                    qd1[CBM_PF - 1] = *reinterpret_cast<const float4*>(dyw + ln + 4);
+                    qiw[CBM_PF - 1] = *reinterpret_cast<const uint2*>(ixw + ln);
+                }
                 cb_bf16x8 fb[NTL];
 #pragma unroll
                 for (int t = 0; t < NTL; ++t)
                     fb[t] = __builtin_bit_cast(cb_bf16x8, *(const lds_u32x4*)(size_t)(
-                        xbase + ((boff[t] ^ wpar ^ (uint32_t)((r & 1) << 5)) + (uint32_t)(r * 256))));
+                        ((r & 1) ? (t == NTL - 1 ? xl1 : xa1) : (t == NTL - 1 ? xl0 : xa0)) + (uint32_t)(r * 256 + t * 1024)));
                 uint32_t tz[4] = {0u, 0u, 0u, 0u};
                 const bool more = r + 1 < POOLW;
                 __builtin_amdgcn_sched_barrier(0);
-                // hi piece; the four mask words of the next position (3 instructions each) in between
+                // hi piece; the four mask words of the next position (2 packed shifts each) in between
 #pragma unroll
                 for (int t = 0; t < NTL; ++t) {
                     acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(cb_bf16x8, ah), fb[t], acc[t], 0, 0, 0);
                     if (more) {
 #pragma unroll
-                        for (int k = (12 * t) / NTL; k < (12 * (t + 1)) / NTL; ++k) {
-                            const int d = k / 3, op = k - 3 * d;
-                            if (op == 0) tz[d] = ip[d] >> (r + 1);
-                            else if (op == 1) tz[d] &= 0x00010001u;
-                            else tz[d] = __umul24(tz[d], 0xffffu);
+                        for (int k = (8 * t) / NTL; k < (8 * (t + 1)) / NTL; ++k) {
+                            // bit r + 1 of each half to the half's sign, then spread over the half
+                            const int d = k / 2;
+                            if ((k & 1) == 0) tz[d] = __builtin_bit_cast(uint32_t, __builtin_bit_cast(cb_u16x2, ip[d]) << (14 - r));
+                            else tz[d] = cbm_spread(tz[d]);
                         }
                     }
                     __builtin_amdgcn_sched_barrier(0);
@@ -844,13 +896,15 @@ __global__ __launch_bounds__(64 * CBM_WAVES, cbm_occ(K)) void conv_bwd_mm_kernel
     // as ONE partial per (sequence block, window half, unit): D[row = unit 4g + i][col c] of tile t
     __syncthreads();
     float* red = reinterpret_cast<float*>(cbsm);                // [waves][NTL][4][64]
+    int tr = tid;                                               // (as te above)
+    asm volatile("" : "+v"(tr));
 #pragma unroll
     for (int t = 0; t < NTL; ++t)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) red[((wave * NTL + t) * 4 + i) * 64 + lane] = acc[t][i];
+        for (int i = 0; i < 4; ++i) red[((wave * NTL + t) * 4 + i) * 64 + (tr & 63)] = acc[t][i];
     __syncthreads();
     const int part = blockIdx.z * gridDim.x + blockIdx.x;
-    for (int e = tid; e < NTL * 4 * 64; e += NTH) {
+    for (int e = tr; e < NTL * 4 * 64; e += NTH) {
         float v = red[e];
 #pragma unroll
         for (int wv = 1; wv < CBM_WAVES; ++wv) v += red[wv * NTL * 256 + e];

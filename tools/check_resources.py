@@ -92,8 +92,11 @@ GATED = (C2_STEP + INPUT_GRAD + ISM + PATHGRAD + METRICS + SCAN + VARIANTS + HAP
 # share a CU (300 units on 256 CUs take two rounds otherwise) -- 64 registers, not one more.
 # passA: three waves per SIMD (512 registers / 3, in allocation units of 8).
 # (mid_fused: the buckets up to 40, whose LDS lets two blocks share a CU; above, one block has the CU)
+# conv_bwd_mm: five waves per SIMD (512 / 5 in units of 8), so that five four-wave workgroups share a CU
+# and the C2 grid of 1216 is resident in one round.
 VGPR_CAP = {r"^mid_fused_kernel<([1-9]|[1-3]\d|40)>": 64, r"^prep2_kernel<true>": 64,
-            r"^passA_kernel<26, 0>": 168, r"^passA_kernel<26, 2>": 168}
+            r"^passA_kernel<26, 0>": 168, r"^passA_kernel<26, 2>": 168,
+            r"^conv_bwd_mm_kernel<19>": 96}
 
 
 def demangle(names):

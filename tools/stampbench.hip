@@ -68,6 +68,93 @@ static void balance(const char* name, const std::vector<unsigned long long>& h, 
         printf("           %d waves/SIMD: %d SIMDs, wave time p50 %.0f p90 %.0f max %.0f\n", kv.first, nsimd[kv.first], d[d.size() / 2], d[d.size() * 9 / 10], d.back());
     }
 }
+
+// The per-workgroup view (wpw waves per workgroup, `resident` workgroups fit the chip at once): which
+// SIMD wave i of a workgroup lands on, how many first waves a SIMD collects, and when the workgroups
+// past the first round start and end.  Times are relative to the first stamp on the wave's own CU (the
+// counters of different XCDs are not aligned).
+static void balance_wg(const char* name, const std::vector<unsigned long long>& h, int waves, int wpw, int nst,
+                       int resident) {
+    const int nwg = waves / wpw;
+    auto cu_of = [](unsigned long long id) {
+        const unsigned hw = (unsigned)id, xcc = (unsigned)(id >> 32) & 15;
+        return (xcc << 16) | (((hw >> 13) & 7) << 12) | (((hw >> 8) & 15) << 4);
+    };
+    std::map<unsigned, unsigned long long> x0;                  // CU -> first start
+    for (int w = 0; w < waves; ++w)
+        if (h[w * 8]) {
+            const unsigned cu = cu_of(h[w * 8 + 7]);
+            auto it = x0.find(cu);
+            if (it == x0.end() || h[w * 8] < it->second) x0[cu] = h[w * 8];
+        }
+    std::vector<long> place(wpw * 4, 0);                        // [wave in workgroup][SIMD]
+    std::map<unsigned, std::vector<int>> on_simd;               // SIMD key -> wave indices (in workgroup) it holds
+    struct G { double start, end, skew; int one_cu, distinct; };
+    std::vector<G> wg;
+    for (int g = 0; g < nwg; ++g) {
+        double s = 1e30, s1 = 0, e = 0;
+        unsigned cu0 = 0, seen = 0;
+        bool ok = true, one_cu = true;
+        for (int i = 0; i < wpw; ++i) {
+            const int w = g * wpw + i;
+            if (!h[w * 8] || !h[w * 8 + nst - 1]) { ok = false; break; }
+            const unsigned long long id = h[w * 8 + 7];
+            const unsigned sd = ((unsigned)id >> 4) & 3, cu = cu_of(id);
+            if (i == 0) cu0 = cu; else if (cu != cu0) one_cu = false;
+            seen |= 1u << sd;
+            place[i * 4 + sd]++;
+            on_simd[cu | sd].push_back(i);
+            const double t0 = (double)(h[w * 8] - x0[cu]), t1 = (double)(h[w * 8 + nst - 1] - x0[cu]);
+            s = std::min(s, t0); s1 = std::max(s1, t0); e = std::max(e, t1);
+        }
+        if (ok) wg.push_back({s, e, s1 - s, one_cu, __builtin_popcount(seen)});
+    }
+    printf("%-10s WORKGROUPS: %zu of %d stamped, %d waves each\n", name, wg.size(), nwg, wpw);
+    for (int i = 0; i < wpw; ++i)
+        printf("           wave %d sits on SIMD 0..3 in %ld %ld %ld %ld workgroups\n", i, place[i * 4], place[i * 4 + 1],
+               place[i * 4 + 2], place[i * 4 + 3]);
+    long onecu = 0, dist[5] = {0, 0, 0, 0, 0};
+    for (auto& g : wg) { onecu += g.one_cu; dist[g.distinct]++; }
+    printf("           workgroups on one CU: %ld; on 1/2/3/4 distinct SIMDs: %ld %ld %ld %ld\n", onecu, dist[1], dist[2],
+           dist[3], dist[4]);
+    std::map<int, int> first_hist;                              // first waves (index 0) per SIMD -> SIMDs
+    std::map<int, int> total_hist;
+    for (auto& kv : on_simd) {
+        int n0 = 0;
+        for (int i : kv.second) n0 += i == 0;
+        first_hist[n0]++; total_hist[(int)kv.second.size()]++;
+    }
+    printf("           SIMDs by number of wave-0s held over the launch:");
+    for (auto& kv : first_hist) printf("  %d: %d", kv.first, kv.second);
+    printf("\n           SIMDs by number of waves held over the launch:");
+    for (auto& kv : total_hist) printf("  %d: %d", kv.first, kv.second);
+    printf("\n");
+    std::sort(wg.begin(), wg.end(), [](const G& a, const G& b) { return a.start < b.start; });
+    auto stat = [&](const char* what, size_t lo, size_t hi, int field) {
+        std::vector<double> d;
+        for (size_t i = lo; i < hi; ++i) d.push_back(field == 0 ? wg[i].start : (field == 1 ? wg[i].end : wg[i].skew));
+        if (d.empty()) return;
+        std::sort(d.begin(), d.end());
+        printf("           %-44s min %.0f p50 %.0f p90 %.0f max %.0f\n", what, d.front(), d[d.size() / 2], d[d.size() * 9 / 10], d.back());
+    };
+    // the first round: every workgroup that starts before the first one ends
+    double first_end = 1e30;
+    for (auto& g : wg) first_end = std::min(first_end, g.end);
+    size_t r1 = 0;
+    while (r1 < wg.size() && wg[r1].start < first_end) ++r1;
+    printf("           %zu workgroups start before the first one ends (%.0f); the register and LDS budget holds %d\n", r1,
+           first_end, resident);
+    stat("first round: workgroup start", 0, r1, 0);
+    stat("first round: workgroup end", 0, r1, 1);
+    stat("first round: start skew inside a workgroup", 0, r1, 2);
+    if (wg.size() > r1) {
+        printf("           %zu workgroups start later:\n", wg.size() - r1);
+        stat("later rounds: workgroup start", r1, wg.size(), 0);
+        stat("later rounds: workgroup end", r1, wg.size(), 1);
+    } else {
+        printf("           no workgroup waits for another to end\n");
+    }
+}
 #endif
 
 // every launch starts from zeroed stamps: a wave that leaves before a stamp (passA's second wave
@@ -79,11 +166,13 @@ static void clear_stamps() {
 }
 
 // (first: the first wave of the report -- the waves of unit group r of logits_bn start at r * waves)
-static void report(const char* name, int waves, int nst, float ms, int first = 0) {
+// (wpw, resident: with -DBALANCE also the per-workgroup view of a kernel of wpw-wave workgroups)
+static void report(const char* name, int waves, int nst, float ms, int first = 0, int wpw = 0, int resident = 0) {
     std::vector<unsigned long long> h((size_t)waves * 8);
     CK(hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(g_stamps), h.size() * 8, (size_t)first * 64));
 #ifdef BALANCE
     balance(name, h, waves, nst);
+    if (wpw) balance_wg(name, h, waves, wpw, nst, resident);
 #endif
     printf("%-10s event %.1f us | median cycles per phase:", name, ms * 1e3);
     for (int p = 1; p < nst; ++p) {
@@ -221,7 +310,9 @@ int main() {
                                    dy, idx, bmask, Dmm, U, n, Bs, B, NT64, Lp, Bs / 16, wper);
                 CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1)); CK(hipEventElapsedTime(&ms, e0, e1));
                 CK(hipGetLastError());
-                if (rep) report("conv_bwd_mm", ((B + 31) / 32) * ((U + 15) / 16) * 2 * CBM_WAVES, 4, ms);
+                // (resident: cbm_occ waves per SIMD over CBM_WAVES-wave workgroups on 256 CUs of four SIMDs)
+                if (rep) report("conv_bwd_mm", ((B + 31) / 32) * ((U + 15) / 16) * 2 * CBM_WAVES, 4, ms, 0, CBM_WAVES,
+                                256 * (4 * cbm_occ(19) / CBM_WAVES));
             }
             clear_stamps();
             CK(hipEventRecord(e0));
