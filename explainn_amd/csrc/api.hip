@@ -1,6 +1,7 @@
 // extern "C" entry points of libexplainn_hip.so (declared in include/explainn_hip.h) and the
 // context that owns the device scratch.  Each entry point enqueues its pipeline stages on the
 // caller's stream and returns; see DESIGN.md section 3 for the stage list.
+#include <assert.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -235,6 +236,17 @@ static int create_ctx(explainn_ctx** out, int groups, int units_per_member, int 
     // memory channel (channel camping: ~8 us per dependent load, profiles/r01_c).
     c->Bs = (max_batch + 63) & ~63;
     if (((c->Bs / 64) & 1) == 0) c->Bs += 64;
+    // fc.hip has no device-side test of b < Bs: a 16-sequence tile that starts below B <= max_batch ends
+    // below Bs because Bs is a multiple of 64 and not below max_batch (both by the two lines above)
+    assert(c->Bs % 64 == 0 && c->Bs >= max_batch);
+    // ... and it addresses a unit's [n][Bs] rows, dead rows of the bucket's last tile included, with 32-bit
+    // byte offsets behind a range-checked descriptor
+    if ((int64_t)(NQ + 32) * c->Bs * 4 > (int64_t)INT32_MAX) {
+        explainn_set_error("max_batch %d: the rows of one unit (%d x %d floats) exceed 32-bit byte offsets",
+                           max_batch, NQ + 32, c->Bs);
+        delete c;
+        return EXPLAINN_E_UNSUPPORTED;
+    }
     c->NW = (sequence_length + 31) / 32 + 2; c->PW = 2 * c->NW;
     c->Lp = ((c->NW * 32 + 63) / 64) * 64;
     {

@@ -318,6 +318,24 @@ extern __device__ unsigned long long g_stamps[];
 // Pattern: issue all loads into an array, KEEP() each element in a second loop, then compute.
 #define KEEP(x) asm volatile("" : "+v"(x))
 
+// A raw buffer descriptor over the `bytes` bytes at p (no stride, no swizzle: the 32-bit offset of an
+// access is range-checked against `bytes`; a load beyond returns 0 and a store beyond is dropped).
+// p and bytes must be the same in every lane of the wave: they are made uniform by hand here, because a
+// descriptor the compiler cannot prove uniform gets a readfirstlane loop around every access.
+template <class P>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t uniform_rsrc(P* p, uint32_t bytes) {
+    const unsigned long long v = reinterpret_cast<unsigned long long>(p);
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0,
+                                             (int)__builtin_amdgcn_readfirstlane(bytes), 0x00020000);
+}
+__device__ __forceinline__ float rsrc_load_f32(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff) {
+    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, (int)soff, 0));
+}
+__device__ __forceinline__ void rsrc_store_f32(float v, __amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff) {
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, (int)voff, (int)soff, 0);
+}
+
 // The sub-batch of an entry point that works through a batch in pieces of one workspace (ISM, IG): the
 // sequences that fit cap_bytes at per_sequence_bytes each, in whole steps (a wave: lane = sequence), at
 // least one step, no more than the batch rounded up to a step.

@@ -30,6 +30,8 @@
 #include "common.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
 __device__ __forceinline__ uint32_t mix32(uint32_t x) {
@@ -155,19 +157,35 @@ __global__ __launch_bounds__(64 * fc_fwd_waves(NQ)) void fc_fwd_kernel(
     float* v2s = sh2s + FC_MT * 16;                          // [112]
     int u, bx;
     if (!unit_chunk_of_block(U, u, bx)) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // wave-uniform: the tile loop's tests stay scalar
     const int c = lane & 15, g = lane >> 4;
-    const float* __restrict__ eu = ext + (size_t)u * n * Bs;
-    const int bt0 = (bx * FW + wave) * FC_BTW;
+    // the lane's sequence in the wave's first tile.  A wave's FC_BTW tiles divide 64 sequences and Bs is a multiple
+    // of 64: if the first tile starts below B, none of them reaches Bs.  A wave wholly past the batch only
+    // helps with the staging; its first fetch below addresses the unit's first sequences instead
+    static_assert(64 % (16 * FC_BTW) == 0, "a wave's tiles must not straddle the batch stride");
+    const int bt0 = (bx * FW + wave) * FC_BTW, bl = (bt0 * 16 < B ? bt0 * 16 : 0) + c;
     STAMP(0);
+    // Addressing: see fc_fwd_bf_kernel.  Row 4s + g of register s: the lane part g and the sequence in
+    // the vector offset, 4s as a scalar offset, except where 4s + 3 can reach n (whole row term in the
+    // vector offset, out of the descriptor's range beyond n).
+    const uint32_t rowb = 4u * (uint32_t)Bs;
+    const __amdgpu_buffer_rsrc_t rex = uniform_rsrc(ext + (size_t)u * n * Bs, (uint32_t)n * rowb);
+    const uint32_t vb4 = 4u * (uint32_t)bl, voff = (uint32_t)g * rowb + vb4;
+    uint32_t vrow[NK4];                                // (only the entries of rows that can reach n are used)
+#pragma unroll
+    for (int s = 0; s < NK4; ++s) vrow[s] = voff + (uint32_t)(4 * s) * rowb;
+    float raw[NK4];
+    auto fetch = [&](uint32_t tile) {                  // tile: compile-time in every call
+#pragma unroll
+        for (int s = 0; s < NK4; ++s) {
+            if (4 * s + 3 <= nq_lower(NQ)) raw[s] = rsrc_load_f32(rex, voff + 64u * tile, (uint32_t)(4 * s) * rowb);
+            else raw[s] = rsrc_load_f32(rex, vrow[s] + 64u * tile, 0u);
+        }
+    };
     // the first tile's raw pooled extremes are requested before the weight fragments are staged:
     // one memory round trip covers both
-    float raw[NK4];
-    {
-        const int b = min(bt0 * 16 + c, Bs - 1);
-#pragma unroll
-        for (int s = 0; s < NK4; ++s) raw[s] = eu[min(4 * s + g, n - 1) * Bs + b];
-    }
+    fetch(0);
     {
         // A fragments (prep2 wrote them in fragment order):
         // Af[(t*NK4Q + sq)*64 + l].{x,y,z,w} = A2[16t + (l&15)][4*(4sq+e) + (l>>4)], e = 0..3
@@ -194,18 +212,20 @@ __global__ __launch_bounds__(64 * fc_fwd_waves(NQ)) void fc_fwd_kernel(
     // (head.hip finishes them inside the combiner launch); fp64, unshifted: a shift would have to be
     // state (the running mean) and make the step's rounding depend on it
     double zs1 = 0, zs2 = 0;
+    const __amdgpu_buffer_rsrc_t rz = uniform_rsrc((TRAIN ? zout : oout) + (size_t)u * Bs, rowb);
+    const __amdgpu_buffer_rsrc_t rbt = uniform_rsrc(bits + (size_t)u * Bs, 4u * rowb);
+#pragma unroll
     for (int it = 0; it < FC_BTW; ++it) {
         const int bt = bt0 + it;
         if (bt * 16 >= B) break;                       // wave-uniform
-        const int b = bt * 16 + c;
+        const int b = bl + 16 * it;
         float qf[NK4];
 #pragma unroll
         for (int s = 0; s < NK4; ++s) qf[s] = (4 * s + g < n) ? qval(a1, raw[s], s1) : 0.f;
-        if (it + 1 < FC_BTW && (bt + 1) * 16 < B) {    // next tile's loads fly under this tile's MFMAs
-            const int bn = min(b + 16, Bs - 1);
-#pragma unroll
-            for (int s = 0; s < NK4; ++s) raw[s] = eu[min(4 * s + g, n - 1) * Bs + bn];
-        }
+        // next tile's loads fly under this tile's MFMAs.  Unconditional: a tile past the batch costs a wave
+        // its last eight loads (they stay inside the unit's descriptor, nobody reads them), and a
+        // conditional refill would keep the old set alive beside the new one -- a register copy per value
+        if (it + 1 < FC_BTW) fetch(it + 1);
         uint32_t rs = 0;
         if (MODE == 2)
             rs = mix32(mix32(seed_lo ^ (uint32_t)(4 * b + g) * 0x9E3779B9U) ^
@@ -247,14 +267,15 @@ __global__ __launch_bounds__(64 * fc_fwd_waves(NQ)) void fc_fwd_kernel(
             words[k] |= __shfl_xor(words[k], 32, 64);
         }
         if (TRAIN && g == 0 && b < B) { const double d = (double)zp; zs1 += d; zs2 = fma(d, d, zs2); }
-        if (g == 0 && b < Bs) {
+        if (g == 0) {                                  // (b < Bs: the tile starts below B, and Bs is a multiple of 64)
             if (TRAIN) {
-                zout[(size_t)u * Bs + b] = zp;
-                bits[(size_t)u * Bs + b] = make_uint4(words[0], words[1], words[2], words[3]);
+                rsrc_store_f32(zp, rz, vb4 + 64u * it, 0u);
+                __builtin_amdgcn_raw_buffer_store_b128(u32x4{words[0], words[1], words[2], words[3]}, rbt,
+                                                       (int)(16u * (uint32_t)bl + 256u * it), 0, 0);
             } else {
                 const float inv = g3[u] / sqrtf(rv3[u] + (float)BN_EPS_D);
                 const float y3 = fmaf(inv, zp + c2[u] - rm3[u], b3[u]);
-                oout[(size_t)u * Bs + b] = fmaxf(y3, 0.f);
+                rsrc_store_f32(fmaxf(y3, 0.f), rz, vb4 + 64u * it, 0u);
             }
         }
     }
@@ -276,7 +297,6 @@ __global__ __launch_bounds__(64 * fc_fwd_waves(NQ)) void fc_fwd_kernel(
 //   sequence c built in registers; D layout as above, so the epilogue is the fp32 kernel's.
 // ---------------------------------------------------------------------------------------------
 typedef __attribute__((ext_vector_type(8))) __bf16 fbf16x8;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 template <int NQ, int MODE>
 __global__ __launch_bounds__(64 * fc_fwd_waves(NQ), fc_ks32(NQ) == 1 ? 5 : 2) void fc_fwd_bf_kernel(
@@ -296,20 +316,41 @@ __global__ __launch_bounds__(64 * fc_fwd_waves(NQ), fc_ks32(NQ) == 1 ? 5 : 2) vo
     float* v2s = sh2s + FC_MT * 16;                          // [112]
     int u, bx;
     if (!unit_chunk_of_block(U, u, bx)) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // wave-uniform: the tile loop's tests stay scalar
     const int c = lane & 15, g = lane >> 4;
-    const float* __restrict__ eu = ext + (size_t)u * n * Bs;
-    const int bt0 = (bx * FW + wave) * FC_BTW;
+    // the lane's sequence in the wave's first tile.  A wave's FC_BTW tiles divide 64 sequences and Bs is a multiple
+    // of 64: if the first tile starts below B, none of them reaches Bs.  A wave wholly past the batch only
+    // helps with the staging; its first fetch below addresses the unit's first sequences instead
+    static_assert(64 % (16 * FC_BTW) == 0, "a wave's tiles must not straddle the batch stride");
+    const int bt0 = (bx * FW + wave) * FC_BTW, bl = (bt0 * 16 < B ? bt0 * 16 : 0) + c;
     STAMP(0);
-    // the first tile's raw pooled extremes are requested before the weight fragments are staged
+    // Addressing (as in passB): the unit's rows through one range-checked descriptor bound to its own
+    // n x Bs elements, one 32-bit byte offset per lane (row part 8g + its sequence in the first tile), the
+    // row 32ks + j of a register as a scalar offset and the tile step as the instruction's immediate (the
+    // tile loop is unrolled).  A row that can reach n in some lane (32ks + 24 + j > nq_lower(NQ)) has
+    // its whole row term in the vector offset, formed once per wave: beyond n it is out of range and
+    // loads 0, which the select on q discards as it discarded the clamped live value.
+    const uint32_t rowb = 4u * (uint32_t)Bs;
+    const __amdgpu_buffer_rsrc_t rex = uniform_rsrc(ext + (size_t)u * n * Bs, (uint32_t)n * rowb);
+    const uint32_t vb4 = 4u * (uint32_t)bl, voff = (uint32_t)(8 * g) * rowb + vb4;
+    uint32_t vrow[KS][8];                              // (only the entries of rows that can reach n are used)
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) vrow[ks][j] = voff + (uint32_t)(32 * ks + j) * rowb;
     float raw[KS][8];
-    {
-        const int b = min(bt0 * 16 + c, Bs - 1);
+    auto fetch = [&](uint32_t tile) {                  // tile: compile-time in every call
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
-            for (int j = 0; j < 8; ++j) raw[ks][j] = eu[min(32 * ks + 8 * g + j, n - 1) * Bs + b];
-    }
+            for (int j = 0; j < 8; ++j) {
+                if (32 * ks + 24 + j <= nq_lower(NQ)) raw[ks][j] = rsrc_load_f32(rex, voff + 64u * tile, (uint32_t)(32 * ks + j) * rowb);
+                else raw[ks][j] = rsrc_load_f32(rex, vrow[ks][j] + 64u * tile, 0u);
+            }
+    };
+    // the first tile's raw pooled extremes are requested before the weight fragments are staged
+    fetch(0);
     {
         const u32x4* src = reinterpret_cast<const u32x4*>(A2h) + (size_t)u * FC_MT * KS * 3 * 64;
         constexpr int N4 = FC_MT * KS * 3 * 64;
@@ -335,10 +376,14 @@ __global__ __launch_bounds__(64 * fc_fwd_waves(NQ), fc_ks32(NQ) == 1 ? 5 : 2) vo
     // (head.hip finishes them inside the combiner launch); fp64, unshifted: a shift would have to be
     // state (the running mean) and make the step's rounding depend on it
     double zs1 = 0, zs2 = 0;
+    const __amdgpu_buffer_rsrc_t rz = uniform_rsrc((TRAIN ? zout : oout) + (size_t)u * Bs, rowb);
+    const __amdgpu_buffer_rsrc_t rbt = uniform_rsrc(bits + (size_t)u * Bs, 4u * rowb);
+    // (unrolled: the tile step is an immediate, and the prefetched set needs no register-to-register copy)
+#pragma unroll
     for (int it = 0; it < FC_BTW; ++it) {
         const int bt = bt0 + it;
         if (bt * 16 >= B) break;                       // wave-uniform
-        const int b = bt * 16 + c;
+        const int b = bl + 16 * it;
         // q of this tile, split into its three bf16 pieces, two elements per word
         u32x4 bq[KS][3];
 #pragma unroll
@@ -358,13 +403,10 @@ __global__ __launch_bounds__(64 * fc_fwd_waves(NQ), fc_ks32(NQ) == 1 ? 5 : 2) vo
                 bq[ks][2][jp] = __builtin_amdgcn_perm(__float_as_uint(r2[1]), __float_as_uint(r2[0]), 0x07060302u);
             }
         }
-        if (it + 1 < FC_BTW && (bt + 1) * 16 < B) {    // next tile's loads fly under this tile's MFMAs
-            const int bn = min(b + 16, Bs - 1);
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) raw[ks][j] = eu[min(32 * ks + 8 * g + j, n - 1) * Bs + bn];
-        }
+        // next tile's loads fly under this tile's MFMAs.  Unconditional: a tile past the batch costs a wave
+        // its last eight loads (they stay inside the unit's descriptor, nobody reads them), and a
+        // conditional refill would keep the old set alive beside the new one -- a register copy per value
+        if (it + 1 < FC_BTW) fetch(it + 1);
         uint32_t rs = 0;
         if (MODE == 2)
             rs = mix32(mix32(seed_lo ^ (uint32_t)(4 * b + g) * 0x9E3779B9U) ^
@@ -416,14 +458,15 @@ __global__ __launch_bounds__(64 * fc_fwd_waves(NQ), fc_ks32(NQ) == 1 ? 5 : 2) vo
             words[k] |= __shfl_xor(words[k], 32, 64);
         }
         if (TRAIN && g == 0 && b < B) { const double d = (double)zp; zs1 += d; zs2 = fma(d, d, zs2); }
-        if (g == 0 && b < Bs) {
+        if (g == 0) {                                  // (b < Bs: the tile starts below B, and Bs is a multiple of 64)
             if (TRAIN) {
-                zout[(size_t)u * Bs + b] = zp;
-                bits[(size_t)u * Bs + b] = make_uint4(words[0], words[1], words[2], words[3]);
+                rsrc_store_f32(zp, rz, vb4 + 64u * it, 0u);
+                __builtin_amdgcn_raw_buffer_store_b128(u32x4{words[0], words[1], words[2], words[3]}, rbt,
+                                                       (int)(16u * (uint32_t)bl + 256u * it), 0, 0);
             } else {
                 const float inv = g3[u] / sqrtf(rv3[u] + (float)BN_EPS_D);
                 const float y3 = fmaf(inv, zp + c2[u] - rm3[u], b3[u]);
-                oout[(size_t)u * Bs + b] = fmaxf(y3, 0.f);
+                rsrc_store_f32(fmaxf(y3, 0.f), rz, vb4 + 64u * it, 0u);
             }
         }
     }
@@ -676,7 +719,6 @@ __device__ __forceinline__ void pa_sums_prologue(const pa_sums_args& ps, int u, 
 }
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 #define PA_LD 72                     // bf16 elements per row of the X image (64 sequences + 8 pad)
 __host__ __device__ constexpr int pa_nw16(int NQ) { return (NQ + 1 + 15) / 16; }   // + the dz column
 __host__ __device__ constexpr int pa_wgt(int NQ) { return pa_nw16(NQ) <= 2 ? pa_nw16(NQ) : 3; }
@@ -975,8 +1017,14 @@ int launch_passA_sums(explainn_ctx* c, int B, const pa_sums_args& ps, hipStream_
 // rows 16j + 4g + i the lane's accumulators hold, so the epilogue's q values are the operand
 // registers themselves.
 // ---------------------------------------------------------------------------------------------
+// register kq = 4j' + i' holds row 16j' + 4g + i' of lane group g: true when that row is below n in every
+// lane, for every n of the bucket (n > nq_lower(NQ))
+__host__ __device__ constexpr bool pb_row_live(int NQ, int kq) { return 16 * (kq >> 2) + 12 + (kq & 3) <= nq_lower(NQ); }
+
+// (up to two w tiles the LDS image lets five workgroups share a CU: the registers must, too -- with the
+// stores out of their EXEC regions the main loop is one block, and the scheduler spends what it is given)
 template <int NQ>
-__global__ __launch_bounds__(256, 2) void passB_kernel(
+__global__ __launch_bounds__(256, fc_nw16(NQ) <= 2 ? 5 : 2) void passB_kernel(
     const float* __restrict__ ext, const float* __restrict__ alpha,
     const float* __restrict__ shift, const float* __restrict__ dz, const uint4* __restrict__ bits,
     const float* __restrict__ Ttf, const float* __restrict__ Mff, const float* __restrict__ k0p,
@@ -990,7 +1038,9 @@ __global__ __launch_bounds__(256, 2) void passB_kernel(
     float* k0s = Mf + WGT * MK * 64;                   // [WGT*16]
     int u, bx;
     if (!unit_chunk_of_block(U, u, bx)) return;
-    const int grp = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int grp = NG == 1 ? 0 : (int)blockIdx.z;     // (one group: the row offsets below are compile-time multiples)
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // wave-uniform: the tile loop's tests stay scalar
     const int c = lane & 15, g = lane >> 4;
     const int j0 = grp * WGT;                          // first w tile of this group
     const int ntile = min(WGT, NW16 - j0);             // w tiles this group really has
@@ -1022,23 +1072,46 @@ __global__ __launch_bounds__(256, 2) void passB_kernel(
     }
     __syncthreads();
     STAMP(1);
-    const float* __restrict__ eu = ext + (size_t)u * n * Bs;
-    float* __restrict__ dyu = dy + (size_t)u * n * Bs;
     const float a1 = alpha[u], s1 = shift[u];
     const float mu = (float)mug[u];
     const float isg = (float)(1.0 / sig1[u]);
+    // Addressing: one range-checked descriptor per array, bound to THIS unit's elements; one 32-bit byte
+    // offset per lane (its row part 4g and its sequence in the wave's first tile), formed once per wave;
+    // the row 16j' + i' of a register and the tile step in the scalar offset.  A row >= n is out of the
+    // descriptor's range: its load returns 0 (the selects below discard it, as they discarded the clamped
+    // live value before) and its store is dropped -- no clamp, no branch around a store.  Only the
+    // VECTOR offset is relied on for that check: a row that can reach n in some lane (16j' + 12 + i' >
+    // nq_lower(NQ), known at compile time) carries its whole row term there; the other rows are live in
+    // every lane (n > nq_lower(NQ)), and the tile step never leaves a row (b < Bs).
+    const uint32_t rowb = 4u * (uint32_t)Bs;
+    const __amdgpu_buffer_rsrc_t rex = uniform_rsrc(ext + (size_t)u * n * Bs, (uint32_t)n * rowb);
+    const __amdgpu_buffer_rsrc_t rdy = uniform_rsrc(dy + (size_t)u * n * Bs, (uint32_t)n * rowb);
+    const __amdgpu_buffer_rsrc_t rbt = uniform_rsrc(bits + (size_t)u * Bs, 4u * rowb);
+    const __amdgpu_buffer_rsrc_t rdz = uniform_rsrc(dz + (size_t)u * Bs, rowb);
+    const __amdgpu_buffer_rsrc_t rs12 = uniform_rsrc(S12p + ((size_t)u * NG + grp) * (Bs / 16) * 2, rowb / 8u);
+    // the lane's sequence in the wave's first tile (PB_BTW tiles divide 64 sequences, Bs is a multiple of 64: a
+    // tile that starts below B ends below Bs; nothing is loaded or stored for a tile past the batch)
+    static_assert(64 % (16 * PB_BTW) == 0, "a wave's tiles must not straddle the batch stride");
+    const int bt0 = (bx * 4 + wave) * PB_BTW, bl = bt0 * 16 + c;
+    const uint32_t vb4 = 4u * (uint32_t)bl, vb16 = 16u * (uint32_t)bl;
+    const uint32_t voff = (uint32_t)(4 * g) * rowb + vb4;
+    uint32_t vrow[MK];                                 // (only the entries of rows that can reach n are used)
+#pragma unroll
+    for (int kq = 0; kq < MK; ++kq) vrow[kq] = voff + (uint32_t)(16 * (kq >> 2) + (kq & 3)) * rowb;
     for (int it = 0; it < PB_BTW; ++it) {
-        const int bt = (bx * 4 + wave) * PB_BTW + it;
+        const int bt = bt0 + it;
         if (bt * 16 >= B) break;                       // wave-uniform
-        const int b = bt * 16 + c;
-        const bool live = b < B;
-        const int bc = min(b, Bs - 1);
+        const bool live = bl + 16 * it < B;
+        const uint32_t toff = 64u * (uint32_t)it;      // the tile step in bytes of a row (scalar)
         // raw pooled extremes of this lane's sequence, rows v = 16j' + 4g + i' (register kq = 4j'+i')
         float exr[MK];
 #pragma unroll
-        for (int kq = 0; kq < MK; ++kq) exr[kq] = eu[min(16 * (kq >> 2) + 4 * g + (kq & 3), n - 1) * Bs + bc];
-        const uint4 wv = bits[(size_t)u * Bs + bc];
-        const float dzb = dz[(size_t)u * Bs + bc];
+        for (int kq = 0; kq < MK; ++kq) {
+            if (pb_row_live(NQ, kq)) exr[kq] = rsrc_load_f32(rex, voff, (uint32_t)(16 * (kq >> 2) + (kq & 3)) * rowb + toff);
+            else exr[kq] = rsrc_load_f32(rex, vrow[kq], toff);
+        }
+        const u32x4 wv = __builtin_amdgcn_raw_buffer_load_b128(rbt, (int)vb16, (int)(4u * toff), 0);
+        const float dzb = rsrc_load_f32(rdz, vb4, toff);
 #pragma unroll
         for (int kq = 0; kq < MK; ++kq) KEEP(exr[kq]);
         float nq[MK];
@@ -1054,16 +1127,17 @@ __global__ __launch_bounds__(256, 2) void passB_kernel(
         f32x4 accP[WGT];
 #pragma unroll
         for (int j = 0; j < WGT; ++j) accP[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        const uint32_t wsv[4] = {wv.x, wv.y, wv.z, wv.w};
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
-            const uint32_t wg = wsv[kk] >> (8 * g);
+            // the lane's eight bits, odd ones copied 15 up: bits 2i and 2i + 1 then sit 16 apart, and the
+            // pair word (bf16 1.0 = 0x3f80 per set bit) is one and + one 24-bit multiply that shifts the
+            // pair down by 2i and up by 7 at once (0x3f80 >> 2i is exact up to 2i = 6; the masked operand
+            // stays below 2^23)
+            const uint32_t wg = __builtin_amdgcn_ubfe(wv[kk], (uint32_t)(8 * g), 8u);
+            const uint32_t y = wg | (wg << 15);
             u32x4 bv;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int m0 = __builtin_amdgcn_sbfe(wg, 2 * i, 1), m1 = __builtin_amdgcn_sbfe(wg, 2 * i + 1, 1);
-                bv[i] = ((uint32_t)m0 & 0x00003f80u) | ((uint32_t)m1 & 0x3f800000u);
-            }
+            for (int i = 0; i < 4; ++i) bv[i] = __umul24(y & (0x00010001u << (2 * i)), 0x3f80u >> (2 * i));
             const bf16x8 bfr = __builtin_bit_cast(bf16x8, bv);
 #pragma unroll
             for (int j = 0; j < WGT; ++j)
@@ -1108,16 +1182,18 @@ __global__ __launch_bounds__(256, 2) void passB_kernel(
                 const float dyv = (live && w < n) ? -acc[j][i] * nqv : 0.f;      // dq * q
                 sA += dyv;
                 sB = fmaf(dyv, (ex - mu) * isg, sB);
-                if (w < n && b < Bs) dyu[w * Bs + b] = dyv;
+                // (the row of the LAST group's tile j decides the class: all groups run this code)
+                const uint32_t st = (uint32_t)(16 * (j0 + j) + i) * rowb;       // block-uniform
+                if (pb_row_live(NQ, 4 * ((NG - 1) * WGT + j) + i)) rsrc_store_f32(dyv, rdy, voff, st + toff);
+                else rsrc_store_f32(dyv, rdy, voff + st, toff);
             }
         }
         if (it == 0) STAMP(4);
         sA = wave_sum(sA);
         sB = wave_sum(sB);
-        if (lane == 0) {
-            float* d = S12p + (((size_t)u * NG + grp) * (Bs / 16) + bt) * 2;
-            d[0] = sA; d[1] = sB;
-        }
+        if (lane == 0)                                 // S12p[u][grp][bt][2]: bt0 in the vector offset, the tile in the scalar one
+            __builtin_amdgcn_raw_buffer_store_b64(u32x2{__float_as_uint(sA), __float_as_uint(sB)}, rs12,
+                                                  8 * bt0, (int)(toff >> 3), 0);
     }
     STAMP(5);
 }

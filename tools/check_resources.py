@@ -94,9 +94,11 @@ GATED = (C2_STEP + INPUT_GRAD + ISM + PATHGRAD + METRICS + SCAN + VARIANTS + HAP
 # (mid_fused: the buckets up to 40, whose LDS lets two blocks share a CU; above, one block has the CU)
 # conv_bwd_mm: five waves per SIMD (512 / 5 in units of 8), so that five four-wave workgroups share a CU
 # and the C2 grid of 1216 is resident in one round.
+# fc_fwd_bf, passB: five waves per SIMD, what their LDS images allow at the pooled length 26.
 VGPR_CAP = {r"^mid_fused_kernel<([1-9]|[1-3]\d|40)>": 64, r"^prep2_kernel<true>": 64,
             r"^passA_kernel<26, 0>": 168, r"^passA_kernel<26, 2>": 168,
-            r"^conv_bwd_mm_kernel<19>": 96}
+            r"^conv_bwd_mm_kernel<19>": 96,
+            r"^fc_fwd_bf_kernel<26, 2>": 96, r"^passB_kernel<26>": 96}
 
 
 def demangle(names):
