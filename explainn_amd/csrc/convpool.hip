@@ -288,15 +288,20 @@ __device__ __forceinline__ void cpm_load_fragments(cpm_state<KS, UT>& S, const c
 // at one wave per SIMD its grid leaves SIMDs idle: so the launch carries `naux` more one-wave
 // workgroups (the leading z slices of the grid; ids past naux return at once) that do the work of
 // moments_kernel and prep1_stats_kernel<true> beside it, off the step's critical path:
-//   phase 1  input moments from the bit masks bm: job (d, a) = the four base pairs (a, a') at gap d,
-//            exact integer pair counts per position, window sums from their prefix sums -> G, m
-//            (every entry an exact count / (B Lo): any split of the jobs gives the same bits);
+//   phase 1  input moments from the bit masks bm: item (d, a, h) = the two base pairs (a, 2h) and
+//            (a, 2h + 1) at gap d, 8k items dealt over the workgroups; exact integer pair counts per
+//            position, window sums from their prefix sums -> G, m (every entry an exact count /
+//            (B Lo): any split of the items gives the same bits);
 //   hand-off G and m stored write-through (agent-scope relaxed atomic stores), drained, then one
 //            relaxed ticket add per workgroup; every workgroup polls the ticket relaxed with s_sleep
 //            until all naux have arrived and then makes ONE agent-scope acquire;
 //   phase 2  the BatchNorm1 fold of units id, id + naux, ... (up to BN1_NU of them per pass over G):
 //            prep1_stats_kernel<true>'s fp64 arithmetic in its order -- lane l plays that kernel's
-//            threads l and l + 64, and the two 64-lane sums are added as its red[0] + red[1].
+//            threads l and l + 64, and the two 64-lane sums are added as its red[0] + red[1];
+//            the units' wave sums run side by side and lane uu finishes unit uu.
+// Where the chain's time goes at C2 (tools/cpm_stamp.hip, profiles/r33_bn1_chain_stamps.txt): phase 1
+// 8.8 us, waiting for the last ticket 4.4, the two trips over G 7.4, sums and finish 1.7 -- 22.6 us
+// beside a filter bank of 26.
 // Progress does not depend on dispatch order or XCD placement: only these workgroups wait, they wait
 // only for each other, and the filter-bank waves never wait for anything.  naux is far below the
 // waves the chip holds at once (>= 1024), so the filter-bank waves in front of a waiting workgroup
@@ -315,16 +320,19 @@ struct cpm_bn1_args {
 };
 typedef __attribute__((address_space(1))) unsigned long long bn1_gu64;
 typedef __attribute__((address_space(1))) int bn1_gi32;
+typedef __attribute__((address_space(1))) float bn1_gf32;
 // Register budget: the chain is dependent round trips (~1 us each beside the matrix load), so it
 // holds as many loads in flight as the form's registers allow without raising its arch VGPR count
 // past what its occupancy leaves (VGPRs and AccVGPRs share one file).  The forms with one wave per
-// SIMD anyway (UT = 2, KS >= 2: 196..203 arch VGPRs + 68..172 AccVGPRs of 512) take whole passes:
-// all tiles of a 64-position pass and 40 rows of G per round trip; the others stay under the ~110
-// arch VGPRs of the UT = 1 forms (4 tiles, 12 rows), or a form loses a wave per SIMD.
+// SIMD anyway (UT = 2, KS >= 2: 196..203 arch VGPRs + 68..172 AccVGPRs of 512) take four position
+// passes at once, six tiles of each (72 64-bit loads), and 38 rows of G per round trip; the others
+// stay under the ~110 arch VGPRs of the UT = 1 forms (two passes of three tiles, 12 rows), or a form
+// loses a wave per SIMD.
 template <int KS, int UT> struct bn1_cfg {
     static constexpr bool big = UT == 2 && KS >= 2;
-    static constexpr int TQ = big ? 16 : 4;   // phase 1: 64-sequence tiles per round trip (5 loads each)
-    static constexpr int CH = big ? 40 : 12;  // phase 2: rows of G per round trip
+    static constexpr int PQ = big ? 4 : 2;    // phase 1: 64-position passes per round trip
+    static constexpr int TQ = big ? 6 : 3;    // phase 1: 64-sequence tiles of each pass per round trip (3 loads each)
+    static constexpr int CH = big ? 38 : 12;  // phase 2: rows of G per round trip (k = 19: 76 rows, two trips)
 };
 #define BN1_NU 2                 // phase 2: units per pass over G
 #define BN1_SPIN_TICKS 10000000ull   // 100 ms of the 100 MHz wall clock
@@ -334,56 +342,84 @@ __device__ __forceinline__ void bn1_store(double* p, double v) {
                        __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// phase 1, job (d, a): lane = position q of a 64-position pass; P = inclusive prefix sums of the pair
-// counts over q (exact integers), G[(a,j),(a',j+d)] = (P(j+Lo-1) - P(j-1)) / (B Lo), kept by lane j
-template <int BN1_TQ>
-__device__ __forceinline__ void bn1_moments_job(const cpm_bn1_args& X, int job, int lane) {
-    const int d = job >> 2, a = job & 3;
+// phase 1, item (d, a, h): base a against the partner bases a' = 2h, 2h + 1 at gap d.  Lane =
+// position q of a 64-position pass; P = inclusive prefix sums of the pair counts over q (exact
+// integers), G[(a,j),(a',j+d)] = (P(j+Lo-1) - P(j-1)) / (B Lo), kept by lane j.  The passes of a
+// round trip are counted first and their scans run side by side (one scan depth per PQ passes).
+// P(j-1) is the first pass's exclusive scan at lane j; P(j+Lo-1) lies in one of two passes; every
+// other pass only adds its total to the carry.
+template <int TQ, int PQ>
+__device__ __forceinline__ void bn1_moments_item(const cpm_bn1_args& X, int item, int lane) {
+    const int d = item >> 3, a = (item >> 1) & 3, ab = (item & 1) * 2;
     const int NT = (X.B + 63) / 64, Lo = X.L - X.k + 1, K4 = 4 * X.k;
     const size_t plane = (size_t)NT * X.Lp;
     const unsigned long long* __restrict__ m0 = X.bm + (size_t)a * plane;
-    long long carry[4] = {0, 0, 0, 0}, plo[4] = {0, 0, 0, 0}, phi[4] = {0, 0, 0, 0};
-    const int jlo = lane - 1, jhi = lane + Lo - 1;
-    for (int qb = 0; qb < X.L; qb += 64) {
-        const int q = qb + lane;
-        int c[4] = {0, 0, 0, 0};
-        if (q + d < X.L) {
-            for (int t0 = 0; t0 < NT; t0 += BN1_TQ) {      // 5 BN1_TQ loads in flight
-                unsigned long long x0[BN1_TQ], x1[4][BN1_TQ];
+    const unsigned long long* __restrict__ m1 = X.bm + (size_t)ab * plane + d;
+    long long carry[2] = {0, 0}, plo[2] = {0, 0}, phi[2] = {0, 0};
+    const int jhi = lane + Lo - 1;
+    const int pa = (Lo - 1) >> 6;                          // the passes that hold a P(jhi): pa, pa + 1
+    for (int p0 = 0; p0 * 64 < X.L; p0 += PQ) {
+        int c[PQ][2], qo[PQ];
+        bool ok[PQ];
 #pragma unroll
-                for (int i = 0; i < BN1_TQ; ++i) {
-                    const size_t o = (size_t)min(t0 + i, NT - 1) * X.Lp + q;
-                    x0[i] = m0[o];
+        for (int p = 0; p < PQ; ++p) {
+            const int q = (p0 + p) * 64 + lane;
+            ok[p] = q + d < X.L;
+            qo[p] = min(q, X.L - 1 - d);                   // (a lane past the end reads a valid word and counts 0)
+            c[p][0] = c[p][1] = 0;
+        }
+        for (int t0 = 0; t0 < NT; t0 += TQ) {              // 3 PQ TQ loads in flight
+            unsigned long long x0[PQ][TQ], x1[PQ][2][TQ];
 #pragma unroll
-                    for (int a2 = 0; a2 < 4; ++a2) x1[a2][i] = X.bm[a2 * plane + d + o];
+            for (int p = 0; p < PQ; ++p)
+#pragma unroll
+                for (int i = 0; i < TQ; ++i) {
+                    const size_t o = (size_t)min(t0 + i, NT - 1) * X.Lp + qo[p];
+                    x0[p][i] = m0[o];
+                    x1[p][0][i] = m1[o];
+                    x1[p][1][i] = m1[plane + o];
                 }
 #pragma unroll
-                for (int i = 0; i < BN1_TQ; ++i)
+            for (int p = 0; p < PQ; ++p)
 #pragma unroll
-                    for (int a2 = 0; a2 < 4; ++a2) c[a2] += (t0 + i < NT) ? __popcll(x0[i] & x1[a2][i]) : 0;
-            }
+                for (int i = 0; i < TQ; ++i)
+#pragma unroll
+                    for (int s = 0; s < 2; ++s)
+                        c[p][s] += (ok[p] && t0 + i < NT) ? __popcll(x0[p][i] & x1[p][s][i]) : 0;
         }
+        int v[PQ][2];
 #pragma unroll
-        for (int a2 = 0; a2 < 4; ++a2) {
-            int v = c[a2];
+        for (int p = 0; p < PQ; ++p) { v[p][0] = c[p][0]; v[p][1] = c[p][1]; }
 #pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const int y = __shfl_up(v, off, 64);
-                if (lane >= off) v += y;
+        for (int off = 1; off < 64; off <<= 1)
+#pragma unroll
+            for (int p = 0; p < PQ; ++p)
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    const int y = __shfl_up(v[p][s], off, 64);
+                    if (lane >= off) v[p][s] += y;
+                }
+#pragma unroll
+        for (int p = 0; p < PQ; ++p) {
+            const int pg = p0 + p;
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                if (pg == 0) plo[s] = v[p][s] - c[p][s];
+                if (pg == pa || pg == pa + 1) {
+                    const int vhi = __shfl(v[p][s], jhi & 63, 64);
+                    if ((jhi >> 6) == pg) phi[s] = carry[s] + vhi;
+                }
+                carry[s] += __builtin_amdgcn_readlane(v[p][s], 63);
             }
-            const int vlo = __shfl(v, jlo & 63, 64), vhi = __shfl(v, jhi & 63, 64);
-            if (jlo >= qb && jlo < qb + 64) plo[a2] = carry[a2] + vlo;
-            if (jhi >= qb && jhi < qb + 64) phi[a2] = carry[a2] + vhi;
-            carry[a2] += __shfl(v, 63, 64);
         }
     }
     const int j = lane;
     if (j < X.k - d) {
 #pragma unroll
-        for (int a2 = 0; a2 < 4; ++a2) {
-            const long long sj = phi[a2] - plo[a2];
+        for (int s = 0; s < 2; ++s) {
+            const long long sj = phi[s] - plo[s];
             const double v = (double)sj / ((double)X.B * (double)Lo);
-            const int row = a * X.k + j, col = a2 * X.k + j + d;
+            const int row = a * X.k + j, col = (ab + s) * X.k + j + d;
             bn1_store(X.G + (size_t)row * K4 + col, v);
             bn1_store(X.G + (size_t)col * K4 + row, v);
             if (row == col) bn1_store(X.m + row, v);
@@ -391,7 +427,10 @@ __device__ __forceinline__ void bn1_moments_job(const cpm_bn1_args& X, int job, 
     }
 }
 
-// phase 2: the BatchNorm1 fold of up to BN1_NU units (us[0..nu)) in one pass over G
+// phase 2: the BatchNorm1 fold of up to BN1_NU units (us[0..nu)) in one pass over G.  The units'
+// parameters and running statistics are asked for together with the filters and m, in front of the
+// passes over G; lane uu plays prep1_stats_kernel's thread 0 of unit us[uu] and finishes the fold of
+// its unit beside the other lanes'.
 template <int CH>
 __device__ __forceinline__ void bn1_fold_units(const cpm_bn1_args& X, const int (&us)[BN1_NU], int nu, int lane) {
     const int K4 = 4 * X.k, Lo = X.L - X.k + 1;
@@ -405,6 +444,30 @@ __device__ __forceinline__ void bn1_fold_units(const cpm_bn1_args& X, const int 
         wl[uu][1] = X.conv_w[(size_t)u * K4 + c1i];
     }
     const double m0 = X.m[c0i], m1 = X.m[c1i];
+    int ul = us[0];
+#pragma unroll
+    for (int uu = 1; uu < BN1_NU; ++uu) ul = lane == uu ? us[uu] : ul;
+    const bool fin = lane < nu && ul < X.U;                // this lane finishes unit ul
+    // the units' five scalars in ONE register across the passes over G: lane 8 uu + f asks for
+    // scalar f of unit us[uu] (g1, b1, conv_b, rm, rv)
+    float par = 0.f;
+    static_assert(BN1_NU <= 8, "lane 8 uu + f: eight units' scalars fit the wave");
+    {
+        const int pu = lane >> 3, pf = lane & 7;
+        int uq = us[0];
+#pragma unroll
+        for (int uu = 1; uu < BN1_NU; ++uu) uq = pu == uu ? us[uu] : uq;
+        // (the array bases go through an opaque asm: a select among kernel arguments the compiler can
+        // see becomes an indexed table of them in scratch, for every wave of the launch)
+        unsigned long long ps[5] = {(unsigned long long)X.g1, (unsigned long long)X.b1, (unsigned long long)X.conv_b,
+                                    (unsigned long long)X.rm, (unsigned long long)X.rv};
+#pragma unroll
+        for (int f = 0; f < 5; ++f) asm volatile("" : "+s"(ps[f]));
+        unsigned long long pa = ps[4];
+#pragma unroll
+        for (int f = 3; f >= 0; --f) pa = pf == f ? ps[f] : pa;
+        if (pu < nu && pf < 5 && uq < X.U) par = ((const bn1_gf32*)pa)[uq];
+    }
     // (G w)[i] = sum_c G[c][i] w[c]: even c into ge, odd c into go, in prep1_stats_kernel's order
     double ge[BN1_NU][2], go[BN1_NU][2];
 #pragma unroll
@@ -436,41 +499,65 @@ __device__ __forceinline__ void bn1_fold_units(const cpm_bn1_args& X, const int 
             }
         }
     }
+    STAMP(4);
+    // prep1_stats_kernel's thread i (i < K4) holds mu_p = w_i m_i and q_p = w_i (G w)_i; its block
+    // sum is wave 0's sum (threads 0..63) + wave 1's (64..127).  The sums of all units side by side.
+    double sm[BN1_NU][2][2];                               // [unit][mu_p, q_p][wave]
 #pragma unroll
     for (int uu = 0; uu < BN1_NU; ++uu) {
-        if (uu >= nu) break;
-        const int u = us[uu];
-        if (u >= X.U) {
-            if (lane == 0) { X.alpha[u] = 0.f; X.shift[u] = 0.f; }
-            continue;
-        }
-        // prep1_stats_kernel's thread i (i < K4) holds mu_p = w_i m_i and q_p = w_i (G w)_i; its block
-        // sum is wave 0's sum (threads 0..63) + wave 1's (64..127)
-        double mu_p[2] = {0, 0}, q_p[2] = {0, 0};
+        const bool live = uu < nu && us[uu] < X.U;
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int i = h ? i1 : i0;
             const double gw = ge[uu][h] + go[uu][h];
-            if (i < K4) {
-                X.Gw[(size_t)u * K4 + i] = gw;
-                mu_p[h] = fma((double)wl[uu][h], h ? m1 : m0, mu_p[h]);
-                q_p[h] = fma((double)wl[uu][h], gw, q_p[h]);
+            double mu_p = 0, q_p = 0;
+            if (live && i < K4) {
+                X.Gw[(size_t)us[uu] * K4 + i] = gw;
+                mu_p = fma((double)wl[uu][h], h ? m1 : m0, mu_p);
+                q_p = fma((double)wl[uu][h], gw, q_p);
             }
+            sm[uu][0][h] = mu_p;
+            sm[uu][1][h] = q_p;
         }
-        const double mu = wave_sum_d(mu_p[0]) + wave_sum_d(mu_p[1]);
-        const double wGw = wave_sum_d(q_p[0]) + wave_sum_d(q_p[1]);
-        if (lane == 0)
-            bn1_fold_finish(mu, wGw, u, X.g1[u], X.b1[u], X.conv_b[u], X.rm[u], X.rv[u], X.B, Lo, X.alpha,
-                            X.shift, X.mug, X.sig1, X.rm, X.rv, X.nbt);
     }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)                 // (wave_sum_d of each, in step)
+#pragma unroll
+        for (int uu = 0; uu < BN1_NU; ++uu)
+#pragma unroll
+            for (int w = 0; w < 2; ++w)
+#pragma unroll
+                for (int h = 0; h < 2; ++h) sm[uu][w][h] += __shfl_xor(sm[uu][w][h], off, 64);
+    double mu = sm[0][0][0] + sm[0][0][1], wGw = sm[0][1][0] + sm[0][1][1];
+#pragma unroll
+    for (int uu = 1; uu < BN1_NU; ++uu) {
+        const double mu_u = sm[uu][0][0] + sm[uu][0][1], wGw_u = sm[uu][1][0] + sm[uu][1][1];
+        mu = lane == uu ? mu_u : mu;
+        wGw = lane == uu ? wGw_u : wGw;
+    }
+    float sc[5];                                           // g1, b1, conv_b, rm, rv of this lane's unit
+#pragma unroll
+    for (int f = 0; f < 5; ++f) {
+        sc[f] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(par), f));
+#pragma unroll
+        for (int uu = 1; uu < BN1_NU; ++uu)
+            sc[f] = lane == uu ? __int_as_float(__builtin_amdgcn_readlane(__float_as_int(par), 8 * uu + f)) : sc[f];
+    }
+    if (fin)
+        bn1_fold_finish(mu, wGw, ul, sc[0], sc[1], sc[2], sc[3], sc[4], X.B, Lo, X.alpha, X.shift, X.mug, X.sig1,
+                        X.rm, X.rv, X.nbt);
+    else if (lane < nu) { X.alpha[ul] = 0.f; X.shift[ul] = 0.f; }      // (a padding row of the unit grid)
 }
 
 // one auxiliary workgroup (id < naux): phase 1, the hand-off, phase 2
 template <int KS, int UT>
 __device__ __forceinline__ void cpm_bn1(const cpm_bn1_args& X, int id, int lane) {
-    for (int job = id; job < 4 * X.k; job += X.naux) bn1_moments_job<bn1_cfg<KS, UT>::TQ>(X, job, lane);
+    typedef bn1_cfg<KS, UT> cfg;
+    STAMP(0);
+    for (int item = id; item < 8 * X.k; item += X.naux) bn1_moments_item<cfg::TQ, cfg::PQ>(X, item, lane);
     // publish: the write-through stores of G / m drained, then this workgroup's ticket
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    STAMP(1);
     if (lane == 0) __hip_atomic_fetch_add((bn1_gi32*)X.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     // wait for every auxiliary workgroup: relaxed polls, bounded, then ONE agent-scope acquire
     const unsigned long long t0 = wall_clock64();
@@ -484,7 +571,9 @@ __device__ __forceinline__ void cpm_bn1(const cpm_bn1_args& X, int id, int lane)
         }
         __builtin_amdgcn_s_sleep(2);
     }
+    STAMP(2);
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    STAMP(3);
     for (int u0 = id; u0 < X.U4; u0 += BN1_NU * X.naux) {
         int us[BN1_NU], nu = 0;
 #pragma unroll
@@ -492,8 +581,9 @@ __device__ __forceinline__ void cpm_bn1(const cpm_bn1_args& X, int id, int lane)
             us[uu] = u0 + uu * X.naux;
             if (us[uu] < X.U4) nu = uu + 1;
         }
-        bn1_fold_units<bn1_cfg<KS, UT>::CH>(X, us, nu, lane);
+        bn1_fold_units<cfg::CH>(X, us, nu, lane);
     }
+    STAMP(5);
 }
 
 template <int KS, int UT, bool IDX>
@@ -622,13 +712,15 @@ static int conv_pool_mm_parts(const explainn_ctx* c, int B, int ut) {
     return best;
 }
 
-// BatchNorm1's workgroups in the filter-bank launch (cpm_bn1): two per moments job (d, a); the
-// second half only joins phase 2.  EXPLAINN_BN1_AUX (experiments; read per step, so that a test can
+// BatchNorm1's workgroups in the filter-bank launch (cpm_bn1): one per phase-1 item (d, a, h) and
+// two units each in phase 2 at C2.  EXPLAINN_BN1_AUX (experiments; read per step, so that a test can
 // run both paths in one process): 0 = the separate launches, N > 0 = N workgroups whatever the shape
 // -- at most 256, a quarter of the waves the chip holds at once even at one wave per SIMD, so that
 // the progress argument of cpm_bn1 stands.
-// Where it pays, measured on MI355X (profiles/r04_bn1_ab.txt): the chain takes ~30 us on these
-// workgroups, so it leaves the critical path only beside a one-round filter bank about that long.
+// Where it pays, measured on MI355X (profiles/r04_bn1_ab.txt): the chain took ~30 us on these
+// workgroups then (22.6 since r33, profiles/r33_bn1_chain_stamps.txt; the bounds below are r04's and
+// have not been measured again), so it leaves the critical path only beside a one-round filter bank
+// about that long.
 // C2 (960 workgroups, 200 bp): 0.2029 -> 0.1972 ms per step.  Forced on, the other shapes lose: the
 // small grids (100 units x 64 sequences 0.0982 -> 0.1006, 300 x 128 0.1306 -> 0.1390; 104 and 520
 // workgroups), multi-round C3 0.550 -> 0.557 and C5 3.45 -> 3.49 (the workgroups take slots from a

@@ -95,7 +95,10 @@ GATED = (C2_STEP + INPUT_GRAD + ISM + PATHGRAD + METRICS + SCAN + VARIANTS + HAP
 # conv_bwd_mm: five waves per SIMD (512 / 5 in units of 8), so that five four-wave workgroups share a CU
 # and the C2 grid of 1216 is resident in one round.
 # fc_fwd_bf, passB: five waves per SIMD, what their LDS images allow at the pooled length 26.
+# conv_pool_mm<5, 2, true>: one wave per SIMD whatever it takes, but its total is set by BatchNorm1's
+# auxiliary path, which may use what the filter bank leaves and no more (390 when the path moved in).
 VGPR_CAP = {r"^mid_fused_kernel<([1-9]|[1-3]\d|40)>": 64, r"^prep2_kernel<true>": 64,
+            r"^conv_pool_mm_kernel<5, 2, true>": 390,
             r"^passA_kernel<26, 0>": 168, r"^passA_kernel<26, 2>": 168,
             r"^conv_bwd_mm_kernel<19>": 96,
             r"^fc_fwd_bf_kernel<26, 2>": 96, r"^passB_kernel<26>": 96}
