@@ -727,18 +727,9 @@ extern "C" int explainn_call_sites(explainn_ctx* c, const uint8_t* seq, int64_t 
     }
     TRY(check_code_range("call_sites", c, seq_len, start, n_positions));
     if (period < 0 || capacity < 0) { explainn_set_error("period and capacity must not be negative"); return EXPLAINN_E_ARG; }
-    const int64_t need = sites_workspace_bytes(c, n_positions);
-    if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 255) != 0) {
-        explainn_set_error("call_sites workspace of %lld bytes (256-byte aligned), %lld needed",
-                           (long long)workspace_bytes, (long long)need);
-        return EXPLAINN_E_ARG;
-    }
+    if (!sites_workspace_ok(c, n_positions, workspace, workspace_bytes)) return EXPLAINN_E_ARG;
     hipStream_t s = static_cast<hipStream_t>(stream);
     TRY(code_scan_begin(c, p, "sites are called", s));
-    if (n_positions == 0) {
-        HIP_TRY(hipMemsetAsync(offsets, 0, (size_t)(c->U + 1) * sizeof(int64_t), s));
-        return EXPLAINN_OK;
-    }
     return launch_call_sites(c, seq, start, n_positions, period, reverse_complement ? 1 : 0, thresholds,
                              offsets, pos, score, capacity, workspace, s);
 }

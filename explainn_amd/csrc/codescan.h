@@ -8,7 +8,9 @@
 // (conv_act_kernel and the MFMA filter bank use another algebra and are tied to this chain by tests.)
 //
 // The chain: accumulate from 0.f, one add per tap in j order, fp32 (no fast-math: the order is the
-// bits), qval (common.h), round to float16.  Device-only, all __forceinline__.
+// bits), qval (common.h), round to float16.  Device-only, all __forceinline__.  It holds the bit pattern
+// of an activation, the tap chain and the staging of a span of codes; what happens to a hit afterwards (its
+// position-order rank, block_hit_ranks) is sitescan.h's.
 #pragma once
 #include <hip/hip_fp16.h>
 
@@ -77,34 +79,4 @@ __device__ __forceinline__ int stage_codes(const uint8_t* __restrict__ src, int 
         else dst[i] = (uint8_t)(rc ? w : v);
     }
     return bad;
-}
-
-// ---- the position-order rank of a hit --------------------------------------------------------------
-// All T threads of the block call it, thread order = position order, for the four units of a quad:
-// rank[uu] = hits of unit uu in the threads below this one, total[uu] = hits of the block.  Ballots and
-// popcounts, per-wave totals in wtot (LDS): no rank depends on the order anything arrives in.
-template <int T>
-__device__ __forceinline__ void block_hit_ranks(const bool (&hit)[4], int (*wtot)[T / 64], int (&rank)[4],
-                                                int (&total)[4]) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-    for (int uu = 0; uu < 4; ++uu) {
-        const unsigned long long bal = __ballot(hit[uu]);
-        rank[uu] = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) wtot[uu][wave] = __popcll(bal);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int uu = 0; uu < 4; ++uu) {
-        int before = 0, all = 0;
-#pragma unroll
-        for (int w = 0; w < T / 64; ++w) {
-            const int t = wtot[uu][w];
-            before += w < wave ? t : 0;
-            all += t;
-        }
-        rank[uu] += before;
-        total[uu] = all;
-    }
-    __syncthreads();                           // wtot is rewritten by the next call
 }

@@ -252,6 +252,7 @@ int launch_stage_haplotypes(explainn_ctx* c, const uint8_t* seq, int64_t seq_len
 
 // motif sites (sites.hip): the compacted (unit, position, score) list of a range of start positions
 int64_t sites_workspace_bytes(const explainn_ctx* c, int64_t npos);
+bool sites_workspace_ok(const explainn_ctx* c, int64_t npos, const void* workspace, int64_t workspace_bytes);
 int launch_call_sites(explainn_ctx* c, const uint8_t* seq, int64_t start, int64_t npos, int64_t period,
                       int rc, const float* thr, int64_t* offsets, int32_t* pos, float* score,
                       int64_t capacity, void* workspace, hipStream_t s);

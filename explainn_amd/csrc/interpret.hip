@@ -10,6 +10,7 @@
 // order of sites is the thread order and a site's global rank is
 //     offset[unit][sequence] (exclusive scan of per-sequence counts) + rank inside the sequence.
 #include "codescan.h"
+#include "sitescan.h"
 
 namespace {
 

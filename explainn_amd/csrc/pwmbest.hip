@@ -5,10 +5,9 @@
 // integer <= 8192, a 15-bit pattern that sorts like the score.
 //
 // Geometry (a first choice): a 256-thread workgroup = (a slice of records, a group of EXPLAINN_PWM_GROUP
-// motifs).  The group's tables sit in LDS once per workgroup, sized by the call's wmax, in
-// pwm_sites_kernel's pair form: a word holds the forward score S[j][c] in its low half and the score the
-// reverse strand takes at the same base, S[w-1-j][3-c], in its high half, so one walk over a window's
-// codes in forward order scores both strands.  Two things differ from pwm_sites_kernel:
+// motifs).  The group's tables sit in LDS once per workgroup, sized by the call's wmax, as
+// pwmtab.h's pair words, so one walk over a window's codes in forward order scores both strands.  Two things
+// differ from pwm_sites_kernel:
 //   * the words of the two motifs a lane walks together lie side by side, [pair][column][code][2], so one
 //     64-bit LDS read serves both chains (a column past a motif's width holds 0: the wider motif of a
 //     pair goes on alone by adding zeros to the other);
@@ -32,6 +31,7 @@
 
 #include "bestsite.h"
 #include "common.h"
+#include "pwmtab.h"
 
 namespace {
 
@@ -44,13 +44,6 @@ constexpr int PB_BLOCKS = 16384;               // the records are cut into slice
 static_assert(PB_SPAN % 64 == 0 && PB_ILP == 4, "pb_walk is instantiated for one to four starts per lane");
 static_assert(PB_G % 2 == 0, "the motifs of a group are walked in pairs");
 static_assert(EXPLAINN_MOTIF_MAX_WIDTH * EXPLAINN_MOTIF_MAX_BINS < 65536, "two sums share a word without a carry");
-
-// the only way a width is read: outside [1, wmax] the motif is empty
-__device__ __forceinline__ int pb_width(const int* __restrict__ widths, int m, int M, int wmax) {
-    if (m >= M) return 0;
-    const int w = widths[m];
-    return (w >= 1 && w <= wmax) ? w : 0;
-}
 
 // the wave's LDS writes are seen by its own later reads (and the other way round): one wave, no s_barrier
 __device__ __forceinline__ void wave_sync() {
@@ -132,11 +125,8 @@ __global__ __launch_bounds__(PB_T) void pwm_best_kernel(
         // word i: pair q, column j, code c, motif 2 q + h
         const int h = i & 1, c = (i >> 1) & 7, j = (i >> 4) % wmax, q = (i >> 4) / wmax, m = m0 + 2 * q + h;
         unsigned word = 0;
-        const int w = pb_width(widths, m, M, wmax);
-        if (j < w && c < 4) {
-            const int16_t* row = S + (size_t)m * wmax * 4;
-            word = (unsigned)(uint16_t)row[j * 4 + c] | ((unsigned)(uint16_t)row[(w - 1 - j) * 4 + 3 - c] << 16);
-        }
+        const int w = pwm_width(widths, m, M, wmax);
+        if (j < w && c < 4) word = pwm_pair_word(S + (size_t)m * wmax * 4, w, j, c);
         words[i] = (int)word;
     }
     __syncthreads();                           // the only block-wide barrier: the waves part here
@@ -157,7 +147,7 @@ __global__ __launch_bounds__(PB_T) void pwm_best_kernel(
         for (int q = 0; q < PB_G / 2; ++q) {
             const int ma = m0 + 2 * q;         // motifs ma, ma + 1
             if (ma >= M) break;                // (the same in every thread)
-            const int w0 = pb_width(widths, ma, M, wmax), w1 = pb_width(widths, ma + 1, M, wmax);
+            const int w0 = pwm_width(widths, ma, M, wmax), w1 = pwm_width(widths, ma + 1, M, wmax);
             const int2* tb = pb_tab + q * wmax * 8;
             const int wb = min(w0, w1), wa = max(w0, w1);
             const bool first = w0 > w1;
@@ -202,13 +192,12 @@ extern "C" int explainn_pwm_record_best(const uint8_t* seq, int64_t seq_len, con
                                         int64_t n_records, int both_strands, const int16_t* scores,
                                         const int32_t* widths, int M, int wmax, uint16_t* best_bits,
                                         int32_t* best_site, int32_t* flags, void* stream) {
-    if (seq_len < 0 || n_records < 0 || n_records >= (int64_t)1 << 31 || M < 0 || M > 65535 * PB_G || wmax < 1 ||
-        wmax > EXPLAINN_MOTIF_MAX_WIDTH) {
-        explainn_set_error("pwm_record_best: need seq_len >= 0, 0 <= n_records < 2^31, 0 <= M <= %d and 1 <= wmax <= %d "
-                           "(seq_len=%lld n_records=%lld M=%d wmax=%d)", 65535 * PB_G, EXPLAINN_MOTIF_MAX_WIDTH,
-                           (long long)seq_len, (long long)n_records, M, wmax);
+    if (seq_len < 0 || n_records < 0 || n_records >= (int64_t)1 << 31) {
+        explainn_set_error("pwm_record_best: need seq_len >= 0 and 0 <= n_records < 2^31 (seq_len=%lld n_records=%lld)",
+                           (long long)seq_len, (long long)n_records);
         return EXPLAINN_E_ARG;
     }
+    if (!pwm_geometry_ok("pwm_record_best", M, wmax, 1)) return EXPLAINN_E_ARG;
     if (M == 0 || n_records == 0) return EXPLAINN_OK;
     if (!rec_offsets || !scores || !widths || !best_bits || (seq_len > 0 && !seq)) {
         explainn_set_error("pwm_record_best: seq, rec_offsets, scores, widths and best_bits must be device pointers");

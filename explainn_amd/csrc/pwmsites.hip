@@ -9,18 +9,18 @@
 //                       background, column by column (a gather: one lane per score value, the four bases in
 //                       order, no atomics), its tail, and the smallest score whose tail is <= pcut
 //   explainn_pwm_sites  every (motif, strand, start) with score >= the motif's threshold, as a compacted
-//                       list: the COUNT / scan / EMIT scheme of sites.hip with one row per (motif, strand)
+//                       list: the COUNT / scan / EMIT scheme of sitescan.h with one row per (motif, strand)
 //
 // Scan geometry (a first choice): a workgroup is a tile of EXPLAINN_SITES_TILE starts x a group of
 // EXPLAINN_PWM_GROUP motifs.  The tile's codes and the group's tables sit in LDS; a table entry (column j,
-// code c) is one 32-bit word holding two int16: the forward score S[j][c] and the score the reverse strand
-// takes at the same base, S[w-1-j][3-c] -- so one pass over the window's codes, in forward order, scores both
+// code c) is pwmtab.h's pair word, so one pass over the window's codes, in forward order, scores both
 // strands.  Code 4 (N) holds a sentinel so negative in both halves that no sum reaches a threshold >= 0.
 #include <limits.h>
 
 #include <algorithm>
 
 #include "codescan.h"
+#include "pwmtab.h"
 #include "sitescan.h"
 
 namespace {
@@ -33,14 +33,6 @@ static_assert(EXPLAINN_SITES_TILE % PS_T == 0, "a tile is a whole number of posi
 static_assert(PS_G % 2 == 0, "block_hit_ranks ranks four rows = two motifs x two strands at a time");
 static_assert(EXPLAINN_MOTIF_MAX_WIDTH * EXPLAINN_MOTIF_MAX_BINS + PS_N < 0, "an N outweighs the rest of a window");
 
-enum { PS_COUNT = 0, PS_EMIT = 1 };
-
-// the only way a width is read: outside [1, wmax] the motif is empty
-__device__ __forceinline__ int motif_width(const int* __restrict__ widths, int m, int wmax) {
-    const int w = widths[m];
-    return (w >= 1 && w <= wmax) ? w : 0;
-}
-
 template <int MODE>
 __global__ __launch_bounds__(PS_T) void pwm_sites_kernel(
     const uint8_t* __restrict__ seq, long long start, int npos, int span, long long period, int both,
@@ -52,8 +44,8 @@ __global__ __launch_bounds__(PS_T) void pwm_sites_kernel(
     uint8_t* cs = reinterpret_cast<uint8_t*>(tab + PS_G * wmax * 8);
     __shared__ int wtot[4][PS_T / 64];
     const int tile = blockIdx.x, tid = threadIdx.x, m0 = blockIdx.y * PS_G;
-    const int t0 = tile * EXPLAINN_SITES_TILE;              // < npos < 2^31
-    const int live_n = min(EXPLAINN_SITES_TILE, npos - t0); // start positions of this tile
+    int t0, live_n;
+    site_tile(tile, npos, t0, live_n);
     // the tile's bases and the wmax-1 behind its last start, as far as the sequence goes: span = the bases
     // from `start` to the end of what the call may read, >= npos (the entry point has checked it)
     const int nstage = min(live_n + wmax - 1, span - t0);
@@ -61,11 +53,10 @@ __global__ __launch_bounds__(PS_T) void pwm_sites_kernel(
     for (int i = tid; i < PS_G * wmax * 8; i += PS_T) {
         const int g = i / (wmax * 8), r = i - g * wmax * 8, j = r >> 3, c = r & 7, m = m0 + g;
         unsigned word = 0;
-        const int w = m < M ? motif_width(widths, m, wmax) : 0;
+        const int w = pwm_width(widths, m, M, wmax);
         if (j < w) {
             const int16_t* row = S + (size_t)m * wmax * 4;
-            word = c < 4 ? (unsigned)(uint16_t)row[j * 4 + c] | ((unsigned)(uint16_t)row[(w - 1 - j) * 4 + 3 - c] << 16)
-                         : (unsigned)(uint16_t)PS_N | ((unsigned)(uint16_t)PS_N << 16);
+            word = c < 4 ? pwm_pair_word(row, w, j, c) : (unsigned)(uint16_t)PS_N | ((unsigned)(uint16_t)PS_N << 16);
         }
         tab[i] = (int)word;
     }
@@ -87,15 +78,10 @@ __global__ __launch_bounds__(PS_T) void pwm_sites_kernel(
         long long base[4];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            const bool ok = ma + i < M;
-            w[i] = ok ? motif_width(widths, ma + i, wmax) : 0;
-            th[i] = ok ? thr[ma + i] : INT_MAX;
+            w[i] = pwm_width(widths, ma + i, M, wmax);
+            th[i] = ma + i < M ? thr[ma + i] : INT_MAX;
         }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = 2 * ma + r;
-            base[r] = (MODE == PS_EMIT && row < 2 * M) ? offsets[row] + cnt[(size_t)row * ntiles + tile] : 0;
-        }
+        site_bases<MODE>(offsets, cnt, ntiles, tile, 2 * ma, 2 * M, base);
         int run[4] = {0, 0, 0, 0};             // sites of this tile in earlier position chunks
 #pragma unroll
         for (int c = 0; c < PS_CHUNKS; ++c) {
@@ -137,23 +123,15 @@ __global__ __launch_bounds__(PS_T) void pwm_sites_kernel(
             }
             int pre[4], total[4];
             block_hit_ranks<PS_T>(hit, wtot, pre, total);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (MODE == PS_EMIT && hit[r]) {
-                    const long long rank = base[r] + run[r] + pre[r];
-                    if (rank < capacity) {
-                        pos[rank] = t0 + p;
-                        if (score) score[rank] = sc[r];
-                        if (pvalue)
-                            pvalue[rank] = (unsigned)sc[r] < (unsigned)tail_stride
-                                               ? tail[(size_t)(ma + (r >> 1)) * tail_stride + sc[r]] : 0.0;
-                    }
-                }
-                run[r] += total[r];
-            }
+            site_step<MODE>(hit, pre, total, base, capacity, run, [=](long long rank, int r) {
+                pos[rank] = t0 + p;
+                if (score) score[rank] = sc[r];
+                if (pvalue)
+                    pvalue[rank] = (unsigned)sc[r] < (unsigned)tail_stride
+                                       ? tail[(size_t)(ma + (r >> 1)) * tail_stride + sc[r]] : 0.0;
+            });
         }
-        if (MODE == PS_COUNT && tid < 4 && 2 * ma + tid < 2 * M)
-            cnt[(size_t)(2 * ma + tid) * ntiles + tile] = tid == 0 ? run[0] : tid == 1 ? run[1] : tid == 2 ? run[2] : run[3];
+        site_counts<MODE>(cnt, ntiles, tile, 2 * ma, 2 * M, run);
     }
 }
 
@@ -177,7 +155,7 @@ __global__ __launch_bounds__(PN_T) void pwm_null_kernel(const int16_t* __restric
     double* nxt = pn_lds + cap;
     double* part = pn_lds + 2 * cap;
     double* trow = tail ? tail + (size_t)m * stride : nullptr;
-    const int w = motif_width(widths, m, wmax);
+    const int w = pwm_width(widths, m, m + 1, wmax);     // one workgroup per motif: m < M
     if (w == 0) {                              // an empty motif: no distribution, the out-of-range threshold
         if (trow) for (int s = tid; s < stride; s += PN_T) trow[s] = 0.0;
         if (tid == 0) thr[m] = 1;
@@ -234,20 +212,6 @@ __global__ __launch_bounds__(PN_T) void pwm_null_kernel(const int16_t* __restric
     if (tid == 0) thr[m] = above;              // n = w bins + 1 when no tail is <= pcut
 }
 
-int64_t align256(int64_t v) { return (v + 255) & ~int64_t(255); }
-int64_t sites_tiles(int64_t npos) { return (npos + EXPLAINN_SITES_TILE - 1) / EXPLAINN_SITES_TILE; }
-int64_t pwm_cnt_bytes(int M, int64_t npos) { return align256(2 * (int64_t)M * sites_tiles(npos) * (int64_t)sizeof(int)); }
-
-bool pwm_geometry_ok(const char* who, int M, int wmax, int bins) {
-    if (M < 0 || M > 65535 * PS_G || wmax < 1 || wmax > EXPLAINN_MOTIF_MAX_WIDTH || bins < 1 ||
-        bins > EXPLAINN_MOTIF_MAX_BINS) {
-        explainn_set_error("%s: need 0 <= M <= %d, 1 <= wmax <= %d and 1 <= bins <= %d (M=%d wmax=%d bins=%d)", who,
-                           65535 * PS_G, EXPLAINN_MOTIF_MAX_WIDTH, EXPLAINN_MOTIF_MAX_BINS, M, wmax, bins);
-        return false;
-    }
-    return true;
-}
-
 }  // namespace
 
 extern "C" int explainn_pwm_null(const int16_t* scores, const int32_t* widths, int M, int wmax, int bins, double bg_a,
@@ -279,10 +243,9 @@ extern "C" int explainn_pwm_null(const int16_t* scores, const int32_t* widths, i
     return EXPLAINN_OK;
 }
 
-// the caller's workspace: cnt int [2M][tiles] | tot int64 [2M]
+// a row of sitescan.h's scheme is a (motif, strand): 2 m = '+', 2 m + 1 = '-'
 extern "C" int64_t explainn_pwm_sites_workspace_bytes(int M, int64_t n_positions) {
-    if (M < 0 || n_positions < 0) return 0;
-    return pwm_cnt_bytes(M, n_positions) + align256(2 * (int64_t)M * (int64_t)sizeof(long long));
+    return (M < 0 || n_positions < 0) ? 0 : site_workspace_bytes(2 * (int64_t)M, n_positions);
 }
 
 extern "C" int explainn_pwm_sites(const uint8_t* seq, int64_t seq_len, int64_t start, int64_t n_positions,
@@ -304,41 +267,24 @@ extern "C" int explainn_pwm_sites(const uint8_t* seq, int64_t seq_len, int64_t s
     if (!offsets) { explainn_set_error("pwm_sites: offsets is required"); return EXPLAINN_E_ARG; }
     if (pvalue && !tail) { explainn_set_error("pwm_sites: pvalue needs tail"); return EXPLAINN_E_ARG; }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (M == 0 || n_positions == 0) {
-        HIP_TRY(hipMemsetAsync(offsets, 0, (size_t)(2 * (int64_t)M + 1) * sizeof(int64_t), s));
-        return EXPLAINN_OK;
-    }
-    if (!seq || !scores || !widths || !thresholds) {
+    const bool none = M == 0 || n_positions == 0;              // takes no pointer but offsets
+    if (!none && (!seq || !scores || !widths || !thresholds)) {
         explainn_set_error("pwm_sites: seq, scores, widths and thresholds must be device pointers");
         return EXPLAINN_E_ARG;
     }
-    const int64_t need = explainn_pwm_sites_workspace_bytes(M, n_positions);
-    if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 255) != 0) {
-        explainn_set_error("pwm_sites workspace of %lld bytes (256-byte aligned), %lld needed",
-                           (long long)workspace_bytes, (long long)need);
+    if (!none && !site_workspace_ok("pwm_sites", workspace, workspace_bytes,
+                                    explainn_pwm_sites_workspace_bytes(M, n_positions)))
         return EXPLAINN_E_ARG;
-    }
-    const int ntiles = (int)sites_tiles(n_positions), rows = 2 * M;
-    int* cnt = static_cast<int*>(workspace);
-    long long* tot = reinterpret_cast<long long*>(static_cast<char*>(workspace) + pwm_cnt_bytes(M, n_positions));
+    const SiteWorkspace w = none ? SiteWorkspace{} : site_workspace(workspace, 2 * M, n_positions);
     long long* off = reinterpret_cast<long long*>(offsets);
     // the bases the call may read from `start` on: n_positions + wmax - 1, clipped to the sequence
     const int span = (int)std::min<int64_t>(n_positions + wmax - 1, seq_len - start);
     const size_t sm = (size_t)PS_G * wmax * 8 * sizeof(int) + ((EXPLAINN_SITES_TILE + wmax - 1 + 15) & ~15);
-    const dim3 grid(ntiles, (M + PS_G - 1) / PS_G);
     const int both = both_strands ? 1 : 0, stride = wmax * bins + 2;
-    hipLaunchKernelGGL(pwm_sites_kernel<PS_COUNT>, grid, dim3(PS_T), sm, s, seq, (long long)start, (int)n_positions,
-                       span, (long long)period, both, scores, widths, thresholds, (const double*)nullptr, stride, cnt,
-                       (const long long*)nullptr, (int*)nullptr, (int*)nullptr, (double*)nullptr, 0ll, M, wmax, ntiles);
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(sites_scan_tiles_kernel, dim3(rows), dim3(64), 0, s, cnt, tot, ntiles);
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(sites_scan_units_kernel, dim3(1), dim3(64), 0, s, tot, off, rows);
-    LAUNCH_CHECK();
-    if (pos == nullptr || capacity <= 0) return EXPLAINN_OK;
-    hipLaunchKernelGGL(pwm_sites_kernel<PS_EMIT>, grid, dim3(PS_T), sm, s, seq, (long long)start, (int)n_positions,
-                       span, (long long)period, both, scores, widths, thresholds, tail, stride, cnt, off, pos, score,
-                       pvalue, (long long)capacity, M, wmax, ntiles);
-    LAUNCH_CHECK();
-    return EXPLAINN_OK;
+    return site_passes(2 * M, n_positions, w, off, pos != nullptr && capacity > 0, s, [&](auto mode) {
+        hipLaunchKernelGGL(pwm_sites_kernel<decltype(mode)::value>, dim3(w.ntiles, (M + PS_G - 1) / PS_G), dim3(PS_T),
+                           sm, s, seq, (long long)start, (int)n_positions, span, (long long)period, both, scores,
+                           widths, thresholds, tail, stride, w.cnt, (const long long*)off, pos, score, pvalue,
+                           (long long)capacity, M, wmax, w.ntiles);
+    });
 }

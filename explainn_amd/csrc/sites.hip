@@ -8,14 +8,8 @@
 // window ever being cut.  The activation is the one definition of codescan.h, which is what makes a
 // site here a position where float16(linears[:3]) > threshold, bit for bit.
 //
-// Block = (tile of SITES_TILE positions, unit quad).  Two passes of the same kernel recompute the
-// activations instead of storing them:
-//   COUNT  sites per (unit, tile)                                            -> cnt[u][tile]
-//   scan   per unit: exclusive scan of cnt over the tiles (in place), total  -> tot[u]
-//          then offsets[u] = exclusive scan of tot over the units (int64, [units + 1])
-//   EMIT   rank = offsets[u] + cnt[u][tile] + rank inside the tile (ballots and popcounts in thread =
-//          position order); records with rank >= capacity are dropped
-// so per unit the sites ascend in position and no rank depends on the order atomics arrive in.
+// Block = (tile of SITES_TILE positions, unit quad); a row of sitescan.h's COUNT / scan / EMIT scheme is a
+// unit, so per unit the sites ascend in position and no rank depends on the order atomics arrive in.
 #include "codescan.h"
 #include "sitescan.h"
 
@@ -23,8 +17,6 @@ namespace {
 
 constexpr int SITES_T = 256;
 static_assert(EXPLAINN_SITES_TILE % SITES_T == 0, "a tile is a whole number of position chunks");
-
-enum { SITES_COUNT = 0, SITES_EMIT = 1 };
 
 template <int MODE>
 __global__ __launch_bounds__(SITES_T) void sites_kernel(
@@ -37,8 +29,8 @@ __global__ __launch_bounds__(SITES_T) void sites_kernel(
     uint8_t* cs = reinterpret_cast<uint8_t*>(Wsm + k * 5);
     __shared__ int wtot[4][SITES_T / 64];
     const int tile = blockIdx.x, quad = blockIdx.y, tid = threadIdx.x;
-    const int t0 = tile * EXPLAINN_SITES_TILE;              // < npos < 2^31
-    const int live_n = min(EXPLAINN_SITES_TILE, npos - t0); // start positions of this tile
+    int t0, live_n;
+    site_tile(tile, npos, t0, live_n);
     const float4* src = reinterpret_cast<const float4*>(Wt) + (size_t)quad * k * 5;
     for (int i = tid; i < k * 5; i += SITES_T) Wsm[i] = src[i];
     // the tile's bases and the k-1 behind its last start: all inside [start, start + npos + k - 1),
@@ -53,8 +45,8 @@ __global__ __launch_bounds__(SITES_T) void sites_kernel(
         al[uu] = alpha[u];
         sh[uu] = shift[u];
         th[uu] = thr[u];
-        base[uu] = MODE == SITES_EMIT ? offsets[u] + cnt[(size_t)u * ntiles + tile] : 0;
     }
+    site_bases<MODE>(offsets, cnt, ntiles, tile, quad * 4, U, base);
     __syncthreads();
     const int first = rc ? k - 1 : 0, step = rc ? -1 : 1;      // (the codes are complemented already)
     int run[4] = {0, 0, 0, 0};                 // sites of this tile in earlier position chunks
@@ -77,55 +69,33 @@ __global__ __launch_bounds__(SITES_T) void sites_kernel(
         for (int uu = 0; uu < 4; ++uu) hit[uu] = live && a16[uu] > th[uu];
         int pre[4], total[4];
         block_hit_ranks<SITES_T>(hit, wtot, pre, total);
-#pragma unroll
-        for (int uu = 0; uu < 4; ++uu) {
-            if (MODE == SITES_EMIT && hit[uu] && quad * 4 + uu < U) {
-                const long long rank = base[uu] + run[uu] + pre[uu];
-                if (rank < capacity) {
-                    pos[rank] = t0 + p;
-                    if (score) score[rank] = a16[uu];
-                }
+        site_step<MODE>(hit, pre, total, base, capacity, run, [=](long long rank, int uu) {
+            if (quad * 4 + uu < U) {
+                pos[rank] = t0 + p;
+                if (score) score[rank] = a16[uu];
             }
-            run[uu] += total[uu];
-        }
+        });
     }
-    if (MODE == SITES_COUNT && tid < 4 && quad * 4 + tid < U)
-        cnt[(size_t)(quad * 4 + tid) * ntiles + tile] = run[tid];
+    site_counts<MODE>(cnt, ntiles, tile, quad * 4, U, run);
 }
-
-int64_t align256(int64_t v) { return (v + 255) & ~int64_t(255); }
-int64_t sites_tiles(int64_t npos) { return (npos + EXPLAINN_SITES_TILE - 1) / EXPLAINN_SITES_TILE; }
 
 }  // namespace
 
-// the caller's workspace: cnt int [U][tiles] | tot int64 [U]
-int64_t sites_workspace_bytes(const explainn_ctx* c, int64_t npos) {
-    return align256((int64_t)c->U * sites_tiles(npos) * (int64_t)sizeof(int)) +
-           align256((int64_t)c->U * (int64_t)sizeof(long long));
+int64_t sites_workspace_bytes(const explainn_ctx* c, int64_t npos) { return site_workspace_bytes(c->U, npos); }
+
+bool sites_workspace_ok(const explainn_ctx* c, int64_t npos, const void* workspace, int64_t workspace_bytes) {
+    return site_workspace_ok("call_sites", workspace, workspace_bytes, sites_workspace_bytes(c, npos));
 }
 
 int launch_call_sites(explainn_ctx* c, const uint8_t* seq, int64_t start, int64_t npos, int64_t period,
                       int rc, const float* thr, int64_t* offsets, int32_t* pos, float* score,
                       int64_t capacity, void* workspace, hipStream_t s) {
-    const int ntiles = (int)sites_tiles(npos);
-    int* cnt = static_cast<int*>(workspace);
-    long long* tot = reinterpret_cast<long long*>(static_cast<char*>(workspace) +
-                                                  align256((int64_t)c->U * ntiles * (int64_t)sizeof(int)));
+    const SiteWorkspace w = site_workspace(workspace, c->U, npos);
     long long* off = reinterpret_cast<long long*>(offsets);
     const size_t sm = (size_t)c->k * 5 * sizeof(float4) + ((EXPLAINN_SITES_TILE + c->k - 1 + 15) & ~15);
-    const dim3 grid(ntiles, c->Uq);
-    hipLaunchKernelGGL(sites_kernel<SITES_COUNT>, grid, dim3(SITES_T), sm, s, seq, (long long)start, (int)npos,
-                       (long long)period, rc, c->Wt, c->alpha, c->shift, thr, cnt, (const long long*)nullptr,
-                       (int*)nullptr, (float*)nullptr, 0ll, c->U, c->k, ntiles, c->flags);
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(sites_scan_tiles_kernel, dim3(c->U), dim3(64), 0, s, cnt, tot, ntiles);
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(sites_scan_units_kernel, dim3(1), dim3(64), 0, s, tot, off, c->U);
-    LAUNCH_CHECK();
-    if (pos == nullptr || capacity <= 0) return EXPLAINN_OK;
-    hipLaunchKernelGGL(sites_kernel<SITES_EMIT>, grid, dim3(SITES_T), sm, s, seq, (long long)start, (int)npos,
-                       (long long)period, rc, c->Wt, c->alpha, c->shift, thr, cnt, off, pos, score,
-                       (long long)capacity, c->U, c->k, ntiles, c->flags);
-    LAUNCH_CHECK();
-    return EXPLAINN_OK;
+    return site_passes(c->U, npos, w, off, pos != nullptr && capacity > 0, s, [&](auto mode) {
+        hipLaunchKernelGGL(sites_kernel<decltype(mode)::value>, dim3(w.ntiles, c->Uq), dim3(SITES_T), sm, s, seq,
+                           (long long)start, (int)npos, (long long)period, rc, c->Wt, c->alpha, c->shift, thr, w.cnt,
+                           (const long long*)off, pos, score, (long long)capacity, c->U, c->k, w.ntiles, c->flags);
+    });
 }

@@ -22,6 +22,7 @@ There is no CPU path.
 import argparse
 import ctypes as C
 import sys
+import types
 
 import numpy as np
 
@@ -153,15 +154,10 @@ def _null(S, live_widths, scale, lo, bins, bg, pvalue, device):
     return PwmNull(tail, thr, scores, widths, scale, lo, bins, bg, pvalue)
 
 
-def _check_pvalue(pvalue):
-    if not 0.0 <= float(pvalue) <= 1.0:
-        raise ValueError("pvalue must be in [0, 1] (got %r)" % (pvalue,))
-
-
 def score_null(motifs, pvalue=1e-4, bg=None, pseudocount=0.1, bins=100, device=None):
     """quantise() and the exact null of every motif (explainn_pwm_null): a PwmNull.  Enqueued on the current
     stream; no host synchronisation."""
-    _check_pvalue(pvalue)
+    _sites.check_pvalue(pvalue)
     _, mats = motif_list(motifs)
     b = _background(bg)
     S, widths, scale, lo = quantise(mats, b, pseudocount, bins)
@@ -211,25 +207,6 @@ def _chunk_for(M, chunk_positions):
     return int(min(_sites.CHUNK_POSITIONS, tiles * _lib.SITES_TILE))
 
 
-def _assemble(blocks, M, widths, names, scale, lo):
-    """PwmCalls from per-chunk blocks [(first position, offsets (2M+1), pos, iscore, pvalue)] in ascending
-    order: a stable sort by row keeps ascending starts inside every (motif, strand)."""
-    if not blocks:
-        z = np.zeros(0)
-        return PwmCalls(np.zeros(M + 1, np.int64), z, z, z, widths, names, z, z)
-    row = np.concatenate([np.repeat(np.arange(2 * M, dtype=np.int64), np.diff(o)) for _, o, _, _, _ in blocks])
-    start = np.concatenate([np.asarray(p, dtype=np.int64) + p0 for p0, _, p, _, _ in blocks])
-    iscore = np.concatenate([b[3] for b in blocks])
-    pvalue = np.concatenate([b[4] for b in blocks])
-    order = np.argsort(row, kind="stable")
-    row, start, iscore, pvalue = row[order], start[order], iscore[order], pvalue[order]
-    unit = row >> 1
-    offsets = np.zeros(M + 1, dtype=np.int64)
-    np.cumsum(np.bincount(unit, minlength=M), out=offsets[1:])
-    score = iscore / scale[unit] + widths[unit] * lo[unit]          # a record's motif is never empty: scale > 0
-    return PwmCalls(offsets, start, 1 - 2 * (row & 1), score, widths, names, iscore, pvalue)
-
-
 def scan_motifs(motifs, codes, pvalue=1e-4, bg=None, pseudocount=0.1, bins=100, strands="both", period=0,
                 chunk_positions=None, max_sites=_sites.MAX_SITES, device=None):
     """Every site of every motif in `codes` at p-value <= pvalue: a PwmCalls.
@@ -250,7 +227,7 @@ def scan_motifs(motifs, codes, pvalue=1e-4, bg=None, pseudocount=0.1, bins=100, 
     from . import _lib
     from .strands import as_codes_1d
     _sites._check_args(strands, chunk_positions, max_sites, period)
-    _check_pvalue(pvalue)
+    _sites.check_pvalue(pvalue)
     names, mats = motif_list(motifs)
     data = as_codes_1d(codes)
     b = sequence_background(data, strands) if isinstance(bg, str) and bg == "sequence" else _background(bg)
@@ -265,7 +242,7 @@ def scan_motifs(motifs, codes, pvalue=1e-4, bg=None, pseudocount=0.1, bins=100, 
         nbytes = int(lib.explainn_pwm_sites_workspace_bytes(M, max(c for _, c in chunks)))
         ws = torch.empty((nbytes,), dtype=torch.uint8, device=device)
         offsets = torch.empty((2 * M + 1,), dtype=torch.int64, device=device)
-        both, counts = int(strands == "both"), np.zeros(M, dtype=np.int64)
+        both = int(strands == "both")
         with torch.cuda.device(device):
             stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
@@ -275,34 +252,32 @@ def scan_motifs(motifs, codes, pvalue=1e-4, bg=None, pseudocount=0.1, bins=100, 
                     null.widths.data_ptr(), M, wmax, null.thresholds.data_ptr(), null.tail.data_ptr(), int(bins),
                     offsets.data_ptr(), pos, score, pv, capacity, ws.data_ptr(), nbytes, stream))
 
-            for p0, cnt in chunks:
-                piece = data[p0:p0 + cnt + wmax - 1].to(device).contiguous()
+            def count(piece, cnt):
                 call(piece, cnt, None, None, None, 0)
-                offs = offsets.cpu().numpy()                                  # the one read of the totals
-                counts += np.diff(offs).reshape(M, 2).sum(axis=1)
-                if int(counts.sum()) > max_sites:
-                    raise ValueError("more than max_sites = %d sites (%d so far): lower pvalue, or raise max_sites"
-                                     % (max_sites, int(counts.sum())))
-                total = int(offs[-1])
-                if total == 0:
-                    continue
-                pos = torch.empty((total,), dtype=torch.int32, device=device)
-                isc = torch.empty((total,), dtype=torch.int32, device=device)
-                pv = torch.empty((total,), dtype=torch.float64, device=device)
-                call(piece, cnt, pos.data_ptr(), isc.data_ptr(), pv.data_ptr(), total)
-                blocks.append((p0, offs, pos.cpu().numpy(), isc.cpu().numpy(), pv.cpu().numpy()))
-    return _assemble(blocks, M, widths, names, scale, lo)
+                return lambda: offsets.cpu().numpy()
+
+            def emit(piece, cnt, total):
+                out = [torch.empty((total,), dtype=dt, device=device)
+                       for dt in (torch.int32, torch.int32, torch.float64)]      # pos, iscore, pvalue
+                call(piece, cnt, *[t.data_ptr() for t in out], total)
+                return lambda: [t.cpu().numpy() for t in out]
+
+            # one leg on the current stream: its rows are the site list's, 2 m + (strand < 0)
+            leg = types.SimpleNamespace(rows=np.arange(2 * M, dtype=np.int64), count=count, emit=emit)
+            pieces = ((p0, cnt, data[p0:p0 + cnt + wmax - 1].to(device).contiguous()) for p0, cnt in chunks)
+            blocks = _sites.site_blocks(pieces, [leg], M, max_sites, lambda *counted: _sites._too_many(
+                *counted, names=names, advice="To list fewer, lower pvalue; or raise max_sites"))
+    unit_offsets, start, strand, iscore, pv = _sites.assemble(blocks, M, (np.int32, np.float64))
+    unit = np.repeat(np.arange(M), np.diff(unit_offsets))
+    score = iscore / scale[unit] + widths[unit] * lo[unit]           # a record's motif is never empty: scale > 0
+    return PwmCalls(unit_offsets, start, strand, score, widths, names, iscore, pv)
 
 
 # ---------------------------------------------------------------- command line
 def bed_rows(seq_id, calls):
-    """Lines `SeqId start end name score strand pvalue` of one record's PwmCalls: 0-based half-open, end =
-    start + the motif's width, sorted by (start, motif, strand) with '+' before '-'."""
-    unit = calls.unit_ids()
-    order = np.lexsort((-calls.strand, unit, calls.start))
-    return ["%s\t%d\t%d\t%s\t%.6g\t%s\t%.6g\n" % (
-        seq_id, calls.start[i], calls.start[i] + calls.widths[unit[i]], calls.names[unit[i]], calls.score[i],
-        "+" if calls.strand[i] > 0 else "-", calls.pvalue[i]) for i in order]
+    """Lines `SeqId start end name score strand pvalue` of one record's PwmCalls: sites.bed_rows with the
+    motifs' names, end = start + the motif's width."""
+    return _sites.bed_rows(seq_id, calls, calls.names, calls.widths)
 
 
 def _bg_arg(text, sequence=True):

@@ -96,28 +96,60 @@ def _check_args(strands, chunk_positions, max_sites, period):
         raise ValueError("period must not be negative")
 
 
-def _too_many(counts, total, max_sites):
+def check_pvalue(pvalue):
+    if not 0.0 <= float(pvalue) <= 1.0:
+        raise ValueError("pvalue must be in [0, 1] (got %r)" % (pvalue,))
+
+
+def _too_many(counts, total, max_sites, names=None,
+              advice="A threshold of 0 makes every position a site: raise those thresholds, or max_sites"):
     top = np.argsort(-counts, kind="stable")[:5]
-    return ValueError(
-        "more than max_sites = %d sites (%d so far); the units with the most: %s.  A threshold of 0 makes "
-        "every position a site: raise those thresholds, or max_sites" % (
-            max_sites, total, ", ".join("filter%d (%d)" % (u, counts[u]) for u in top if counts[u] > 0)))
+    name = (lambda u: "filter%d" % u) if names is None else (lambda u: names[u])
+    return ValueError("more than max_sites = %d sites (%d so far); the units with the most: %s.  %s" % (
+        max_sites, total, ", ".join("%s (%d)" % (name(u), counts[u]) for u in top if counts[u] > 0), advice))
 
 
-def assemble(blocks, units, kernel_size):
-    """SiteCalls from per-call blocks [(strand, first position, offsets (units+1), pos, score), ...]
-    given forward strand first and chunks in ascending order within a strand: a stable sort by unit
-    keeps, inside every unit, '+' before '-' and ascending starts."""
+# ---------------------------------------------------------------- one site list from chunks and legs
+# A site list's rows are 2 * unit + (strand < 0).  A LEG is one device-side lister of some of those rows
+# (call_sites: a strand of a model, rows = its units; scan_motifs: all rows at once):
+#   leg.rows                     int64, the canonical row of each of the leg's own rows
+#   leg.count(piece, cnt)        enqueues the count of a chunk's cnt starts; returns a callable that finishes
+#                                it and gives the host offsets (len(rows) + 1)
+#   leg.emit(piece, cnt, total)  likewise for the records: (pos relative to the chunk, *columns)
+def site_blocks(pieces, legs, units, max_sites, too_many):
+    """Blocks (first position, rows, offsets, pos, *columns) of every chunk and leg.  pieces: (first start,
+    number of starts, the chunk's codes with the overlap behind them) in ascending order; what has to happen
+    around a chunk happens in that iterator.  Per chunk every leg's count is started before any is finished,
+    the counts are added (more than max_sites records: raise too_many(counts per unit, total) before
+    anything of the chunk is emitted), and the same for emit, into buffers of exactly the counted size."""
+    counts, blocks = np.zeros(2 * units, dtype=np.int64), []
+    for p0, cnt, piece in pieces:
+        offs = [finish() for finish in [leg.count(piece, cnt) for leg in legs]]     # the one read of the totals
+        for leg, o in zip(legs, offs):
+            counts[leg.rows] += np.diff(o)
+        if int(counts.sum()) > max_sites:
+            raise too_many(counts.reshape(units, 2).sum(axis=1), int(counts.sum()), int(max_sites))
+        emits = [(leg, o, leg.emit(piece, cnt, int(o[-1]))) for leg, o in zip(legs, offs) if int(o[-1]) > 0]
+        for leg, o, finish in emits:
+            blocks.append((p0, leg.rows, o) + tuple(finish()))
+    return blocks
+
+
+def assemble(blocks, units, columns):
+    """(offsets over units, start int64, strand int8, *columns) of site_blocks' blocks, chunks in ascending
+    order; columns: the dtype of each record column.  One stable sort by canonical row keeps, inside every
+    unit, '+' before '-' and ascending starts."""
     if not blocks:
-        return SiteCalls(np.zeros(units + 1, np.int64), [], [], [], kernel_size)
-    unit = np.concatenate([np.repeat(np.arange(units, dtype=np.int64), np.diff(o)) for _, _, o, _, _ in blocks])
-    start = np.concatenate([np.asarray(p, dtype=np.int64) + p0 for _, p0, _, p, _ in blocks])
-    strand = np.concatenate([np.full(len(p), s, dtype=np.int8) for s, _, _, p, _ in blocks])
-    score = np.concatenate([np.asarray(sc, dtype=np.float32) for _, _, _, _, sc in blocks])
-    order = np.argsort(unit, kind="stable")
+        return (np.zeros(units + 1, np.int64), np.zeros(0, np.int64), np.zeros(0, np.int8)) + tuple(
+            np.zeros(0, dt) for dt in columns)
+    row = np.concatenate([np.repeat(np.asarray(rows, dtype=np.int64), np.diff(o)) for _, rows, o, *_ in blocks])
+    start = np.concatenate([np.asarray(b[3], dtype=np.int64) + b[0] for b in blocks])
+    order = np.argsort(row, kind="stable")
+    per_row = np.bincount(row, minlength=2 * units)
     offsets = np.zeros(units + 1, dtype=np.int64)
-    np.cumsum(np.bincount(unit, minlength=units), out=offsets[1:])
-    return SiteCalls(offsets, start[order], strand[order], score[order], kernel_size)
+    np.cumsum(per_row.reshape(units, 2).sum(axis=1), out=offsets[1:])
+    return (offsets, start[order], np.repeat(np.tile(np.array([1, -1], np.int8), units), per_row)) + tuple(
+        np.concatenate([np.asarray(b[4 + i], dtype=dt) for b in blocks])[order] for i, dt in enumerate(columns))
 
 
 def concat_units(a, b):
@@ -128,6 +160,31 @@ def concat_units(a, b):
     return SiteCalls(np.concatenate([a.offsets, b.offsets[1:] + a.offsets[-1]]), np.concatenate([a.start, b.start]),
                      np.concatenate([a.strand, b.strand]), np.concatenate([a.score, b.score]),
                      max(a.kernel_size, b.kernel_size), pvalue)
+
+
+class _StrandLeg:
+    """One strand of a model (or of its eval_replica()) on one stream: rows = the units."""
+
+    def __init__(self, model, stream, thr, period, strand):
+        self.model, self.stream, self.thr, self.period, self.rc = model, stream, thr, period, strand < 0
+        self.rows = 2 * np.arange(model._units(), dtype=np.int64) + int(self.rc)
+
+    def _launch(self, piece, cnt, keep, **kwargs):
+        with torch.cuda.stream(self.stream):
+            out = self.model._launch_call_sites(piece, self.thr, 0, cnt, self.period, self.rc, **kwargs)
+            host = [t.to("cpu", non_blocking=True) for t in out[keep]]
+
+        def finish():
+            self.stream.synchronize()
+            return [t.numpy() for t in host]
+        return finish
+
+    def count(self, piece, cnt):
+        finish = self._launch(piece, cnt, slice(0, 1))
+        return lambda: finish()[0]
+
+    def emit(self, piece, cnt, total):
+        return self._launch(piece, cnt, slice(1, 3), capacity=total)
 
 
 def call_sites(model, codes, thresholds, strands="both", chunk_positions=None, max_sites=MAX_SITES, period=0,
@@ -159,46 +216,30 @@ def call_sites(model, codes, thresholds, strands="both", chunk_positions=None, m
         raise NotImplementedError("calling sites is an eval-mode export path; call model.eval()")
     device = model._device()
     both = strands == "both"
-    blocks = {1: [], -1: []}
-    counts = np.zeros(units, dtype=np.int64)
+    blocks = []
     if n_positions > 0:
         thr = thr.to(device)
         chunk = int(chunk_positions) if chunk_positions is not None else CHUNK_POSITIONS
-        # count and emit of the two strands interleave, so the legs are driven here, not by ts.run
+        # count and emit of the two strands interleave, so the legs are driven by site_blocks, not by ts.run
         with TwoStrands(model, both) as ts:
-            cur, rep, side = ts.cur, ts.rep, ts.side
-            legs = [(1, model, cur)] + ([(-1, rep, side)] if both else [])
-            for p0, cnt in position_chunks(n_positions, chunk, period):
-                piece = data[p0:p0 + cnt + k - 1].to(device).contiguous()
-                if both:
-                    side.wait_stream(cur)                       # the chunk and thresholds are on the device
-                    piece.record_stream(side)
-                    thr.record_stream(side)
-                offs = {}
-                for s, m, stream in legs:                       # count, both strands in flight
-                    with torch.cuda.stream(stream):
-                        offs[s] = m._launch_call_sites(piece, thr, 0, cnt, period, s < 0)[0].to(
-                            "cpu", non_blocking=True)
-                for s, m, stream in legs:
-                    stream.synchronize()                        # the one read of the totals
-                    counts += np.diff(offs[s].numpy())
-                if int(counts.sum()) > max_sites:
-                    raise _too_many(counts, int(counts.sum()), int(max_sites))
-                out = {}
-                for s, m, stream in legs:                       # emit, into buffers of exactly that size
-                    total = int(offs[s][-1])
-                    if total == 0:
-                        continue
-                    with torch.cuda.stream(stream):
-                        _, pos, score = m._launch_call_sites(piece, thr, 0, cnt, period, s < 0, capacity=total)
-                        out[s] = (pos.to("cpu", non_blocking=True), score.to("cpu", non_blocking=True))
-                for s, m, stream in legs:
-                    if s in out:
-                        stream.synchronize()
-                        blocks[s].append((s, p0, offs[s].numpy(), out[s][0].numpy(), out[s][1].numpy()))
-                if both:
-                    cur.wait_stream(side)
-    calls = assemble(blocks[1] + blocks[-1], units, k)
+            cur, side = ts.cur, ts.side
+
+            def pieces():
+                for p0, cnt in position_chunks(n_positions, chunk, period):
+                    piece = data[p0:p0 + cnt + k - 1].to(device).contiguous()
+                    if both:
+                        side.wait_stream(cur)                   # the chunk and thresholds are on the device
+                        piece.record_stream(side)
+                        thr.record_stream(side)
+                    yield p0, cnt, piece
+                    if both:
+                        cur.wait_stream(side)
+
+            legs = [_StrandLeg(model, cur, thr, period, 1)]
+            if both:
+                legs.append(_StrandLeg(ts.rep, side, thr, period, -1))
+            blocks = site_blocks(pieces(), legs, units, max_sites, _too_many)
+    calls = SiteCalls(*assemble(blocks, units, (np.float32,)), k)
     if null is not None:
         calls.pvalue = null.pvalue(calls.unit_ids(), calls.score)
     return calls
@@ -251,8 +292,7 @@ class ActivationNull:
         """(units,) float32: per unit the smallest float16 value t such that at most
         floor(pvalue * total) of the null's activations are > t -- call_sites with it calls at most that
         many of the background's positions; +inf for a unit without a null."""
-        if not 0.0 <= float(pvalue) <= 1.0:
-            raise ValueError("pvalue must be in [0, 1] (got %r)" % (pvalue,))
+        check_pvalue(pvalue)
         return _null_stats(self.hist, pvalue, want_thresholds=True)[2].cpu().numpy()
 
     def pvalue(self, unit_ids, scores):
@@ -364,19 +404,21 @@ def call_sites_records(model, records, thresholds, **kwargs):
         yield rid, call_sites(model, codes, thresholds, **kwargs)
 
 
-def bed_rows(seq_id, calls):
-    """BED6 lines of one record: `SeqId start end filter<u> score strand`, 0-based half-open, sorted by
-    (start, filter, strand) with '+' before '-'.  Calls that carry p-values get them as a seventh column."""
+def bed_rows(seq_id, calls, names=None, widths=None):
+    """BED6 lines of one record: `SeqId start end name score strand`, 0-based half-open, sorted by
+    (start, unit, strand) with '+' before '-'.  name: names[unit], filter<u> without names; end: start +
+    widths[unit], start + the kernel size without widths.  Calls that carry p-values get them as a seventh
+    column."""
     unit = calls.unit_ids()
     order = np.lexsort((-calls.strand, unit, calls.start))
-    k = calls.kernel_size
-    if calls.pvalue is not None:
-        return ["%s\t%d\t%d\tfilter%d\t%.6g\t%s\t%.6g\n" % (
-            seq_id, calls.start[i], calls.start[i] + k, unit[i], calls.score[i],
-            "+" if calls.strand[i] > 0 else "-", calls.pvalue[i]) for i in order]
-    return ["%s\t%d\t%d\tfilter%d\t%.6g\t%s\n" % (seq_id, calls.start[i], calls.start[i] + k, unit[i],
-                                                calls.score[i], "+" if calls.strand[i] > 0 else "-")
-            for i in order]
+    rows = []
+    for i in order:
+        u = unit[i]
+        row = "%s\t%d\t%d\t%s\t%.6g\t%s" % (
+            seq_id, calls.start[i], calls.start[i] + (calls.kernel_size if widths is None else widths[u]),
+            "filter%d" % u if names is None else names[u], calls.score[i], "+" if calls.strand[i] > 0 else "-")
+        rows.append(row + ("\n" if calls.pvalue is None else "\t%.6g\n" % calls.pvalue[i]))
+    return rows
 
 
 def write_thresholds(path, thresholds):

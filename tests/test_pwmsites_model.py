@@ -144,6 +144,14 @@ def _pwm_calls(c, names):
                              c["pvalue"])
 
 
+def _assembled(blocks, widths, scale, lo):
+    """PwmCalls of site_blocks' blocks, as scan_motifs makes them."""
+    offsets, start, strand, iscore, pvalue = sites.assemble(blocks, 3, (np.int32, np.float64))
+    unit = np.repeat(np.arange(3), np.diff(offsets))
+    return pwmsites.PwmCalls(offsets, start, strand, iscore / scale[unit] + widths[unit] * lo[unit], widths,
+                             list("abc"), iscore, pvalue)
+
+
 def test_assembly_of_chunks_equals_the_whole():
     mats, codes = _model_case()
     want = pm.calls(mats, codes, 1e-2)
@@ -153,12 +161,12 @@ def test_assembly_of_chunks_equals_the_whole():
     for p0, cnt in sites.position_chunks(len(codes), 97):
         off, pos, isc = pm.scan(S, lw, want["thresholds"], codes[:p0 + cnt + S.shape[1] - 1], p0, cnt)
         row = np.repeat(np.arange(6), np.diff(off))
-        blocks.append((p0, off, pos, isc, want["tail"][row // 2, isc]))
-    got = pwmsites._assemble(blocks, 3, widths, list("abc"), scale, lo)
+        blocks.append((p0, np.arange(6), off, pos, isc, want["tail"][row // 2, isc]))
+    got = _assembled(blocks, widths, scale, lo)
     for key in ("offsets", "start", "strand", "iscore", "score", "pvalue"):
         assert np.array_equal(getattr(got, key), want[key]), key
     assert got.units == 3 and got.kernel_size == 11 and got.names == list("abc") and len(got) == len(want["start"])
-    empty = pwmsites._assemble([], 3, widths, list("abc"), scale, lo)
+    empty = _assembled([], widths, scale, lo)
     assert len(empty) == 0 and empty.units == 3 and empty.pvalue.shape == (0,)
 
 

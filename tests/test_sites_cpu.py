@@ -36,10 +36,15 @@ def test_chunks_with_a_period_begin_on_record_boundaries():
 
 def _calls():
     # unit 0: '+' 5, 9 then '-' 5; unit 1: none; unit 2: '-' 0, '+' would precede
-    blocks = [(1, 0, np.array([0, 1, 1, 1]), np.array([5], np.int32), np.array([1.5], np.float32)),
-              (1, 8, np.array([0, 1, 1, 2]), np.array([1, 4], np.int32), np.array([2.5, 0.25], np.float32)),
-              (-1, 0, np.array([0, 1, 1, 2]), np.array([5, 0], np.int32), np.array([3.5, 0.5], np.float32))]
-    return sites.assemble(blocks, 3, 4)
+    fwd, rev = 2 * np.arange(3), 2 * np.arange(3) + 1             # a strand's rows: 2 * unit + (strand < 0)
+    blocks = [(0, fwd, np.array([0, 1, 1, 1]), np.array([5], np.int32), np.array([1.5], np.float32)),
+              (0, rev, np.array([0, 1, 1, 2]), np.array([5, 0], np.int32), np.array([3.5, 0.5], np.float32)),
+              (8, fwd, np.array([0, 1, 1, 2]), np.array([1, 4], np.int32), np.array([2.5, 0.25], np.float32))]
+    return _site_calls(blocks)
+
+
+def _site_calls(blocks):
+    return sites.SiteCalls(*sites.assemble(blocks, 3, (np.float32,)), 4)
 
 
 def test_assemble_and_unit():
@@ -55,7 +60,7 @@ def test_assemble_and_unit():
     assert c.unit_ids().tolist() == [0, 0, 0, 2, 2]
     with pytest.raises(IndexError):
         c.unit(3)
-    empty = sites.assemble([], 3, 4)
+    empty = _site_calls([])
     assert len(empty) == 0 and empty.offsets.tolist() == [0, 0, 0, 0]
     with pytest.raises(ValueError):
         sites.SiteCalls([0, 2], [1], [1], [1.0], 4)
@@ -68,7 +73,7 @@ def test_bed_rows_sorted_by_start_filter_strand():
                     "chrT\t5\t9\tfilter0\t3.5\t-\n",
                     "chrT\t9\t13\tfilter0\t2.5\t+\n",
                     "chrT\t12\t16\tfilter2\t0.25\t+\n"]
-    assert sites.bed_rows("x", sites.assemble([], 3, 4)) == []
+    assert sites.bed_rows("x", _site_calls([])) == []
 
 
 def test_argument_errors():
