@@ -123,6 +123,7 @@ SIGNATURES = {
     "explainn_backward_input": (_i, [_ctx, _fp, _i, _pp, _gp, _i, _fp, _fp]),
     "explainn_ism_workspace_bytes": (_i64, [_ctx, _i]),
     "explainn_ism": (_i, [_ctx, _fp, _i, _pp, _fp, _fp, _fp, _i64, _fp]),
+    "explainn_evolve_pick": (_i, [_fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, C.c_float, _fp, _fp, _fp, _fp, _fp]),
     "explainn_integrated_gradients_workspace_bytes": (_i64, [_ctx, _i]),
     "explainn_integrated_gradients": (_i, [_ctx, _fp, _i, _pp, _i, _fp, _fp, _i, _fp, _fp, _fp, _fp, _i64, _fp]),
     "explainn_loss_grad": (_i, [_ctx, _i, _fp, _fp, _i, _fp, _fp, _fp]),

@@ -946,6 +946,74 @@ class ExplaiNN(_Model):
             self._settle(read)
         return logits, delta
 
+    def evolve(self, codes, weights, rounds=10, mutable=None, both_strands=False, lock=True, min_gain=0.0):
+        """Greedy in-silico evolution in eval mode: `rounds` times, apply to every sequence the single
+        substitution that raises sum_t weights[b,t] * logit_t the most -- the mean of the two strands'
+        logits with both_strands.  A round is in_silico_mutagenesis() per strand and one selection
+        launch (explainn_evolve_pick) that reduces the maps, picks the winner and edits the codes on the
+        device.  Maps, codes, mask and log stay there; the rounds are a Python loop, so every
+        in_silico_mutagenesis call allocates its workspace and map and validates its input as usual
+        (validate_input: a read of the sticky flag, a host sync, on the first calls and every
+        VALIDATE_EVERY-th).  codes: a contiguous uint8 (B,L) tensor
+        of base codes on the model's device, EDITED IN PLACE.  weights: fp32 (T,) or (B,T).  mutable:
+        None or a (B,L) mask, 0 = the position stays as it is.  lock: a substituted position is not
+        revisited.  min_gain >= 0: a round moves a sequence only for a gain above it.  Ties go to the
+        lowest position, then the lowest base.  Returns (pos int32, ref uint8, alt uint8, gain float64,
+        each (rounds, B), and logits (rounds+1, S, B, T) fp32, S = 2 (forward, reverse) with
+        both_strands): pos -1 and ref = alt = 255 where a round found no move; logits[r, s] is
+        forward() on the codes before round r (logits[rounds]: the result), bit for bit."""
+        if self.training:
+            raise RuntimeError("evolve is an eval-mode path; call model.eval()")
+        rounds = int(rounds)
+        if rounds < 1:
+            raise ValueError("evolve needs rounds >= 1 (got %d)" % rounds)
+        min_gain = float(min_gain)
+        if not (min_gain >= 0.0 and min_gain != float("inf")):
+            raise ValueError("min_gain must be finite and not negative (got %r)" % min_gain)
+        if self.dense_input:
+            raise ValueError("evolve substitutes base codes (dense_input is True)")
+        dev = self._device()
+        T, L = self._options["n_features"], self._options["sequence_length"]
+        if not torch.is_tensor(codes) or codes.dtype != torch.uint8 or codes.dim() != 2 or codes.shape[1] != L \
+                or not codes.is_contiguous():
+            raise ValueError("codes must be a contiguous uint8 tensor of shape (B, %d)" % L)
+        if codes.device != dev:
+            raise RuntimeError("input is on %s but the model is on %s" % (codes.device, dev))
+        B, S = codes.shape[0], 2 if both_strands else 1
+        w = torch.as_tensor(weights).to(device=dev, dtype=torch.float32).contiguous()
+        if tuple(w.shape) not in ((T,), (B, T)):
+            raise ValueError("weights must have shape (%d,) or (%d, %d), got %s" % (T, B, T, tuple(w.shape)))
+        mask = None
+        if mutable is not None:
+            if not torch.is_tensor(mutable) or tuple(mutable.shape) != (B, L):
+                raise ValueError("mutable must be a tensor of shape (%d, %d)" % (B, L))
+            mask = (mutable.to(dev) != 0).to(torch.uint8).contiguous()       # the working copy locking closes
+        elif lock:
+            mask = torch.ones(B, L, device=dev, dtype=torch.uint8)
+        pos = torch.empty(rounds, B, device=dev, dtype=torch.int32)
+        ref = torch.empty(rounds, B, device=dev, dtype=torch.uint8)
+        alt = torch.empty(rounds, B, device=dev, dtype=torch.uint8)
+        gain = torch.empty(rounds, B, device=dev, dtype=torch.float64)
+        logits = torch.empty(rounds + 1, S, B, T, device=dev, dtype=torch.float32)
+        if B == 0:
+            return pos, ref, alt, gain, logits
+        lib = _lib.load()
+        with torch.no_grad():
+            for r in range(rounds):
+                maps = []
+                for s in range(S):
+                    logits[r, s], delta = self.in_silico_mutagenesis(BaseCodes(codes, bool(s)))
+                    maps.append(delta)
+                with torch.cuda.device(dev):
+                    _lib.check(lib.explainn_evolve_pick(
+                        maps[0].data_ptr(), maps[1].data_ptr() if S == 2 else None, codes.data_ptr(),
+                        mask.data_ptr() if mask is not None else None, w.data_ptr(), int(w.dim() == 2), B, T, L,
+                        int(bool(lock)), min_gain, pos[r].data_ptr(), ref[r].data_ptr(), alt[r].data_ptr(),
+                        gain[r].data_ptr(), self._stream(dev)))
+            for s in range(S):
+                logits[rounds, s] = self.forward(BaseCodes(codes, bool(s)))
+        return pos, ref, alt, gain, logits
+
     def integrated_gradients_workspace_bytes(self, B):
         """Bytes of workspace integrated_gradients() runs a batch of B sequences with
         (explainn_integrated_gradients_workspace_bytes); the value for B = 64 is the smallest
@@ -1387,6 +1455,9 @@ class ExplaiNNBank(ExplaiNN):
 
     def integrated_gradients(self, x, dlogits, baseline="zero", steps=32, workspace=None):
         raise self._member_only("integrated_gradients")
+
+    def evolve(self, codes, weights, rounds=10, mutable=None, both_strands=False, lock=True, min_gain=0.0):
+        raise self._member_only("evolve")
 
     # -- plumbing --------------------------------------------------------------------------
     def _units(self):

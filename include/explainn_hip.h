@@ -209,6 +209,30 @@ int explainn_integrated_gradients(explainn_ctx* ctx, const float* x, int B, cons
                                   int steps, float* ig, float* logits_x, float* logits_base,
                                   void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Greedy in-silico evolution: one round's selection.  In-silico evolution changes each sequence toward
+ * an objective one substitution per round -- take the ISM maps, apply the best admissible single
+ * substitution, repeat.  The reference has no such call.
+ *
+ * The objective of base a at position p of sequence b (coordinates of the given strand), fp64:
+ *   O_f[a,p] = sum_t (double)w[b,t] * (double)delta_f[b,t,a,p]            t ascending
+ *   O_r[a,p] = sum_t (double)w[b,t] * (double)delta_r[b,t,3-a,L-1-p]      both strands only
+ *   gain     = O_f, or 0.5 * (O_f + O_r) with both strands
+ * delta_fwd / delta_rev: device fp32 (B,T,4,L), explainn_ism's maps of the batch staged with
+ * reverse_complement = 0 / 1 (the reverse map is in its own strand's coordinates, see explainn_ism);
+ * delta_rev NULL = one strand.  weights: device fp32, (T) for every sequence or, weights_per_row != 0,
+ * (B,T).  A candidate is admissible when a is not the base at p (at an N, any code above 3, all four
+ * bases are), mutable_mask[b,p] != 0 (NULL: every position) and gain > min_gain, min_gain >= 0 and
+ * finite (else EXPLAINN_E_ARG).  The winner is the largest gain, then the lowest p, then the lowest a:
+ * it is written into codes (B,L, in place), logged in pos / ref / alt (ref = the byte it replaced) /
+ * gain, (B) each, and, with lock != 0, its position is closed in mutable_mask (in place; with a NULL
+ * mask there is nothing to lock), so a later round cannot revisit it.  A sequence without an admissible
+ * candidate logs pos = -1, ref = alt = 255, gain = 0 and keeps its codes.  No context, no workspace, no
+ * allocation, no host sync, no atomics: one launch on `stream`. */
+int explainn_evolve_pick(const float* delta_fwd, const float* delta_rev, uint8_t* codes,
+                         uint8_t* mutable_mask, const float* weights, int weights_per_row, int B, int T, int L,
+                         int lock, float min_gain, int32_t* pos, uint8_t* ref, uint8_t* alt, double* gain,
+                         void* stream);
+
 /* get_loss (architectures/__init__.py:446-456), mean reduction, fused with its gradient:
  * loss_out (1 float, device) and dlogits (B,T, device). */
 int explainn_loss_grad(explainn_ctx* ctx, int loss_kind, const float* logits, const float* targets,

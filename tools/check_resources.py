@@ -84,7 +84,9 @@ SITES = [r"^sites_kernel<0>", r"^sites_kernel<1>", r"^sites_scan_tiles_kernel", 
 PWMSITES = [r"^pwm_null_kernel", r"^pwm_sites_kernel<0>", r"^pwm_sites_kernel<1>"]
 # known-motif enrichment (pwmbest.hip): the per-record best PWM site
 PWMBEST = [r"^pwm_best_kernel"]
-GATED = (C2_STEP + INPUT_GRAD + ISM + PATHGRAD + METRICS + SCAN + VARIANTS + HAPLOTYPES + SHUFFLE + MOTIFS + ACTNULL +
+# greedy in-silico evolution (evolve.hip): one round's selection
+EVOLVE = [r"^evolve_select_kernel"]
+GATED = (C2_STEP + INPUT_GRAD + ISM + EVOLVE + PATHGRAD + METRICS + SCAN + VARIANTS + HAPLOTYPES + SHUFFLE + MOTIFS + ACTNULL +
          SPACING + ENRICH + CENTRAL + SITES + PWMSITES + PWMBEST)
 
 
