@@ -21,6 +21,8 @@ SCAN_AUTO, SCAN_WINDOWS, SCAN_SHARED = 0, 1, 2
 MOTIF_MAX_WIDTH = 64      # EXPLAINN_MOTIF_MAX_WIDTH: columns per motif of explainn_motif_compare
 MOTIF_MAX_BINS = 128      # EXPLAINN_MOTIF_MAX_BINS: score bins per column of explainn_motif_significance
 MOTIF_NO_SCORE = 255      # EXPLAINN_MOTIF_NO_SCORE: a colscore entry without a column
+LINKAGE_SINGLE, LINKAGE_COMPLETE, LINKAGE_AVERAGE = 0, 1, 2
+MOTIF_TREE_MAX_LEAVES = 12288   # EXPLAINN_MOTIF_TREE_MAX_LEAVES: motifs of one explainn_motif_tree call
 SITES_TILE = 1024        # EXPLAINN_SITES_TILE: start positions per workgroup of explainn_call_sites
 PWM_GROUP = 16           # EXPLAINN_PWM_GROUP: motifs per workgroup of explainn_pwm_sites
 ACT_BINS = 32768         # EXPLAINN_ACT_BINS: one bin per non-negative float16 bit pattern
@@ -168,6 +170,10 @@ SIGNATURES = {
     "explainn_motif_significance_workspace_bytes": (_i64, [_i, _i, _i, _i, _i]),
     "explainn_motif_significance": (_i, [_fp, _fp, _i, _fp, _fp, _i, _i, C.c_float, _i, _i, _i, _fp, _fp, _fp, _fp,
                                          _fp, _fp, _i64, _fp]),
+    "explainn_motif_tree_workspace_bytes": (_i64, [_i, _i]),
+    "explainn_motif_tree": (_i, [_fp, _fp, _fp, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _i64, _fp]),
+    "explainn_motif_tree_cut": (_i, [_fp, _fp, _fp, _fp, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp]),
+    "explainn_motif_tree_pool": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _fp, _fp, _fp]),
     "explainn_pwm_null": (_i, [_fp, _fp, _i, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _fp,
                                _fp, _fp]),
     "explainn_pwm_sites_workspace_bytes": (_i64, [_i, _i64]),

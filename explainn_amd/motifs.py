@@ -13,6 +13,12 @@ writes the filters in the format an external Tomtom reads.
 
   python -m explainn_amd.motifs annotate MOTIFS DB -o OUT.tsv [--by pvalue [--max-qvalue Q] [--bins B]]
   python -m explainn_amd.motifs cluster MOTIFS [MOTIFS ...] -o OUT.tsv
+  python -m explainn_amd.motifs merge MOTIFS [MOTIFS ...] -o OUT.meme [--linkage average|complete|single]
+      [--min-ncor 0.4] [--min-support 0.5] [--min-ic 0] [--tree OUT.nwk] [--table OUT.tsv]
+`tree` agglomerates a self-comparison into a dendrogram on the device (csrc/motiftree.hip; single, complete or
+average linkage of Ncor quantised to 2^-20, so the tree is the same on every run), `MotifTree.cut` cuts it and
+places every member in its cluster's frame from the alignments `compare` found, and `merge` sums the placed
+count matrices per cluster: the non-redundant motifs of a model ("Motif tree").
 MOTIFS / DB: a MEME file, a JASPAR file (the layout interpret.format_jaspar writes, any number of motifs),
 or a directory of filter*.jaspar.
 """
@@ -501,7 +507,276 @@ def reproducibility(pfms, nsites=None, min_ncor=0.4, min_cor=0.6, result=None, *
     return has.sum(dim=2).cpu().numpy().astype(np.int64), partner.cpu().numpy().astype(np.int64)
 
 
+# ---------------------------------------------------------------- motif tree and merged cluster motifs
+LINKAGES = {"single": 0, "complete": 1, "average": 2}
+TREE_SCALE = 1 << 20          # linkage values are Ncor quantised to 2^-20
+MAX_LEAVES = 12288            # EXPLAINN_MOTIF_TREE_MAX_LEAVES: the per-slot cache of the tree kernel is in LDS
+
+
+def _cut_threshold(min_ncor):
+    """min_ncor on the tree's integer scale: a step is above the cut when sum >= threshold * pairs."""
+    if not float(min_ncor) > 0:
+        raise ValueError("min_ncor must be positive (got %r)" % (min_ncor,))
+    return min(int(np.ceil(float(min_ncor) * TREE_SCALE)), (1 << 31) - 1)
+
+
+class MotifTree:
+    """The dendrogram of `tree`.  log int32 (M-1,8): lo, hi, leaves of the merged cluster, leaf_i, leaf_j, F, H,
+    0 per step; link int64 (M-1,2): the linkage as (sum, pairs), height = sum / pairs / 2^20; gone int32 [M]: the
+    step that merged slot c away (-1: never); flips, shifts int32 [M]: every leaf in the root's frame (meaningful
+    as far as the steps had an overlap); widths int32 [M].  Tensors, on the device when `tree` made them."""
+
+    def __init__(self, log, link, gone, flips, shifts, widths, linkage):
+        self.log, self.link, self.gone, self.flips, self.shifts = log, link, gone, flips, shifts
+        self.widths, self.linkage = widths, linkage
+
+    @property
+    def M(self):
+        return int(self.widths.shape[0])
+
+    @property
+    def heights(self):
+        """float64 [M-1] on the host: the linkage (an Ncor) at which each step merged; never increasing."""
+        link = self.link.cpu().numpy()
+        return link[:, 0].astype(np.float64) / link[:, 1].astype(np.float64) / TREE_SCALE
+
+    def _nodes(self):
+        """Per step the node ids (leaves 0..M-1, step t makes node M + t) of its two clusters."""
+        log = self.log.cpu().numpy()
+        node = list(range(self.M))
+        out = np.zeros((len(log), 2), dtype=np.int64)
+        for t, rec in enumerate(log):
+            out[t] = node[rec[0]], node[rec[1]]
+            node[rec[0]] = self.M + t
+        return out, log
+
+    def linkage_matrix(self):
+        """The (M-1, 4) float64 matrix scipy.cluster.hierarchy.dendrogram draws: the two node ids, the distance
+        1 - height, the leaves of the new node."""
+        nodes, log = self._nodes()
+        out = np.zeros((len(log), 4), dtype=np.float64)
+        out[:, :2] = nodes
+        out[:, 2] = 1.0 - self.heights
+        out[:, 3] = log[:, 2]
+        return out
+
+    def newick(self, names=None):
+        """The tree as Newick text, branch lengths in distance 1 - height; names default to the leaf numbers."""
+        names = [str(i) for i in range(self.M)] if names is None else [re.sub(r"[\s():;,\[\]']", "_", str(n))
+                                                                      for n in names]
+        if len(names) != self.M:
+            raise ValueError("newick needs one name per motif")
+        if self.M == 0:
+            return ";"
+        log = self.log.cpu().numpy()
+        dist = 1.0 - self.heights
+        text, depth = list(names), [0.0] * self.M
+        for t, rec in enumerate(log):
+            lo, hi = int(rec[0]), int(rec[1])
+            text[lo] = "(%s:%.6g,%s:%.6g)" % (text[lo], dist[t] - depth[lo], text[hi], dist[t] - depth[hi])
+            depth[lo] = dist[t]
+        return text[0] + ";"
+
+    def _cut(self, min_ncor):
+        import ctypes as C
+
+        import torch
+
+        from . import _lib
+        thr = _cut_threshold(min_ncor)
+        dev = self.widths.device
+        if dev.type != "cuda":
+            raise RuntimeError("MotifTree.cut runs only on a HIP device (there is no CPU fallback)")
+        M = self.M
+        slots, flips, shifts, lo, hi = (torch.empty((M,), dtype=torch.int32, device=dev) for _ in range(5))
+        if M:
+            lib = _lib.load()
+            with torch.cuda.device(dev):
+                _lib.check(lib.explainn_motif_tree_cut(
+                    self.log.data_ptr(), self.link.data_ptr(), self.gone.data_ptr(), self.widths.data_ptr(), M, thr,
+                    slots.data_ptr(), flips.data_ptr(), shifts.data_ptr(), lo.data_ptr(), hi.data_ptr(),
+                    C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        uniq, labels = torch.unique(slots, sorted=True, return_inverse=True)      # a slot is its smallest member
+        spans = (hi - lo)[uniq.long()].cpu().numpy().astype(np.int32)             # the host synchronisation
+        return labels.to(torch.int64), flips, shifts, spans, slots, uniq.to(torch.int32)
+
+    def cut(self, min_ncor=0.4):
+        """The clusters the steps with height >= min_ncor leave (min_ncor is taken on the tree's scale:
+        ceil(min_ncor 2^20) / 2^20).  Returns (labels int64 [M], numbered 0.. in the order of the smallest member;
+        flips, shifts int32 [M]: frame column shifts + c of a member's cluster holds column c of the member,
+        reverse-complemented when flips is 1, the smallest shift of a cluster being 0 -- device tensors; spans
+        int32 [C] on the host: the columns of each cluster's frame).  One host synchronisation."""
+        return self._cut(min_ncor)[:4]
+
+
+def tree(result, widths=None, linkage="average", max_bytes=2 << 30):
+    """The agglomerative tree of a self-comparison (compare(motifs)): M - 1 merges of the two clusters with the
+    largest linkage -- single (max), complete (min) or average Ncor over the leaf pairs, Ncor quantised to
+    2^-20 so that every value is exact -- ties to the smaller slots (a cluster's slot is its smallest member).
+    Only the upper triangle of `result` is read.  widths: int32 [M], the motif widths the placements need
+    (default: the overlap of every motif with itself, which is its width unless it has no variance).  One
+    workgroup runs the loop on the device (csrc/motiftree.hip); nothing is synchronised.  ValueError when the
+    two M x M work matrices exceed max_bytes or M exceeds what the kernel holds."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib
+    M = int(result.ncor.shape[0])
+    if tuple(result.ncor.shape) != (M, M):
+        raise ValueError("tree needs a self-comparison (M, M)")
+    if linkage not in LINKAGES:
+        raise ValueError("linkage must be one of %s (got %r)" % (", ".join(sorted(LINKAGES)), linkage))
+    if M > 65535:
+        raise ValueError("tree takes at most 65535 motifs: a leaf has 16 bits of the packed key (got %d)" % M)
+    if 16 * M * M > int(max_bytes):
+        raise ValueError("the two %d x %d work matrices take %d bytes, more than max_bytes = %d"
+                         % (M, M, 16 * M * M, int(max_bytes)))
+    if M > MAX_LEAVES:
+        raise ValueError("tree takes at most %d motifs: the kernel caches one entry per slot in LDS (got %d)"
+                         % (MAX_LEAVES, M))
+    dev = result.ncor.device
+    if dev.type != "cuda":
+        raise RuntimeError("motifs.tree runs only on a HIP device (there is no CPU fallback)")
+    ncor = result.ncor.to(torch.float32).contiguous()
+    align = torch.stack([result.offset, result.strand, result.overlap], dim=-1).to(torch.int16).contiguous()
+    if widths is None:
+        widths = torch.diagonal(result.overlap)
+    widths = torch.as_tensor(widths).to(device=dev, dtype=torch.int32).contiguous()
+    if widths.shape != (M,):
+        raise ValueError("widths must hold one entry per motif")
+    log = torch.empty((max(M - 1, 0), 8), dtype=torch.int32, device=dev)
+    link = torch.empty((max(M - 1, 0), 2), dtype=torch.int64, device=dev)
+    gone, flips, shifts = (torch.empty((M,), dtype=torch.int32, device=dev) for _ in range(3))
+    if M:
+        lib = _lib.load()
+        kind = LINKAGES[linkage]
+        nbytes = int(lib.explainn_motif_tree_workspace_bytes(M, kind))
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.explainn_motif_tree(
+                ncor.data_ptr(), align.data_ptr(), widths.data_ptr(), M, kind, log.data_ptr(), link.data_ptr(),
+                gone.data_ptr(), flips.data_ptr(), shifts.data_ptr(), ws.data_ptr(), nbytes,
+                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return MotifTree(log, link, gone, flips, shifts, widths, linkage)
+
+
+_tree = tree                   # merge has a parameter of that name
+
+
+def _column_ic(pfm):
+    """Information content (bits) of count columns (.., 4); 0 for an empty column."""
+    tot = pfm.sum(axis=-1, keepdims=True)
+    p = np.where(tot > 0, pfm / np.where(tot > 0, tot, 1.0), 0.25)
+    return 2.0 + np.where(p > 0, p * np.log2(np.where(p > 0, p, 1.0)), 0.0).sum(axis=-1)
+
+
+class MergedMotifs:
+    """The pooled motif of every cluster (`merge`), on the host.  pfm float64 (C, span_max, 4): per frame column
+    the sum of the members' placed matrices; widths int32 [C]: the columns of each cluster; support int32
+    (C, span_max): the members covering a column; labels int64 [M]; members: per cluster the member indices,
+    ascending; flips, shifts int32 [M]: a member's placement in its cluster's frame; names: cluster<c>_n<size>;
+    tree: the MotifTree that was cut."""
+
+    def __init__(self, pfm, widths, support, labels, members, flips, shifts, names, tree=None):
+        self.pfm, self.widths, self.support, self.labels, self.members = pfm, widths, support, labels, members
+        self.flips, self.shifts, self.names, self.tree = flips, shifts, names, tree
+
+    def __len__(self):
+        return len(self.widths)
+
+    def as_motifs(self):
+        """[(name, "", (w, 4) float64 counts)]: what write_meme, compare, annotate, pwmsites.scan_motifs and
+        pwmenrich.motif_enrichment take."""
+        return [(self.names[c], "", self.pfm[c, :int(self.widths[c])].copy()) for c in range(len(self))]
+
+    def trimmed(self, min_support=0.5, min_ic=0.0):
+        """Cut the flanking columns that fewer than min_support of the cluster's members cover, or whose
+        information content is below min_ic bits; inner columns stay.  A cluster without a column left has
+        width 0.  Shifts are moved with the frame (a trimmed member's shift may become negative)."""
+        if not 0 <= float(min_support) <= 1:
+            raise ValueError("min_support must lie in [0, 1]")
+        C = len(self)
+        ic = _column_ic(self.pfm)
+        left, widths = np.zeros(C, dtype=np.int64), np.zeros(C, dtype=np.int32)
+        for c in range(C):
+            w = int(self.widths[c])
+            ok = (self.support[c, :w] >= float(min_support) * len(self.members[c])) & (ic[c, :w] >= float(min_ic))
+            keep = np.nonzero(ok)[0]
+            if len(keep):
+                left[c], widths[c] = keep[0], keep[-1] + 1 - keep[0]
+        smax = int(widths.max()) if C else 0
+        pfm = np.zeros((C, smax, 4), dtype=np.float64)
+        support = np.zeros((C, smax), dtype=np.int32)
+        for c in range(C):
+            pfm[c, :widths[c]] = self.pfm[c, left[c]:left[c] + widths[c]]
+            support[c, :widths[c]] = self.support[c, left[c]:left[c] + widths[c]]
+        shifts = (np.asarray(self.shifts, dtype=np.int64) - left[np.asarray(self.labels, dtype=np.int64)]) \
+            .astype(np.int32) if len(self.labels) else np.zeros(0, dtype=np.int32)
+        return MergedMotifs(pfm, widths, support, self.labels, self.members, self.flips, shifts, self.names,
+                            self.tree)
+
+
+def merge(motifs, tree=None, min_ncor=0.4, linkage="average", device=None, **compare_args):
+    """The non-redundant motifs of a set: cut the set's tree at min_ncor, place every member in its cluster's
+    frame by the alignments `compare` found, and sum the placed count matrices per cluster (fp64, members in
+    ascending order, on the device: the same bits on every run).  motifs: anything `compare` accepts; matrices
+    are summed as given, so pre-scale them to weight them.  tree: a MotifTree of the same set (default:
+    compare(motifs, **compare_args), then tree(..., linkage)).  Returns a MergedMotifs."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib
+    _cut_threshold(min_ncor)
+    device = _device_for(device, (motifs,), "merge")
+    x, w = _as_set(motifs, device)
+    if x.shape[1] > MAX_WIDTH:
+        raise ValueError("motifs wider than %d columns are not supported (got %d)" % (MAX_WIDTH, x.shape[1]))
+    x = _pad(x, max(x.shape[1], 1))
+    M, wmax = int(x.shape[0]), int(x.shape[1])
+    if tree is None:
+        tree = _tree(compare((x, w), None, device=device, **compare_args), w, linkage)
+    if tree.M != M:
+        raise ValueError("the tree holds %d motifs, the set %d" % (tree.M, M))
+    w = torch.where((w < 0) | (w > wmax), torch.zeros_like(w), w)
+    labels, flips, shifts, spans, slots, cluster_slots = tree._cut(min_ncor)
+    n, smax = len(spans), (int(spans.max()) if len(spans) else 0)
+    pfm = torch.empty((n, smax, 4), dtype=torch.float64, device=device)
+    support = torch.empty((n, smax), dtype=torch.int32, device=device)
+    if n and smax:
+        with torch.cuda.device(device):
+            _lib.check(_lib.load().explainn_motif_tree_pool(
+                x.data_ptr(), w.data_ptr(), slots.data_ptr(), flips.data_ptr(), shifts.data_ptr(),
+                cluster_slots.data_ptr(), M, wmax, n, smax, pfm.data_ptr(), support.data_ptr(),
+                C.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+    labels = labels.cpu().numpy()
+    members = [np.nonzero(labels == c)[0] for c in range(n)]
+    names = ["cluster%d_n%d" % (c, len(m)) for c, m in enumerate(members)]
+    return MergedMotifs(pfm.cpu().numpy(), spans, support.cpu().numpy(), labels, members, flips.cpu().numpy(),
+                        shifts.cpu().numpy(), names, tree)
+
+
 # ---------------------------------------------------------------- command line
+def _cli_merge(a):
+    motifs = []
+    for path in a.motifs:
+        motifs.extend(read_motifs(path))
+    merged = merge(motifs, min_ncor=a.min_ncor, linkage=a.linkage, min_overlap=a.min_overlap,
+                   pseudocount=a.pseudocount)
+    out = merged.trimmed(a.min_support, a.min_ic)
+    write_meme(a.output, out.as_motifs())
+    if a.tree:
+        with open(a.tree, "wt") as fh:
+            fh.write(merged.tree.newick([m[0] for m in motifs]) + "\n")
+    if a.table:
+        with open(a.table, "wt") as fh:
+            fh.write("Motif\tCluster\tStrand\tShift\tWidth\n")
+            for i, (ident, _, m) in enumerate(motifs):
+                fh.write("%s\t%s\t%s\t%d\t%d\n" % (ident, out.names[out.labels[i]], "-" if out.flips[i] else "+",
+                                                   out.shifts[i], len(np.asarray(m).reshape(-1, 4))))
+
+
 def _cli_annotate(a):
     queries, db = read_motifs(a.motifs), read_motifs(a.db)
     by_p = a.by == "pvalue"
@@ -559,6 +834,18 @@ def main(argv=None):
     p.add_argument("motifs", nargs="+")
     common(p)
     p.set_defaults(run=_cli_cluster)
+    p = sub.add_parser("merge", help="the merged motif of every cluster of a hierarchical tree")
+    p.add_argument("motifs", nargs="+")
+    p.add_argument("-o", "--output", required=True, help="the merged motifs, MEME text")
+    p.add_argument("--linkage", choices=("average", "complete", "single"), default="average")
+    p.add_argument("--min-ncor", type=float, default=0.4)
+    p.add_argument("--min-overlap", type=int, default=5)
+    p.add_argument("--pseudocount", type=float, default=0.0)
+    p.add_argument("--min-support", type=float, default=0.5)
+    p.add_argument("--min-ic", type=float, default=0.0)
+    p.add_argument("--tree", help="write the tree as Newick text")
+    p.add_argument("--table", help="write the placement of every motif: Motif Cluster Strand Shift Width")
+    p.set_defaults(run=_cli_merge)
     a = ap.parse_args(argv)
     a.run(a)
 

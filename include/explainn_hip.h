@@ -800,6 +800,51 @@ int explainn_motif_significance(const float* q, const int32_t* q_widths, int Q, 
                                 uint8_t* colscore, int32_t* hist, void* workspace, int64_t workspace_bytes,
                                 void* stream);
 
+/* Motif tree and merged cluster motifs (csrc/motiftree.hip, DESIGN.md section 3, "Motif tree"): agglomerate
+ * the M motifs of a self-comparison, cut the tree, place every member in its cluster's frame and pool the
+ * placed matrices.  Context-free; no allocation, no host synchronisation; integer-exact, so the same input
+ * gives the same bits on every call.
+ * Input: ncor fp32 (M,M) and align int16 (M,M,3) as explainn_motif_compare writes them (the upper triangle is
+ * read: q[i][j] = (int32) rintf(ncor[i][j] 2^20), (offset, strand) of the pair for i < j) and int32 widths[M],
+ * taken as they are.  Linkage of two clusters over their leaf pairs: SINGLE max q, COMPLETE min q, AVERAGE
+ * (double) sum q / (double) pairs.  A cluster's slot is its smallest leaf; of the live pairs lo < hi the one with
+ * the largest linkage merges into slot lo, ties to the smaller lo, then the smaller hi; M - 1 steps.  The best
+ * leaf pair (i < j) of a step is the one with the largest q across the two clusters, ties to the smaller i, then
+ * j.  Placement: leaf x at (f, h) has column c of rc^f(m_x) in frame column h + c; the pair's (s, o) says that
+ * in a frame where i is (0,0), j is (s,-o); a step keeps cluster lo and sends every leaf of hi through
+ * f ^= F, h = (F ? -(h + w) : h) + H so that the best pair meets as compared.
+ * explainn_motif_tree writes log int32 (M-1,8) = lo, hi, leaves of the merged cluster, leaf_i, leaf_j, F, H, 0;
+ * link int64 (M-1,2) = sum, pairs ((q, 1) for SINGLE and COMPLETE; height = sum / pairs / 2^20); gone int32 [M],
+ * the step that merged slot c away (-1: never); flips, shifts int32 [M], every leaf in the root's frame.
+ * workspace: 16-byte aligned, explainn_motif_tree_workspace_bytes(M, linkage) bytes (two M x M matrices of 8
+ * bytes; 0 for arguments the call refuses), dead after the call.  One workgroup runs the M - 1 steps.
+ * M < 0, an unknown linkage, a short workspace: EXPLAINN_E_ARG; M > EXPLAINN_MOTIF_TREE_MAX_LEAVES:
+ * EXPLAINN_E_UNSUPPORTED.  M == 0 launches nothing.
+ * explainn_motif_tree_cut: a step is above the cut when sum >= threshold pairs (threshold = ceil(min_ncor 2^20),
+ * at least 1, else EXPLAINN_E_ARG).  Per leaf: labels = the slot of its cluster at the cut, flips and shifts in
+ * that cluster's frame, the shifts moved so that the smallest of a cluster is 0; per slot that is a cluster,
+ * slot_hi - slot_lo is the cluster's span (other slots hold INT32_MAX, INT32_MIN).  All int32 [M], overwritten.
+ * explainn_motif_tree_pool: x fp32 (M,wmax,4) and widths as explainn_motif_compare's (a width outside
+ * [0,wmax] is a width of 0), labels / flips / shifts as the cut wrote them, cluster_slots int32 [C] the slots of
+ * the clusters to pool; merged double (C,span,4): per (column, base) the sum over the members in ascending leaf
+ * order of the placed entries, plain fp64 adds; support int32 (C,span): members covering the column.  Columns
+ * at or past span are dropped.  Overwritten.  M, C, span < 0, C > M, wmax outside [1, EXPLAINN_MOTIF_MAX_WIDTH]:
+ * EXPLAINN_E_ARG.  C == 0 or span == 0 launches nothing. */
+#define EXPLAINN_LINKAGE_SINGLE 0
+#define EXPLAINN_LINKAGE_COMPLETE 1
+#define EXPLAINN_LINKAGE_AVERAGE 2
+#define EXPLAINN_MOTIF_TREE_MAX_LEAVES 12288
+int64_t explainn_motif_tree_workspace_bytes(int M, int linkage);
+int explainn_motif_tree(const float* ncor, const int16_t* align, const int32_t* widths, int M, int linkage,
+                        int32_t* log, int64_t* link, int32_t* gone, int32_t* flips, int32_t* shifts,
+                        void* workspace, int64_t workspace_bytes, void* stream);
+int explainn_motif_tree_cut(const int32_t* log, const int64_t* link, const int32_t* gone, const int32_t* widths,
+                            int M, int threshold, int32_t* labels, int32_t* flips, int32_t* shifts,
+                            int32_t* slot_lo, int32_t* slot_hi, void* stream);
+int explainn_motif_tree_pool(const float* x, const int32_t* widths, const int32_t* labels, const int32_t* flips,
+                             const int32_t* shifts, const int32_t* cluster_slots, int M, int wmax, int C, int span,
+                             double* merged, int32_t* support, void* stream);
+
 /* Known-motif sites (csrc/pwmsites.hip, DESIGN.md section 8, "Known-motif sites"): where the motifs of a
  * database occur in a sequence, at an exact p-value cutoff -- what FIMO lists.  A motif is an integer score
  * table: scores, device int16 (M,wmax,4), rows A,C,G,T per column, every entry in [0, bins], and int32

@@ -68,6 +68,9 @@ SHUFFLE = [r"^dinuc_shuffle_kernel"]
 MOTIFS = [r"^motif_prep_kernel", r"^motif_compare_kernel",
           # motif significance: column scores, histograms, range nulls, alignment p-values
           r"^motif_colscore_kernel", r"^motif_hist_kernel", r"^motif_null_kernel", r"^motif_pvalue_kernel"]
+# motif tree (motiftree.hip): the quantisation, the one-workgroup agglomeration, the cut and the pooling
+MOTIFTREE = [r"^motif_tree_prepare_kernel", r"^motif_tree_kernel", r"^motif_tree_cut_walk_kernel",
+             r"^motif_tree_pool_kernel"]
 # the activation null (actnull.hip): the LDS histogram and the tail / threshold scan
 ACTNULL = [r"^act_hist_kernel", r"^act_null_kernel"]
 # motif spacing (spacing.hip): the per-pair distance histogram and the binomial test
@@ -86,7 +89,7 @@ PWMSITES = [r"^pwm_null_kernel", r"^pwm_sites_kernel<0>", r"^pwm_sites_kernel<1>
 PWMBEST = [r"^pwm_best_kernel"]
 # greedy in-silico evolution (evolve.hip): one round's selection
 EVOLVE = [r"^evolve_select_kernel"]
-GATED = (C2_STEP + INPUT_GRAD + ISM + EVOLVE + PATHGRAD + METRICS + SCAN + VARIANTS + HAPLOTYPES + SHUFFLE + MOTIFS + ACTNULL +
+GATED = (C2_STEP + INPUT_GRAD + ISM + EVOLVE + PATHGRAD + METRICS + SCAN + VARIANTS + HAPLOTYPES + SHUFFLE + MOTIFS + MOTIFTREE + ACTNULL +
          SPACING + ENRICH + CENTRAL + SITES + PWMSITES + PWMBEST)
 
 
