@@ -226,6 +226,70 @@ def check(rc):
     raise ExplainnError("libexplainn_hip: %s (code %d)" % (msg, rc))
 
 
+# ---------------------------------------------------------------- the context-free entry points' call path
+def device_for(device, candidates, what):
+    """The device of a call: the one asked for, else that of the first HIP tensor among `candidates` (looking
+    one level into tuples and lists), else the current one.  There is no CPU path: anything else raises, before
+    the library is loaded."""
+    import torch
+    if device is None:
+        for obj in candidates:
+            first = obj[0] if isinstance(obj, (tuple, list)) and len(obj) else obj
+            if torch.is_tensor(first) and first.device.type == "cuda":
+                device = first.device
+                break
+    if device is None and torch.cuda.is_available():
+        device = "cuda"
+    device = None if device is None else torch.device(device)
+    if device is None or device.type != "cuda":
+        raise RuntimeError("%s runs only on a HIP device (there is no CPU fallback)" % what)
+    if device.index is None and torch.cuda.is_available():
+        device = torch.device("cuda", torch.cuda.current_device())
+    return device
+
+
+def require(t, dtype, shape, device, name):
+    """The precondition of a tensor argument: contiguous, of `dtype` and `shape` (None: any size), on `device`
+    (None: any HIP device)."""
+    import torch
+    if not (torch.is_tensor(t) and t.device.type == "cuda" and device in (None, t.device) and t.dtype == dtype and
+            t.dim() == len(shape) and all(want in (None, have) for have, want in zip(t.shape, shape)) and
+            t.is_contiguous()):
+        raise RuntimeError("%s must be a contiguous %s tensor of shape (%s) on %s (there is no CPU fallback)" % (
+            name, str(dtype).replace("torch.", ""), ", ".join("*" if n is None else str(n) for n in shape),
+            "a HIP device" if device is None else device))
+    return t
+
+
+def call(name, device, *args):
+    """Enqueue the C function `name` on the current stream of `device`: a tensor goes as its address (it must be
+    contiguous and on `device`), None as NULL, anything else as it is; the stream is the last argument."""
+    import torch
+    device = torch.device(device)
+    argv = []
+    for i, a in enumerate(args):
+        if torch.is_tensor(a):
+            if a.device != device or not a.is_contiguous():
+                raise RuntimeError("%s: argument %d must be a contiguous tensor on %s (a %s tensor on %s)" % (
+                    name, i, device, "contiguous" if a.is_contiguous() else "strided", a.device))
+            a = a.data_ptr()
+        argv.append(a)
+    fn = getattr(load(), name)
+    with torch.cuda.device(device):
+        check(fn(*argv, C.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+
+
+def workspace(name, device, *dims):
+    """(uint8 tensor on `device`, nbytes) for the size export `name` at `dims`; a negative size is the export's
+    refusal and raises ValueError with its text."""
+    import torch
+    lib = load()
+    nbytes = int(getattr(lib, name)(*dims))
+    if nbytes < 0:
+        raise ValueError(lib.explainn_last_error().decode("utf-8", "replace"))
+    return torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=device), nbytes
+
+
 class Context:
     """Owner of one explainn_ctx (device scratch for a fixed model geometry and max batch)."""
 

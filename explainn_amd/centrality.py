@@ -142,29 +142,16 @@ class SitePositions:
             return cls(z["hist"], z["counts"], z["thresholds"], int(z["k"]), int(z["length"]), str(z["strands"]))
 
 
-def _is_device(t, dtype, shape):
-    return torch.is_tensor(t) and t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.device.type == "cuda" and \
-        t.is_contiguous()
-
-
 def positions_device(bits, site, labels, thresholds, starts, hist=None):
     """explainn_site_positions on device tensors: bits int16 and site int32 (units, N) as _launch_record_best
     gives them, labels uint8 (N,), thresholds float32 (units, T), `starts` = M.  hist: int32 (units, T, 2, M)
     on the device, added into (None: zeros).  Thresholds whose [T][2][M] histogram would pass 64 KiB go over
     in groups.  Returns (hist, counts int64 (2,) of this call)."""
-    import ctypes as C
-
     from . import _lib
-    if not torch.is_tensor(bits) or bits.dtype != torch.int16 or bits.dim() != 2 or bits.device.type != "cuda" or \
-            not bits.is_contiguous():
-        raise RuntimeError("bits must be a contiguous int16 tensor of shape (units, N) on a HIP device (there is "
-                           "no CPU fallback)")
-    units, n = bits.shape
-    dev, M = bits.device, int(starts)
-    if not _is_device(site, torch.int32, (units, n)) or not _is_device(labels, torch.uint8, (n,)) or \
-            site.device != dev or labels.device != dev:
-        raise RuntimeError("site must be a contiguous int32 (%d, %d) tensor and labels a uint8 (%d,) tensor on %s" % (
-            units, n, n, dev))
+    (units, n), dev = _lib.require(bits, torch.int16, (None, None), None, "bits").shape, bits.device
+    M = int(starts)
+    _lib.require(site, torch.int32, (units, n), dev, "site")
+    _lib.require(labels, torch.uint8, (n,), dev, "labels")
     if not torch.is_tensor(thresholds) or thresholds.dtype != torch.float32 or thresholds.dim() != 2 or \
             thresholds.shape[0] != units or thresholds.device != dev:
         raise RuntimeError("thresholds must be a float32 (%d, T) tensor on %s" % (units, dev))
@@ -173,22 +160,17 @@ def positions_device(bits, site, labels, thresholds, starts, hist=None):
         raise ValueError("records of %d starts: the histogram of one threshold must fit %d bytes" % (M, HIST_BYTES))
     if hist is None:
         hist = torch.zeros((units, T, 2, M), device=dev, dtype=torch.int32)
-    elif not _is_device(hist, torch.int32, (units, T, 2, M)) or hist.device != dev:
-        raise RuntimeError("hist must be a contiguous int32 (%d, %d, 2, %d) tensor on %s" % (units, T, M, dev))
+    else:
+        _lib.require(hist, torch.int32, (units, T, 2, M), dev, "hist")
     counts = torch.empty(2, device=dev, dtype=torch.int64)
     group = min(HIST_BYTES // (2 * M * 4), MAX_THRESHOLDS)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        for t0 in range(0, T, group):
-            whole = t0 == 0 and T <= group
-            thr = thresholds.contiguous() if whole else thresholds[:, t0:t0 + group].contiguous()
-            part = hist if whole else torch.zeros((units, thr.shape[1], 2, M), device=dev, dtype=torch.int32)
-            _lib.check(lib.explainn_site_positions(bits.data_ptr(), site.data_ptr(), labels.data_ptr(), thr.data_ptr(),
-                                                   units, n, thr.shape[1], M, part.data_ptr(), counts.data_ptr(),
-                                                   stream))
-            if not whole:
-                hist[:, t0:t0 + group] += part
+    for t0 in range(0, T, group):
+        whole = t0 == 0 and T <= group
+        thr = thresholds.contiguous() if whole else thresholds[:, t0:t0 + group].contiguous()
+        part = hist if whole else torch.zeros((units, thr.shape[1], 2, M), device=dev, dtype=torch.int32)
+        _lib.call("explainn_site_positions", dev, bits, site, labels, thr, units, n, thr.shape[1], M, part, counts)
+        if not whole:
+            hist[:, t0:t0 + group] += part
     return hist, counts
 
 
@@ -196,27 +178,17 @@ def test_device(hist, counts, local=False, min_width=1, max_width=None, min_site
     """explainn_centrality_test on device tensors: hist int32 (units, T, 2, M), counts int64 (2,).  Returns a
     dict of device tensors, each (units,): best_t, best_lo, best_width (int32), sites, count, n_tests, ctrl_sites,
     ctrl_count (int64), log_pvalue, log_padj, log_fisher (float64)."""
-    import ctypes as C
-
     from . import _lib
     lo, hi, need = check_widths(min_width, max_width, min_sites)
-    if not torch.is_tensor(hist) or hist.dtype != torch.int32 or hist.dim() != 4 or hist.shape[2] != 2 or \
-            hist.device.type != "cuda" or not hist.is_contiguous():
-        raise RuntimeError("hist must be a contiguous int32 tensor of shape (units, T, 2, M) on a HIP device (there "
-                           "is no CPU fallback)")
-    units, T, _, M = hist.shape
-    dev = hist.device
-    if not _is_device(counts, torch.int64, (2,)) or counts.device != dev:
-        raise RuntimeError("counts must be an int64 (2,) tensor on %s" % dev)
+    (units, T, _, M), dev = _lib.require(hist, torch.int32, (None, None, 2, None), None, "hist").shape, hist.device
+    _lib.require(counts, torch.int64, (2,), dev, "counts")
     if T > MAX_THRESHOLDS or T * 2 * M * 4 > HIST_BYTES:
         raise ValueError("%d thresholds of %d starts: one test takes at most %d thresholds and %d bytes of "
                          "[T][2][M] counts; test fewer thresholds at once" % (T, M, MAX_THRESHOLDS, HIST_BYTES))
     hi = max(M, lo) if hi is None else hi
     out = {f: torch.empty(units, device=dev, dtype=field_dtype(f, torch)) for f in _FIELDS}
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().explainn_centrality_test(
-            hist.data_ptr(), counts.data_ptr(), units, T, M, 1 if local else 0, lo, hi, need,
-            *(out[f].data_ptr() for f in _FIELDS), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    _lib.call("explainn_centrality_test", dev, hist, counts, units, T, M, 1 if local else 0, lo, hi, need,
+              *(out[f] for f in _FIELDS))
     return out
 
 

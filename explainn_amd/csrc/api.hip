@@ -10,6 +10,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "workspace.h"
 
 static thread_local char g_err[512] = "";
 
@@ -23,17 +24,6 @@ void explainn_set_error(const char* fmt, ...) {
 extern "C" const char* explainn_last_error(void) { return g_err; }
 
 namespace {
-struct Carver {
-    int64_t off = 0;
-    char* base = nullptr;
-    template <typename T>
-    void take(T** p, int64_t count) {
-        off = (off + 255) & ~int64_t(255);
-        if (base) *p = reinterpret_cast<T*>(base + off);
-        off += count * (int64_t)sizeof(T);
-    }
-};
-
 void carve(explainn_ctx* c, Carver& cv) {
     const int64_t U = c->U, U4 = c->U4, n = c->n, Bs = c->Bs, NS = c->NS, K4 = c->K4;
     cv.take(&c->codesT, (int64_t)c->L * Bs);
@@ -103,7 +93,6 @@ void carve(explainn_ctx* c, Carver& cv) {
     cv.take(&c->igR, K4);
     cv.take(&c->igH, D * D * 16);
     cv.take(&c->igC, D * 4);
-    cv.off = (cv.off + 255) & ~int64_t(255);
 }
 
 int check_batch(const explainn_ctx* c, int B) {
@@ -272,15 +261,14 @@ static int create_ctx(explainn_ctx** out, int groups, int units_per_member, int 
     }
     Carver dry;
     carve(c, dry);
-    c->bytes = dry.off;
+    c->bytes = dry.bytes();
     hipError_t e = hipMalloc(&c->base, c->bytes);
     if (e != hipSuccess) {
         explainn_set_error("hipMalloc(%lld bytes) failed: %s", (long long)c->bytes, hipGetErrorString(e));
         delete c;
         return EXPLAINN_E_HIP;
     }
-    Carver real;
-    real.base = c->base;
+    Carver real(c->base);
     carve(c, real);
     e = hipMemset(c->base, 0, c->bytes);
     if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -375,11 +363,7 @@ extern "C" int explainn_ism(explainn_ctx* c, const float* x, int B, const explai
         return EXPLAINN_E_ARG;
     }
     if (c->dense) { explainn_set_error("in-silico mutagenesis works on base codes: one-hot input only"); return EXPLAINN_E_UNSUPPORTED; }
-    const int64_t need = ism_workspace_bytes(c, B);
-    if (workspace_bytes < need) {
-        explainn_set_error("ISM workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)need);
-        return EXPLAINN_E_ARG;
-    }
+    if (!workspace_ok("ism", workspace, workspace_bytes, ism_workspace_bytes(c, B), 1)) return EXPLAINN_E_ARG;
     hipStream_t s = static_cast<hipStream_t>(stream);
     TRY(eval_forward(c, x, B, p, false, logits, nullptr, s));
     return launch_ism(c, p, B, delta, static_cast<float*>(workspace), s);
@@ -547,12 +531,8 @@ extern "C" int explainn_scan(explainn_ctx* c, const uint8_t* seq, int64_t seq_le
         return score_rows(c, n_windows, p, logits, nullptr, s, [&](int64_t i0, int Bw) {
             return launch_stage_windows(c, seq, seq_len, start + i0 * stride, stride, Bw, rc, s);
         });
-    const int64_t need = scan_shared_bytes(c, n_windows, stride);
-    if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 255) != 0) {
-        explainn_set_error("scan workspace of %lld bytes (256-byte aligned), %lld needed", (long long)workspace_bytes,
-                           (long long)need);
+    if (!workspace_ok("scan", workspace, workspace_bytes, scan_shared_bytes(c, n_windows, stride), 256))
         return EXPLAINN_E_ARG;
-    }
     // the pooled track: tiles of L bases placed 7n apart, through the filter bank in blocks of up to
     // max_batch tiles.  Each block is the filter bank's whole output array, so the filter bank writes
     // it straight into the workspace (its output pointer is swapped for the launch): no copy.

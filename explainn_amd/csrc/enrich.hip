@@ -18,6 +18,7 @@
 #include "bestsite.h"
 #include "codescan.h"
 #include "tails.h"                             // hypergeom_logsf
+#include "workspace.h"
 
 namespace {
 
@@ -272,12 +273,9 @@ extern "C" int explainn_enrichment_test(const uint16_t* best_bits, const uint8_t
         explainn_set_error("enrichment_test: best_bits, labels and the nine outputs must be device pointers");
         return EXPLAINN_E_ARG;
     }
-    const int64_t need = explainn_enrichment_workspace_bytes(units, n_records);
-    if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 255) != 0) {
-        explainn_set_error("enrichment_test workspace of %lld bytes (256-byte aligned), %lld needed",
-                           (long long)workspace_bytes, (long long)need);
+    if (!workspace_ok("enrichment_test", workspace, workspace_bytes,
+                      explainn_enrichment_workspace_bytes(units, n_records), 256))
         return EXPLAINN_E_ARG;
-    }
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&enrich_test_kernel),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)EN_LDS));
     hipLaunchKernelGGL(enrich_test_kernel, dim3(enrich_grid(units)), dim3(EN_T), EN_LDS,

@@ -29,6 +29,7 @@
 // block per segment over the block partials (at most 64 per thread, then the same tree).  The longest
 // sequential chain is 64 additions.  No float atomics; the only atomic is the OR into the status word.
 #include "common.h"
+#include "workspace.h"
 
 #include <math.h>
 
@@ -556,12 +557,16 @@ __global__ __launch_bounds__(MT) void metrics_linear_final_kernel(const double* 
 struct Layout {
     u32 n, nblk, hist_nb;
     int S, segs;                      // columns; sorted segments (S binary, 2S linear)
-    size_t keys_a, keys_b, hist, hist_sums, run_sums, part, aux, end_at, d, total;
+    // the workspace's pieces (null after a dry run) and its size
+    u64 *keys_a = nullptr, *keys_b = nullptr, *run_sums = nullptr;
+    u32 *hist = nullptr, *hist_sums = nullptr, *end_at = nullptr;
+    double *part = nullptr, *aux = nullptr;
+    int* d = nullptr;
+    int64_t total;
 };
 
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-int make_layout(int64_t N, int T, int mode, int kind, Layout* L) {
+// the geometry of a call and its workspace carved from ws (ws == nullptr: a dry run for the size)
+int make_layout(int64_t N, int T, int mode, int kind, Layout* L, void* ws = nullptr) {
     if (N < 1 || T < 1) {
         explainn_set_error("metrics: need N >= 1 and T >= 1 (N=%lld T=%d)", (long long)N, T);
         return EXPLAINN_E_ARG;
@@ -589,38 +594,37 @@ int make_layout(int64_t N, int T, int mode, int kind, Layout* L) {
     L->segs = segs;
     L->nblk = (L->n + TILE - 1) / TILE;
     L->hist_nb = (256u * L->nblk + TILE - 1) / TILE;
-    size_t o = 0;
-    const size_t cells = (size_t)segs * L->n;
-    L->keys_a = o; o += up256(cells * 8);
-    L->keys_b = o; o += up256(cells * 8);
-    L->hist = o; o += up256((size_t)segs * 256 * L->nblk * 4);
-    L->hist_sums = o; o += up256((size_t)segs * L->hist_nb * 4);
-    L->run_sums = o; o += up256((size_t)segs * L->nblk * 8);
-    L->end_at = L->d = L->aux = 0;
+    Carver cv(ws);
+    const int64_t cells = (int64_t)segs * L->n;
+    cv.take(&L->keys_a, cells);
+    cv.take(&L->keys_b, cells);
+    cv.take(&L->hist, (int64_t)segs * 256 * L->nblk);
+    cv.take(&L->hist_sums, (int64_t)segs * L->hist_nb);
+    cv.take(&L->run_sums, (int64_t)segs * L->nblk);
     if (kind == EXPLAINN_METRICS_BINARY) {
-        L->part = o; o += up256((size_t)S * L->nblk * 16);      // u64 U2 partials | fp64 AP partials
+        cv.take(&L->part, (int64_t)S * L->nblk * 2);            // u64 U2 partials | fp64 AP partials
     } else {
-        L->part = o; o += up256((size_t)S * L->nblk * 6 * 8);   // also holds pass one's 2 sums
-        L->aux = o; o += up256((size_t)S * 2 * 8);              // means
-        L->end_at = o; o += up256(cells * 4);
-        L->d = o; o += up256(cells * 4);
+        cv.take(&L->part, (int64_t)S * L->nblk * 6);            // also holds pass one's 2 sums
+        cv.take(&L->aux, (int64_t)S * 2);                       // means
+        cv.take(&L->end_at, cells);
+        cv.take(&L->d, cells);
     }
-    L->total = o;
+    L->total = cv.bytes();
     return EXPLAINN_OK;
 }
 
 // ascending LSD sort of the keys' upper words: four 8-bit passes, result back in keys_a
-int sort_segments(const Layout& L, char* ws, hipStream_t st) {
-    u64* a = (u64*)(ws + L.keys_a);
-    u64* b = (u64*)(ws + L.keys_b);
-    u32* hist = (u32*)(ws + L.hist);
+int sort_segments(const Layout& L, hipStream_t st) {
+    u64* a = L.keys_a;
+    u64* b = L.keys_b;
+    u32* hist = L.hist;
     const dim3 grid(L.nblk, L.segs);
     for (int pass = 0; pass < 4; ++pass) {
         const int shift = 32 + 8 * pass;
         hipLaunchKernelGGL(metrics_hist_kernel, grid, dim3(MT), 0, st, a, hist, L.n, shift, L.nblk);
         LAUNCH_CHECK();
         HistScan hs{hist, 256u * L.nblk};
-        const int rc = launch_scan(hs, (u32*)(ws + L.hist_sums), L.segs, st);
+        const int rc = launch_scan(hs, L.hist_sums, L.segs, st);
         if (rc != EXPLAINN_OK) return rc;
         hipLaunchKernelGGL(metrics_scatter_kernel, grid, dim3(MT), 0, st, a, b, hist, L.n, shift, L.nblk);
         LAUNCH_CHECK();
@@ -635,12 +639,7 @@ int check_call(const void* y, const void* s, const void* o1, const void* o2, con
         explainn_set_error("%s: null pointer argument", who);
         return EXPLAINN_E_ARG;
     }
-    if (ws_bytes < (int64_t)L.total) {
-        explainn_set_error("%s: workspace of %lld bytes, explainn_metrics_workspace_bytes asks for %lld",
-                           who, (long long)ws_bytes, (long long)L.total);
-        return EXPLAINN_E_ARG;
-    }
-    return EXPLAINN_OK;
+    return workspace_ok(who, ws, ws_bytes, L.total, 1) ? EXPLAINN_OK : EXPLAINN_E_ARG;
 }
 
 }  // namespace
@@ -648,14 +647,14 @@ int check_call(const void* y, const void* s, const void* o1, const void* o2, con
 extern "C" int64_t explainn_metrics_workspace_bytes(int64_t N, int T, int mode, int kind) {
     Layout L;
     const int rc = make_layout(N, T, mode, kind, &L);
-    return rc == EXPLAINN_OK ? (int64_t)L.total : (int64_t)rc;
+    return rc == EXPLAINN_OK ? L.total : (int64_t)rc;
 }
 
 extern "C" int explainn_metrics_binary(const float* y, const float* s, int64_t N, int T, int mode,
                                        double* auroc, double* ap, int64_t* counts, unsigned int* status,
                                        void* workspace, int64_t workspace_bytes, void* stream) {
     Layout L;
-    int rc = make_layout(N, T, mode, EXPLAINN_METRICS_BINARY, &L);
+    int rc = make_layout(N, T, mode, EXPLAINN_METRICS_BINARY, &L, workspace);
     if (rc != EXPLAINN_OK) return rc;
     rc = check_call(y, s, auroc, ap, status, workspace, workspace_bytes, L, "metrics_binary");
     if (rc != EXPLAINN_OK) return rc;
@@ -664,20 +663,18 @@ extern "C" int explainn_metrics_binary(const float* y, const float* s, int64_t N
         return EXPLAINN_E_ARG;
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);
     const int per_task = mode == EXPLAINN_METRICS_PER_TASK;
     const dim3 grid(L.nblk, L.segs);
-    u64* keys = (u64*)(ws + L.keys_a);
-    u64* scan = (u64*)(ws + L.keys_b);
+    u64 *keys = L.keys_a, *scan = L.keys_b;
     hipLaunchKernelGGL(metrics_keys_binary_kernel, grid, dim3(MT), 0, st, y, s, keys, L.n, T, per_task, status);
     LAUNCH_CHECK();
-    rc = sort_segments(L, ws, st);
+    rc = sort_segments(L, st);
     if (rc != EXPLAINN_OK) return rc;
     RunScan<true> rs{keys, scan, L.n};
-    rc = launch_scan(rs, (u64*)(ws + L.run_sums), L.segs, st);
+    rc = launch_scan(rs, L.run_sums, L.segs, st);
     if (rc != EXPLAINN_OK) return rc;
-    u64* part_u = (u64*)(ws + L.part);
-    double* part_ap = (double*)(part_u + (size_t)L.S * L.nblk);
+    u64* part_u = reinterpret_cast<u64*>(L.part);
+    double* part_ap = L.part + (size_t)L.S * L.nblk;
     hipLaunchKernelGGL(metrics_binary_terms_kernel, grid, dim3(MT), 0, st, keys, scan, part_u, part_ap, L.n,
                        L.nblk);
     LAUNCH_CHECK();
@@ -691,27 +688,24 @@ extern "C" int explainn_metrics_linear(const float* y, const float* s, int64_t N
                                        double* pearson, double* spearman, unsigned int* status,
                                        void* workspace, int64_t workspace_bytes, void* stream) {
     Layout L;
-    int rc = make_layout(N, T, mode, EXPLAINN_METRICS_LINEAR, &L);
+    int rc = make_layout(N, T, mode, EXPLAINN_METRICS_LINEAR, &L, workspace);
     if (rc != EXPLAINN_OK) return rc;
     rc = check_call(y, s, pearson, spearman, status, workspace, workspace_bytes, L, "metrics_linear");
     if (rc != EXPLAINN_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);
     const int per_task = mode == EXPLAINN_METRICS_PER_TASK;
     const dim3 grid(L.nblk, L.segs), cols(L.nblk, L.S);
-    u64* keys = (u64*)(ws + L.keys_a);
-    u64* scan = (u64*)(ws + L.keys_b);
-    u32* end_at = (u32*)(ws + L.end_at);
-    int* d = (int*)(ws + L.d);
-    double* part = (double*)(ws + L.part);
-    double* mean = (double*)(ws + L.aux);
+    u64 *keys = L.keys_a, *scan = L.keys_b;
+    u32* end_at = L.end_at;
+    int* d = L.d;
+    double *part = L.part, *mean = L.aux;
     hipLaunchKernelGGL(metrics_keys_linear_kernel, grid, dim3(MT), 0, st, y, s, keys, L.n, T, per_task, L.S,
                        status);
     LAUNCH_CHECK();
-    rc = sort_segments(L, ws, st);
+    rc = sort_segments(L, st);
     if (rc != EXPLAINN_OK) return rc;
     RunScan<false> rs{keys, scan, L.n};
-    rc = launch_scan(rs, (u64*)(ws + L.run_sums), L.segs, st);
+    rc = launch_scan(rs, L.run_sums, L.segs, st);
     if (rc != EXPLAINN_OK) return rc;
     hipLaunchKernelGGL(metrics_run_ends_kernel, grid, dim3(MT), 0, st, keys, scan, end_at, L.n);
     LAUNCH_CHECK();

@@ -26,6 +26,7 @@
 // The second half of the file is motif significance (explainn_motif_significance): p-values of alignment
 // scores under a per-query null, on the same preparation and conventions.
 #include "common.h"
+#include "workspace.h"
 
 namespace {
 
@@ -42,15 +43,11 @@ __host__ inline size_t mc_lds_bytes(int wmax) {
 }
 
 // workspace: D [M][2][wmax] float4 | P [M][2][wmax+1] double | W [M] int32, each 256-byte aligned
-struct mc_layout { int64_t d, p, w, bytes; };
-__host__ inline mc_layout mc_workspace(int64_t M, int wmax) {
-    auto up = [](int64_t v) { return (v + 255) & ~(int64_t)255; };
-    mc_layout l;
-    l.d = 0;
-    l.p = up(M * 2 * wmax * 16);
-    l.w = l.p + up(M * 2 * (wmax + 1) * 8);
-    l.bytes = l.w + up(M * 4);
-    return l;
+struct mc_pieces { float4* D; double* P; int32_t* W; };
+__host__ inline void mc_workspace(Carver& cv, int64_t M, int wmax, mc_pieces* w) {
+    cv.take(&w->D, M * 2 * wmax);
+    cv.take(&w->P, M * 2 * (wmax + 1));
+    cv.take(&w->W, M);
 }
 
 __global__ __launch_bounds__(64) void motif_prep_kernel(const float* __restrict__ m, const int32_t* __restrict__ widths,
@@ -241,7 +238,10 @@ __global__ __launch_bounds__(MC_WAVES * 64) void motif_compare_kernel(
 
 extern "C" int64_t explainn_motif_compare_workspace_bytes(int Q, int T, int wmax) {
     if (Q < 0 || T < 0 || wmax < 1) return 0;
-    return mc_workspace((int64_t)Q + T, wmax).bytes;
+    Carver dry;
+    mc_pieces w;
+    mc_workspace(dry, (int64_t)Q + T, wmax, &w);
+    return dry.bytes();
 }
 
 extern "C" int explainn_motif_compare(const float* q, const int32_t* q_widths, int Q, const float* t,
@@ -269,22 +269,19 @@ extern "C" int explainn_motif_compare(const float* q, const int32_t* q_widths, i
         return EXPLAINN_E_ARG;
     }
     const int64_t M = (int64_t)Q + (t ? T : 0);
-    const mc_layout l = mc_workspace(M, wmax);
-    if (!workspace || ((uintptr_t)workspace & 15u) || workspace_bytes < l.bytes) {
-        explainn_set_error("motif_compare: workspace of %lld bytes, 16-byte aligned, needed (%lld given)",
-                           (long long)l.bytes, (long long)workspace_bytes);
-        return EXPLAINN_E_ARG;
-    }
+    Carver cv(workspace);
+    mc_pieces w;
+    mc_workspace(cv, M, wmax, &w);
+    if (!workspace_ok("motif_compare", workspace, workspace_bytes, cv.bytes(), 16)) return EXPLAINN_E_ARG;
     const int64_t ntt = ((int64_t)T + MC_TT - 1) / MC_TT, ntq = ((int64_t)Q + MC_TQ - 1) / MC_TQ;
     if (ntt * ntq > 0x7fffffffLL) {
         explainn_set_error("motif_compare: %d x %d pairs exceed one launch; split the queries", Q, T);
         return EXPLAINN_E_UNSUPPORTED;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);
-    float4* D = reinterpret_cast<float4*>(ws + l.d);
-    double* P = reinterpret_cast<double*>(ws + l.p);
-    int32_t* W = reinterpret_cast<int32_t*>(ws + l.w);
+    float4* D = w.D;
+    double* P = w.P;
+    int32_t* W = w.W;
     hipLaunchKernelGGL(motif_prep_kernel, dim3((unsigned)((Q + 63) / 64)), dim3(64), 0, s, q, q_widths, Q, wmax,
                        pseudocount, D, P, W);
     LAUNCH_CHECK();
@@ -352,19 +349,15 @@ __host__ __device__ inline int64_t ms_sf_off(int lo, int w, int wmax, int bins) 
 }
 __host__ __device__ inline int ms_tp(int T) { return (T + 15) & ~15; }
 
-// workspace: the preparation's (mc_layout) | cs [Q*wmax][S*wmax*Tp] uint8 | hist [Q*wmax][bins+1] int32 |
-// sf [Q][ms_c(wmax)] double, each 256-byte aligned
-struct ms_layout { int64_t cs, hist, sf, bytes, ld, sfq; };
-__host__ inline ms_layout ms_workspace(int64_t Q, int64_t M, int T, int wmax, int bins, int S) {
-    auto up = [](int64_t v) { return (v + 255) & ~(int64_t)255; };
-    ms_layout l;
-    l.ld = (int64_t)S * wmax * ms_tp(T);
-    l.sfq = ms_c(wmax, bins);
-    l.cs = mc_workspace(M, wmax).bytes;
-    l.hist = l.cs + up(Q * wmax * l.ld);
-    l.sf = l.hist + up(Q * wmax * (bins + 1) * 4);
-    l.bytes = l.sf + up(Q * l.sfq * 8);
-    return l;
+// workspace: the preparation's (mc_workspace) | cs [Q*wmax][ld] uint8 | hist [Q*wmax][bins+1] int32 |
+// sf [Q][sfq] double, each 256-byte aligned
+__host__ inline int64_t ms_ld(int T, int wmax, int S) { return (int64_t)S * wmax * ms_tp(T); }   // a row of cs
+struct ms_pieces { mc_pieces prep; uint8_t* cs; int32_t* hist; double* sf; };
+__host__ inline void ms_workspace(Carver& cv, int64_t Q, int64_t M, int T, int wmax, int bins, int S, ms_pieces* w) {
+    mc_workspace(cv, M, wmax, &w->prep);
+    cv.take(&w->cs, Q * wmax * ms_ld(T, wmax, S));
+    cv.take(&w->hist, Q * wmax * (bins + 1));
+    cv.take(&w->sf, Q * ms_c(wmax, bins));
 }
 __host__ inline size_t ms_colscore_lds(int wmax) { return (size_t)(MS_TT + MS_TQ) * wmax * 16; }
 __host__ inline size_t ms_null_lds(int wmax, int bins) {
@@ -590,7 +583,10 @@ __global__ __launch_bounds__(MS_THREADS) void motif_colscore_copy_kernel(const u
 extern "C" int64_t explainn_motif_significance_workspace_bytes(int Q, int T, int wmax, int bins, int both_strands) {
     if (Q < 0 || T < 0 || wmax < 1 || wmax > EXPLAINN_MOTIF_MAX_WIDTH || bins < 2 || bins > EXPLAINN_MOTIF_MAX_BINS)
         return 0;
-    return ms_workspace(Q, (int64_t)Q + T, T, wmax, bins, both_strands ? 2 : 1).bytes;
+    Carver dry;
+    ms_pieces w;
+    ms_workspace(dry, Q, (int64_t)Q + T, T, wmax, bins, both_strands ? 2 : 1, &w);
+    return dry.bytes();
 }
 
 extern "C" int explainn_motif_significance(const float* q, const int32_t* q_widths, int Q, const float* t,
@@ -621,13 +617,11 @@ extern "C" int explainn_motif_significance(const float* q, const int32_t* q_widt
     }
     const int S = both_strands ? 2 : 1;
     const int64_t M = (int64_t)Q + (t ? T : 0);
-    const mc_layout pl = mc_workspace(M, wmax);
-    const ms_layout l = ms_workspace(Q, M, T, wmax, bins, S);
-    if (!workspace || ((uintptr_t)workspace & 15u) || workspace_bytes < l.bytes) {
-        explainn_set_error("motif_significance: workspace of %lld bytes, 16-byte aligned, needed (%lld given)",
-                           (long long)l.bytes, (long long)workspace_bytes);
-        return EXPLAINN_E_ARG;
-    }
+    const int64_t ld = ms_ld(T, wmax, S), sfq = ms_c(wmax, bins);
+    Carver cv(workspace);
+    ms_pieces w;
+    ms_workspace(cv, Q, M, T, wmax, bins, S, &w);
+    if (!workspace_ok("motif_significance", workspace, workspace_bytes, cv.bytes(), 16)) return EXPLAINN_E_ARG;
     const int64_t ntt = ((int64_t)T + MS_TT - 1) / MS_TT, ntq = ((int64_t)Q + MS_TQ - 1) / MS_TQ;
     const int64_t ntw = ((int64_t)Q + MS_WAVES - 1) / MS_WAVES;
     if (ntt * ntq > 0x7fffffffLL || ntt * ntw > 0x7fffffffLL || (int64_t)Q * wmax > 0x7fffffffLL) {
@@ -635,13 +629,12 @@ extern "C" int explainn_motif_significance(const float* q, const int32_t* q_widt
         return EXPLAINN_E_UNSUPPORTED;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);
-    float4* D = reinterpret_cast<float4*>(ws + pl.d);
-    double* P = reinterpret_cast<double*>(ws + pl.p);
-    int32_t* W = reinterpret_cast<int32_t*>(ws + pl.w);
-    uint8_t* cs = reinterpret_cast<uint8_t*>(ws + l.cs);
-    int32_t* hs = reinterpret_cast<int32_t*>(ws + l.hist);
-    double* sf = reinterpret_cast<double*>(ws + l.sf);
+    float4* D = w.prep.D;
+    double* P = w.prep.P;
+    int32_t* W = w.prep.W;
+    uint8_t* cs = w.cs;
+    int32_t* hs = w.hist;
+    double* sf = w.sf;
     hipLaunchKernelGGL(motif_prep_kernel, dim3((unsigned)((Q + 63) / 64)), dim3(64), 0, s, q, q_widths, Q, wmax,
                        pseudocount, D, P, W);
     LAUNCH_CHECK();
@@ -665,22 +658,22 @@ extern "C" int explainn_motif_significance(const float* q, const int32_t* q_widt
                                     hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)ms_null_lds(EXPLAINN_MOTIF_MAX_WIDTH, EXPLAINN_MOTIF_MAX_BINS)));
     hipLaunchKernelGGL(motif_colscore_kernel, dim3((unsigned)(ntt * ntq)), dim3(MS_THREADS), lds1, s, D, W, Q, Dt, Wt,
-                       T, wmax, (int)ntt, both_strands != 0, bins, cs, l.ld);
+                       T, wmax, (int)ntt, both_strands != 0, bins, cs, ld);
     LAUNCH_CHECK();
-    hipLaunchKernelGGL(motif_hist_kernel, dim3((unsigned)(Q * wmax)), dim3(MS_THREADS), 0, s, cs, l.ld, W, wmax, bins,
+    hipLaunchKernelGGL(motif_hist_kernel, dim3((unsigned)(Q * wmax)), dim3(MS_THREADS), 0, s, cs, ld, W, wmax, bins,
                        hs, hist);
     LAUNCH_CHECK();
     hipLaunchKernelGGL(motif_null_kernel, dim3((unsigned)(Q * wmax)), dim3(MS_THREADS), lds3, s, hs, W, wmax, bins, sf,
-                       l.sfq);
+                       sfq);
     LAUNCH_CHECK();
-    hipLaunchKernelGGL(motif_pvalue_kernel, dim3((unsigned)(ntt * ntw)), dim3(MS_THREADS), 0, s, cs, l.ld, sf, l.sfq, W,
+    hipLaunchKernelGGL(motif_pvalue_kernel, dim3((unsigned)(ntt * ntw)), dim3(MS_THREADS), 0, s, cs, ld, sf, sfq, W,
                        Q, Wt, T, wmax, (int)ntt, min_overlap, S, bins, pvalue, align, score);
     LAUNCH_CHECK();
     if (colscore) {
         const int64_t total = (int64_t)Q * wmax * S * wmax * T;
         const int64_t blocks = (total + MS_THREADS - 1) / MS_THREADS;
         hipLaunchKernelGGL(motif_colscore_copy_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)),
-                           dim3(MS_THREADS), 0, s, cs, l.ld, W, T, wmax, S, total, colscore);
+                           dim3(MS_THREADS), 0, s, cs, ld, W, T, wmax, S, total, colscore);
         LAUNCH_CHECK();
     }
     return EXPLAINN_OK;

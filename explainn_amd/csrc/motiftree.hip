@@ -26,6 +26,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "workspace.h"
 
 namespace {
 
@@ -36,16 +37,12 @@ constexpr int MT_BATCH = 4;      // slots a lane reads at a time in the placemen
 constexpr int MT_POOL_THREADS = 256;
 
 // workspace: L [M][M] int64 | K [M][M] uint64 | size [M] int32 | slot [M] int32, each 256-byte aligned
-struct mt_layout { int64_t l, k, size, slot, bytes; };
-__host__ inline mt_layout mt_workspace(int64_t M) {
-    auto up = [](int64_t v) { return (v + 255) & ~(int64_t)255; };
-    mt_layout w;
-    w.l = 0;
-    w.k = up(M * M * 8);
-    w.size = w.k + up(M * M * 8);
-    w.slot = w.size + up(M * 4);
-    w.bytes = w.slot + up(M * 4);
-    return w;
+struct mt_pieces { int64_t* L; uint64_t* K; int* size; int* slot; };
+__host__ inline void mt_workspace(Carver& cv, int64_t M, mt_pieces* w) {
+    cv.take(&w->L, M * M);
+    cv.take(&w->K, M * M);
+    cv.take(&w->size, M);
+    cv.take(&w->slot, M);
 }
 // LDS: val [M] double | part [M] uint16 | list [M] uint16 | rv [16] double | rc [16] int | pv [16] double |
 // pc [16] int | n_list int
@@ -405,7 +402,10 @@ inline bool mt_linkage_ok(int linkage) {
 
 extern "C" int64_t explainn_motif_tree_workspace_bytes(int M, int linkage) {
     if (M < 0 || M > EXPLAINN_MOTIF_TREE_MAX_LEAVES || !mt_linkage_ok(linkage)) return 0;
-    return mt_workspace(M).bytes;
+    Carver dry;
+    mt_pieces w;
+    mt_workspace(dry, M, &w);
+    return dry.bytes();
 }
 
 extern "C" int explainn_motif_tree(const float* ncor, const int16_t* align, const int32_t* widths, int M, int linkage,
@@ -425,30 +425,23 @@ extern "C" int explainn_motif_tree(const float* ncor, const int16_t* align, cons
         explainn_set_error("motif_tree: ncor, align, widths, log, link, gone, flips, shifts must be device pointers");
         return EXPLAINN_E_ARG;
     }
-    const mt_layout l = mt_workspace(M);
-    if (!workspace || ((uintptr_t)workspace & 15u) || workspace_bytes < l.bytes) {
-        explainn_set_error("motif_tree: workspace of %lld bytes, 16-byte aligned, needed (%lld given)",
-                           (long long)l.bytes, (long long)workspace_bytes);
-        return EXPLAINN_E_ARG;
-    }
+    Carver cv(workspace);
+    mt_pieces w;
+    mt_workspace(cv, M, &w);
+    if (!workspace_ok("motif_tree", workspace, workspace_bytes, cv.bytes(), 16)) return EXPLAINN_E_ARG;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);
-    int64_t* L = reinterpret_cast<int64_t*>(ws + l.l);
-    uint64_t* K = reinterpret_cast<uint64_t*>(ws + l.k);
-    int* size = reinterpret_cast<int*>(ws + l.size);
-    int* slot = reinterpret_cast<int*>(ws + l.slot);
     const int64_t total = (int64_t)M * M;
     const int64_t blocks = (total + 255) / 256;
     hipLaunchKernelGGL(motif_tree_prepare_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, s,
-                       ncor, M, total, L, K);
+                       ncor, M, total, w.L, w.K);
     LAUNCH_CHECK();
     const size_t lds = mt_lds_bytes(M);
     if (lds > 48 * 1024)
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&motif_tree_kernel),
                                     hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)mt_lds_bytes(EXPLAINN_MOTIF_TREE_MAX_LEAVES)));
-    hipLaunchKernelGGL(motif_tree_kernel, dim3(1), dim3(MT_THREADS), lds, s, align, widths, M, linkage, L, K, size,
-                       slot, log, link, gone, flips, shifts);
+    hipLaunchKernelGGL(motif_tree_kernel, dim3(1), dim3(MT_THREADS), lds, s, align, widths, M, linkage, w.L, w.K,
+                       w.size, w.slot, log, link, gone, flips, shifts);
     LAUNCH_CHECK();
     return EXPLAINN_OK;
 }

@@ -272,10 +272,11 @@ extern "C" int explainn_pwm_sites(const uint8_t* seq, int64_t seq_len, int64_t s
         explainn_set_error("pwm_sites: seq, scores, widths and thresholds must be device pointers");
         return EXPLAINN_E_ARG;
     }
-    if (!none && !site_workspace_ok("pwm_sites", workspace, workspace_bytes,
-                                    explainn_pwm_sites_workspace_bytes(M, n_positions)))
+    if (!none && !workspace_ok("pwm_sites", workspace, workspace_bytes,
+                               explainn_pwm_sites_workspace_bytes(M, n_positions), 256))
         return EXPLAINN_E_ARG;
-    const SiteWorkspace w = none ? SiteWorkspace{} : site_workspace(workspace, 2 * M, n_positions);
+    Carver cv(workspace);
+    const SiteWorkspace w = none ? SiteWorkspace{} : site_workspace(cv, 2 * M, n_positions);
     long long* off = reinterpret_cast<long long*>(offsets);
     // the bases the call may read from `start` on: n_positions + wmax - 1, clipped to the sequence
     const int span = (int)std::min<int64_t>(n_positions + wmax - 1, seq_len - start);

@@ -84,13 +84,14 @@ __global__ __launch_bounds__(SITES_T) void sites_kernel(
 int64_t sites_workspace_bytes(const explainn_ctx* c, int64_t npos) { return site_workspace_bytes(c->U, npos); }
 
 bool sites_workspace_ok(const explainn_ctx* c, int64_t npos, const void* workspace, int64_t workspace_bytes) {
-    return site_workspace_ok("call_sites", workspace, workspace_bytes, sites_workspace_bytes(c, npos));
+    return workspace_ok("call_sites", workspace, workspace_bytes, sites_workspace_bytes(c, npos), 256);
 }
 
 int launch_call_sites(explainn_ctx* c, const uint8_t* seq, int64_t start, int64_t npos, int64_t period,
                       int rc, const float* thr, int64_t* offsets, int32_t* pos, float* score,
                       int64_t capacity, void* workspace, hipStream_t s) {
-    const SiteWorkspace w = site_workspace(workspace, c->U, npos);
+    Carver cv(workspace);
+    const SiteWorkspace w = site_workspace(cv, c->U, npos);
     long long* off = reinterpret_cast<long long*>(offsets);
     const size_t sm = (size_t)c->k * 5 * sizeof(float4) + ((EXPLAINN_SITES_TILE + c->k - 1 + 15) & ~15);
     return site_passes(c->U, npos, w, off, pos != nullptr && capacity > 0, s, [&](auto mode) {

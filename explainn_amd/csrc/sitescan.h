@@ -12,6 +12,7 @@
 // into ranks -- the workspace, the four launches, the tile geometry, the rank rule -- is here.
 #pragma once
 #include "common.h"
+#include "workspace.h"
 
 namespace {
 
@@ -19,29 +20,26 @@ enum { SITES_COUNT = 0, SITES_EMIT = 1 };
 
 // ---- the workspace: cnt int [rows][tiles] | tot int64 [rows] ---------------------------------------
 struct SiteWorkspace {
-    int* cnt;
-    long long* tot;
-    int ntiles;
+    int* cnt = nullptr;
+    long long* tot = nullptr;
+    int ntiles = 0;
 };
 
-int64_t align256(int64_t v) { return (v + 255) & ~int64_t(255); }
 int64_t sites_tiles(int64_t npos) { return (npos + EXPLAINN_SITES_TILE - 1) / EXPLAINN_SITES_TILE; }
-int64_t site_cnt_bytes(int64_t rows, int64_t npos) { return align256(rows * sites_tiles(npos) * (int64_t)sizeof(int)); }
+
+SiteWorkspace site_workspace(Carver& cv, int64_t rows, int64_t npos) {
+    const int64_t tiles = sites_tiles(npos);
+    SiteWorkspace w;
+    w.ntiles = (int)tiles;
+    cv.take(&w.cnt, rows * tiles);
+    cv.take(&w.tot, rows);
+    return w;
+}
 
 int64_t site_workspace_bytes(int64_t rows, int64_t npos) {
-    return site_cnt_bytes(rows, npos) + align256(rows * (int64_t)sizeof(long long));
-}
-
-SiteWorkspace site_workspace(void* ws, int64_t rows, int64_t npos) {
-    return {static_cast<int*>(ws), reinterpret_cast<long long*>(static_cast<char*>(ws) + site_cnt_bytes(rows, npos)),
-            (int)sites_tiles(npos)};
-}
-
-bool site_workspace_ok(const char* who, const void* ws, int64_t bytes, int64_t need) {
-    if (ws && bytes >= need && (reinterpret_cast<uintptr_t>(ws) & 255) == 0) return true;
-    explainn_set_error("%s workspace of %lld bytes (256-byte aligned), %lld needed", who, (long long)bytes,
-                       (long long)need);
-    return false;
+    Carver dry;
+    site_workspace(dry, rows, npos);
+    return dry.bytes();
 }
 
 // ---- the two scans ---------------------------------------------------------------------------------

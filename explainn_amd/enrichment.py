@@ -67,18 +67,9 @@ def enrichment_test(bits, labels, want_tails=False):
     (N,).  Returns a dict of device tensors: n_thresholds, best_pattern (int32), tp, fp, u2 (int64), log_pvalue,
     log_padj, auroc (float64), each (units,), counts int64 (2,) = (Np, Nc) and, with want_tails, tails int32
     (units, 2, 32768): a_t and b_t (below 2^31)."""
-    import ctypes as C
-
     from . import _lib
-    if not torch.is_tensor(bits) or bits.dtype != torch.int16 or bits.dim() != 2 or bits.device.type != "cuda" or \
-            not bits.is_contiguous():
-        raise RuntimeError("bits must be a contiguous int16 tensor of shape (units, N) on a HIP device (there is "
-                           "no CPU fallback)")
-    units, n = bits.shape
-    dev = bits.device
-    if not torch.is_tensor(labels) or labels.dtype != torch.uint8 or tuple(labels.shape) != (n,) or \
-            labels.device != dev or not labels.is_contiguous():
-        raise RuntimeError("labels must be a contiguous uint8 tensor of shape (%d,) on %s" % (n, dev))
+    (units, n), dev = _lib.require(bits, torch.int16, (None, None), None, "bits").shape, bits.device
+    _lib.require(labels, torch.uint8, (n,), dev, "labels")
     out = {"n_thresholds": torch.empty(units, device=dev, dtype=torch.int32),
            "best_pattern": torch.empty(units, device=dev, dtype=torch.int32),
            "tp": torch.empty(units, device=dev, dtype=torch.int64),
@@ -89,20 +80,16 @@ def enrichment_test(bits, labels, want_tails=False):
            "auroc": torch.empty(units, device=dev, dtype=torch.float64),
            "counts": torch.zeros(2, device=dev, dtype=torch.int64)}
     tails = torch.empty((units, 2, _lib.ACT_BINS), device=dev, dtype=torch.int32) if want_tails else None
-    lib = _lib.load()
-    nbytes = int(lib.explainn_enrichment_workspace_bytes(units, n))
-    ws = torch.empty(max(nbytes, 1), device=dev, dtype=torch.uint8)
-    with torch.cuda.device(dev):
-        _lib.check(lib.explainn_enrichment_test(
-            bits.data_ptr(), labels.data_ptr(), units, n, *(out[f].data_ptr() for f in _FIELDS),
-            out["counts"].data_ptr(), tails.data_ptr() if want_tails else None, ws.data_ptr(), nbytes,
-            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    ws, nbytes = _lib.workspace("explainn_enrichment_workspace_bytes", dev, units, n)
+    _lib.call("explainn_enrichment_test", dev, bits, labels, units, n, *(out[f] for f in _FIELDS), out["counts"], tails,
+              ws, nbytes)
     if want_tails:
         out["tails"] = tails
     return out
 
 
 def benjamini_hochberg(pvalue):
+    """The 1-D numpy adapter of motifs.benjamini_hochberg ((Q,T) torch, per row): p-values (n,) -> q-values (n,)."""
     from .motifs import benjamini_hochberg as bh
     return bh(torch.as_tensor(np.asarray(pvalue, dtype=np.float64))[None, :])[0].numpy()
 

@@ -185,26 +185,19 @@ def workspace_bytes(N, T, per_task, kind):
 def _run(kind, y, s, per_task):
     dev, y, s = _prepare(y, s)
     N, T = y.shape
-    nbytes = workspace_bytes(N, T, per_task, kind)
-    lib = _lib.load()
     mode = _lib.METRICS_PER_TASK if per_task else _lib.METRICS_GLOBAL
+    ws, nbytes = _lib.workspace("explainn_metrics_workspace_bytes", dev, N, T, mode,
+                                _lib.METRICS_BINARY if kind == BINARY else _lib.METRICS_LINEAR)
     shape = (T,) if per_task else ()
-    with torch.cuda.device(dev):
-        first = torch.empty(shape, device=dev, dtype=torch.float64)
-        second = torch.empty(shape, device=dev, dtype=torch.float64)
-        status = torch.zeros(1, device=dev, dtype=torch.int32)
-        ws = torch.empty(max(nbytes, 1), device=dev, dtype=torch.uint8)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        if kind == BINARY:
-            counts = torch.empty(shape + (2,), device=dev, dtype=torch.int64)
-            _lib.check(lib.explainn_metrics_binary(
-                y.data_ptr(), s.data_ptr(), N, T, mode, first.data_ptr(), second.data_ptr(),
-                counts.data_ptr(), status.data_ptr(), ws.data_ptr(), nbytes, stream))
-        else:
-            counts = None
-            _lib.check(lib.explainn_metrics_linear(
-                y.data_ptr(), s.data_ptr(), N, T, mode, first.data_ptr(), second.data_ptr(),
-                status.data_ptr(), ws.data_ptr(), nbytes, stream))
+    first = torch.empty(shape, device=dev, dtype=torch.float64)
+    second = torch.empty(shape, device=dev, dtype=torch.float64)
+    status = torch.zeros(1, device=dev, dtype=torch.int32)
+    if kind == BINARY:
+        counts = torch.empty(shape + (2,), device=dev, dtype=torch.int64)
+        _lib.call("explainn_metrics_binary", dev, y, s, N, T, mode, first, second, counts, status, ws, nbytes)
+    else:
+        counts = None
+        _lib.call("explainn_metrics_linear", dev, y, s, N, T, mode, first, second, status, ws, nbytes)
     call = _Call(kind, first, second, status, counts)
     return _wrap(first, call, 0), _wrap(second, call, 1)
 

@@ -213,26 +213,6 @@ def _pad(x, wmax):
     return out
 
 
-def _device_for(device, sets, what):
-    """The device of a call: the one asked for, else that of the first device tensor among the sets, else the
-    current one.  There is no CPU path."""
-    import torch
-    if device is None:
-        for obj in sets:
-            first = obj[0] if isinstance(obj, (tuple, list)) and len(obj) else obj
-            if torch.is_tensor(first) and first.device.type == "cuda":
-                device = first.device
-                break
-    if device is None:
-        if not torch.cuda.is_available():
-            raise RuntimeError("motifs.%s runs only on a HIP device (there is no CPU fallback)" % what)
-        device = torch.device("cuda", torch.cuda.current_device())
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError("motifs.%s runs only on a HIP device (there is no CPU fallback)" % what)
-    return device
-
-
 def _padded_sets(queries, targets, device):
     """Both sets on the device at one common wmax: (q, qw, t or None, tw or None, wmax)."""
     q, qw = _as_set(queries, device)
@@ -253,8 +233,6 @@ def compare(queries, targets=None, min_overlap=5, pseudocount=0.0, both_strands=
     filter with nsites == 0, is given width 0) or filter_pwms' whole result.  Returns a MotifComparison of
     device tensors (Q,T): ncor and cor (float32), offset, strand, overlap (int16; views of one tensor).
     Enqueued on the current stream; no host synchronisation."""
-    import ctypes as C
-
     import torch
 
     from . import _lib
@@ -262,22 +240,16 @@ def compare(queries, targets=None, min_overlap=5, pseudocount=0.0, both_strands=
         raise ValueError("min_overlap must be at least 1")
     if not float(pseudocount) >= 0:
         raise ValueError("pseudocount must not be negative")
-    device = _device_for(device, (queries, targets), "compare")
+    device = _lib.device_for(device, (queries, targets), "motifs.compare")
     q, qw, t, tw, wmax = _padded_sets(queries, targets, device)
     Q, T = len(q), len(t) if t is not None else len(q)
     ncor = torch.empty((Q, T), dtype=torch.float32, device=device)      # every entry is overwritten
     cor = torch.empty((Q, T), dtype=torch.float32, device=device)
     align = torch.empty((Q, T, 3), dtype=torch.int16, device=device)
     if Q and T:
-        lib = _lib.load()
-        nbytes = int(lib.explainn_motif_compare_workspace_bytes(Q, T, wmax))
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=device)
-        with torch.cuda.device(device):
-            _lib.check(lib.explainn_motif_compare(
-                q.data_ptr(), qw.data_ptr(), Q, t.data_ptr() if t is not None else None,
-                tw.data_ptr() if t is not None else None, T, wmax, float(pseudocount), int(min_overlap),
-                int(bool(both_strands)), ncor.data_ptr(), cor.data_ptr(), align.data_ptr(), ws.data_ptr(), nbytes,
-                C.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+        ws, nbytes = _lib.workspace("explainn_motif_compare_workspace_bytes", device, Q, T, wmax)
+        _lib.call("explainn_motif_compare", device, q, qw, Q, t, tw, T, wmax, float(pseudocount), int(min_overlap),
+                  int(bool(both_strands)), ncor, cor, align, ws, nbytes)
     return MotifComparison(ncor, cor, align[..., 0], align[..., 1], align[..., 2])
 
 
@@ -345,13 +317,11 @@ def significance(queries, targets=None, min_overlap=5, pseudocount=0.0, both_str
     workspace_bytes: the budget of device scratch; the queries are split into as many calls as it takes (one
     query per call when even that exceeds it) and the result does not depend on the split.  Enqueued on the
     current stream; no host synchronisation."""
-    import ctypes as C
-
     import torch
 
     from . import _lib
     _significance_args(min_overlap, pseudocount, bins, workspace_bytes)
-    device = _device_for(device, (queries, targets), "significance")
+    device = _lib.device_for(device, (queries, targets), "motifs.significance")
     q, qw, t, tw, wmax = _padded_sets(queries, targets, device)
     Q, T = len(q), len(t) if t is not None else len(q)
     both, bins = int(bool(both_strands)), int(bins)
@@ -359,21 +329,15 @@ def significance(queries, targets=None, min_overlap=5, pseudocount=0.0, both_str
     align = torch.empty((Q, T, 3), dtype=torch.int16, device=device)
     score = torch.empty((Q, T), dtype=torch.int32, device=device)
     if Q and T:
-        lib = _lib.load()
-        step = _query_chunk(lib, Q, T, wmax, bins, both, int(workspace_bytes))
+        step = _query_chunk(_lib.load(), Q, T, wmax, bins, both, int(workspace_bytes))
         if step < Q and t is None:                                       # the database is all of the queries
             t, tw = q, qw
-        nbytes = int(lib.explainn_motif_significance_workspace_bytes(step, T, wmax, bins, both))
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=device)
-        with torch.cuda.device(device):
-            stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-            for a in range(0, Q, step):
-                n = min(step, Q - a)
-                _lib.check(lib.explainn_motif_significance(
-                    q[a:a + n].data_ptr(), qw[a:a + n].data_ptr(), n, t.data_ptr() if t is not None else None,
-                    tw.data_ptr() if t is not None else None, T, wmax, float(pseudocount), int(min_overlap), both,
-                    bins, pvalue[a:a + n].data_ptr(), align[a:a + n].data_ptr(), score[a:a + n].data_ptr(), None,
-                    None, ws.data_ptr(), nbytes, stream))
+        ws, nbytes = _lib.workspace("explainn_motif_significance_workspace_bytes", device, step, T, wmax, bins, both)
+        for a in range(0, Q, step):
+            n = min(step, Q - a)
+            _lib.call("explainn_motif_significance", device, q[a:a + n], qw[a:a + n], n, t, tw, T, wmax,
+                      float(pseudocount), int(min_overlap), both, bins, pvalue[a:a + n], align[a:a + n],
+                      score[a:a + n], None, None, ws, nbytes)
     return MotifSignificance(pvalue, pvalue * T, benjamini_hochberg(pvalue), align[..., 0], align[..., 1],
                              align[..., 2], score)
 
@@ -578,24 +542,16 @@ class MotifTree:
         return text[0] + ";"
 
     def _cut(self, min_ncor):
-        import ctypes as C
-
         import torch
 
         from . import _lib
         thr = _cut_threshold(min_ncor)
-        dev = self.widths.device
-        if dev.type != "cuda":
-            raise RuntimeError("MotifTree.cut runs only on a HIP device (there is no CPU fallback)")
+        dev = _lib.device_for(self.widths.device, (), "MotifTree.cut")
         M = self.M
         slots, flips, shifts, lo, hi = (torch.empty((M,), dtype=torch.int32, device=dev) for _ in range(5))
         if M:
-            lib = _lib.load()
-            with torch.cuda.device(dev):
-                _lib.check(lib.explainn_motif_tree_cut(
-                    self.log.data_ptr(), self.link.data_ptr(), self.gone.data_ptr(), self.widths.data_ptr(), M, thr,
-                    slots.data_ptr(), flips.data_ptr(), shifts.data_ptr(), lo.data_ptr(), hi.data_ptr(),
-                    C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            _lib.call("explainn_motif_tree_cut", dev, self.log, self.link, self.gone, self.widths, M, thr, slots,
+                      flips, shifts, lo, hi)
         uniq, labels = torch.unique(slots, sorted=True, return_inverse=True)      # a slot is its smallest member
         spans = (hi - lo)[uniq.long()].cpu().numpy().astype(np.int32)             # the host synchronisation
         return labels.to(torch.int64), flips, shifts, spans, slots, uniq.to(torch.int32)
@@ -617,8 +573,6 @@ def tree(result, widths=None, linkage="average", max_bytes=2 << 30):
     (default: the overlap of every motif with itself, which is its width unless it has no variance).  One
     workgroup runs the loop on the device (csrc/motiftree.hip); nothing is synchronised.  ValueError when the
     two M x M work matrices exceed max_bytes or M exceeds what the kernel holds."""
-    import ctypes as C
-
     import torch
 
     from . import _lib
@@ -635,9 +589,7 @@ def tree(result, widths=None, linkage="average", max_bytes=2 << 30):
     if M > MAX_LEAVES:
         raise ValueError("tree takes at most %d motifs: the kernel caches one entry per slot in LDS (got %d)"
                          % (MAX_LEAVES, M))
-    dev = result.ncor.device
-    if dev.type != "cuda":
-        raise RuntimeError("motifs.tree runs only on a HIP device (there is no CPU fallback)")
+    dev = _lib.device_for(result.ncor.device, (), "motifs.tree")
     ncor = result.ncor.to(torch.float32).contiguous()
     align = torch.stack([result.offset, result.strand, result.overlap], dim=-1).to(torch.int16).contiguous()
     if widths is None:
@@ -649,15 +601,9 @@ def tree(result, widths=None, linkage="average", max_bytes=2 << 30):
     link = torch.empty((max(M - 1, 0), 2), dtype=torch.int64, device=dev)
     gone, flips, shifts = (torch.empty((M,), dtype=torch.int32, device=dev) for _ in range(3))
     if M:
-        lib = _lib.load()
         kind = LINKAGES[linkage]
-        nbytes = int(lib.explainn_motif_tree_workspace_bytes(M, kind))
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.explainn_motif_tree(
-                ncor.data_ptr(), align.data_ptr(), widths.data_ptr(), M, kind, log.data_ptr(), link.data_ptr(),
-                gone.data_ptr(), flips.data_ptr(), shifts.data_ptr(), ws.data_ptr(), nbytes,
-                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        ws, nbytes = _lib.workspace("explainn_motif_tree_workspace_bytes", dev, M, kind)
+        _lib.call("explainn_motif_tree", dev, ncor, align, widths, M, kind, log, link, gone, flips, shifts, ws, nbytes)
     return MotifTree(log, link, gone, flips, shifts, widths, linkage)
 
 
@@ -723,13 +669,11 @@ def merge(motifs, tree=None, min_ncor=0.4, linkage="average", device=None, **com
     ascending order, on the device: the same bits on every run).  motifs: anything `compare` accepts; matrices
     are summed as given, so pre-scale them to weight them.  tree: a MotifTree of the same set (default:
     compare(motifs, **compare_args), then tree(..., linkage)).  Returns a MergedMotifs."""
-    import ctypes as C
-
     import torch
 
     from . import _lib
     _cut_threshold(min_ncor)
-    device = _device_for(device, (motifs,), "merge")
+    device = _lib.device_for(device, (motifs,), "motifs.merge")
     x, w = _as_set(motifs, device)
     if x.shape[1] > MAX_WIDTH:
         raise ValueError("motifs wider than %d columns are not supported (got %d)" % (MAX_WIDTH, x.shape[1]))
@@ -745,11 +689,8 @@ def merge(motifs, tree=None, min_ncor=0.4, linkage="average", device=None, **com
     pfm = torch.empty((n, smax, 4), dtype=torch.float64, device=device)
     support = torch.empty((n, smax), dtype=torch.int32, device=device)
     if n and smax:
-        with torch.cuda.device(device):
-            _lib.check(_lib.load().explainn_motif_tree_pool(
-                x.data_ptr(), w.data_ptr(), slots.data_ptr(), flips.data_ptr(), shifts.data_ptr(),
-                cluster_slots.data_ptr(), M, wmax, n, smax, pfm.data_ptr(), support.data_ptr(),
-                C.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+        _lib.call("explainn_motif_tree_pool", device, x, w, slots, flips, shifts, cluster_slots, M, wmax, n, smax, pfm,
+                  support)
     labels = labels.cpu().numpy()
     members = [np.nonzero(labels == c)[0] for c in range(n)]
     names = ["cluster%d_n%d" % (c, len(m)) for c, m in enumerate(members)]

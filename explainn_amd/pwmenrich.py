@@ -31,11 +31,11 @@ There is no CPU path.
 """
 import argparse
 import contextlib
-import ctypes as C
 
 import numpy as np
 import torch
 
+from . import _lib
 from . import centrality as _cen
 from . import enrichment as _enr
 from . import pwmsites as _pwm
@@ -95,24 +95,18 @@ def record_best_device(scores, widths, seq, offsets, both=True, want_site=True, 
     """explainn_pwm_record_best on device tensors: scores int16 (M,wmax,4), widths int32 (M,), seq uint8 (n,),
     offsets int64 (R+1,).  Returns (bits int16 (M,R), site int32 (M,R) or None) on the device; `flags`: an int32
     (1,) device tensor that bit 0 is ORed into for forged offsets.  Enqueued on the current stream."""
-    from . import _lib
-    dev = seq.device
-    for t, dt, nd in ((scores, torch.int16, 3), (widths, torch.int32, 1), (seq, torch.uint8, 1), (offsets, torch.int64, 1)):
-        if not torch.is_tensor(t) or t.dtype != dt or t.dim() != nd or t.device.type != "cuda" or t.device != dev or \
-                not t.is_contiguous():
-            raise RuntimeError("scores (int16 (M,wmax,4)), widths (int32), seq (uint8) and offsets (int64) must be "
-                               "contiguous tensors on one HIP device (there is no CPU fallback)")
+    dev = _lib.require(seq, torch.uint8, (None,), None, "seq").device
+    _lib.require(scores, torch.int16, (None, None, None), dev, "scores")
+    _lib.require(widths, torch.int32, (None,), dev, "widths")
+    _lib.require(offsets, torch.int64, (None,), dev, "offsets")
     M, wmax = scores.shape[0], scores.shape[1]
     if scores.shape[2] != 4 or widths.shape[0] != M or offsets.shape[0] < 1:
         raise ValueError("scores must be (M,wmax,4), widths (M,) and offsets (R+1,)")
     R = offsets.shape[0] - 1
     bits = torch.empty((M, R), dtype=torch.int16, device=dev)
     site = torch.empty((M, R), dtype=torch.int32, device=dev) if want_site else None
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().explainn_pwm_record_best(
-            seq.data_ptr(), seq.shape[0], offsets.data_ptr(), R, int(bool(both)), scores.data_ptr(), widths.data_ptr(),
-            M, max(wmax, 1), bits.data_ptr(), site.data_ptr() if want_site else None,
-            flags.data_ptr() if flags is not None else None, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    _lib.call("explainn_pwm_record_best", dev, seq, seq.shape[0], offsets, R, int(bool(both)), scores, widths, M,
+              max(wmax, 1), bits, site, flags)
     return bits, site
 
 
@@ -199,7 +193,7 @@ def best_motif_sites(motifs, records, bg=None, pseudocount=0.1, bins=100, strand
     both = _enr._strands(strands) == 2
     tab = _Tables(motifs, bg, pseudocount, bins)
     ids, codes = record_codes(records)
-    scorer = MotifScorer(tab, both, _pwm._device_for(device, None, "best_motif_sites"))
+    scorer = MotifScorer(tab, both, _lib.device_for(device, (), "pwmsites.best_motif_sites"))
     bits, site = best_over_records(scorer, codes, chunk_bases, True)
     return MotifBest.from_device(bits.cpu().numpy(), site.cpu().numpy(), [len(c) for c in codes], tab.widths, tab.ids,
                                  tab.scale, tab.lo, ids)
@@ -253,7 +247,7 @@ def motif_enrichment(motifs, primary, control=None, shuffles=1, seed=0, bg=None,
     the call; `excluded` counts them).  Returns a MotifEnrichment."""
     both = _enr._strands(strands) == 2
     tab = _Tables(motifs, bg, pseudocount, bins)
-    scorer = MotifScorer(tab, both, _pwm._device_for(device, None, "motif_enrichment"))
+    scorer = MotifScorer(tab, both, _lib.device_for(device, (), "pwmsites.motif_enrichment"))
     bits, labels, shuffles = enrichment_bits(scorer, primary, control, shuffles, seed, chunk_bases)
     out = _enr.enrichment_test(bits, torch.from_numpy(labels).to(scorer.device))
     if tab.M:
@@ -307,7 +301,7 @@ def filters_and_motifs(filter_primary, motif_primary, filter_control, motif_cont
     mp = motif_primary
     need = max([filter_primary.kernel_size] + [int(w) for w in mp.live_widths])
     labels = record_labels(filter_primary.lengths, filter_control.lengths, need)
-    device = _pwm._device_for(device, None, "filters_and_motifs")
+    device = _lib.device_for(device, (), "pwmsites.filters_and_motifs")
     bits = torch.from_numpy(np.ascontiguousarray(np.concatenate(sets, axis=1)).view(np.int16)).to(device)
     out = _enr.enrichment_test(bits, torch.from_numpy(labels).to(device))
     res = Enrichment(*(out[f].cpu().numpy() for f in _EFIELDS), out["counts"].cpu().numpy(), need)
@@ -396,7 +390,7 @@ def motif_centrality(motifs, records, pvalues=(1e-4,), control=None, local=False
     if tab.widest == 0:
         raise ValueError("no motif is live (every motif is empty)")
     codes, labels_np, L = _cen.centred_records(records, control, tab.widest)
-    device = _pwm._device_for(device, None, "motif_centrality")
+    device = _lib.device_for(device, (), "pwmsites.motif_centrality")
     labels = torch.from_numpy(labels_np).to(device)
     scorer = MotifScorer(tab, both, device)
     thr = np.stack([_pwm._null(tab.S, tab.live, tab.scale, tab.lo, tab.bins, tab.bg, p, device).thresholds.cpu().numpy()

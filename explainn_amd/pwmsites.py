@@ -20,7 +20,6 @@ smallest integer score whose tail is <= pvalue.  The scan (explainn_pwm_sites, c
 There is no CPU path.
 """
 import argparse
-import ctypes as C
 import sys
 import types
 
@@ -107,20 +106,6 @@ def quantise(motifs, bg=None, pseudocount=0.1, bins=100):
 
 
 # ---------------------------------------------------------------- the device calls
-def _device_for(device, codes, what):
-    import torch
-    if device is None and torch.is_tensor(codes) and codes.device.type == "cuda":
-        device = codes.device
-    if device is None:
-        if not torch.cuda.is_available():
-            raise RuntimeError("pwmsites.%s runs only on a HIP device (there is no CPU fallback)" % what)
-        device = torch.device("cuda", torch.cuda.current_device())
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError("pwmsites.%s runs only on a HIP device (there is no CPU fallback)" % what)
-    return device
-
-
 class PwmNull:
     """The exact null of a set of quantised motifs, on the device: `tail` float64 (M, wmax bins + 2),
     tail[m][s] = P(score of a random w-mer >= s) (zero past w bins, all zero for an empty motif) and
@@ -146,11 +131,8 @@ def _null(S, live_widths, scale, lo, bins, bg, pvalue, device):
     widths = torch.from_numpy(live_widths).to(device)
     tail = torch.empty((M, wmax * int(bins) + 2), dtype=torch.float64, device=device)     # every entry is overwritten
     thr = torch.empty((M,), dtype=torch.int32, device=device)
-    with torch.cuda.device(device):
-        _lib.check(_lib.load().explainn_pwm_null(
-            scores.data_ptr(), widths.data_ptr(), M, wmax, int(bins), float(bg[0]), float(bg[1]), float(bg[2]),
-            float(bg[3]), float(pvalue), tail.data_ptr(), thr.data_ptr(),
-            C.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+    _lib.call("explainn_pwm_null", device, scores, widths, M, wmax, int(bins), float(bg[0]), float(bg[1]),
+              float(bg[2]), float(bg[3]), float(pvalue), tail, thr)
     return PwmNull(tail, thr, scores, widths, scale, lo, bins, bg, pvalue)
 
 
@@ -161,7 +143,8 @@ def score_null(motifs, pvalue=1e-4, bg=None, pseudocount=0.1, bins=100, device=N
     _, mats = motif_list(motifs)
     b = _background(bg)
     S, widths, scale, lo = quantise(mats, b, pseudocount, bins)
-    device = _device_for(device, None, "score_null")
+    from . import _lib
+    device = _lib.device_for(device, (), "pwmsites.score_null")
     return _null(S, np.where(scale > 0, widths, 0).astype(np.int32), scale, lo, bins, b, pvalue, device)
 
 
@@ -232,25 +215,20 @@ def scan_motifs(motifs, codes, pvalue=1e-4, bg=None, pseudocount=0.1, bins=100, 
     data = as_codes_1d(codes)
     b = sequence_background(data, strands) if isinstance(bg, str) and bg == "sequence" else _background(bg)
     S, widths, scale, lo = quantise(mats, b, pseudocount, bins)
-    device = _device_for(device, data, "scan_motifs")
+    device = _lib.device_for(device, (data,), "pwmsites.scan_motifs")
     M, wmax, n = len(mats), S.shape[1], int(data.shape[0])
     blocks = []
     if M and n:
-        lib = _lib.load()
         null = _null(S, np.where(scale > 0, widths, 0).astype(np.int32), scale, lo, bins, b, pvalue, device)
         chunks = _sites.position_chunks(n, _chunk_for(M, chunk_positions), period)
-        nbytes = int(lib.explainn_pwm_sites_workspace_bytes(M, max(c for _, c in chunks)))
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=device)
+        ws, nbytes = _lib.workspace("explainn_pwm_sites_workspace_bytes", device, M, max(c for _, c in chunks))
         offsets = torch.empty((2 * M + 1,), dtype=torch.int64, device=device)
         both = int(strands == "both")
         with torch.cuda.device(device):
-            stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
             def call(piece, cnt, pos, score, pv, capacity):
-                _lib.check(lib.explainn_pwm_sites(
-                    piece.data_ptr(), piece.shape[0], 0, cnt, int(period), both, null.scores.data_ptr(),
-                    null.widths.data_ptr(), M, wmax, null.thresholds.data_ptr(), null.tail.data_ptr(), int(bins),
-                    offsets.data_ptr(), pos, score, pv, capacity, ws.data_ptr(), nbytes, stream))
+                _lib.call("explainn_pwm_sites", device, piece, piece.shape[0], 0, cnt, int(period), both, null.scores,
+                          null.widths, M, wmax, null.thresholds, null.tail, int(bins), offsets, pos, score, pv,
+                          capacity, ws, nbytes)
 
             def count(piece, cnt):
                 call(piece, cnt, None, None, None, 0)
@@ -259,7 +237,7 @@ def scan_motifs(motifs, codes, pvalue=1e-4, bg=None, pseudocount=0.1, bins=100, 
             def emit(piece, cnt, total):
                 out = [torch.empty((total,), dtype=dt, device=device)
                        for dt in (torch.int32, torch.int32, torch.float64)]      # pos, iscore, pvalue
-                call(piece, cnt, *[t.data_ptr() for t in out], total)
+                call(piece, cnt, *out, total)
                 return lambda: [t.cpu().numpy() for t in out]
 
             # one leg on the current stream: its rows are the site list's, 2 m + (strand < 0)

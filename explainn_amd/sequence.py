@@ -168,8 +168,6 @@ def dinucleotide_shuffle_device(codes, n=1, seed=0, row0=0, max_rounds=0, return
     come back as 4.  max_rounds caps the cycle-popping rounds of the last-exit sampler (0: 64*L, not
     reachable in practice); return_capped=True also returns a uint8 (n,) or (N,n) tensor, 1 where the cap
     was hit and the row's own last exits were used instead."""
-    import ctypes as C
-
     import torch
 
     from . import _lib
@@ -191,12 +189,8 @@ def dinucleotide_shuffle_device(codes, n=1, seed=0, row0=0, max_rounds=0, return
     out = torch.empty((N, n, L), dtype=torch.uint8, device=rows.device)
     capped = torch.empty((N, n), dtype=torch.uint8, device=rows.device) if return_capped else None
     if N:
-        lib = _lib.load()
-        with torch.cuda.device(rows.device):
-            _lib.check(lib.explainn_dinucleotide_shuffle(
-                rows.data_ptr(), N, L, int(n), int(seed) & (2 ** 64 - 1), int(row0), int(max_rounds),
-                out.data_ptr(), capped.data_ptr() if return_capped else None,
-                C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream)))
+        _lib.call("explainn_dinucleotide_shuffle", rows.device, rows, N, L, int(n), int(seed) & (2 ** 64 - 1), int(row0),
+                  int(max_rounds), out, capped)
     if codes.dim() == 1:
         out = out[0]
         capped = capped[0] if return_capped else None

@@ -252,18 +252,12 @@ ACT_INF = 0x7C00             # the pattern of +inf; the patterns above it are Na
 def _null_stats(hist, alpha, want_tail=False, want_thresholds=False):
     """(tail, total, thresholds) of a device int64 (units, ACT_BINS) histogram (explainn_activation_null);
     tail / thresholds None unless asked for."""
-    import ctypes as C
-
     from . import _lib
     units, dev = hist.shape[0], hist.device
     total = torch.empty(units, device=dev, dtype=torch.int64)
     tail = torch.empty_like(hist) if want_tail else None
     thr = torch.empty(units, device=dev, dtype=torch.float32) if want_thresholds else None
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().explainn_activation_null(
-            hist.data_ptr(), units, float(alpha), tail.data_ptr() if want_tail else None, total.data_ptr(),
-            thr.data_ptr() if want_thresholds else None,
-            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    _lib.call("explainn_activation_null", dev, hist, units, float(alpha), tail, total, thr)
     return tail, total, thr
 
 

@@ -146,9 +146,8 @@ class SpacingCounts:
         return self.site_counts.shape[0]
 
     def _device_sets(self):
-        dev = self.hist.device
-        if dev.type != "cuda":
-            raise RuntimeError("the spacing test runs only on a HIP device (there is no CPU fallback)")
+        from . import _lib
+        dev = _lib.device_for(self.hist.device, (), "the spacing test")
         return torch.from_numpy(self.anchors).to(dev), torch.from_numpy(self.partners).to(dev)
 
     def test(self, min_distance=None, min_count=10, n_positions=None):
@@ -165,8 +164,6 @@ class SpacingCounts:
         m sum_s n_{a,s} n_{b,+-s} / n_positions (halved for the same filter on opposite strands), and
         `ratio` = total / expected.  The test is one launch on the current stream; selecting the tested
         entries for the q-values reads their number back."""
-        import ctypes as C
-
         from . import _lib
         from .motifs import benjamini_hochberg
         D = self.max_distance
@@ -180,11 +177,8 @@ class SpacingCounts:
         best_distance = torch.zeros((A, P, 2), dtype=torch.int32, device=dev)
         best_count = torch.zeros((A, P, 2), dtype=torch.int64, device=dev)
         pvalue = torch.ones((A, P, 2), dtype=torch.float64, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().explainn_spacing_test(
-                self.hist.data_ptr(), A, P, anchors.data_ptr(), partners.data_ptr(), D, md, int(min_count),
-                total.data_ptr(), best_distance.data_ptr(), best_count.data_ptr(), pvalue.data_ptr(),
-                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        _lib.call("explainn_spacing_test", dev, self.hist, A, P, anchors, partners, D, md, int(min_count), total,
+                  best_distance, best_count, pvalue)
         # the admissible bins of every entry: plain arithmetic on D and min_distance
         side = max(D - max(md, 1) + 1, 0)                          # bins with d > 0
         same = (anchors[:, None] == partners[None, :])
@@ -243,8 +237,6 @@ def spacing(calls, max_distance=100, period=0, anchors=None, partners=None, out=
     The sites must be ascending per (unit, strand), '+' first (ValueError otherwise).  The starts and the
     list offsets go to the device once; the counting is one launch on the current stream and nothing is
     read back."""
-    import ctypes as C
-
     from . import _lib
     D = _check_distance(max_distance)
     start, offsets2, k = site_lists(calls, D, period)
@@ -266,14 +258,7 @@ def spacing(calls, max_distance=100, period=0, anchors=None, partners=None, out=
                 "the histogram of %d x %d filter pairs at max_distance %d takes %d bytes, more than max_bytes = %d: "
                 "pass anchors= / partners= (subsets of the units) or a smaller max_distance" % (
                     A, P, D, nbytes, int(max_bytes)))
-    if out is not None:
-        dev = out.hist.device
-    else:
-        if device is None and not torch.cuda.is_available():
-            raise RuntimeError("spacing runs only on a HIP device (there is no CPU fallback)")
-        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("spacing runs only on a HIP device (there is no CPU fallback); got %s" % dev)
+    dev = _lib.device_for(device if out is None else out.hist.device, (), "spacing")
     if out is None:
         out = SpacingCounts(torch.zeros((A, P, 2, 2 * D + 1), dtype=torch.int64, device=dev), an, pa, D, k,
                             np.zeros_like(counts))
@@ -281,11 +266,7 @@ def spacing(calls, max_distance=100, period=0, anchors=None, partners=None, out=
         pos, off = torch.from_numpy(start).to(dev), torch.from_numpy(offsets2).to(dev)
         an_d = None if an is None else torch.from_numpy(an).to(dev)
         pa_d = None if pa is None else torch.from_numpy(pa).to(dev)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().explainn_site_spacing(
-                pos.data_ptr(), off.data_ptr(), units, None if an is None else an_d.data_ptr(), A,
-                None if pa is None else pa_d.data_ptr(), P, D, out.hist.data_ptr(),
-                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        _lib.call("explainn_site_spacing", dev, pos, off, units, an_d, A, pa_d, P, D, out.hist)
     out.site_counts = out.site_counts + counts
     return out
 
