@@ -226,7 +226,7 @@ def check(rc):
     raise ExplainnError("libexplainn_hip: %s (code %d)" % (msg, rc))
 
 
-# ---------------------------------------------------------------- the context-free entry points' call path
+# ---------------------------------------------------------------- the call path (context-bound: Context.call)
 def device_for(device, candidates, what):
     """The device of a call: the one asked for, else that of the first HIP tensor among `candidates` (looking
     one level into tuples and lists), else the current one.  There is no CPU path: anything else raises, before
@@ -261,22 +261,39 @@ def require(t, dtype, shape, device, name):
     return t
 
 
-def call(name, device, *args):
-    """Enqueue the C function `name` on the current stream of `device`: a tensor goes as its address (it must be
-    contiguous and on `device`), None as NULL, anything else as it is; the stream is the last argument."""
+def arguments(name, device, args):
+    """The arguments of the C function `name` as ctypes takes them: a tensor goes as its address (it must be
+    contiguous and on `device`, a torch.device with an index), None as NULL, anything else as it is -- numbers,
+    ctypes values, byref()s, addresses, and a Structure instance, which ctypes passes by reference where the
+    signature says POINTER.  Nothing is loaded or enqueued here."""
     import torch
-    device = torch.device(device)
-    argv = []
-    for i, a in enumerate(args):
-        if torch.is_tensor(a):
+    argv = list(args)
+    for i, a in enumerate(argv):
+        if isinstance(a, torch.Tensor):
             if a.device != device or not a.is_contiguous():
                 raise RuntimeError("%s: argument %d must be a contiguous tensor on %s (a %s tensor on %s)" % (
                     name, i, device, "contiguous" if a.is_contiguous() else "strided", a.device))
-            a = a.data_ptr()
-        argv.append(a)
+            argv[i] = a.data_ptr()
+    return argv
+
+
+def current_stream(device):
+    """The current stream of `device` as the C functions take it.  The raw handle, as torch's own generated
+    launchers read it: torch.cuda.current_stream() builds a Stream object around it at 2 us a call, more than
+    the rest of Context.call together."""
+    import torch
+    return C.c_void_p(torch._C._cuda_getCurrentRawStream(device.index))
+
+
+def call(name, device, *args):
+    """Enqueue the C function `name` on the current stream of `device` with `arguments`; the stream is the last
+    argument."""
+    import torch
+    device = torch.device(device)
+    argv = arguments(name, device, args)
     fn = getattr(load(), name)
     with torch.cuda.device(device):
-        check(fn(*argv, C.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+        check(fn(*argv, current_stream(device)))
 
 
 def workspace(name, device, *dims):
@@ -308,6 +325,23 @@ class Context:
             check(self.lib.explainn_create_bank(C.byref(h), groups, cnn_units, kernel_size,
                                                 sequence_length, n_features, max_batch, device))
         self.handle = h
+        import torch
+        self.torch_device = torch.device("cuda", device)
+
+    def call(self, name, *args):
+        """Enqueue the C function `name` of this context on the current stream of its device: the handle, then
+        `arguments`, then the stream.  No torch.cuda.device scope is entered: the caller is in one
+        (ExplaiNN._launch).  The entry points without a stream argument are called on `lib` directly."""
+        argv = arguments(name, self.torch_device, args)
+        check(getattr(self.lib, name)(self.handle, *argv, current_stream(self.torch_device)))
+
+    def workspace(self, name, *dims):
+        """(uint8 tensor on this context's device, nbytes) for the size export `name`(handle, *dims); a negative
+        size is a return code and raises as `check` does."""
+        import torch
+        nbytes = int(getattr(self.lib, name)(self.handle, *dims))
+        check(min(nbytes, 0))
+        return torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=self.torch_device), nbytes
 
     def stage_timing(self, enable=True):
         check(self.lib.explainn_stage_timing(self.handle, int(bool(enable))))

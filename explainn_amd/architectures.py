@@ -596,7 +596,7 @@ class ExplaiNN(_Model):
         # a model that has met a soft batch once keeps validating (and routing) per call
         return v == "always" or self._rt.soft_seen or self._rt.calls <= 2
 
-    def _stage(self, ctx, x, stream, policy=SCHEDULED):
+    def _stage(self, ctx, x, policy=SCHEDULED):
         """Hand the batch (from _prep_input) to the context: returns (xp, read), xp the device
         pointer the entry point takes -- None for a batch staged in the context ("the staged batch",
         include/explainn_hip.h) -- and read True when nothing is left for _settle: the validation
@@ -621,8 +621,7 @@ class ExplaiNN(_Model):
         if isinstance(x, BaseCodes):
             self._rt.calls += 1
             _lib.check(lib.explainn_dense_input(h, 0))
-            _lib.check(lib.explainn_stage_codes(h, x.codes.data_ptr(), x.codes.shape[0],
-                                                int(x.reverse_complement), stream))
+            ctx.call("explainn_stage_codes", x.codes, x.codes.shape[0], int(x.reverse_complement))
             return None, False
         if self.dense_input:
             if policy == ONEHOT_ONLY:
@@ -636,9 +635,9 @@ class ExplaiNN(_Model):
         if policy == SCHEDULED and not self._validate_now():
             _lib.check(lib.explainn_dense_input(h, 0))
             return x.data_ptr(), False
-        _lib.check(lib.explainn_stage_onehot(h, x.data_ptr(), x.shape[0], stream))
+        ctx.call("explainn_stage_onehot", x, x.shape[0])
         flags = C.c_int(0)
-        _lib.check(lib.explainn_input_flags(h, C.byref(flags), stream))
+        ctx.call("explainn_input_flags", C.byref(flags))
         if flags.value & 1:
             if policy == ONEHOT_ONLY:
                 raise ValueError(
@@ -659,16 +658,24 @@ class ExplaiNN(_Model):
     def _front(self, x, dev, policy=SCHEDULED, bump=True):
         """Front half of a launch, inside the caller's torch.cuda.device(dev) with x from
         _prep_input: bump the token (an eval launch overwrites the scratch of a train forward still
-        awaiting its backward; train forwards bump it after their launch instead), resolve context,
-        params table and stream, and stage x.  Returns (ctx, ps, keep, stream, xp, read); the
-        entry point makes its call and hands `read` to _settle."""
+        awaiting its backward; train forwards bump it after their launch instead), resolve context
+        and params table, and stage x.  Returns (ctx, ps, keep, xp, read); the entry point makes
+        its call and hands `read` to _settle -- _launch is the two halves around a body."""
         if bump:
             self._rt.token += 1
         ctx = self._context(x.shape[0], dev)
         ps, keep = self._params_struct(dev)
-        stream = self._stream(dev)
-        xp, read = self._stage(ctx, x, stream, policy)
-        return ctx, ps, keep, stream, xp, read
+        xp, read = self._stage(ctx, x, policy)
+        return ctx, ps, keep, xp, read
+
+    @contextlib.contextmanager
+    def _launch(self, x, dev, policy=SCHEDULED, bump=True):
+        """The scope of one launch: torch.cuda.device(dev), _front, the body with (ctx, ps, xp) -- its
+        calls go through ctx.call -- then _settle.  A body that raises is not settled."""
+        with torch.cuda.device(dev):
+            ctx, ps, _, xp, read = self._front(x, dev, policy, bump)
+            yield ctx, ps, xp
+            self._settle(read)
 
     def _settle(self, read):
         """Back half of a launch: read the sticky flag when _stage has not and the schedule says
@@ -699,7 +706,8 @@ class ExplaiNN(_Model):
             return 0
         dev = self._device()
         flags = C.c_int(0)
-        _lib.check(ctx.lib.explainn_input_flags(ctx.handle, C.byref(flags), self._stream(dev)))
+        with torch.cuda.device(dev):
+            ctx.call("explainn_input_flags", C.byref(flags))
         return flags.value
 
     # -- forward / backward ---------------------------------------------------------------
@@ -717,10 +725,8 @@ class ExplaiNN(_Model):
         logits = self._logits_empty(B, dev)
         if B == 0:                                   # torch returns an empty (0, T) tensor in eval
             return logits
-        with torch.cuda.device(dev):
-            ctx, ps, _, stream, xp, read = self._front(x, dev)
-            _lib.check(ctx.lib.explainn_forward_eval(ctx.handle, xp, B, C.byref(ps), logits.data_ptr(), stream))
-            self._settle(read)
+        with self._launch(x, dev) as (ctx, ps, xp):
+            ctx.call("explainn_forward_eval", xp, B, ps, logits)
         return logits
 
     def _launch_scan(self, win, mode=_lib.SCAN_AUTO):
@@ -735,16 +741,10 @@ class ExplaiNN(_Model):
         logits = self._logits_empty(win.n_windows, dev)
         if win.n_windows == 0:
             return logits
-        with torch.cuda.device(dev):
-            ctx, ps, _, stream, xp, read = self._front(win, dev)
-            lib, h = ctx.lib, ctx.handle
-            nbytes = int(lib.explainn_scan_workspace_bytes(h, win.n_windows, win.stride, mode))
-            _lib.check(min(nbytes, 0))
-            ws = torch.empty(max(nbytes, 1), device=dev, dtype=torch.uint8)
-            _lib.check(lib.explainn_scan(h, xp, win.codes.numel(), win.start, win.n_windows, win.stride,
-                                         int(win.reverse_complement), C.byref(ps), logits.data_ptr(), mode,
-                                         ws.data_ptr(), nbytes, stream))
-            self._settle(read)
+        with self._launch(win, dev) as (ctx, ps, xp):
+            ws, nbytes = ctx.workspace("explainn_scan_workspace_bytes", win.n_windows, win.stride, mode)
+            ctx.call("explainn_scan", xp, win.codes.numel(), win.start, win.n_windows, win.stride,
+                     int(win.reverse_complement), ps, logits, mode, ws, nbytes)
         return logits
 
     def _launch_score_rows(self, rows, symbol, noun, want_outs):
@@ -758,13 +758,9 @@ class ExplaiNN(_Model):
         logits = self._logits_empty(rows.n_rows, dev)
         outs = torch.empty(rows.n_rows, self._units(), device=dev, dtype=torch.float32) if want_outs else None
         if rows.n_rows > 0:
-            with torch.cuda.device(dev):
-                ctx, ps, _, stream, xp, read = self._front(rows, dev)
-                st = rows.struct()
-                _lib.check(getattr(ctx.lib, symbol)(
-                    ctx.handle, xp, rows.codes.numel(), C.byref(st), rows.n_rows, int(rows.reverse_complement),
-                    C.byref(ps), logits.data_ptr(), outs.data_ptr() if want_outs else None, stream))
-                self._settle(read)
+            with self._launch(rows, dev) as (ctx, ps, xp):
+                ctx.call(symbol, xp, rows.codes.numel(), rows.struct(), rows.n_rows, int(rows.reverse_complement),
+                         ps, logits, outs)
         return (logits, outs) if want_outs else logits
 
     def _launch_score_edits(self, ew, want_outs=False):
@@ -778,15 +774,15 @@ class ExplaiNN(_Model):
     def _codes_front(self, codes, path, verb, start=0, reverse_complement=False):
         """Front half of the launches that read a device-resident sequence of base codes with the
         eval-mode tables: the eval-mode check (`path` is the message's subject), the check of `codes`
-        (`verb` is what is done on them), then _front.  Returns (ctx, ps, stream, xp, dev); the caller
+        (`verb` is what is done on them), then _front.  Returns (ctx, ps, xp, dev); the caller
         checks its other arguments and makes its call inside torch.cuda.device(dev)."""
         if self.training:
             raise NotImplementedError("%s an eval-mode export path; call model.eval()" % path)
         dev = self._device()
         _check_codes(codes, dev, verb + " on")
         with torch.cuda.device(dev):
-            ctx, ps, _, stream, xp, _ = self._front(SequenceWindows(codes, start, 1, 1, reverse_complement, 1), dev)
-        return ctx, ps, stream, xp, dev
+            ctx, ps, _, xp, _ = self._front(SequenceWindows(codes, start, 1, 1, reverse_complement, 1), dev)
+        return ctx, ps, xp, dev
 
     def _launch_call_sites(self, codes, thresholds, start=0, n_positions=None, period=0,
                            reverse_complement=False, capacity=0, pos=None, score=None):
@@ -797,12 +793,9 @@ class ExplaiNN(_Model):
         (start-relative) and score fp32 hold the first `capacity` records, unit by unit in ascending
         position.  capacity 0 counts only (pos and score are None); pos / score may be given as
         buffers of at least `capacity` elements.  n_positions None: every start the sequence holds."""
-        ctx, ps, stream, xp, dev = self._codes_front(codes, "calling sites is", "sites are called", start,
-                                                     reverse_complement)
+        ctx, ps, xp, dev = self._codes_front(codes, "calling sites is", "sites are called", start, reverse_complement)
         k, U = self._options["kernel_size"], self._units()
-        if not torch.is_tensor(thresholds) or tuple(thresholds.shape) != (U,) or \
-                thresholds.dtype != torch.float32 or thresholds.device != dev or not thresholds.is_contiguous():
-            raise RuntimeError("thresholds must be a contiguous float32 tensor of shape (%d,) on %s" % (U, dev))
+        _lib.require(thresholds, torch.float32, (U,), dev, "thresholds")
         if n_positions is None:
             n_positions = max(codes.numel() - int(start) - k + 1, 0)
         capacity = int(capacity)
@@ -813,21 +806,14 @@ class ExplaiNN(_Model):
             if score is None:
                 score = torch.empty(capacity, device=dev, dtype=torch.float32)
             for name, t, dt in (("pos", pos, torch.int32), ("score", score, torch.float32)):
-                if t.dtype != dt or t.device != dev or t.dim() != 1 or t.numel() < capacity or \
-                        not t.is_contiguous():
-                    raise RuntimeError("%s must be a contiguous 1-D %s tensor of at least %d elements on %s"
-                                       % (name, dt, capacity, dev))
+                if _lib.require(t, dt, (None,), dev, name).numel() < capacity:
+                    raise RuntimeError("%s must hold at least %d elements (holds %d)" % (name, capacity, t.numel()))
         else:
             pos = score = None
         with torch.cuda.device(dev):
-            lib, h = ctx.lib, ctx.handle
-            nbytes = int(lib.explainn_call_sites_workspace_bytes(h, int(n_positions)))
-            ws = torch.empty(max(nbytes, 1), device=dev, dtype=torch.uint8)
-            _lib.check(lib.explainn_call_sites(
-                h, xp, codes.numel(), int(start), int(n_positions), int(period), int(bool(reverse_complement)),
-                C.byref(ps), thresholds.data_ptr(), offsets.data_ptr(),
-                pos.data_ptr() if pos is not None else None, score.data_ptr() if score is not None else None,
-                capacity, ws.data_ptr(), nbytes, stream))
+            ws, nbytes = ctx.workspace("explainn_call_sites_workspace_bytes", int(n_positions))
+            ctx.call("explainn_call_sites", xp, codes.numel(), int(start), int(n_positions), int(period),
+                     int(bool(reverse_complement)), ps, thresholds, offsets, pos, score, capacity, ws, nbytes)
         return offsets, pos, score
 
     def _launch_record_best(self, codes, rec_offsets, strands=2, want_site=True):
@@ -837,20 +823,17 @@ class ExplaiNN(_Model):
         on the device, unit-major (units, n_records): bits int16, the largest float16 activation's bit
         pattern (below 0x8000) over the record's live starts (0 without one), and site int32, (start << 1) | is_minus of
         the site that holds it (-1 without one; None unless want_site)."""
-        ctx, ps, stream, xp, dev = self._codes_front(codes, "the best sites are", "best sites are found")
+        ctx, ps, xp, dev = self._codes_front(codes, "the best sites are", "best sites are found")
         U = self._units()
-        if not torch.is_tensor(rec_offsets) or rec_offsets.dtype != torch.int64 or rec_offsets.dim() != 1 or \
-                rec_offsets.numel() < 1 or rec_offsets.device != dev or not rec_offsets.is_contiguous():
-            raise RuntimeError("rec_offsets must be a contiguous 1-D int64 tensor of n_records + 1 entries on %s" % dev)
+        if _lib.require(rec_offsets, torch.int64, (None,), dev, "rec_offsets").numel() < 1:
+            raise RuntimeError("rec_offsets must hold n_records + 1 entries (holds none)")
         if strands not in (1, 2):
             raise ValueError("strands must be 1 (forward) or 2 (both)")
         n = rec_offsets.numel() - 1
         bits = torch.empty((U, n), device=dev, dtype=torch.int16)
         site = torch.empty((U, n), device=dev, dtype=torch.int32) if want_site else None
         with torch.cuda.device(dev):
-            _lib.check(ctx.lib.explainn_record_best(
-                ctx.handle, xp, codes.numel(), rec_offsets.data_ptr(), n, int(strands), C.byref(ps),
-                bits.data_ptr(), site.data_ptr() if want_site else None, stream))
+            ctx.call("explainn_record_best", xp, codes.numel(), rec_offsets, n, int(strands), ps, bits, site)
         return bits, site
 
     def _launch_activation_histogram(self, codes, hist, start=0, n_positions=None, period=0,
@@ -861,19 +844,15 @@ class ExplaiNN(_Model):
         device, added into.  Live as in _launch_call_sites: with a period, a start whose k-mer would
         cross a record boundary is not counted.  n_positions None: every start the sequence holds.
         Returns hist."""
-        ctx, ps, stream, xp, dev = self._codes_front(codes, "the activation null is", "activations are counted",
-                                                     start, reverse_complement)
+        ctx, ps, xp, dev = self._codes_front(codes, "the activation null is", "activations are counted", start,
+                                             reverse_complement)
         k, U = self._options["kernel_size"], self._units()
-        if not torch.is_tensor(hist) or tuple(hist.shape) != (U, _lib.ACT_BINS) or \
-                hist.dtype != torch.int64 or hist.device != dev or not hist.is_contiguous():
-            raise RuntimeError("hist must be a contiguous int64 tensor of shape (%d, %d) on %s"
-                               % (U, _lib.ACT_BINS, dev))
+        _lib.require(hist, torch.int64, (U, _lib.ACT_BINS), dev, "hist")
         if n_positions is None:
             n_positions = max(codes.numel() - int(start) - k + 1, 0)
         with torch.cuda.device(dev):
-            _lib.check(ctx.lib.explainn_activation_histogram(
-                ctx.handle, xp, codes.numel(), int(start), int(n_positions), int(period),
-                int(bool(reverse_complement)), C.byref(ps), hist.data_ptr(), stream))
+            ctx.call("explainn_activation_histogram", xp, codes.numel(), int(start), int(n_positions), int(period),
+                     int(bool(reverse_complement)), ps, hist)
         return hist
 
     def _launch_eval_keep(self, x):
@@ -884,12 +863,9 @@ class ExplaiNN(_Model):
         x = self._prep_input(x, dev)
         B = x.shape[0]
         logits = self._logits_empty(B, dev)
-        with torch.cuda.device(dev):
-            ctx, ps, _, stream, xp, read = self._front(x, dev, VALIDATE_FIRST)
+        with self._launch(x, dev, VALIDATE_FIRST) as (ctx, ps, xp):
             self._rt.x_keep = x                # a dense batch is read again by the input gradient
-            _lib.check(ctx.lib.explainn_forward_eval_keep(ctx.handle, xp, B, C.byref(ps), logits.data_ptr(),
-                                                          stream))
-            self._settle(read)
+            ctx.call("explainn_forward_eval_keep", xp, B, ps, logits)
         return logits, self._rt.token
 
     def _launch_input_grad(self, dlogits, token):
@@ -904,8 +880,7 @@ class ExplaiNN(_Model):
         B = dl.shape[0]
         dx = torch.empty(B, 4, self._options["sequence_length"], device=dev, dtype=torch.float32)
         with torch.cuda.device(dev):
-            _lib.check(ctx.lib.explainn_input_grad(ctx.handle, dl.data_ptr(), B, C.byref(ps),
-                                                   dx.data_ptr(), self._stream(dev)))
+            ctx.call("explainn_input_grad", dl, B, ps, dx)
         return dx
 
     def input_gradient(self, x, dlogits):
@@ -936,14 +911,9 @@ class ExplaiNN(_Model):
         delta = torch.empty(B, T, 4, L, device=dev, dtype=torch.float32)
         if B == 0:
             return logits, delta
-        with torch.cuda.device(dev):
-            ctx, ps, _, stream, xp, read = self._front(x, dev, ONEHOT_ONLY)
-            lib, h = ctx.lib, ctx.handle
-            nbytes = int(lib.explainn_ism_workspace_bytes(h, B))
-            ws = torch.empty(max(nbytes, 1), device=dev, dtype=torch.uint8)
-            _lib.check(lib.explainn_ism(h, xp, B, C.byref(ps), logits.data_ptr(), delta.data_ptr(),
-                                        ws.data_ptr(), nbytes, stream))
-            self._settle(read)
+        with self._launch(x, dev, ONEHOT_ONLY) as (ctx, ps, xp):
+            ws, nbytes = ctx.workspace("explainn_ism_workspace_bytes", B)
+            ctx.call("explainn_ism", xp, B, ps, logits, delta, ws, nbytes)
         return logits, delta
 
     def evolve(self, codes, weights, rounds=10, mutable=None, both_strands=False, lock=True, min_gain=0.0):
@@ -997,19 +967,14 @@ class ExplaiNN(_Model):
         logits = torch.empty(rounds + 1, S, B, T, device=dev, dtype=torch.float32)
         if B == 0:
             return pos, ref, alt, gain, logits
-        lib = _lib.load()
         with torch.no_grad():
             for r in range(rounds):
                 maps = []
                 for s in range(S):
                     logits[r, s], delta = self.in_silico_mutagenesis(BaseCodes(codes, bool(s)))
                     maps.append(delta)
-                with torch.cuda.device(dev):
-                    _lib.check(lib.explainn_evolve_pick(
-                        maps[0].data_ptr(), maps[1].data_ptr() if S == 2 else None, codes.data_ptr(),
-                        mask.data_ptr() if mask is not None else None, w.data_ptr(), int(w.dim() == 2), B, T, L,
-                        int(bool(lock)), min_gain, pos[r].data_ptr(), ref[r].data_ptr(), alt[r].data_ptr(),
-                        gain[r].data_ptr(), self._stream(dev)))
+                _lib.call("explainn_evolve_pick", dev, maps[0], maps[1] if S == 2 else None, codes, mask, w,
+                          int(w.dim() == 2), B, T, L, int(bool(lock)), min_gain, pos[r], ref[r], alt[r], gain[r])
             for s in range(S):
                 logits[rounds, s] = self.forward(BaseCodes(codes, bool(s)))
         return pos, ref, alt, gain, logits
@@ -1068,20 +1033,12 @@ class ExplaiNN(_Model):
         lb = torch.empty(B, T, device=dev, dtype=torch.float32)
         if B == 0:
             return ig, lx, lb
-        with torch.cuda.device(dev):
-            ctx, ps, _, stream, xp, read = self._front(x, dev, ONEHOT_ONLY)
-            lib, h = ctx.lib, ctx.handle
+        with self._launch(x, dev, ONEHOT_ONLY) as (ctx, ps, xp):
             if workspace is None:
-                nbytes = int(lib.explainn_integrated_gradients_workspace_bytes(h, B))
-                workspace = torch.empty(max(nbytes, 1), device=dev, dtype=torch.uint8)
-            elif not torch.is_tensor(workspace) or workspace.dtype != torch.uint8 or workspace.device != dev \
-                    or not workspace.is_contiguous():
-                raise RuntimeError("workspace must be a contiguous uint8 tensor on %s" % dev)
-            _lib.check(lib.explainn_integrated_gradients(
-                h, xp, B, C.byref(ps), kind, codes.data_ptr() if codes is not None else None, dl.data_ptr(),
-                steps, ig.data_ptr(), lx.data_ptr(), lb.data_ptr(), workspace.data_ptr(), workspace.numel(),
-                stream))
-            self._settle(read)
+                workspace = ctx.workspace("explainn_integrated_gradients_workspace_bytes", B)[0]
+            _lib.require(workspace, torch.uint8, (None,), dev, "workspace")
+            ctx.call("explainn_integrated_gradients", xp, B, ps, kind, codes, dl, steps, ig, lx, lb, workspace,
+                     workspace.numel())
         return ig, lx, lb
 
     def _empty_batch_error(self):
@@ -1119,13 +1076,13 @@ class ExplaiNN(_Model):
         mask, seed = self._dropout_args(dev, B, red.rank)
         gs = _lib.Grads()
         with torch.cuda.device(dev):
-            ctx, ps, keep, stream, xp, read = self._front(x, dev, bump=False)
+            ctx, ps, keep, xp, read = self._front(x, dev, bump=False)
             bufs = self._rt.sync_bufs = sync_buffers(ctx, dev, self._rt.sync_bufs)
             a = _lib.SyncArgs(x=xp, B_local=B, B_global=Bg, params=C.pointer(ps),
                               grads=C.pointer(gs), dropout_p=float(self.dropout_p), seed=seed,
                               keep_mask=mask.data_ptr() if mask is not None else None,
                               logits=logits.data_ptr())
-            for xb in sync_run(ctx, a, bufs, range(1, 5), stream):
+            for xb in sync_run(ctx, a, bufs, range(1, 5)):
                 red.reduce(xb)
             self._settle(read)
         self._touched()
@@ -1151,7 +1108,7 @@ class ExplaiNN(_Model):
         a.grads = C.pointer(gs)
         a.freeze_top_n_filters = int(self.freeze_top_n_filters)
         with torch.cuda.device(dev):
-            for xb in sync_run(ctx, a, self._rt.sync_bufs, range(5, 9), self._stream(dev)):
+            for xb in sync_run(ctx, a, self._rt.sync_bufs, range(5, 9)):
                 self.sync_bn.reduce(xb)
         self._rt.sync = None
         return views
@@ -1169,12 +1126,8 @@ class ExplaiNN(_Model):
             raise self._empty_batch_error()
         logits = self._logits_empty(B, dev)
         mask, seed = self._dropout_args(dev, B)
-        with torch.cuda.device(dev):
-            ctx, ps, _, stream, xp, read = self._front(x, dev, policy, bump=False)
-            _lib.check(ctx.lib.explainn_forward_train(
-                ctx.handle, xp, B, C.byref(ps), mask.data_ptr() if mask is not None else None,
-                float(self.dropout_p), C.c_uint64(seed), logits.data_ptr(), stream))
-            self._settle(read)
+        with self._launch(x, dev, policy, bump=False) as (ctx, ps, xp):
+            ctx.call("explainn_forward_train", xp, B, ps, mask, float(self.dropout_p), C.c_uint64(seed), logits)
         self._touched()
         self._rt.token += 1
         return logits, self._rt.token
@@ -1202,13 +1155,9 @@ class ExplaiNN(_Model):
         with torch.cuda.device(dev):
             if want_dx:
                 dx = torch.empty(B, 4, self._options["sequence_length"], device=dev, dtype=torch.float32)
-                _lib.check(ctx.lib.explainn_backward_input(ctx.handle, dl.data_ptr(), B, C.byref(ps),
-                                                           C.byref(gs), int(self.freeze_top_n_filters),
-                                                           dx.data_ptr(), self._stream(dev)))
+                ctx.call("explainn_backward_input", dl, B, ps, gs, int(self.freeze_top_n_filters), dx)
             else:
-                _lib.check(ctx.lib.explainn_backward(ctx.handle, dl.data_ptr(), B, C.byref(ps),
-                                                     C.byref(gs), int(self.freeze_top_n_filters),
-                                                     self._stream(dev)))
+                ctx.call("explainn_backward", dl, B, ps, gs, int(self.freeze_top_n_filters))
         if self.grad_sync is not None:
             self.grad_sync(flat)
         return (views, dx) if want_dx else views
@@ -1230,10 +1179,8 @@ class ExplaiNN(_Model):
         x = self._prep_input(self._first_four_rows(x_rep), dev)
         B = x.shape[0]
         outs = torch.empty(B, self._units(), device=dev, dtype=torch.float32)
-        with torch.cuda.device(dev):
-            ctx, ps, _, stream, xp, read = self._front(x, dev)
-            _lib.check(ctx.lib.explainn_unit_outputs(ctx.handle, xp, B, C.byref(ps), outs.data_ptr(), stream))
-            self._settle(read)
+        with self._launch(x, dev) as (ctx, ps, xp):
+            ctx.call("explainn_unit_outputs", xp, B, ps, outs)
         return outs
 
     def _unit_activations(self, x_rep):
@@ -1246,11 +1193,8 @@ class ExplaiNN(_Model):
         o = self._options
         acts = torch.empty(B, self._units(), o["sequence_length"] - o["kernel_size"] + 1,
                            device=dev, dtype=torch.float32)
-        with torch.cuda.device(dev):
-            ctx, ps, _, stream, xp, read = self._front(x, dev)
-            _lib.check(ctx.lib.explainn_unit_activations(ctx.handle, xp, B, C.byref(ps), acts.data_ptr(),
-                                                         stream))
-            self._settle(read)
+        with self._launch(x, dev) as (ctx, ps, xp):
+            ctx.call("explainn_unit_activations", xp, B, ps, acts)
         return acts
 
     # -- filter -> PWM export (interpret.py:363-459 on the device; see explainn_amd/interpret.py) --
@@ -1271,12 +1215,9 @@ class ExplaiNN(_Model):
         """unit_max[u] (float32 [U], zeroed by the caller before the first batch) <- running max of
         the float16-rounded eval-mode activations of the selected sequences of this batch."""
         dev, x, B, select = self._export_args(x, select)
-        with torch.cuda.device(dev):
-            ctx, ps, _, stream, xp, read = self._front(x, dev, bump=False)
-            _lib.check(ctx.lib.explainn_filter_act_max(
-                ctx.handle, xp, B, C.byref(ps), select.data_ptr() if select is not None else None,
-                unit_max.data_ptr(), stream))
-            self._settle(read)
+        _lib.require(unit_max, torch.float32, (self._units(),), dev, "unit_max")
+        with self._launch(x, dev, bump=False) as (ctx, ps, xp):
+            ctx.call("explainn_filter_act_max", xp, B, ps, select, unit_max)
         return unit_max
 
     def filter_sites(self, x, thresholds, site_total, pfm, select=None, site_cap=1000000,
@@ -1286,20 +1227,12 @@ class ExplaiNN(_Model):
         dev, x, B, select = self._export_args(x, select)
         o = self._options
         U, k = self._units(), o["kernel_size"]
-        for name, t, shape, dt in (("thresholds", thresholds, (U,), torch.float32),
-                                   ("site_total", site_total, (U,), torch.int32),
-                                   ("pfm", pfm, (U, k, 4), torch.int32)):
-            if tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous():
-                raise RuntimeError("%s must be a contiguous %s tensor of shape %s on %s" % (
-                    name, dt, shape, dev))
+        _lib.require(thresholds, torch.float32, (U,), dev, "thresholds")
+        _lib.require(site_total, torch.int32, (U,), dev, "site_total")
+        _lib.require(pfm, torch.int32, (U, k, 4), dev, "pfm")
         hit = torch.empty(B, U, device=dev, dtype=torch.uint8) if want_hit else None
-        with torch.cuda.device(dev):
-            ctx, ps, _, stream, xp, read = self._front(x, dev, bump=False)
-            _lib.check(ctx.lib.explainn_filter_sites(
-                ctx.handle, xp, B, C.byref(ps), select.data_ptr() if select is not None else None,
-                thresholds.data_ptr(), int(site_cap), site_total.data_ptr(), pfm.data_ptr(),
-                hit.data_ptr() if hit is not None else None, stream))
-            self._settle(read)
+        with self._launch(x, dev, bump=False) as (ctx, ps, xp):
+            ctx.call("explainn_filter_sites", xp, B, ps, select, thresholds, int(site_cap), site_total, pfm, hit)
         return hit
 
 
@@ -1496,13 +1429,8 @@ class PWM(nn.Module):
             raise RuntimeError("expected input of shape (B, 4, %d) on %s" % (o["sequence_length"], w.device))
         x = x.detach().to(torch.float32).contiguous()
         scores = torch.empty(x.shape[0], o["groups"], device=w.device, dtype=torch.float32)
-        lib = _lib.load()
-        with torch.cuda.device(w.device):
-            _lib.check(lib.explainn_pwm_scan(
-                x.data_ptr(), x.shape[0], o["sequence_length"], w.detach().contiguous().data_ptr(),
-                o["groups"], o["kernel_size"],
-                _lib.PWM_MAX if o["scoring"] == "max" else _lib.PWM_SUM, scores.data_ptr(),
-                C.c_void_p(torch.cuda.current_stream(w.device).cuda_stream)))
+        _lib.call("explainn_pwm_scan", w.device, x, x.shape[0], o["sequence_length"], w.detach().contiguous(),
+                  o["groups"], o["kernel_size"], _lib.PWM_MAX if o["scoring"] == "max" else _lib.PWM_SUM, scores)
         # the reference adds conv1d.bias (zeros by construction) to every window score
         windows = 1 if o["scoring"] == "max" else 2 * (o["sequence_length"] - o["kernel_size"] + 1)
         return scores.add_(self.conv1d.bias.detach() * windows)

@@ -24,18 +24,16 @@ def sync_buffers(ctx, dev, bufs=None):
     return [torch.zeros(max(n, 1), device=dev, dtype=torch.float64) for n in need]
 
 
-def sync_run(ctx, args, bufs, phases, stream):
-    """Enqueue the sync-BN phases `phases` (explainn_sync_phase) with `args`; yields each exchange
-    buffer the caller must sum over the ranks in place before resuming.  A phase reads the
-    exchange of the last exchanging phase before it."""
+def sync_run(ctx, args, bufs, phases):
+    """Enqueue the sync-BN phases `phases` (explainn_sync_phase) with `args` on the current stream of
+    the context's device; yields each exchange buffer the caller must sum over the ranks in place
+    before resuming.  A phase reads the exchange of the last exchanging phase before it."""
     lib, h = ctx.lib, ctx.handle
     for phase in phases:
         prev = [q for q in range(1, phase) if int(lib.explainn_sync_exchange_elems(h, q)) > 0]
-        xin = bufs[prev[-1] - 1].data_ptr() if prev else None
         has_out = int(lib.explainn_sync_exchange_elems(h, phase)) > 0
         xb = bufs[phase - 1]
-        _lib.check(lib.explainn_sync_phase(h, phase, C.byref(args), xin, xb.data_ptr() if has_out else None,
-                                           stream))
+        ctx.call("explainn_sync_phase", phase, args, bufs[prev[-1] - 1] if prev else None, xb if has_out else None)
         if has_out:
             yield xb
 
@@ -109,7 +107,7 @@ class StepEngine:
         # steps read the flag before computing and route a soft batch to the dense kernels, as
         # forward() does; later steps enqueue without a host sync and the Trainer reads the sticky
         # flag periodically; dense_input=True goes straight to the dense kernels
-        xp, _ = m._stage(self.ctx, x, stream)
+        xp, _ = m._stage(self.ctx, x)
         return xp, stream
 
     def sync_phases(self, x, y, B_global, seed=None, freeze_top_n_filters=0, keep_mask=None, rank=0):
@@ -131,7 +129,7 @@ class StepEngine:
         mask = None
         if keep_mask is not None:
             mask = keep_mask.to(device=self.dev, dtype=torch.uint8).contiguous()
-        xp, stream = self._front(x)
+        xp, _ = self._front(x)
         self._xbufs = sync_buffers(self.ctx, self.dev, getattr(self, "_xbufs", None))
         a = _lib.SyncArgs(x=xp, targets=y.data_ptr(), dlogits=None, dl_scale=1.0, B_local=B,
                           B_global=int(B_global), params=C.pointer(self.ps), grads=C.pointer(self.gs),
@@ -139,7 +137,7 @@ class StepEngine:
                           keep_mask=mask.data_ptr() if mask is not None else None,
                           freeze_top_n_filters=int(freeze_top_n_filters), logits=self.logits.data_ptr(),
                           loss_out=self.loss.data_ptr())
-        yield from sync_run(self.ctx, a, self._xbufs, range(1, _lib.SYNC_PHASES + 1), stream)
+        yield from sync_run(self.ctx, a, self._xbufs, range(1, _lib.SYNC_PHASES + 1))
         m._touched()
         m._rt.token += 1
 

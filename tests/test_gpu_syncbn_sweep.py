@@ -107,16 +107,15 @@ def _dlogits_step(c, d, engines, xs, ys):
     from explainn_amd import _lib
     from explainn_amd.engine import sync_buffers, sync_run
     Bg = sum(c.shards)
-    args, bufs, streams = [], [], []
+    args, bufs = [], []
     for e, x in zip(engines, xs):
-        xp, stream = e._front(x)
+        xp, _ = e._front(x)
         bufs.append(sync_buffers(e.ctx, e.dev))
-        streams.append(stream)
         args.append(_lib.SyncArgs(x=xp, targets=None, dlogits=None, dl_scale=1.0, B_local=int(x.shape[0]),
                                   B_global=Bg, params=ctypes.pointer(e.ps), grads=ctypes.pointer(e.gs),
                                   loss_kind=e.loss_kind, dropout_p=0.0, seed=0, keep_mask=None,
                                   freeze_top_n_filters=0, logits=e.logits.data_ptr(), loss_out=None))
-    _lockstep([sync_run(e.ctx, a, b, range(1, 5), s) for e, a, b, s in zip(engines, args, bufs, streams)])
+    _lockstep([sync_run(e.ctx, a, b, range(1, 5)) for e, a, b in zip(engines, args, bufs)])
     keep, losses = [], []
     for e, a, y, (lo, hi) in zip(engines, args, ys, sm.bounds(c)):
         if c.backward == "dlogits_shard_mean":
@@ -131,7 +130,7 @@ def _dlogits_step(c, d, engines, xs, ys):
         dl = dl.to(torch.float32).contiguous()
         keep.append(dl)
         a.dlogits = dl.data_ptr()
-    _lockstep([sync_run(e.ctx, a, b, range(5, 9), s) for e, a, b, s in zip(engines, args, bufs, streams)])
+    _lockstep([sync_run(e.ctx, a, b, range(5, 9)) for e, a, b in zip(engines, args, bufs)])
     for e in engines:
         e.model._touched()
         e.model._rt.token += 1

@@ -229,6 +229,27 @@ def test_require_refuses_host_tensors():
         _lib.require(np.zeros(3), torch.uint8, (3,), None, "labels")
 
 
+def test_arguments_convert_without_a_device(monkeypatch):
+    """The conversion _lib.call and Context.call share: None is NULL, a Structure instance goes through untouched
+    (ctypes takes it by reference where the signature says POINTER), numbers, byref()s and addresses stay, and a
+    host tensor is refused for a HIP device -- all before the library is loaded."""
+    import ctypes as C
+
+    import torch
+
+    from explainn_amd import _lib
+    monkeypatch.setattr(_lib, "load", lambda: pytest.fail("the library was loaded"))
+    dev = torch.device("cuda", 0)
+    ps, flags = _lib.Params(), C.c_int(0)
+    ref = C.byref(flags)
+    argv = _lib.arguments("explainn_x", dev, (None, ps, 7, 0.5, ref, 4096))
+    assert argv[0] is None and C.c_void_p(argv[0]).value is None
+    assert argv[1] is ps and C.POINTER(_lib.Params).from_param(argv[1]) is not None
+    assert argv[2:] == [7, 0.5, ref, 4096]
+    with pytest.raises(RuntimeError, match=r"^explainn_x: argument 2 must be a contiguous tensor on cuda:0 .*on cpu"):
+        _lib.arguments("explainn_x", dev, (None, ps, torch.zeros(3)))
+
+
 # ---------------------------------------------------------------- on the device
 @pytest.mark.gpu
 def test_call_refuses_a_strided_tensor_and_one_on_the_host():

@@ -71,9 +71,8 @@ def main(argv=None):
                              for i in range(1, _lib.SYNC_PHASES + 1)}
     acc = [0.0] * _lib.SYNC_PHASES
     n = 10
-    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     for _ in range(n):
-        xp, _ = m1._stage(e1.ctx, x, stream)
+        xp, _ = m1._stage(e1.ctx, x)
         args = _lib.SyncArgs(x=xp, targets=y.data_ptr(), dl_scale=1.0, B_local=B, B_global=B,
                              params=C.pointer(e1.ps), grads=C.pointer(e1.gs), loss_kind=e1.loss_kind,
                              dropout_p=float(m1.dropout_p), seed=7, logits=e1.logits.data_ptr(),
@@ -81,7 +80,7 @@ def main(argv=None):
         for ph in range(1, _lib.SYNC_PHASES + 1):
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ev0.record()
-            for _x in sync_run(e1.ctx, args, e1._xbufs, [ph], stream):
+            for _x in sync_run(e1.ctx, args, e1._xbufs, [ph]):
                 pass
             ev1.record()
             torch.cuda.synchronize()
