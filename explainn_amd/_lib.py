@@ -25,6 +25,8 @@ LINKAGE_SINGLE, LINKAGE_COMPLETE, LINKAGE_AVERAGE = 0, 1, 2
 MOTIF_TREE_MAX_LEAVES = 12288   # EXPLAINN_MOTIF_TREE_MAX_LEAVES: motifs of one explainn_motif_tree call
 SITES_TILE = 1024        # EXPLAINN_SITES_TILE: start positions per workgroup of explainn_call_sites
 PWM_GROUP = 16           # EXPLAINN_PWM_GROUP: motifs per workgroup of explainn_pwm_sites
+PWM_HIST_SLICE = 1 << 30  # EXPLAINN_PWM_HIST_SLICE: starts per workgroup of explainn_pwm_score_histogram at the most
+SITEQ_MAX_BINS = 32768   # EXPLAINN_SITEQ_MAX_BINS: score bins per unit of explainn_site_qvalues
 ACT_BINS = 32768         # EXPLAINN_ACT_BINS: one bin per non-negative float16 bit pattern
 ACT_SPAN = 8192          # EXPLAINN_ACT_SPAN: start positions a workgroup of explainn_activation_histogram takes at a time
 BEST_SPAN = 256          # EXPLAINN_BEST_SPAN: starts a wavefront of explainn_record_best takes per pass over its record
@@ -179,6 +181,8 @@ SIGNATURES = {
     "explainn_pwm_sites_workspace_bytes": (_i64, [_i, _i64]),
     "explainn_pwm_sites": (_i, [_fp, _i64, _i64, _i64, _i64, _i, _fp, _fp, _i, _i, _fp, _fp, _i, _fp, _fp, _fp, _fp,
                                 _i64, _fp, _i64, _fp]),
+    "explainn_pwm_score_histogram": (_i, [_fp, _i64, _i64, _i64, _i64, _i, _fp, _fp, _i, _i, _i, _fp, _fp]),
+    "explainn_site_qvalues": (_i, [_fp, _fp, _i, _i, C.c_double, _fp, _fp, _fp, _fp]),
     "explainn_pwm_record_best": (_i, [_fp, _i64, _fp, _i64, _i, _fp, _fp, _i, _i, _fp, _fp, _fp, _fp]),
     "explainn_adam_step": (_i, [_i, C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp),
                                 C.POINTER(_i64), _i64, C.c_double, C.c_double, C.c_double, C.c_double,

@@ -2,6 +2,7 @@
 
     python -m explainn_amd.calibrate MODEL FASTA -o thresholds.tsv --pvalue 1e-4
         [--background shuffle|sequence] [--shuffles R] [--seed S] [--period L] [--save-null NULL.npz]
+        [--qvalue Q --target FASTA]
 
 Builds the empirical null of every filter's activation over a background (sites.activation_null: the
 exact per-filter histogram of the float16 activation, on the device) and writes, per filter, the
@@ -14,6 +15,9 @@ device: a background without the motifs but with the records' composition.  Shuf
 one length: --period L cuts the records into rows of L bases (every record a multiple of L long); by
 default L is the records' common length.  With a period no k-mer crosses a row boundary.
 --save-null keeps the null for `python -m explainn_amd.sites --null`, which adds p-values.
+--qvalue Q --target FASTA writes, in place of --pvalue's, the thresholds of a false discovery rate: those at
+which `python -m explainn_amd.sites` lists exactly the sites of the target FASTA whose Benjamini-Hochberg
+q-value, over every position and strand of that file, is at most Q (sites.site_qvalues).
 """
 import argparse
 
@@ -32,13 +36,14 @@ def _parser():
     ap.add_argument("--period", type=int, default=None,
                     help="row length; default: the records' common length, 0 (none) if they differ")
     ap.add_argument("--save-null", help="write the null as .npz (sites --null)")
+    ap.add_argument("--qvalue", type=float, default=None,
+                    help="with --target: thresholds of this false discovery rate in place of --pvalue's")
+    ap.add_argument("--target", help="FASTA to be scanned: --qvalue's thresholds list its sites with q-value <= Q")
     return ap
 
 
 def background_null(model, records, background="shuffle", shuffles=10, seed=0, period=None):
     """The ActivationNull of (id, codes) records (loader.read_fasta_records) as the CLI builds it."""
-    import torch
-
     from . import sites
     codes = [np.asarray(c, dtype=np.uint8) for _, c in records if len(c)]
     if not codes:
@@ -56,14 +61,7 @@ def background_null(model, records, background="shuffle", shuffles=10, seed=0, p
     if background == "shuffle":
         raise ValueError("--background shuffle needs records of one length, or --period L")
     # records of unequal lengths: one histogram over all of them, no k-mer across two records
-    hist = torch.zeros(model._units(), sites.ACT_BINS, device=model._device(), dtype=torch.int64)
-    with torch.no_grad(), model.eval_cache():
-        for c in codes:
-            data, _ = sites._null_args(model, c, 0, 0, "both", None)
-            sites._count_activations(model, data, hist, 0, 0, seed, True, sites.CHUNK_POSITIONS)
-    if model.validate_input:
-        model.check_input()
-    return sites.ActivationNull(hist, model._options["kernel_size"], "both", 0, seed)
+    return sites.records_null(model, codes, "both", seed)
 
 
 def main(argv=None):
@@ -75,11 +73,19 @@ def main(argv=None):
     from .sites import write_thresholds
     if not 0.0 <= args.pvalue <= 1.0:
         raise SystemExit("--pvalue must be in [0, 1]")
+    if (args.qvalue is None) != (args.target is None) or not 0.0 <= (args.qvalue or 0.0) <= 1.0:
+        raise SystemExit("--qvalue (in [0, 1]) and --target go together")
     records = read_fasta_records(args.fasta_file)
     model = _load_model(args.model_file)
     model.eval()
     null = background_null(model, records, args.background, args.shuffles, args.seed, args.period)
-    write_thresholds(args.output_file, null.thresholds(args.pvalue))
+    if args.qvalue is None:
+        thresholds = null.thresholds(args.pvalue)
+    else:
+        from .sites import records_null, site_qvalues
+        observed = records_null(model, (c for _, c in read_fasta_records(args.target)), null.strands)
+        thresholds = site_qvalues(observed, null).thresholds(args.qvalue)
+    write_thresholds(args.output_file, thresholds)
     if args.save_null:
         null.save(args.save_null)
 

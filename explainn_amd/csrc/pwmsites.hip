@@ -10,6 +10,8 @@
 //                       order, no atomics), its tail, and the smallest score whose tail is <= pcut
 //   explainn_pwm_sites  every (motif, strand, start) with score >= the motif's threshold, as a compacted
 //                       list: the COUNT / scan / EMIT scheme of sitescan.h with one row per (motif, strand)
+//   explainn_pwm_score_histogram  per motif the histogram of the scores of ALL live windows, both strands:
+//                       what a q-value over every test needs (siteq.hip); the scan's walk, counted in LDS
 //
 // Scan geometry (a first choice): a workgroup is a tile of EXPLAINN_SITES_TILE starts x a group of
 // EXPLAINN_PWM_GROUP motifs.  The tile's codes and the group's tables sit in LDS; a table entry (column j,
@@ -33,6 +35,30 @@ static_assert(EXPLAINN_SITES_TILE % PS_T == 0, "a tile is a whole number of posi
 static_assert(PS_G % 2 == 0, "block_hit_ranks ranks four rows = two motifs x two strands at a time");
 static_assert(EXPLAINN_MOTIF_MAX_WIDTH * EXPLAINN_MOTIF_MAX_BINS + PS_N < 0, "an N outweighs the rest of a window");
 
+// tab [G][wmax][8] <- the pair words of motifs m0 .. m0 + G - 1 (zero past a motif's width and for an empty
+// motif), the sentinel in both halves at code 4, by nthreads threads
+__device__ __forceinline__ void stage_pair_tables(const int16_t* __restrict__ S, const int* __restrict__ widths,
+                                                  int m0, int G, int M, int wmax, int tid, int nthreads, int* tab) {
+    for (int i = tid; i < G * wmax * 8; i += nthreads) {
+        const int g = i / (wmax * 8), r = i - g * wmax * 8, j = r >> 3, c = r & 7, m = m0 + g;
+        unsigned word = 0;
+        const int w = pwm_width(widths, m, M, wmax);
+        if (j < w) {
+            const int16_t* row = S + (size_t)m * wmax * 4;
+            word = c < 4 ? pwm_pair_word(row, w, j, c) : (unsigned)(uint16_t)PS_N | ((unsigned)(uint16_t)PS_N << 16);
+        }
+        tab[i] = (int)word;
+    }
+}
+
+// the widest motif that may start at position p of a tile that staged nstage bases: it ends inside the staged
+// bases and, with a period, inside its record; 0 past the tile's live_n starts
+__device__ __forceinline__ int pwm_start_limit(int p, int live_n, int nstage, long long first, long long period) {
+    int l = p < live_n ? nstage - p : 0;
+    if (period > 0 && l > 0) l = (int)min((long long)l, period - (first + p) % period);
+    return l;
+}
+
 template <int MODE>
 __global__ __launch_bounds__(PS_T) void pwm_sites_kernel(
     const uint8_t* __restrict__ seq, long long start, int npos, int span, long long period, int both,
@@ -50,26 +76,11 @@ __global__ __launch_bounds__(PS_T) void pwm_sites_kernel(
     // from `start` to the end of what the call may read, >= npos (the entry point has checked it)
     const int nstage = min(live_n + wmax - 1, span - t0);
     stage_codes<false>(seq + start + t0, nstage, tid, PS_T, cs, 0, nullptr);
-    for (int i = tid; i < PS_G * wmax * 8; i += PS_T) {
-        const int g = i / (wmax * 8), r = i - g * wmax * 8, j = r >> 3, c = r & 7, m = m0 + g;
-        unsigned word = 0;
-        const int w = pwm_width(widths, m, M, wmax);
-        if (j < w) {
-            const int16_t* row = S + (size_t)m * wmax * 4;
-            word = c < 4 ? pwm_pair_word(row, w, j, c) : (unsigned)(uint16_t)PS_N | ((unsigned)(uint16_t)PS_N << 16);
-        }
-        tab[i] = (int)word;
-    }
-    // per position chunk: the widest motif that may start at this lane's position -- it ends inside the
-    // staged bases and, with a period, inside its record; 0 past the tile's starts
+    stage_pair_tables(S, widths, m0, PS_G, M, wmax, tid, PS_T, tab);
+    // per position chunk: the widest motif that may start at this lane's position
     int lim[PS_CHUNKS];
 #pragma unroll
-    for (int c = 0; c < PS_CHUNKS; ++c) {
-        const int p = c * PS_T + tid;
-        int l = p < live_n ? nstage - p : 0;
-        if (period > 0 && l > 0) l = (int)min((long long)l, period - (start + t0 + p) % period);
-        lim[c] = l;
-    }
+    for (int c = 0; c < PS_CHUNKS; ++c) lim[c] = pwm_start_limit(c * PS_T + tid, live_n, nstage, start + t0, period);
     __syncthreads();
     for (int q = 0; q < PS_G / 2; ++q) {
         const int ma = m0 + 2 * q;             // motifs ma, ma + 1: rows 2 ma .. 2 ma + 3
@@ -133,6 +144,94 @@ __global__ __launch_bounds__(PS_T) void pwm_sites_kernel(
         }
         site_counts<MODE>(cnt, ntiles, tile, 2 * ma, 2 * M, run);
     }
+}
+
+// ---- the observed score histogram --------------------------------------------------------------------
+// hist[m][s] += the live windows of motif m, on either requested strand, whose integer score is s: every test
+// the scan above would make, not only the sites -- what a q-value over all tests needs (siteq.hip).
+//
+// Geometry (a first choice): block = (motif group, slice).  A group is G motifs, G chosen by the entry point
+// so that G rows of wmax bins + 2 uint32 bins, the group's pair-word tables and one tile's codes fit the LDS;
+// the tiles of EXPLAINN_SITES_TILE starts are dealt round robin to the slices.  One lane per start, PH_Q motifs
+// at a time: the walk is pwm_sites_kernel's (pair words, the N sentinel), the count an integer LDS atomic.
+// A block flushes its non-zero bins once, with 64-bit integer global atomics.  Integers throughout: the
+// result does not depend on G, on the slices or on how a caller chunks the sequence.
+constexpr int PH_T = EXPLAINN_SITES_TILE;      // one lane per start of a tile
+constexpr int PH_Q = 4;                        // motifs a lane walks together
+constexpr int PH_BLOCKS = 1024;                // slices are cut so that a call has about this many blocks
+constexpr int PH_LDS = 160 * 1024;
+constexpr int PH_SLICE_TILES = EXPLAINN_PWM_HIST_SLICE / EXPLAINN_SITES_TILE;
+static_assert(PH_T == 1024, "a tile is one workgroup of the largest size");
+static_assert(2ll * EXPLAINN_PWM_HIST_SLICE <= (1ll << 31), "two counts per start stay inside a 32-bit bin");
+
+__global__ __launch_bounds__(PH_T) void pwm_hist_kernel(
+    const uint8_t* __restrict__ seq, long long start, int npos, int span, long long period, int both,
+    const int16_t* __restrict__ S, const int* __restrict__ widths, unsigned long long* __restrict__ hist, int M,
+    int wmax, int row_len, int G, int ntiles) {
+    extern __shared__ int ph_sm[];             // bins [G][row_len] | tables [G][wmax][8] | codes [TILE + wmax - 1] bytes
+    unsigned* h = reinterpret_cast<unsigned*>(ph_sm);
+    int* tab = ph_sm + G * row_len;
+    uint8_t* cs = reinterpret_cast<uint8_t*>(tab + G * wmax * 8);
+    const int tid = threadIdx.x, m0 = blockIdx.x * G;
+    for (int b = tid; b < G * row_len; b += PH_T) h[b] = 0u;
+    stage_pair_tables(S, widths, m0, G, M, wmax, tid, PH_T, tab);
+    for (int tile = blockIdx.y; tile < ntiles; tile += gridDim.y) {
+        int t0, live_n;
+        site_tile(tile, npos, t0, live_n);
+        __syncthreads();                       // the bins and tables are written / the last tile's codes are read
+        const int nstage = min(live_n + wmax - 1, span - t0);
+        stage_codes<false>(seq + start + t0, nstage, tid, PH_T, cs, 0, nullptr);
+        const int lim = pwm_start_limit(tid, live_n, nstage, start + t0, period);
+        __syncthreads();
+        const uint8_t* cp = cs + tid;          // cp[j] is read for j < w <= lim only
+        // PH_Q motifs walk the window together: one code read serves all, and their table reads are independent
+        // chains (one chain per lane left the walk waiting on LDS latency: DESIGN.md section 8).  A table is
+        // zero past its motif's width, so every chain may run to the widest live motif of the set.
+        for (int g = 0; g < G; g += PH_Q) {
+            int w[PH_Q], fw[PH_Q], rw[PH_Q], wl = 0;
+            const int* tb[PH_Q];
+#pragma unroll
+            for (int i = 0; i < PH_Q; ++i) {
+                const int wi = g + i < G ? pwm_width(widths, m0 + g + i, M, wmax) : 0;
+                w[i] = wi <= lim ? wi : 0;     // 0: an empty motif, past the group, or no live window here
+                tb[i] = tab + min(g + i, G - 1) * wmax * 8;
+                wl = max(wl, w[i]);
+                fw[i] = rw[i] = 0;
+            }
+            for (int j = 0; j < wl; ++j) {
+                const int code = cp[j];
+#pragma unroll
+                for (int i = 0; i < PH_Q; ++i) {
+                    const int v = tb[i][j * 8 + code];
+                    fw[i] += (int)(short)(v & 0xFFFF);
+                    rw[i] += v >> 16;
+                }
+            }
+            // an N makes both sums negative; a table entry outside [0, bins] may leave the row: neither counts
+#pragma unroll
+            for (int i = 0; i < PH_Q; ++i) {
+                if (w[i] == 0) continue;
+                unsigned* row = h + (g + i) * row_len;
+                if ((unsigned)fw[i] < (unsigned)row_len) atomicAdd(&row[fw[i]], 1u);
+                if (both && (unsigned)rw[i] < (unsigned)row_len) atomicAdd(&row[rw[i]], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    const int nb = min(G, M - m0) * row_len;
+    unsigned long long* out = hist + (size_t)m0 * row_len;
+    for (int b = tid; b < nb; b += PH_T) {
+        const unsigned v = h[b];
+        if (v) atomicAdd(&out[b], (unsigned long long)v);
+    }
+}
+
+// motifs per workgroup: as many rows, with their tables, as the LDS holds beside a tile's codes, one at least
+// (the largest row, 64 x 128 + 2 bins, is 32.8 KB: four fit), EXPLAINN_PWM_GROUP at the most
+int pwm_hist_group(int wmax, int row_len) {
+    const size_t per = ((size_t)row_len + (size_t)wmax * 8) * sizeof(int);
+    const size_t room = PH_LDS - ((EXPLAINN_SITES_TILE + wmax - 1 + 15) & ~15);
+    return (int)std::min<size_t>(EXPLAINN_PWM_GROUP, room / per);
 }
 
 // ---- the null ----------------------------------------------------------------------------------------
@@ -288,4 +387,41 @@ extern "C" int explainn_pwm_sites(const uint8_t* seq, int64_t seq_len, int64_t s
                            widths, thresholds, tail, stride, w.cnt, (const long long*)off, pos, score, pvalue,
                            (long long)capacity, M, wmax, w.ntiles);
     });
+}
+
+extern "C" int explainn_pwm_score_histogram(const uint8_t* seq, int64_t seq_len, int64_t start, int64_t n_positions,
+                                            int64_t period, int both_strands, const int16_t* scores,
+                                            const int32_t* widths, int M, int wmax, int bins, int64_t* hist,
+                                            void* stream) {
+    if (!pwm_geometry_ok("pwm_score_histogram", M, wmax, bins)) return EXPLAINN_E_ARG;
+    if (start < 0 || n_positions < 0 || start + n_positions > seq_len || n_positions + wmax >= (int64_t)INT_MAX) {
+        explainn_set_error("pwm_score_histogram: need 0 <= start, start + n_positions <= seq_len and n_positions + "
+                           "wmax < 2^31 (start=%lld n_positions=%lld seq_len=%lld)", (long long)start,
+                           (long long)n_positions, (long long)seq_len);
+        return EXPLAINN_E_ARG;
+    }
+    if (period < 0) {
+        explainn_set_error("pwm_score_histogram: period must not be negative");
+        return EXPLAINN_E_ARG;
+    }
+    if (M == 0 || n_positions == 0) return EXPLAINN_OK;
+    if (!seq || !scores || !widths || !hist) {
+        explainn_set_error("pwm_score_histogram: seq, scores, widths and hist must be device pointers");
+        return EXPLAINN_E_ARG;
+    }
+    const int row_len = wmax * bins + 2, G = pwm_hist_group(wmax, row_len);
+    const int span = (int)std::min<int64_t>(n_positions + wmax - 1, seq_len - start);
+    const size_t sm = (size_t)G * (row_len + wmax * 8) * sizeof(int) + ((EXPLAINN_SITES_TILE + wmax - 1 + 15) & ~15);
+    if (sm > 64 * 1024)
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&pwm_hist_kernel),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
+    // about PH_BLOCKS blocks, and no slice of more than EXPLAINN_PWM_HIST_SLICE starts
+    const int ntiles = (int)sites_tiles(n_positions), groups = (M + G - 1) / G;
+    const int slices = std::min(ntiles, std::max({1, (PH_BLOCKS + groups - 1) / groups,
+                                                  (ntiles + PH_SLICE_TILES - 1) / PH_SLICE_TILES}));
+    hipLaunchKernelGGL(pwm_hist_kernel, dim3(groups, slices), dim3(PH_T), sm, static_cast<hipStream_t>(stream), seq,
+                       (long long)start, (int)n_positions, span, (long long)period, both_strands ? 1 : 0, scores,
+                       widths, reinterpret_cast<unsigned long long*>(hist), M, wmax, row_len, G, ntiles);
+    LAUNCH_CHECK();
+    return EXPLAINN_OK;
 }

@@ -18,6 +18,14 @@ smallest integer score whose tail is <= pvalue.  The scan (explainn_pwm_sites, c
 
 `python -m explainn_amd.pwmsites MOTIFS FASTA -o OUT.bed` writes `SeqId start end name score strand pvalue`.
 There is no CPU path.
+
+    calls = scan_motifs(motifs, codes, qvalue=0.05)     # only sites at a false discovery rate of 5 %
+    calls.qvalue                                        # Benjamini-Hochberg over ALL windows and strands
+
+A site's score is an integer, so its q-value is a function of (motif, score): `score_histogram` counts the score
+of every live window (explainn_pwm_score_histogram), and explainn_site_qvalues turns that histogram and the
+null's tail into the table -- exact, and independent of the p-value cutoff.  `--qvalues [--max-qvalue Q]` adds
+the column over the whole file (a first pass counts, the second lists).
 """
 import argparse
 import sys
@@ -152,12 +160,14 @@ class PwmCalls(SiteCalls):
     """SiteCalls of known motifs: unit m = motif m, per motif '+' sites in ascending start, then '-' sites.
     `score` is the real log-odds (float32, bits), `iscore` the integer score (int32) the threshold and the
     p-value are functions of, `pvalue` float64; `widths` (int32, per motif) and `names` are carried, and
-    kernel_size is the largest width."""
+    kernel_size is the largest width.  `qvalue` (float64, None unless scan_motifs was asked for it) is the
+    Benjamini-Hochberg q-value of the record over all the tests of its motif."""
 
-    def __init__(self, offsets, start, strand, score, widths, names, iscore, pvalue):
+    def __init__(self, offsets, start, strand, score, widths, names, iscore, pvalue, qvalue=None):
         self.widths = np.asarray(widths, dtype=np.int32)
         self.names = list(names)
-        super().__init__(offsets, start, strand, score, int(self.widths.max()) if len(self.widths) else 0, pvalue)
+        super().__init__(offsets, start, strand, score, int(self.widths.max()) if len(self.widths) else 0, pvalue,
+                         qvalue)
         self.iscore = np.asarray(iscore, dtype=np.int32)
         if self.pvalue is None or self.iscore.shape != self.pvalue.shape:
             raise ValueError("iscore and pvalue must hold one value per record")
@@ -190,8 +200,52 @@ def _chunk_for(M, chunk_positions):
     return int(min(_sites.CHUNK_POSITIONS, tiles * _lib.SITES_TILE))
 
 
+def _count_scores(null, data, hist, both, period, chunk_positions):
+    """Adds the scores of every live window of `data` (1-D uint8 tensor) under null's tables into hist, chunk by
+    chunk (explainn_pwm_score_histogram)."""
+    from . import _lib
+    M, wmax, device = null.scores.shape[0], null.wmax, hist.device
+    chunk = _sites.CHUNK_POSITIONS if chunk_positions is None else int(chunk_positions)
+    for p0, cnt in _sites.position_chunks(int(data.shape[0]), chunk, period):
+        piece = data[p0:p0 + cnt + wmax - 1].to(device).contiguous()
+        _lib.call("explainn_pwm_score_histogram", device, piece, piece.shape[0], 0, cnt, int(period), int(both),
+                  null.scores, null.widths, M, wmax, null.bins, hist)
+
+
+def score_histogram(motifs, codes, bg=None, pseudocount=0.1, bins=100, strands="both", period=0, chunk_positions=None,
+                    out=None, device=None):
+    """The observed score histogram of `codes`: a device int64 (M, wmax bins + 2) tensor, [m][s] = the live windows
+    of motif m, on either requested strand, whose integer score is s -- every test scan_motifs makes on these
+    codes, the sites and all the others (each strand is a test).  motifs: as scan_motifs takes them (with bg,
+    pseudocount and bins), or a PwmNull (score_null), whose tables are then used as they are.  The row stride is
+    PwmNull.tail's.  out: a histogram to ADD into and return (one q-value over many records or files); None: a
+    new one.  The sequence goes to the device in chunks of chunk_positions starts that overlap by wmax - 1 bases;
+    the counts are integers, so the result does not depend on the chunking.  No host synchronisation."""
+    import torch
+
+    from . import _lib
+    from .strands import as_codes_1d
+    _sites._check_args(strands, chunk_positions, 0, period)
+    data = as_codes_1d(codes)
+    if isinstance(motifs, PwmNull):
+        null = motifs
+        device = null.scores.device
+    else:
+        b = sequence_background(data, strands) if isinstance(bg, str) and bg == "sequence" else _background(bg)
+        null = score_null(motifs, 1.0, b, pseudocount, bins,
+                          _lib.device_for(device, (data, out), "pwmsites.score_histogram"))
+        device = null.scores.device
+    M, stride = null.scores.shape[0], null.wmax * null.bins + 2
+    if out is None:
+        out = torch.zeros((M, stride), dtype=torch.int64, device=device)
+    _lib.require(out, torch.int64, (M, stride), device, "out")
+    if M and data.shape[0]:
+        _count_scores(null, data, out, strands == "both", period, chunk_positions)
+    return out
+
+
 def scan_motifs(motifs, codes, pvalue=1e-4, bg=None, pseudocount=0.1, bins=100, strands="both", period=0,
-                chunk_positions=None, max_sites=_sites.MAX_SITES, device=None):
+                chunk_positions=None, max_sites=_sites.MAX_SITES, device=None, qvalue=None, observed=None):
     """Every site of every motif in `codes` at p-value <= pvalue: a PwmCalls.
 
     motifs: [(id, name, (w,4) matrix)] as read_meme / read_jaspar / read_motifs give them, or anything
@@ -204,22 +258,40 @@ def scan_motifs(motifs, codes, pvalue=1e-4, bg=None, pseudocount=0.1, bins=100, 
     device in chunks of start positions that overlap by wmax - 1 bases, sized so that the call's workspace
     stays under WORKSPACE_BYTES (or chunk_positions starts); each chunk takes a count call, one read of the
     total, and an emit call into buffers of exactly that size; the result does not depend on the chunking.
-    More than max_sites records raise ValueError."""
+    More than max_sites records raise ValueError.
+
+    qvalue = alpha: the result carries `qvalue`, the Benjamini-Hochberg q-value of every record over ALL the tests
+    of its motif (explainn_site_qvalues on the observed score histogram and the null's tail: exact, and unlike a
+    q-value estimated from the listed sites independent of pvalue), and only sites with q-value <= alpha are
+    listed: each motif's integer threshold is raised to the smallest score that qualifies.  observed: a
+    score_histogram accumulated beforehand over everything that forms one family of tests (many records, files)
+    under the same motifs, bg, pseudocount, bins and strands; None counts `codes` alone.  observed without qvalue
+    lists at pvalue and only adds the column."""
     import torch
 
     from . import _lib
     from .strands import as_codes_1d
     _sites._check_args(strands, chunk_positions, max_sites, period)
     _sites.check_pvalue(pvalue)
+    want_q = qvalue is not None or observed is not None
+    alpha = 1.0 if qvalue is None else float(qvalue)
+    _sites.check_qvalue(alpha)
     names, mats = motif_list(motifs)
     data = as_codes_1d(codes)
     b = sequence_background(data, strands) if isinstance(bg, str) and bg == "sequence" else _background(bg)
     S, widths, scale, lo = quantise(mats, b, pseudocount, bins)
     device = _lib.device_for(device, (data,), "pwmsites.scan_motifs")
     M, wmax, n = len(mats), S.shape[1], int(data.shape[0])
-    blocks = []
+    blocks, q = [], None
     if M and n:
         null = _null(S, np.where(scale > 0, widths, 0).astype(np.int32), scale, lo, bins, b, pvalue, device)
+        thr = null.thresholds
+        if want_q:
+            if observed is None:
+                observed = score_histogram(null, data, strands=strands, period=period, chunk_positions=chunk_positions)
+            q, _, first = _sites.site_qtable(_lib.require(observed, torch.int64, tuple(null.tail.shape), device,
+                                                          "observed"), null.tail, alpha)
+            thr = torch.maximum(thr, first)
         chunks = _sites.position_chunks(n, _chunk_for(M, chunk_positions), period)
         ws, nbytes = _lib.workspace("explainn_pwm_sites_workspace_bytes", device, M, max(c for _, c in chunks))
         offsets = torch.empty((2 * M + 1,), dtype=torch.int64, device=device)
@@ -227,7 +299,7 @@ def scan_motifs(motifs, codes, pvalue=1e-4, bg=None, pseudocount=0.1, bins=100, 
         with torch.cuda.device(device):
             def call(piece, cnt, pos, score, pv, capacity):
                 _lib.call("explainn_pwm_sites", device, piece, piece.shape[0], 0, cnt, int(period), both, null.scores,
-                          null.widths, M, wmax, null.thresholds, null.tail, int(bins), offsets, pos, score, pv,
+                          null.widths, M, wmax, thr, null.tail, int(bins), offsets, pos, score, pv,
                           capacity, ws, nbytes)
 
             def count(piece, cnt):
@@ -248,7 +320,11 @@ def scan_motifs(motifs, codes, pvalue=1e-4, bg=None, pseudocount=0.1, bins=100, 
     unit_offsets, start, strand, iscore, pv = _sites.assemble(blocks, M, (np.int32, np.float64))
     unit = np.repeat(np.arange(M), np.diff(unit_offsets))
     score = iscore / scale[unit] + widths[unit] * lo[unit]           # a record's motif is never empty: scale > 0
-    return PwmCalls(unit_offsets, start, strand, score, widths, names, iscore, pv)
+    qv = None
+    if want_q:
+        qv = np.zeros(0) if q is None or not len(unit) else q.view(-1)[
+            torch.from_numpy(unit * q.shape[1] + iscore).to(device)].cpu().numpy()
+    return PwmCalls(unit_offsets, start, strand, score, widths, names, iscore, pv, qv)
 
 
 # ---------------------------------------------------------------- command line
@@ -284,23 +360,42 @@ def _parser():
     ap.add_argument("--pseudocount", type=float, default=0.1)
     ap.add_argument("--bins", type=int, default=100)
     ap.add_argument("--strands", choices=("both", "fwd"), default="both")
+    ap.add_argument("--qvalues", action="store_true",
+                    help="a first pass counts the score of every window of the file, and an eighth column holds the "
+                         "site's Benjamini-Hochberg q-value over all windows and strands of the file")
+    ap.add_argument("--max-qvalue", type=float, default=None,
+                    help="with --qvalues: list only the sites at or below this q-value (and at --pvalue)")
     return ap
 
 
 def main(argv=None):
     """FASTA records of any length -> `SeqId start end name score strand pvalue`: one row per site of a known
     motif at p-value <= --pvalue, 0-based half-open, sorted by (start, motif, strand) within a record.  With
-    --bg sequence every record is scored against its own base frequencies."""
+    --bg sequence every record is scored against its own base frequencies.  With --qvalues an eighth column holds
+    the site's q-value over the whole file."""
     args = _parser().parse_args(argv)
+    if args.qvalues and args.bg == "sequence":
+        raise SystemExit("--qvalues does not go with --bg sequence: every record is then scored against its own "
+                         "table, and the records do not form one family of tests")
+    if args.max_qvalue is not None and not (args.qvalues and 0.0 <= args.max_qvalue <= 1.0):
+        raise SystemExit("--max-qvalue needs --qvalues and a value in [0, 1]")
     from .loader import read_fasta_records
     motifs = _motifs.read_motifs(args.motifs)
     records = read_fasta_records(args.fasta_file)
+    kwargs = {}
+    if args.qvalues:
+        # q-values are over the whole file: one pass counts every test, the second lists the sites
+        null = score_null(motifs, args.pvalue, args.bg, args.pseudocount, args.bins)
+        hist = None
+        for _, codes in records:
+            hist = score_histogram(null, codes, strands=args.strands, out=hist)
+        kwargs = {"observed": hist, "qvalue": args.max_qvalue}
     fh = open(args.output_file, "w") if args.output_file else sys.stdout
     try:
         for rid, codes in records:
             fh.writelines(bed_rows(rid, scan_motifs(motifs, codes, pvalue=args.pvalue, bg=args.bg,
                                                     pseudocount=args.pseudocount, bins=args.bins,
-                                                    strands=args.strands)))
+                                                    strands=args.strands, **kwargs)))
     finally:
         if fh is not sys.stdout:
             fh.close()

@@ -21,6 +21,13 @@ with an error rate behind it, what `python -m explainn_amd.calibrate` writes fro
 The float16 activation is never negative, so its 32768 bit patterns sort like the values: the null is a
 32768-bin integer histogram per filter (explainn_activation_histogram, csrc/actnull.hip), and tails,
 thresholds and p-values are exact functions of integers.  `--null NULL.npz` adds the p-value column.
+
+    sq = site_qvalues(activation_null(model, codes), null)     # the scanned sequences' own histogram, no shuffles
+    calls = call_sites(model, codes, sq.thresholds(0.05), null=null, qvalues=sq)
+    calls.qvalue                                        # Benjamini-Hochberg over ALL positions and strands
+
+A site's q-value is a function of (unit, bit pattern) too: explainn_site_qvalues (csrc/siteq.hip) forms the
+table from the two histograms.  `--qvalues [--max-qvalue Q]` adds the column over the whole file.
 """
 import argparse
 import sys
@@ -39,7 +46,7 @@ class SiteCalls:
     start of the k-mer on the forward strand), `strand` (int8, +1 / -1) and `score` (float32: the
     float16 activation).  Per unit: '+' sites in ascending start, then '-' sites in ascending start."""
 
-    def __init__(self, offsets, start, strand, score, kernel_size, pvalue=None):
+    def __init__(self, offsets, start, strand, score, kernel_size, pvalue=None, qvalue=None):
         self.offsets = np.asarray(offsets, dtype=np.int64)
         self.start = np.asarray(start, dtype=np.int64)
         self.strand = np.asarray(strand, dtype=np.int8)
@@ -53,6 +60,11 @@ class SiteCalls:
         self.pvalue = None if pvalue is None else np.asarray(pvalue, dtype=np.float64)
         if self.pvalue is not None and self.pvalue.shape != (n,):
             raise ValueError("pvalue must hold one value per record")
+        # float64 Benjamini-Hochberg q-value of every record over all the tests of its unit (SiteQvalues); None
+        # without one
+        self.qvalue = None if qvalue is None else np.asarray(qvalue, dtype=np.float64)
+        if self.qvalue is not None and self.qvalue.shape != (n,):
+            raise ValueError("qvalue must hold one value per record")
 
     @property
     def units(self):
@@ -154,12 +166,14 @@ def assemble(blocks, units, columns):
 
 def concat_units(a, b):
     """A SiteCalls whose units are a's followed by b's (two calls over the same coordinates: a model's filters
-    and known motifs, say); kernel_size is the larger of the two, and pvalue is kept only if both carry one.
-    spacing.spacing() of it counts filter-versus-filter, filter-versus-motif and motif-versus-motif pairs."""
+    and known motifs, say); kernel_size is the larger of the two, and pvalue and qvalue are each kept only if both
+    carry one.  spacing.spacing() of it counts filter-versus-filter, filter-versus-motif and motif-versus-motif
+    pairs."""
     pvalue = None if a.pvalue is None or b.pvalue is None else np.concatenate([a.pvalue, b.pvalue])
+    qvalue = None if a.qvalue is None or b.qvalue is None else np.concatenate([a.qvalue, b.qvalue])
     return SiteCalls(np.concatenate([a.offsets, b.offsets[1:] + a.offsets[-1]]), np.concatenate([a.start, b.start]),
                      np.concatenate([a.strand, b.strand]), np.concatenate([a.score, b.score]),
-                     max(a.kernel_size, b.kernel_size), pvalue)
+                     max(a.kernel_size, b.kernel_size), pvalue, qvalue)
 
 
 class _StrandLeg:
@@ -188,7 +202,7 @@ class _StrandLeg:
 
 
 def call_sites(model, codes, thresholds, strands="both", chunk_positions=None, max_sites=MAX_SITES, period=0,
-               null=None):
+               null=None, qvalues=None):
     """Every site of every unit of `model` (an ExplaiNN, or an ExplaiNNBank: global unit indices) in
     `codes`: 1-D uint8 base codes (0..3 = A,C,G,T, 4 = N), numpy array or tensor, host or device.
 
@@ -200,9 +214,13 @@ def call_sites(model, codes, thresholds, strands="both", chunk_positions=None, m
     k - 1 bases; each chunk and strand takes a count call, one read of the total, and an emit call
     into a buffer of exactly that size.  The two strands run on the model and its eval_replica() on two
     streams.  More than max_sites records raise ValueError.  null: an ActivationNull of this model; the
-    result then carries `pvalue`, the empirical p-value of every record.  Returns a SiteCalls."""
+    result then carries `pvalue`, the empirical p-value of every record.  qvalues: a SiteQvalues of this model
+    (site_qvalues); the result then carries `qvalue`.  Returns a SiteCalls."""
     _check_args(strands, chunk_positions, max_sites, period)
     k, units = model._options["kernel_size"], model._units()
+    if qvalues is not None and (qvalues.units, qvalues.kernel_size) != (units, k):
+        raise ValueError("the q-values are of %d units of kernel size %d, the model of %d of %d" % (
+            qvalues.units, qvalues.kernel_size, units, k))
     if null is not None and (null.units, null.kernel_size) != (units, k):
         raise ValueError("the null is of %d units of kernel size %d, the model of %d of %d" % (
             null.units, null.kernel_size, units, k))
@@ -242,6 +260,8 @@ def call_sites(model, codes, thresholds, strands="both", chunk_positions=None, m
     calls = SiteCalls(*assemble(blocks, units, (np.float32,)), k)
     if null is not None:
         calls.pvalue = null.pvalue(calls.unit_ids(), calls.score)
+    if qvalues is not None:
+        calls.qvalue = qvalues.qvalue(calls.unit_ids(), calls.score)
     return calls
 
 
@@ -259,6 +279,20 @@ def _null_stats(hist, alpha, want_tail=False, want_thresholds=False):
     thr = torch.empty(units, device=dev, dtype=torch.float32) if want_thresholds else None
     _lib.call("explainn_activation_null", dev, hist, units, float(alpha), tail, total, thr)
     return tail, total, thr
+
+
+def _unit_bits(unit_ids, scores, units):
+    """(int64 unit ids, int64 float16 bit patterns of the scores), checked: the index of a record in a
+    (units, ACT_BINS) table."""
+    unit = np.asarray(unit_ids, dtype=np.int64)
+    with np.errstate(over="ignore"):                  # a score past 65504 is +inf in float16
+        bits = (np.asarray(scores, dtype=np.float32).astype(np.float16).view(np.uint16).astype(np.int64)
+                & (ACT_BINS - 1))
+    if unit.shape != bits.shape or unit.ndim != 1:
+        raise ValueError("unit_ids and scores must be 1-D and of one length")
+    if len(unit) and (unit.min() < 0 or unit.max() >= units):
+        raise IndexError("unit ids outside [0, %d)" % units)
+    return unit, bits
 
 
 class ActivationNull:
@@ -292,16 +326,9 @@ class ActivationNull:
     def pvalue(self, unit_ids, scores):
         """float64 (n,): (1 + null activations of the unit >= float16(score)) / (1 + total): the add-one
         empirical p-value, resolution 1 / (total + 1).  Gathered on the device; only the n values cross."""
-        unit = np.asarray(unit_ids, dtype=np.int64)
-        with np.errstate(over="ignore"):                  # a score past 65504 is +inf in float16
-            bits = (np.asarray(scores, dtype=np.float32).astype(np.float16).view(np.uint16).astype(np.int64)
-                    & (ACT_BINS - 1))
-        if unit.shape != bits.shape or unit.ndim != 1:
-            raise ValueError("unit_ids and scores must be 1-D and of one length")
+        unit, bits = _unit_bits(unit_ids, scores, self.units)
         if len(unit) == 0:
             return np.zeros(0, dtype=np.float64)
-        if unit.min() < 0 or unit.max() >= self.units:
-            raise IndexError("unit ids outside [0, %d)" % self.units)
         dev = self.hist.device
         u = torch.from_numpy(unit).to(dev)
         idx = u * ACT_BINS + torch.from_numpy(bits).to(dev)
@@ -392,6 +419,99 @@ def activation_null(model, codes, period=0, shuffles=0, seed=0, strands="both", 
     return ActivationNull(hist, model._options["kernel_size"], strands, shuffles, seed)
 
 
+def records_null(model, records, strands="both", seed=0):
+    """One ActivationNull over the k-mers of every record's own codes (records of any lengths: an iterable of 1-D
+    uint8 arrays), no k-mer across two records: the observed histogram site_qvalues needs, and the background of
+    `calibrate --background sequence` when the records' lengths differ."""
+    check_strands(strands)
+    hist = torch.zeros(model._units(), ACT_BINS, device=model._device(), dtype=torch.int64)
+    with torch.no_grad(), model.eval_cache():
+        for c in records:
+            if len(c):
+                data, _ = _null_args(model, np.asarray(c, dtype=np.uint8), 0, 0, strands, None)
+                _count_activations(model, data, hist, 0, 0, seed, strands == "both", CHUNK_POSITIONS)
+    if model.validate_input:
+        model.check_input()
+    return ActivationNull(hist, model._options["kernel_size"], strands, 0, seed)
+
+
+# ---------------------------------------------------------------- q-values
+def check_qvalue(alpha):
+    if not 0.0 <= float(alpha) <= 1.0:
+        raise ValueError("qvalue must be in [0, 1] (got %r)" % (alpha,))
+
+
+def site_qtable(obs, p, alpha=0.0):
+    """(q float64 (units, bins), total int64 (units,), first int32 (units,)) of explainn_site_qvalues, on the
+    device: the Benjamini-Hochberg q-value of every score bin over ALL the tests of its unit.  obs: device int64
+    (units, bins), the tests per bin; p: device float64 (units, bins), the p-value of the bin, non-increasing in
+    the bin; first[u] = the smallest bin with q <= alpha (bins if none).  No host synchronisation."""
+    from . import _lib
+    if not torch.is_tensor(obs) or obs.dim() != 2 or not 1 <= obs.shape[1] <= _lib.SITEQ_MAX_BINS:
+        raise ValueError("obs must be a (units, bins) tensor with 1 <= bins <= %d" % _lib.SITEQ_MAX_BINS)
+    check_qvalue(alpha)
+    units, bins = obs.shape
+    _lib.require(obs, torch.int64, (units, bins), None, "obs")
+    _lib.require(p, torch.float64, (units, bins), obs.device, "p")
+    q = torch.empty((units, bins), dtype=torch.float64, device=obs.device)
+    total = torch.empty((units,), dtype=torch.int64, device=obs.device)
+    first = torch.empty((units,), dtype=torch.int32, device=obs.device)
+    _lib.call("explainn_site_qvalues", obs.device, obs, p, units, bins, float(alpha), q, total, first)
+    return q, total, first
+
+
+class SiteQvalues:
+    """The q-values of a model's filter sites: `q` float64 (units, 32768) on the device, q[u][b] = the
+    Benjamini-Hochberg q-value of a site of unit u whose float16 activation has the bit pattern b, over all
+    `total[u]` tests of the unit -- every live start and strand of the scanned sequences, not only the called
+    sites, so it does not depend on a threshold.  Exact: a function of two integer histograms."""
+
+    def __init__(self, observed, p, kernel_size, strands):
+        self._obs, self._p, self.kernel_size, self.strands = observed, p, int(kernel_size), strands
+        self.q, self.total, _ = site_qtable(observed, p)
+
+    @property
+    def units(self):
+        return self.q.shape[0]
+
+    def first(self, alpha):
+        """int64 (units,): per unit the smallest bit pattern with q <= alpha; 32768 if none."""
+        return site_qtable(self._obs, self._p, alpha)[2].cpu().numpy().astype(np.int64)
+
+    def thresholds(self, alpha):
+        """(units,) float32 thresholds at which call_sites (activation > threshold) lists exactly the sites with
+        q <= alpha: the float16 value one bit pattern below the first that qualifies; +inf where none does (or
+        only NaN patterns would), -1 where every pattern does."""
+        first = self.first(alpha)
+        below = np.clip(first - 1, 0, ACT_INF).astype(np.uint16).view(np.float16).astype(np.float32)
+        return np.where(first == 0, np.float32(-1.0), below).astype(np.float32)
+
+    def qvalue(self, unit_ids, scores):
+        """float64 (n,): q[unit][bits(float16(score))], gathered on the device; only the n values cross."""
+        unit, bits = _unit_bits(unit_ids, scores, self.units)
+        if len(unit) == 0:
+            return np.zeros(0, dtype=np.float64)
+        dev = self.q.device
+        return self.q.view(-1)[torch.from_numpy(unit).to(dev) * ACT_BINS + torch.from_numpy(bits).to(dev)].cpu().numpy()
+
+
+def site_qvalues(observed, null):
+    """The SiteQvalues of scanned sequences against a background.  observed: the ActivationNull of the scanned
+    sequences themselves -- activation_null(model, codes, period=..., strands=...) without shuffles, with the
+    strands and period call_sites will use (records_null for records of unequal lengths) -- so that its histogram
+    holds every test call_sites makes.  null: the background's ActivationNull; a pattern's p-value is
+    (1 + null.tail) / (1 + null.total) in fp64, the expression ActivationNull.pvalue evaluates."""
+    if (observed.units, observed.kernel_size, observed.strands) != (null.units, null.kernel_size, null.strands):
+        raise ValueError("observed is of %d units of kernel size %d on strands %r, the null of %d of %d on %r" % (
+            observed.units, observed.kernel_size, observed.strands, null.units, null.kernel_size, null.strands))
+    if observed.shuffles:
+        raise ValueError("observed must count the scanned sequences themselves, not shuffles of them")
+    if observed.hist.device != null.hist.device:
+        raise ValueError("observed and null must be on one device")
+    p = (1.0 + null.tail.to(torch.float64)) / (1.0 + null.total.to(torch.float64))[:, None]
+    return SiteQvalues(observed.hist, p, null.kernel_size, null.strands)
+
+
 def call_sites_records(model, records, thresholds, **kwargs):
     """call_sites() over (id, codes) pairs (loader.read_fasta_records): yields (id, SiteCalls)."""
     for rid, codes in records:
@@ -411,7 +531,11 @@ def bed_rows(seq_id, calls, names=None, widths=None):
         row = "%s\t%d\t%d\t%s\t%.6g\t%s" % (
             seq_id, calls.start[i], calls.start[i] + (calls.kernel_size if widths is None else widths[u]),
             "filter%d" % u if names is None else names[u], calls.score[i], "+" if calls.strand[i] > 0 else "-")
-        rows.append(row + ("\n" if calls.pvalue is None else "\t%.6g\n" % calls.pvalue[i]))
+        if calls.pvalue is not None:
+            row += "\t%.6g" % calls.pvalue[i]
+        if calls.qvalue is not None:
+            row += "\t%.6g" % calls.qvalue[i]
+        rows.append(row + "\n")
     return rows
 
 
@@ -453,14 +577,23 @@ def _parser():
     ap.add_argument("--strands", choices=("both", "fwd"), default="both")
     ap.add_argument("--null", help="NULL.npz of `python -m explainn_amd.calibrate --save-null`: adds a seventh "
                                    "column, the empirical p-value of the site's score")
+    ap.add_argument("--qvalues", action="store_true",
+                    help="needs --null: a first pass counts every activation of the file, and a further column holds "
+                         "the site's Benjamini-Hochberg q-value over all positions and strands of the file")
+    ap.add_argument("--max-qvalue", type=float, default=None,
+                    help="with --qvalues: list only the sites at or below this q-value (and above the thresholds)")
     return ap
 
 
 def main(argv=None):
     """FASTA records of any length -> BED6 (SeqId, start, end, filter<u>, score, strand): one row per
     motif site, 0-based half-open, sorted by (start, filter, strand) within a record.  With --null a
-    seventh column holds the site's empirical p-value."""
+    seventh column holds the site's empirical p-value; with --qvalues an eighth its q-value over the whole file."""
     args = _parser().parse_args(argv)
+    if args.qvalues and not args.null:
+        raise SystemExit("--qvalues needs --null")
+    if args.max_qvalue is not None and not (args.qvalues and 0.0 <= args.max_qvalue <= 1.0):
+        raise SystemExit("--max-qvalue needs --qvalues and a value in [0, 1]")
     from .loader import read_fasta_records
     from .predict import _load_model
     records = read_fasta_records(args.fasta_file)
@@ -468,9 +601,16 @@ def main(argv=None):
     model.eval()
     thresholds = read_thresholds(args.thresholds, model._units())
     null = ActivationNull.load(args.null, model._device()) if args.null else None
+    kwargs = {"null": null} if null is not None else {}
+    if args.qvalues:
+        # q-values are over the whole file: one pass counts every test, the second lists the sites
+        if null.strands != args.strands:
+            raise SystemExit("the null counts strands %r, --strands is %r" % (null.strands, args.strands))
+        kwargs["qvalues"] = site_qvalues(records_null(model, (c for _, c in records), args.strands), null)
+        if args.max_qvalue is not None:
+            thresholds = np.maximum(thresholds, kwargs["qvalues"].thresholds(args.max_qvalue))
     fh = open(args.output_file, "w") if args.output_file else sys.stdout
     try:
-        kwargs = {"null": null} if null is not None else {}
         for rid, calls in call_sites_records(model, records, thresholds, strands=args.strands, **kwargs):
             fh.writelines(bed_rows(rid, calls))
     finally:

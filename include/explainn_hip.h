@@ -893,6 +893,48 @@ int explainn_pwm_sites(const uint8_t* seq, int64_t seq_len, int64_t start, int64
                        int32_t* score, double* pvalue, int64_t capacity, void* workspace, int64_t workspace_bytes,
                        void* stream);
 
+/* The observed score histogram of known motifs (csrc/pwmsites.hip, DESIGN.md section 8, "Site q-values"): every
+ * test explainn_pwm_sites would make, counted by its integer score -- the sites and all the windows that are none.
+ *
+ * explainn_pwm_score_histogram: seq, seq_len, start, n_positions, period and both_strands, and scores, widths, M,
+ * wmax and bins, as explainn_pwm_sites takes them.  For every motif m and every start p that is live for m there
+ * (its w bases inside the bases the call reads, no N, inside its record):
+ *     hist[m][score of row 2m at p] += 1,   and with both_strands != 0   hist[m][score of row 2m+1 at p] += 1
+ * (each strand is a test).  An empty motif counts nothing, so sum_s hist[m][s] grows by the number of tests of m.
+ * hist: device int64 [M][wmax bins + 2], the row stride of explainn_pwm_null's tail, ADDED INTO: the caller zeroes
+ * it once and may accumulate any number of calls, chunks, records and files.  A score outside the row -- possible
+ * only with a table entry outside [0, bins] -- is not counted.  All additions are integer (32-bit counters in LDS,
+ * flushed with 64-bit atomics): the result is a function of the input alone, whatever the grid, and whatever
+ * chunks a caller cuts.  A workgroup holds as many motifs' rows as the 160 KB of LDS allow beside their tables and
+ * a tile's codes (EXPLAINN_PWM_GROUP at the most, four for the largest row) and takes at most
+ * EXPLAINN_PWM_HIST_SLICE starts, two counts each, so no 32-bit counter overflows.  No context, no workspace, no
+ * allocation, no host synchronisation.  EXPLAINN_E_ARG as explainn_pwm_sites (geometry, 0 <= start, start +
+ * n_positions <= seq_len, n_positions + wmax < 2^31, period >= 0).  M == 0 or n_positions == 0 launches nothing. */
+#define EXPLAINN_PWM_HIST_SLICE (1 << 30)
+int explainn_pwm_score_histogram(const uint8_t* seq, int64_t seq_len, int64_t start, int64_t n_positions,
+                                 int64_t period, int both_strands, const int16_t* scores, const int32_t* widths,
+                                 int M, int wmax, int bins, int64_t* hist, void* stream);
+
+/* Site q-values (csrc/siteq.hip, DESIGN.md section 8, "Site q-values"): the Benjamini-Hochberg q-value of every
+ * score bin of every unit, for filter sites (bins = EXPLAINN_ACT_BINS bit patterns) and known-motif sites (bins =
+ * wmax bins + 2 integer scores) alike.  obs: device int64 [units][bins], the tests of unit u that scored in bin b
+ * (all of them: explainn_activation_histogram / explainn_pwm_score_histogram of the scanned sequences), none
+ * negative; p: device double [units][bins], the p-value of the bin, not NaN, which the caller's null makes
+ * non-increasing in b.  With N = sum_b obs[u][b] and R[b] = sum_{b' >= b} obs[u][b']:
+ *     q[u][b]  = min(1, min over b' <= b with R[b'] > 0 of (p[u][b'] * (double) N) / (double) R[b'])     (1 if none)
+ *     total[u] = N
+ *     first[u] = the number of b with q[u][b] > alpha = the smallest b with q[u][b] <= alpha (bins if none)
+ * Bins of equal p need no tie rule: the lower one has the larger R and lies inside the minimum.  This is BH over
+ * all N tests of the unit -- it does not depend on a p-value cutoff, as a q-value estimated from a truncated site
+ * list does.  Every term is one fp64 multiply and one fp64 divide, every sum is an integer sum and a minimum is
+ * exact: the same input gives the same bits, those of the expression above evaluated in IEEE double.
+ * q: device double [units][bins]; total: device int64 [units]; first: device int32 [units], may be NULL.
+ * EXPLAINN_E_ARG unless units >= 0, 1 <= bins <= EXPLAINN_SITEQ_MAX_BINS and 0 <= alpha <= 1.  units == 0 launches
+ * nothing.  No context, no workspace, no allocation, no host synchronisation, no atomics on floats. */
+#define EXPLAINN_SITEQ_MAX_BINS 32768
+int explainn_site_qvalues(const int64_t* obs, const double* p, int units, int bins, double alpha, double* q,
+                          int64_t* total, int32_t* first, void* stream);
+
 /* Known-motif enrichment and centrality (csrc/pwmbest.hip, DESIGN.md section 3 item 21, section 8 "Known-motif
  * enrichment"): explainn_record_best for the score tables of explainn_pwm_sites in place of a model's filters.
  *

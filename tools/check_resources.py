@@ -85,12 +85,15 @@ SITES = [r"^sites_kernel<0>", r"^sites_kernel<1>", r"^sites_scan_tiles_kernel", 
          r"^site_kernel<0>", r"^site_kernel<1>", r"^site_kernel<2>", r"^site_scan_kernel"]
 # known-motif sites (pwmsites.hip): the exact null and the count / emit scan (its two scans are SITES')
 PWMSITES = [r"^pwm_null_kernel", r"^pwm_sites_kernel<0>", r"^pwm_sites_kernel<1>"]
+# site q-values: the observed PWM score histogram (pwmsites.hip; dynamic LDS only, up to 160 KB: G rows of
+# wmax bins + 2 bins, the tables, a tile's codes) and the BH table (siteq.hip; 4112 bytes of static LDS)
+SITEQ = [r"^pwm_hist_kernel", r"^site_q_kernel"]
 # known-motif enrichment (pwmbest.hip): the per-record best PWM site
 PWMBEST = [r"^pwm_best_kernel"]
 # greedy in-silico evolution (evolve.hip): one round's selection
 EVOLVE = [r"^evolve_select_kernel"]
 GATED = (C2_STEP + INPUT_GRAD + ISM + EVOLVE + PATHGRAD + METRICS + SCAN + VARIANTS + HAPLOTYPES + SHUFFLE + MOTIFS + MOTIFTREE + ACTNULL +
-         SPACING + ENRICH + CENTRAL + SITES + PWMSITES + PWMBEST)
+         SPACING + ENRICH + CENTRAL + SITES + PWMSITES + PWMBEST + SITEQ)
 
 
 # Register cliffs measured in the pipeline: 1024-thread blocks of which TWO must
