@@ -19,6 +19,8 @@ import argparse
 import numpy as np
 import torch
 
+from .strands import eval_pass
+
 LETTERS = "ACGTN"
 
 
@@ -121,7 +123,7 @@ def evolve(model, codes, target=None, rounds=10, maximize=True, mutable=None, re
     res = dict(codes=np.empty((N, L), np.uint8), pos=np.empty((N, rounds), np.int32),
                ref=np.empty((N, rounds), np.uint8), alt=np.empty((N, rounds), np.uint8),
                gain=np.empty((N, rounds), np.float64), logits=np.empty((N, rounds + 1, S, T), np.float32))
-    with torch.no_grad(), model.eval_cache():
+    with eval_pass(model):
         for i in range(0, N, batch_size):
             j = min(i + batch_size, N)
             cb = data[i:j].to(dev).clone().contiguous()           # evolve() edits it in place
@@ -132,8 +134,6 @@ def evolve(model, codes, target=None, rounds=10, maximize=True, mutable=None, re
             for key, t in (("pos", pos), ("ref", ref), ("alt", alt), ("gain", gain)):
                 res[key][i:j] = t.cpu().numpy().T
             res["logits"][i:j] = logits.permute(2, 0, 1, 3).cpu().numpy()
-    if model.validate_input:
-        model.check_input()
     return Evolution(weights=w, **res)
 
 

@@ -29,6 +29,7 @@ from . import metrics
 from .architectures import BaseCodes
 from .loader import read_tsv_codes
 from .predict import _load_model
+from .strands import eval_pass
 
 _CHUNK = 4096        # sequences per device pass, as in predict()
 TABLE = "performance-metrics.tsv"
@@ -42,15 +43,13 @@ def scores(model, codes, batch_size=100, rev_complement=False):
     data = torch.as_tensor(np.ascontiguousarray(codes))
     chunk = max(int(batch_size), _CHUNK)
     out = torch.empty(len(data), model._options["n_features"], device=dev, dtype=torch.float32)
-    with torch.no_grad(), model.eval_cache():
+    with eval_pass(model):
         for i in range(0, len(data), chunk):
             xb = data[i:i + chunk].to(dev)
             fwd = model(BaseCodes(xb))
             if rev_complement:
                 fwd = (fwd + model(BaseCodes(xb, reverse_complement=True))) / 2
             out[i:i + len(xb)] = fwd
-    if model.validate_input:
-        model.check_input()
     return out
 
 

@@ -25,6 +25,8 @@ import time
 import numpy as np
 import torch
 
+from .strands import eval_mode, eval_pass
+
 SITE_CAP = 1000000          # interpret.py:423-424: a filter with 1e6 sites is "way too ubiquitous"
 
 
@@ -47,6 +49,38 @@ def _as_tensor(Xs):
     return Xs if torch.is_tensor(Xs) else torch.as_tensor(np.asarray(Xs), dtype=torch.float32)
 
 
+def _attribution_input(model, Xs, target):
+    """What the attribution drivers open with: `target` checked, Xs as a tensor -- uint8 base codes
+    (N,L) as they are, anything else as fp32 (N,4,L).  Returns (Xs, codes, T, L, device), codes True
+    for base codes."""
+    T, L = model._options["n_features"], model._options["sequence_length"]
+    if target is not None and not 0 <= int(target) < T:
+        raise ValueError("target must be a task index in [0, %d)" % T)
+    codes = (torch.is_tensor(Xs) and Xs.dtype == torch.uint8) or \
+        (isinstance(Xs, np.ndarray) and Xs.dtype == np.uint8)
+    return torch.as_tensor(Xs) if codes else _as_tensor(Xs), codes, T, L, model.final.weight.device
+
+
+def _target_dlogits(B, T, target, dev):
+    """(B,T) d F / d logits of F = logit[target], or of the sum of the logits with target=None."""
+    dl = torch.zeros(B, T, device=dev, dtype=torch.float32)
+    if target is None:
+        dl.fill_(1.0)
+    else:
+        dl[:, int(target)] = 1.0
+    return dl
+
+
+def _on_strand(xb, codes, rev_complement):
+    """(xb, xin): the device batch as given (one-hot: as fp32) and what the model takes for the chosen
+    strand -- codes are staged reverse-complemented, a one-hot batch is flipped here."""
+    if codes:
+        from .architectures import BaseCodes
+        return xb, BaseCodes(xb, rev_complement)
+    xb = xb.to(torch.float32)
+    return xb, xb.flip(1, 2) if rev_complement else xb
+
+
 def _get_outs_preds(exp_model, Xs, batch_size=100):
     """The (N,U) unit outputs and (N,T) predictions of test.py:128-166, float16 like there.
     Eval-mode outputs do not depend on batch composition, so the device passes take at least 4096
@@ -57,7 +91,7 @@ def _get_outs_preds(exp_model, Xs, batch_size=100):
     outputs = np.zeros((len(Xs), U), dtype=np.float16)
     predictions = np.zeros((len(Xs), T), dtype=np.float16)
     Xs = _as_tensor(Xs)
-    with torch.no_grad(), exp_model.eval_cache():
+    with eval_pass(exp_model, settle=False):
         for i, xb in _batches(Xs, batch_size):
             outs = exp_model.linears(xb.to(dev))
             outputs[i:i + len(xb)] = outs.cpu().numpy()
@@ -75,7 +109,7 @@ def _get_acts_outs_preds(exp_model, data_loader):
     predictions = np.zeros((N, o["n_features"]), dtype=np.float16)
     dev = exp_model.final.weight.device
     idx = 0
-    with torch.no_grad(), exp_model.eval_cache():
+    with eval_pass(exp_model, settle=False):
         for Xs, _ in data_loader:
             Xs = Xs.to(dev)
             outs = exp_model.linears(Xs)
@@ -130,32 +164,25 @@ def filter_pwms(exp_model, Xs, idxs, rev_complement=False, batch_size=1024, site
     if rev_complement:
         sel[idxs + half] = 1
     select = torch.from_numpy(sel).to(dev)
-    was_training = exp_model.training
-    exp_model.eval()
-    try:
-        with exp_model.eval_cache():
-            unit_max = torch.zeros(U, device=dev, dtype=torch.float32)
-            for i, xb in _batches(Xs, batch_size):
-                exp_model.filter_act_max(xb.to(dev), unit_max, select[i:i + len(xb)])
-            # interpret.py:373: 0.5 * amax of a float16 array stays float16
-            thresholds = (0.5 * unit_max.cpu().numpy().astype(np.float16)).astype(np.float16)
-            thr_dev = torch.from_numpy(thresholds.astype(np.float32)).to(dev)
-            site_total = torch.zeros(U, device=dev, dtype=torch.int32)
-            pfm = torch.zeros(U, k, 4, device=dev, dtype=torch.int32)
-            hit = np.zeros((N, U), dtype=bool)
-            # forward strand first, then the reverse strand (interpret.py:385-429); a batch never
-            # straddles the two halves, so site ranks follow the reference's order
-            bounds = [(0, half)] + ([(half, N)] if rev_complement else [])
-            for lo, hi in bounds:
-                for i in range(lo, hi, batch_size):
-                    j = min(i + batch_size, hi)
-                    h = exp_model.filter_sites(Xs[i:j].to(dev), thr_dev, site_total, pfm, select[i:j],
-                                               site_cap=site_cap, want_hit=True)
-                    hit[i:j] = h.cpu().numpy().astype(bool)
-        if exp_model.validate_input:
-            exp_model.check_input()
-    finally:
-        exp_model.train(was_training)
+    with eval_mode(exp_model), eval_pass(exp_model):
+        unit_max = torch.zeros(U, device=dev, dtype=torch.float32)
+        for i, xb in _batches(Xs, batch_size):
+            exp_model.filter_act_max(xb.to(dev), unit_max, select[i:i + len(xb)])
+        # interpret.py:373: 0.5 * amax of a float16 array stays float16
+        thresholds = (0.5 * unit_max.cpu().numpy().astype(np.float16)).astype(np.float16)
+        thr_dev = torch.from_numpy(thresholds.astype(np.float32)).to(dev)
+        site_total = torch.zeros(U, device=dev, dtype=torch.int32)
+        pfm = torch.zeros(U, k, 4, device=dev, dtype=torch.int32)
+        hit = np.zeros((N, U), dtype=bool)
+        # forward strand first, then the reverse strand (interpret.py:385-429); a batch never
+        # straddles the two halves, so site ranks follow the reference's order
+        bounds = [(0, half)] + ([(half, N)] if rev_complement else [])
+        for lo, hi in bounds:
+            for i in range(lo, hi, batch_size):
+                j = min(i + batch_size, hi)
+                h = exp_model.filter_sites(Xs[i:j].to(dev), thr_dev, site_total, pfm, select[i:j],
+                                           site_cap=site_cap, want_hit=True)
+                hit[i:j] = h.cpu().numpy().astype(bool)
     return {"thresholds": thresholds, "pfm": pfm.cpu().numpy().astype(np.int64),
             "nsites": site_total.cpu().numpy().astype(np.int64), "hit": hit}
 
@@ -187,12 +214,8 @@ def filter_site_list(exp_model, Xs, idxs, thresholds, rev_complement=False, site
         return [np.zeros((0, 3), dtype=np.int64) for _ in range(U)]
     X = Xs.cpu().numpy() if torch.is_tensor(Xs) else np.asarray(Xs)
     codes = _onehot_to_codes(X[rows]).reshape(-1)
-    was_training = exp_model.training
-    exp_model.eval()
-    try:
+    with eval_mode(exp_model):
         calls = call_sites(exp_model, codes, np.asarray(thresholds, dtype=np.float32), strands="fwd", period=L)
-    finally:
-        exp_model.train(was_training)
     out = []
     for u in range(U):
         start = calls.unit(u)[0][:site_cap]
@@ -240,45 +263,24 @@ def input_gradients(model, Xs, target=None, batch_size=4096, rev_complement=Fals
     4 = N).  rev_complement=True runs the model on each sequence's reverse complement and maps the
     gradient back onto the given strand (base and position flipped), so that it multiplies the
     given one-hot."""
-    dev = model.final.weight.device
-    T, L = model._options["n_features"], model._options["sequence_length"]
-    if target is not None and not 0 <= int(target) < T:
-        raise ValueError("target must be a task index in [0, %d)" % T)
-    codes = (torch.is_tensor(Xs) and Xs.dtype == torch.uint8) or \
-        (isinstance(Xs, np.ndarray) and Xs.dtype == np.uint8)
-    Xs = torch.as_tensor(Xs) if codes else _as_tensor(Xs)
+    Xs, codes, T, L, dev = _attribution_input(model, Xs, target)
     out = np.zeros((len(Xs), 4, L), dtype=np.float32)
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad(), model.eval_cache():
-            for i, xb in _batches(Xs, batch_size):
-                xb = xb.to(dev, non_blocking=True)
-                B = xb.shape[0]
-                dl = torch.zeros(B, T, device=dev, dtype=torch.float32)
-                if target is None:
-                    dl.fill_(1.0)
-                else:
-                    dl[:, int(target)] = 1.0
-                if codes:
-                    from .architectures import BaseCodes
-                    dx = model.input_gradient(BaseCodes(xb, rev_complement), dl)
-                    if rev_complement:
-                        dx = dx.flip(1, 2)
-                    if times_input:
-                        onehot = torch.zeros(B, 5, L, device=dev, dtype=torch.float32)
-                        onehot.scatter_(1, xb.long().clamp(max=4).unsqueeze(1), 1.0)
-                        dx = dx * onehot[:, :4]
-                else:
-                    xb = xb.to(torch.float32)
-                    dx = model.input_gradient(xb.flip(1, 2) if rev_complement else xb, dl)
-                    if rev_complement:
-                        dx = dx.flip(1, 2)
-                    if times_input:
-                        dx = dx * xb
-                out[i:i + B] = dx.cpu().numpy()
-    finally:
-        model.train(was_training)
+    with eval_mode(model), eval_pass(model):
+        for i, xb in _batches(Xs, batch_size):
+            xb = xb.to(dev, non_blocking=True)
+            B = xb.shape[0]
+            dl = _target_dlogits(B, T, target, dev)
+            xb, xin = _on_strand(xb, codes, rev_complement)
+            dx = model.input_gradient(xin, dl)
+            if rev_complement:
+                dx = dx.flip(1, 2)
+            if times_input and codes:
+                onehot = torch.zeros(B, 5, L, device=dev, dtype=torch.float32)
+                onehot.scatter_(1, xb.long().clamp(max=4).unsqueeze(1), 1.0)
+                dx = dx * onehot[:, :4]
+            elif times_input:
+                dx = dx * xb
+            out[i:i + B] = dx.cpu().numpy()
     return out
 
 
@@ -304,14 +306,7 @@ def integrated_gradients(model, Xs, baselines="zero", target=None, steps=32, bat
     maps base and position back onto the given strand.
     return_delta=True returns (ig, delta), delta (N,) the convergence delta sum(ig) - (F(x) - F(x'))
     (the mean over the R baselines), F the target logit or the sum of the logits."""
-    from .architectures import BaseCodes
-    dev = model.final.weight.device
-    T, L = model._options["n_features"], model._options["sequence_length"]
-    if target is not None and not 0 <= int(target) < T:
-        raise ValueError("target must be a task index in [0, %d)" % T)
-    codes = (torch.is_tensor(Xs) and Xs.dtype == torch.uint8) or \
-        (isinstance(Xs, np.ndarray) and Xs.dtype == np.uint8)
-    Xs = torch.as_tensor(Xs) if codes else _as_tensor(Xs)
+    Xs, codes, T, L, dev = _attribution_input(model, Xs, target)
     N = len(Xs)
     base = None
     if not isinstance(baselines, str):
@@ -335,53 +330,39 @@ def integrated_gradients(model, Xs, baselines="zero", target=None, steps=32, bat
     R = n_shuffles if shuffle else 1 if base is None else base.shape[1]
     out = np.zeros((N, 4, L), dtype=np.float32)
     delta = np.zeros(N, dtype=np.float32)
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad(), model.eval_cache():
-            for i, xb in _batches(Xs, batch_size):
-                xb = xb.to(dev, non_blocking=True)
-                B = xb.shape[0]
-                dl = torch.zeros(B, T, device=dev, dtype=torch.float32)
-                if target is None:
-                    dl.fill_(1.0)
-                else:
-                    dl[:, int(target)] = 1.0
-                if codes:
-                    xin = BaseCodes(xb, rev_complement)
-                else:
-                    xb = xb.to(torch.float32)
-                    xin = xb.flip(1, 2) if rev_complement else xb
-                if shuffle:
-                    cb = xb if codes else src[i:i + B].to(dev, non_blocking=True)
-                    shuf = dinucleotide_shuffle_device(cb, n_shuffles, seed, row0=i)
-                acc = dcc = None
-                for r in range(R):
-                    bl = baselines
-                    if shuffle or base is not None:
-                        bl = shuf[:, r].contiguous() if shuffle else \
-                            base[i:i + B, r].to(dev, non_blocking=True).contiguous()
-                        if rev_complement and not codes:     # the one-hot batch was flipped here, not staged flipped
-                            bl = torch.where(bl < 4, 3 - bl, bl).flip(1)
-                    ig, lx, lb = model.integrated_gradients(xin, dl, bl, steps)
-                    d = ig.sum(dim=(1, 2)) - (dl * (lx - lb)).sum(dim=1)
-                    acc = ig if acc is None else acc.add_(ig)
-                    dcc = d if dcc is None else dcc.add_(d)
-                if R > 1:
-                    acc.div_(R)
-                    dcc.div_(R)
-                if rev_complement:
-                    acc = acc.flip(1, 2)
-                out[i:i + B] = acc.cpu().numpy()
-                delta[i:i + B] = dcc.cpu().numpy()
-        if model.validate_input:
-            model.check_input()
-    finally:
-        model.train(was_training)
+    with eval_mode(model), eval_pass(model):
+        for i, xb in _batches(Xs, batch_size):
+            xb = xb.to(dev, non_blocking=True)
+            B = xb.shape[0]
+            dl = _target_dlogits(B, T, target, dev)
+            xb, xin = _on_strand(xb, codes, rev_complement)
+            if shuffle:
+                cb = xb if codes else src[i:i + B].to(dev, non_blocking=True)
+                shuf = dinucleotide_shuffle_device(cb, n_shuffles, seed, row0=i)
+            acc = dcc = None
+            for r in range(R):
+                bl = baselines
+                if shuffle or base is not None:
+                    bl = shuf[:, r].contiguous() if shuffle else \
+                        base[i:i + B, r].to(dev, non_blocking=True).contiguous()
+                    if rev_complement and not codes:     # the one-hot batch was flipped here, not staged flipped
+                        bl = torch.where(bl < 4, 3 - bl, bl).flip(1)
+                ig, lx, lb = model.integrated_gradients(xin, dl, bl, steps)
+                d = ig.sum(dim=(1, 2)) - (dl * (lx - lb)).sum(dim=1)
+                acc = ig if acc is None else acc.add_(ig)
+                dcc = d if dcc is None else dcc.add_(d)
+            if R > 1:
+                acc.div_(R)
+                dcc.div_(R)
+            if rev_complement:
+                acc = acc.flip(1, 2)
+            out[i:i + B] = acc.cpu().numpy()
+            delta[i:i + B] = dcc.cpu().numpy()
     return (out, delta) if return_delta else out
 
 
-def in_silico_mutagenesis(model, Xs, target=None, batch_size=4096, rev_complement=False, absolute=False):
+def in_silico_mutagenesis(model, Xs, target=None, batch_size=4096, rev_complement=False, absolute=False,
+                          return_logits=False):
     """In-silico mutagenesis in eval mode, float32 numpy (N,T,4,L) -- (N,4,L) for one `target`:
     row a at position p is logit(sequence with base a at p) - logit(sequence), 0 at the reference
     base; absolute=True gives the mutant logits themselves.  One device pass per batch
@@ -390,39 +371,25 @@ def in_silico_mutagenesis(model, Xs, target=None, batch_size=4096, rev_complemen
     Xs: (N,4,L) one-hot (numpy or tensor) or (N,L) uint8 base codes (0..3 = A,C,G,T, 4 = N).
     rev_complement=True runs the model on each sequence's reverse complement and maps rows and
     positions back (base a <-> 3-a, p <-> L-1-p), so that row a at p means "base a at p of the given
-    strand"."""
-    from .architectures import BaseCodes
-    dev = model.final.weight.device
-    T, L = model._options["n_features"], model._options["sequence_length"]
-    if target is not None and not 0 <= int(target) < T:
-        raise ValueError("target must be a task index in [0, %d)" % T)
-    codes = (torch.is_tensor(Xs) and Xs.dtype == torch.uint8) or \
-        (isinstance(Xs, np.ndarray) and Xs.dtype == np.uint8)
-    Xs = torch.as_tensor(Xs) if codes else _as_tensor(Xs)
+    strand".
+    return_logits=True returns (result, logits), logits (N,T) float32: the logits of the strand the
+    model ran on, all tasks whatever `target` says, the bits forward() gives."""
+    Xs, codes, T, L, dev = _attribution_input(model, Xs, target)
     out = np.zeros((len(Xs), T, 4, L) if target is None else (len(Xs), 4, L), dtype=np.float32)
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad(), model.eval_cache():
-            for i, xb in _batches(Xs, batch_size):
-                xb = xb.to(dev, non_blocking=True)
-                if codes:
-                    logits, delta = model.in_silico_mutagenesis(BaseCodes(xb, rev_complement))
-                else:
-                    xb = xb.to(torch.float32)
-                    logits, delta = model.in_silico_mutagenesis(xb.flip(1, 2) if rev_complement else xb)
-                if rev_complement:
-                    delta = delta.flip(2, 3)
-                if absolute:
-                    delta = delta + logits[:, :, None, None]
-                if target is not None:
-                    delta = delta[:, int(target)]
-                out[i:i + xb.shape[0]] = delta.cpu().numpy()
-        if model.validate_input:
-            model.check_input()
-    finally:
-        model.train(was_training)
-    return out
+    all_logits = np.zeros((len(Xs), T), dtype=np.float32)
+    with eval_mode(model), eval_pass(model):
+        for i, xb in _batches(Xs, batch_size):
+            xb, xin = _on_strand(xb.to(dev, non_blocking=True), codes, rev_complement)
+            logits, delta = model.in_silico_mutagenesis(xin)
+            if rev_complement:
+                delta = delta.flip(2, 3)
+            if absolute:
+                delta = delta + logits[:, :, None, None]
+            if target is not None:
+                delta = delta[:, int(target)]
+            out[i:i + xb.shape[0]] = delta.cpu().numpy()
+            all_logits[i:i + xb.shape[0]] = logits.cpu().numpy()
+    return (out, all_logits) if return_logits else out
 
 
 def filter_importances(outs, final_weight, idxs, hit):

@@ -17,7 +17,9 @@ Order and contents of the batches are those of the reference's loader under the 
 state (the same `RandomSampler`/`BatchSampler` objects draw the indices), and the model consumes
 codes bit-identically to the fp32 one-hot (tests/test_gpu_parity.py::test_base_codes_equal_onehot_path).
 """
+import contextlib
 import gzip
+import sys
 
 import numpy as np
 import torch
@@ -28,6 +30,17 @@ from .sequence import _LUT
 
 def _open(path, mode="rb"):
     return gzip.open(path, mode) if str(path).endswith(".gz") else open(path, mode)
+
+
+@contextlib.contextmanager
+def open_output(path):
+    """The text file a command line writes: `path` opened with "w" and closed behind the block, or --
+    without a path -- sys.stdout as it is when the block is entered, left open."""
+    if not path:
+        yield sys.stdout
+        return
+    with open(path, "w") as fh:
+        yield fh
 
 
 def codes_from_strings(seqs):

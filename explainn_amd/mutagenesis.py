@@ -15,7 +15,6 @@ given strand (logits are then those of the reverse strand).
 import argparse
 
 import numpy as np
-import torch
 
 from .interpret import in_silico_mutagenesis
 from .loader import read_fasta_codes
@@ -36,15 +35,8 @@ def main(argv=None):
     L = model._options["sequence_length"]
     if codes.shape[1] != L:
         raise SystemExit("sequences are %d bp, the model takes %d" % (codes.shape[1], L))
-    delta = in_silico_mutagenesis(model, codes, batch_size=args.batch_size,
-                                  rev_complement=args.rev_complement, absolute=args.absolute)
-    from .architectures import BaseCodes
-    dev = model.final.weight.device
-    logits = np.empty((len(codes), model._options["n_features"]), dtype=np.float32)
-    with torch.no_grad():
-        for i in range(0, len(codes), args.batch_size):
-            xb = torch.as_tensor(codes[i:i + args.batch_size]).to(dev)
-            logits[i:i + len(xb)] = model(BaseCodes(xb, args.rev_complement)).cpu().numpy()
+    delta, logits = in_silico_mutagenesis(model, codes, batch_size=args.batch_size, rev_complement=args.rev_complement,
+                                          absolute=args.absolute, return_logits=True)
     np.savez(args.output_file, ids=np.asarray(ids), logits=logits, delta=delta)
 
 

@@ -28,7 +28,6 @@ null's tail into the table -- exact, and independent of the p-value cutoff.  `--
 the column over the whole file (a first pass counts, the second lists).
 """
 import argparse
-import sys
 import types
 
 import numpy as np
@@ -379,7 +378,7 @@ def main(argv=None):
                          "table, and the records do not form one family of tests")
     if args.max_qvalue is not None and not (args.qvalues and 0.0 <= args.max_qvalue <= 1.0):
         raise SystemExit("--max-qvalue needs --qvalues and a value in [0, 1]")
-    from .loader import read_fasta_records
+    from .loader import open_output, read_fasta_records
     motifs = _motifs.read_motifs(args.motifs)
     records = read_fasta_records(args.fasta_file)
     kwargs = {}
@@ -390,15 +389,11 @@ def main(argv=None):
         for _, codes in records:
             hist = score_histogram(null, codes, strands=args.strands, out=hist)
         kwargs = {"observed": hist, "qvalue": args.max_qvalue}
-    fh = open(args.output_file, "w") if args.output_file else sys.stdout
-    try:
+    with open_output(args.output_file) as fh:
         for rid, codes in records:
             fh.writelines(bed_rows(rid, scan_motifs(motifs, codes, pvalue=args.pvalue, bg=args.bg,
                                                     pseudocount=args.pseudocount, bins=args.bins,
                                                     strands=args.strands, **kwargs)))
-    finally:
-        if fh is not sys.stdout:
-            fh.close()
 
 
 if __name__ == "__main__":

@@ -14,6 +14,8 @@ import contextlib
 import numpy as np
 import torch
 
+from .strands import eval_pass
+
 CHUNK_BASES = 1 << 26        # bases per device call of best_over_records
 LABEL_PRIMARY, LABEL_CONTROL, LABEL_EXCLUDED = 1, 0, 2
 
@@ -145,7 +147,7 @@ class FilterScorer:
     def span(self):
         if self.model.training:
             raise NotImplementedError("the best sites are an eval-mode export path; call model.eval()")
-        with torch.no_grad(), self.model.eval_cache():
+        with eval_pass(self.model, settle=False):       # best_over_records opens several spans before one finish()
             yield
 
     def finish(self):

@@ -12,7 +12,6 @@ run once over the sequence instead of once per window (mode "shared", DESIGN.md 
 `python -m explainn_amd.scan MODEL FASTA` writes the windows of every FASTA record as TSV.
 """
 import argparse
-import sys
 
 import numpy as np
 import torch
@@ -141,21 +140,17 @@ def main(argv=None):
         _check_args(args.stride, args.strands, args.mode)
     except ValueError as e:
         ap.error(str(e))
-    from .loader import read_fasta_records
+    from .loader import open_output, read_fasta_records
     records = read_fasta_records(args.fasta_file)
     model = _load_model(args.model_file)
     L = model._options["sequence_length"]
-    fh = open(args.output_file, "w") if args.output_file else sys.stdout
-    try:
+    with open_output(args.output_file) as fh:
         fh.write("SeqId\tStart\tEnd\tClass\tFwd\tRev\tMean\tMax\n")
         for rid, starts, preds in scan_records(model, records, stride=args.stride, strands=args.strands,
                                                mode=args.mode, apply_sigmoid=args.apply_sigmoid):
             for s, row in zip(starts, preds):
                 for t in range(row.shape[0]):
                     fh.write("%s\t%d\t%d\t%d\t%s\n" % (rid, s, s + L, t, "\t".join(repr(float(v)) for v in row[t])))
-    finally:
-        if fh is not sys.stdout:
-            fh.close()
 
 
 if __name__ == "__main__":

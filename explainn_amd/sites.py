@@ -30,12 +30,11 @@ A site's q-value is a function of (unit, bit pattern) too: explainn_site_qvalues
 table from the two histograms.  `--qvalues [--max-qvalue Q]` adds the column over the whole file.
 """
 import argparse
-import sys
 
 import numpy as np
 import torch
 
-from .strands import TwoStrands, as_codes_1d, check_strands
+from .strands import TwoStrands, as_codes_1d, check_strands, eval_pass
 
 CHUNK_POSITIONS = 1 << 24    # start positions per device call
 MAX_SITES = 50000000         # records a call_sites() result may hold (17 bytes each on the host)
@@ -412,10 +411,8 @@ def activation_null(model, codes, period=0, shuffles=0, seed=0, strands="both", 
     device = model._device()
     hist = torch.zeros(model._units(), ACT_BINS, device=device, dtype=torch.int64)
     chunk = int(chunk_positions) if chunk_positions is not None else CHUNK_POSITIONS
-    with torch.no_grad(), model.eval_cache():
+    with eval_pass(model):
         _count_activations(model, data, hist, period, int(shuffles), seed, strands == "both", chunk)
-    if model.validate_input:
-        model.check_input()
     return ActivationNull(hist, model._options["kernel_size"], strands, shuffles, seed)
 
 
@@ -425,13 +422,11 @@ def records_null(model, records, strands="both", seed=0):
     `calibrate --background sequence` when the records' lengths differ."""
     check_strands(strands)
     hist = torch.zeros(model._units(), ACT_BINS, device=model._device(), dtype=torch.int64)
-    with torch.no_grad(), model.eval_cache():
+    with eval_pass(model):
         for c in records:
             if len(c):
                 data, _ = _null_args(model, np.asarray(c, dtype=np.uint8), 0, 0, strands, None)
                 _count_activations(model, data, hist, 0, 0, seed, strands == "both", CHUNK_POSITIONS)
-    if model.validate_input:
-        model.check_input()
     return ActivationNull(hist, model._options["kernel_size"], strands, 0, seed)
 
 
@@ -594,7 +589,7 @@ def main(argv=None):
         raise SystemExit("--qvalues needs --null")
     if args.max_qvalue is not None and not (args.qvalues and 0.0 <= args.max_qvalue <= 1.0):
         raise SystemExit("--max-qvalue needs --qvalues and a value in [0, 1]")
-    from .loader import read_fasta_records
+    from .loader import open_output, read_fasta_records
     from .predict import _load_model
     records = read_fasta_records(args.fasta_file)
     model = _load_model(args.model_file)
@@ -609,13 +604,9 @@ def main(argv=None):
         kwargs["qvalues"] = site_qvalues(records_null(model, (c for _, c in records), args.strands), null)
         if args.max_qvalue is not None:
             thresholds = np.maximum(thresholds, kwargs["qvalues"].thresholds(args.max_qvalue))
-    fh = open(args.output_file, "w") if args.output_file else sys.stdout
-    try:
+    with open_output(args.output_file) as fh:
         for rid, calls in call_sites_records(model, records, thresholds, strands=args.strands, **kwargs):
             fh.writelines(bed_rows(rid, calls))
-    finally:
-        if fh is not sys.stdout:
-            fh.close()
 
 
 if __name__ == "__main__":

@@ -1,7 +1,10 @@
 """Both strands of a sequence, as predict(), scan(), call_sites() and the variant scorers run them:
 the forward strand on the model, the reverse complement on its eval_replica() (same tensors, own
 device context) on a second stream, so that the launches of one strand fill the gaps between the
-dependent launches of the other."""
+dependent launches of the other.  eval_pass and eval_mode are the scope every eval-mode pass over data
+opens, whichever strands it runs."""
+import contextlib
+
 import numpy as np
 import torch
 
@@ -25,11 +28,40 @@ def stack_strands(fwd, rev, dim=-1):
     return torch.stack((fwd, rev, (fwd + rev) / 2, torch.maximum(fwd, rev)), dim=dim)
 
 
+@contextlib.contextmanager
+def eval_mode(model):
+    """The model in eval mode for the block, and back in the mode it was in behind it."""
+    was = model.training
+    model.eval()
+    try:
+        yield model
+    finally:
+        model.train(was)
+
+
+@contextlib.contextmanager
+def eval_pass(model, *others, settle=True):
+    """One eval-mode pass over data: nothing records gradients and the eval tables of the model (and of
+    `others`: its replica) are folded once for the block.  With `settle`, a clean exit settles input
+    validation by ONE read of each context's sticky device flag."""
+    with contextlib.ExitStack() as scopes:
+        scopes.enter_context(torch.no_grad())
+        for m in (model,) + others:
+            scopes.enter_context(m.eval_cache())
+        yield
+    if settle and model.validate_input:
+        # every flag is read (and cleared) before anything raises: a raise from the replica's must not
+        # leave the model's set for a later call to trip over
+        also = 0
+        for m in others:
+            also |= m.input_flags()
+        model.check_input(also)
+
+
 class TwoStrands:
-    """with TwoStrands(model, both) as ts: the eval tables of the model (and, with `both`, of its
-    replica) are folded once for the block, nothing records gradients, and a clean exit settles input
-    validation by ONE read of each context's sticky device flag.  cur is the caller's stream; rep and
-    side, the replica and its stream, are None for the forward strand alone."""
+    """with TwoStrands(model, both) as ts: an eval_pass of the model (and, with `both`, of its
+    replica).  cur is the caller's stream; rep and side, the replica and its stream, are None for the
+    forward strand alone."""
 
     def __init__(self, model, both=True):
         device = model.final.weight.device
@@ -42,20 +74,12 @@ class TwoStrands:
             self.side = model._rt.side_stream
 
     def __enter__(self):
-        self._scopes = [torch.no_grad(), self.model.eval_cache()]
-        if self.rep is not None:
-            self._scopes.append(self.rep.eval_cache())
-        for scope in self._scopes:                      # (none of the three can fail to open)
-            scope.__enter__()
+        self._scope = eval_pass(self.model, *(() if self.rep is None else (self.rep,)))
+        self._scope.__enter__()
         return self
 
     def __exit__(self, *exc):
-        for scope in reversed(self._scopes):
-            scope.__exit__(*exc)
-        if exc[0] is None and self.model.validate_input:
-            # both flags are read (and cleared) before either raises: a raise from the replica's must not
-            # leave the model's set for a later call to trip over
-            self.model.check_input(self.rep.input_flags() if self.rep is not None else 0)
+        return self._scope.__exit__(*exc)
 
     def run(self, launch, held=()):
         """launch(m, reverse_complement) on the model and, with both strands, on the replica on the side

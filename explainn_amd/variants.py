@@ -474,7 +474,7 @@ def _haplotypes_main(args, ap):
     region, sample, haplotype (1, 2) and class; regions in file order."""
     if not args.regions:
         ap.error("--haplotypes needs --regions BED")
-    from .loader import read_fasta_records
+    from .loader import open_output, read_fasta_records
     from .predict import _load_model
     variants, names, carried, unphased = read_vcf_genotypes(
         args.vcf_file, args.samples.split(",") if args.samples else None)
@@ -508,14 +508,10 @@ def _haplotypes_main(args, ap):
             lines[j] = rows
     if len(lines) < len(regions):
         sys.stderr.write("%d region(s) on sequences the FASTA does not hold\n" % (len(regions) - len(lines)))
-    fh = open(args.output_file, "w") if args.output_file else sys.stdout
-    try:
+    with open_output(args.output_file) as fh:
         fh.write("Chrom\tStart\tEnd\tSample\tHap\tClass\tRefMean\tHapFwd\tHapRev\tHapMean\tDelta\n")
         for j in sorted(lines):
             fh.writelines(lines[j])
-    finally:
-        if fh is not sys.stdout:
-            fh.close()
 
 
 def allele_codes(allele):
@@ -572,7 +568,7 @@ def main(argv=None):
         return _haplotypes_main(args, ap)
     if args.shifts < 1:
         ap.error("--shifts must be at least 1")
-    from .loader import read_fasta_records
+    from .loader import open_output, read_fasta_records
     from .predict import _load_model
     variants, skipped = read_vcf(args.vcf_file)
     records = read_fasta_records(args.fasta_file)
@@ -584,8 +580,7 @@ def main(argv=None):
     if skipped or len(where) < len(variants):
         sys.stderr.write("%d symbolic allele(s) skipped, %d variant(s) on sequences the FASTA does not hold\n"
                          % (skipped, len(variants) - len(where)))
-    fh = open(args.output_file, "w") if args.output_file else sys.stdout
-    try:
+    with open_output(args.output_file) as fh:
         fh.write("Chrom\tPos\tId\tRef\tAlt\tClass\tRefFwd\tRefRev\tRefMean\tAltFwd\tAltRev\tAltMean\tDelta"
                  + ("\tUnits" if args.top_units > 0 else "") + "\n")
         for i, v in enumerate(variants):
@@ -601,9 +596,6 @@ def main(argv=None):
                     top = np.argsort(-np.abs(eff), kind="stable")[:args.top_units]
                     row.append(",".join("%d:%s" % (u, repr(float(eff[u]))) for u in top))
                 fh.write("\t".join(row) + "\n")
-    finally:
-        if fh is not sys.stdout:
-            fh.close()
 
 
 if __name__ == "__main__":
