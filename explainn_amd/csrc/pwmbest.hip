@@ -120,15 +120,7 @@ __global__ __launch_bounds__(PB_T) void pwm_best_kernel(
     const int span_bytes = (PB_SPAN + wmax - 1 + 15) & ~15;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, m0 = blockIdx.y * PB_G;
     uint8_t* cs = reinterpret_cast<uint8_t*>(pb_tab + (PB_G / 2) * wmax * 8) + wave * span_bytes;
-    int* words = reinterpret_cast<int*>(pb_tab);
-    for (int i = tid; i < PB_G * wmax * 8; i += PB_T) {
-        // word i: pair q, column j, code c, motif 2 q + h
-        const int h = i & 1, c = (i >> 1) & 7, j = (i >> 4) % wmax, q = (i >> 4) / wmax, m = m0 + 2 * q + h;
-        unsigned word = 0;
-        const int w = pwm_width(widths, m, M, wmax);
-        if (j < w && c < 4) word = pwm_pair_word(S + (size_t)m * wmax * 4, w, j, c);
-        words[i] = (int)word;
-    }
+    pwm_stage_pair_tables<PB_G, PB_T>(reinterpret_cast<int*>(pb_tab), S, widths, m0, M, wmax, tid);
     __syncthreads();                           // the only block-wide barrier: the waves part here
     const int total = PB_SPAN + wmax - 1;
     int bad = 0;

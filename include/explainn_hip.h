@@ -966,6 +966,37 @@ int explainn_pwm_record_best(const uint8_t* seq, int64_t seq_len, const int64_t*
                              int both_strands, const int16_t* scores, const int32_t* widths, int M, int wmax,
                              uint16_t* best_bits, int32_t* best_site, int32_t* flags, void* stream);
 
+/* Variant effects on known motifs (csrc/pwmvariants.hip, DESIGN.md section 3 item 25, section 8 "Variant effects
+ * on known motifs"): explainn_pwm_record_best for the two haplotypes of every variant, restricted to the windows
+ * the allele touches; neither haplotype is materialised.
+ *
+ * explainn_pwm_variant_best: seq / seq_len are device base codes; pos (int64), ref_len, alt_len, alt_off (int32) and
+ * alt (uint8, alt_bytes of them) are the edit table of explainn_edits, one record per variant, all on the device;
+ * scores, widths, M and wmax as explainn_pwm_record_best takes them.  For variant v and allele A -- index 0 the
+ * reference with l = ref_len[v], index 1 the alternative with l = alt_len[v] -- the haplotype is
+ *     H_A = seq[:pos] + allele + seq[pos + ref_len:]          of n_A = seq_len - ref_len + l bases
+ * and a motif of live width w has the starts s = pos - w + 1 + i, i = 0 .. w + l - 2: with l >= 1 the windows that
+ * overlap the allele, with l == 0 the w - 1 windows that span the junction (none for w == 1).  A start is live when
+ * 0 <= s, s + w <= n_A and the window holds no N.  '+' and '-' score as in explainn_pwm_record_best.
+ *     best_bits[m][v][A] (uint16) = the largest score over the live starts and the requested strands, 0 without one
+ *     best_site[m][v][A] (int32; may be NULL) = (i << 1) | is_minus of the maximum, -1 without a live start
+ * Among equal maxima the lowest i wins, and at one start '+' before '-' (explainn_record_best's key with i in place
+ * of the start): a maximum over integer keys, the same bits for any grid.  Both outputs are [M][n_variants][2] and
+ * OVERWRITTEN.  The host never reads the tables, so the kernel stays inside its arrays on bad ones: a source index
+ * outside [0, seq_len) reads as N; a byte above 4 reads as N and ORs bit 0 into *flags (device int32, may be NULL;
+ * never cleared here) when it lies in seq within wmax - 1 bases of an allele or in the alt allele itself; a variant
+ * with pos < 0, a negative length, pos + ref_len > seq_len, alt_off < 0, alt_off + alt_len > alt_bytes or an
+ * allele longer than EXPLAINN_PWM_VARIANT_MAX_ALLELE ORs bit 1 into *flags and has no site on either allele for
+ * every motif -- compares only, before any byte of its alleles is read.  EXPLAINN_E_ARG unless seq_len >= 0,
+ * alt_bytes >= 0, 0 <= n_variants < 2^30, 0 <= M <= 65535 EXPLAINN_PWM_GROUP and 1 <= wmax <=
+ * EXPLAINN_MOTIF_MAX_WIDTH.  M == 0 or n_variants == 0 launches nothing.  No context, no workspace, no allocation,
+ * no host synchronisation, no atomics but the flags. */
+#define EXPLAINN_PWM_VARIANT_MAX_ALLELE 128
+int explainn_pwm_variant_best(const uint8_t* seq, int64_t seq_len, const int64_t* pos, const int32_t* ref_len,
+                              const int32_t* alt_len, const int32_t* alt_off, const uint8_t* alt, int64_t alt_bytes,
+                              int64_t n_variants, int both_strands, const int16_t* scores, const int32_t* widths,
+                              int M, int wmax, uint16_t* best_bits, int32_t* best_site, int32_t* flags, void* stream);
+
 /* One Adam step over n_tensors parameter tensors in a single launch -- torch.optim.Adam(params, lr)
  * with its defaults, the optimiser the reference builds (architectures/__init__.py:463-464) and
  * steps at selene/__init__.py:291.  params/grads/exp_avg/exp_avg_sq: HOST arrays of n_tensors

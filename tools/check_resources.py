@@ -90,10 +90,12 @@ PWMSITES = [r"^pwm_null_kernel", r"^pwm_sites_kernel<0>", r"^pwm_sites_kernel<1>
 SITEQ = [r"^pwm_hist_kernel", r"^site_q_kernel"]
 # known-motif enrichment (pwmbest.hip): the per-record best PWM site
 PWMBEST = [r"^pwm_best_kernel"]
+# variant effects on known motifs (pwmvariants.hip): the best ref / alt PWM site per (motif, variant)
+PWMVARIANTS = [r"^pwm_variant_kernel"]
 # greedy in-silico evolution (evolve.hip): one round's selection
 EVOLVE = [r"^evolve_select_kernel"]
 GATED = (C2_STEP + INPUT_GRAD + ISM + EVOLVE + PATHGRAD + METRICS + SCAN + VARIANTS + HAPLOTYPES + SHUFFLE + MOTIFS + MOTIFTREE + ACTNULL +
-         SPACING + ENRICH + CENTRAL + SITES + PWMSITES + PWMBEST + SITEQ)
+         SPACING + ENRICH + CENTRAL + SITES + PWMSITES + PWMBEST + SITEQ + PWMVARIANTS)
 
 
 # Register cliffs measured in the pipeline: 1024-thread blocks of which TWO must
