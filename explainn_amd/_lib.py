@@ -32,6 +32,8 @@ ACT_SPAN = 8192          # EXPLAINN_ACT_SPAN: start positions a workgroup of exp
 BEST_SPAN = 256          # EXPLAINN_BEST_SPAN: starts a wavefront of explainn_record_best takes per pass over its record
 PWM_BEST_SPAN = 256      # EXPLAINN_PWM_BEST_SPAN: the same of explainn_pwm_record_best
 PWM_VARIANT_MAX_ALLELE = 128  # EXPLAINN_PWM_VARIANT_MAX_ALLELE: bases per allele of explainn_pwm_variant_best
+WORD_MIN_WIDTH, WORD_MAX_WIDTH = 3, 10   # EXPLAINN_WORD_MIN_WIDTH, EXPLAINN_WORD_MAX_WIDTH: the k of the word entry points
+WORD_SPAN = 256          # EXPLAINN_WORD_SPAN: starts a workgroup of the word kernels takes per pass over its record
 SPACING_MAX_DISTANCE = 1024  # EXPLAINN_SPACING_MAX_DISTANCE: the largest max_distance of explainn_site_spacing
 CENTRALITY_MAX_THRESHOLDS = 16      # EXPLAINN_CENTRALITY_MAX_THRESHOLDS: thresholds of one explainn_site_positions call
 CENTRALITY_MAX_REGIONS = 4194304    # EXPLAINN_CENTRALITY_MAX_REGIONS: regions per unit of explainn_centrality_test
@@ -187,6 +189,9 @@ SIGNATURES = {
     "explainn_pwm_record_best": (_i, [_fp, _i64, _fp, _i64, _i, _fp, _fp, _i, _i, _fp, _fp, _fp, _fp]),
     "explainn_pwm_variant_best": (_i, [_fp, _i64, _fp, _fp, _fp, _fp, _fp, _i64, _i64, _i, _fp, _fp, _i, _i, _fp, _fp,
                                        _fp, _fp]),
+    "explainn_word_counts": (_i, [_fp, _i64, _fp, _i64, _i, _i, _fp, _fp, _fp]),
+    "explainn_word_test": (_i, [_fp, _fp, _i64, _i64, _i64, _i64, _fp, _fp, _fp, _fp]),
+    "explainn_word_sites": (_i, [_fp, _i64, _fp, _i64, _i, _i, _i64, C.c_uint64, _fp, _fp, _fp, _fp, _fp]),
     "explainn_adam_step": (_i, [_i, C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp),
                                 C.POINTER(_i64), _i64, C.c_double, C.c_double, C.c_double, C.c_double,
                                 _fp]),

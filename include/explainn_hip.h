@@ -997,6 +997,63 @@ int explainn_pwm_variant_best(const uint8_t* seq, int64_t seq_len, const int64_t
                               int64_t n_variants, int both_strands, const int16_t* scores, const int32_t* widths,
                               int M, int wmax, uint16_t* best_bits, int32_t* best_site, int32_t* flags, void* stream);
 
+/* De novo word discovery (csrc/words.hip, DESIGN.md section 3 item 26, section 8 "Word discovery"): which k-mers
+ * occur in more records of a primary set than of a control set, and the sites of the best one widened by its
+ * enriched one-mismatch neighbours -- the three device steps of explainn_amd/discover.py's DREME-style loop.
+ * seq, seq_len, rec_offsets and n_records as explainn_pwm_record_best takes them.
+ *
+ * Word code.  Base codes are A,C,G,T = 0..3, and any byte >= 4 is "not a base".  A k-mer's code is
+ * sum b_i 4^(k-1-i), first base most significant; rc(code) is the code of the reverse complement.  With both
+ * strands a word is indexed by its canonical code min(code, rc(code)), and non-canonical entries of a table stay
+ * 0; with both_strands == 0 it is indexed by code.  EXPLAINN_WORD_MIN_WIDTH <= k <= EXPLAINN_WORD_MAX_WIDTH.
+ * Live start.  Start s of record r is live when the k bases s .. s+k-1 lie inside the record and all are < 4.
+ *
+ * explainn_word_counts: presence counts.  counts[w] (int32 [4^k], ADDED INTO, so files accumulate) grows by the
+ * number of records with at least one live start whose (canonical) code is w: a record counts once however often
+ * the word occurs in it.
+ *
+ * explainn_word_test: for the counts a = pos[w], b = neg[w] (int32 [n_words]) and the record totals Np, Nc
+ *     logp[w] = hypergeom_logsf(a, a+b, Np, Nc) (csrc/tails.h: ln P[X >= a], X ~ Hypergeometric(Np+Nc, Np, a+b))
+ *               when a >= min_count and the primary set is enriched, a (Np+Nc) > (a+b) Np in integers;
+ *               otherwise exactly 0.0 (also for an entry outside 0 <= a <= Np, 0 <= b <= Nc)
+ *     best[0] = the word of the smallest logp, ties to the lowest code; -1 when no entry is below 0
+ *     best[1] = n_tested, the number of entries with a + b > 0
+ *     best_logp[0] = that smallest logp, 0.0 without one
+ * logp (double [n_words]), best (int64 [2]) and best_logp (double [1]) are OVERWRITTEN.  Equal counts give
+ * bit-equal values, and the minimum and the tie rule are integer atomics: the same answer for any grid.
+ *
+ * explainn_word_sites: the sites of the pattern (k, seed, accept) in one set.  accept is a bit mask with bit
+ * 4 i + b for motif position i (0 = first base) and base b.  A window with code c MATCHES when its Hamming
+ * distance to seed is 0, or when it is 1 with the differing position i holding base b and bit 4i+b of accept set.
+ * A start is a SITE when it is live and its window matches ('+'), or, with both strands, when rc(window) matches
+ * ('-'); a start that matches both ways is one '+' site.
+ *     totals[0] += nsites, the number of sites (overlapping sites all count)
+ *     totals[1] += nrecords, the number of records with at least one site          (int64 [2], ADDED INTO)
+ *     pfm[i][b] += the sites with base b at motif position i, a '-' site contributing 3 - base[start + k-1-i]
+ *                                                                (int64 [k][4], ADDED INTO; may be NULL)
+ *     seq_out[0 .. seq_len) = seq with every base covered by at least one site replaced by 4 and every other
+ *                             byte copied (may be NULL; another array than seq).  It is decided on the input
+ *                             alone, in gather form, one output byte per lane, so overlaps cannot race.
+ *
+ * flags (device int32, may be NULL; ORed into, never cleared here) of word_counts and word_sites: bit 0 = a byte
+ * above 4 was read (it reads as N; every byte of a record of at least k bases is read); bit 1 = a record whose
+ * offsets are not 0 <= o[r] <= o[r+1] <= seq_len was skipped -- a compare before any byte of it is read; it
+ * contributes nothing.  EXPLAINN_E_ARG, without a launch, for k outside its range, negative sizes, Np + Nc >=
+ * 2^31, n_words > 4^EXPLAINN_WORD_MAX_WIDTH, a seed outside [0, 4^k), an accept bit from 4k on and null required
+ * pointers.  n_records == 0 counts nothing (word_sites still copies seq).  No context, no workspace, no
+ * allocation, no host synchronisation; every sum is an integer atomic, so the results are functions of the input.
+ * EXPLAINN_WORD_SPAN: starts a workgroup takes per pass over its record (tests place repeats around it). */
+#define EXPLAINN_WORD_MIN_WIDTH 3
+#define EXPLAINN_WORD_MAX_WIDTH 10
+#define EXPLAINN_WORD_SPAN 256
+int explainn_word_counts(const uint8_t* seq, int64_t seq_len, const int64_t* rec_offsets, int64_t n_records, int k,
+                         int both_strands, int32_t* counts, int32_t* flags, void* stream);
+int explainn_word_test(const int32_t* pos, const int32_t* neg, int64_t n_words, int64_t Np, int64_t Nc,
+                       int64_t min_count, double* logp, int64_t* best, double* best_logp, void* stream);
+int explainn_word_sites(const uint8_t* seq, int64_t seq_len, const int64_t* rec_offsets, int64_t n_records, int k,
+                        int both_strands, int64_t seed, uint64_t accept, uint8_t* seq_out, int64_t* pfm,
+                        int64_t* totals, int32_t* flags, void* stream);
+
 /* One Adam step over n_tensors parameter tensors in a single launch -- torch.optim.Adam(params, lr)
  * with its defaults, the optimiser the reference builds (architectures/__init__.py:463-464) and
  * steps at selene/__init__.py:291.  params/grads/exp_avg/exp_avg_sq: HOST arrays of n_tensors

@@ -92,10 +92,13 @@ SITEQ = [r"^pwm_hist_kernel", r"^site_q_kernel"]
 PWMBEST = [r"^pwm_best_kernel"]
 # variant effects on known motifs (pwmvariants.hip): the best ref / alt PWM site per (motif, variant)
 PWMVARIANTS = [r"^pwm_variant_kernel"]
+# word discovery (words.hip): presence counts (dynamic LDS: 4^k bits, 128 KiB at k = 10), the Fisher test and
+# its arg-min, the sites pass
+WORDS = [r"^word_count_kernel", r"^word_test_kernel", r"^word_pick_kernel", r"^word_sites_kernel"]
 # greedy in-silico evolution (evolve.hip): one round's selection
 EVOLVE = [r"^evolve_select_kernel"]
 GATED = (C2_STEP + INPUT_GRAD + ISM + EVOLVE + PATHGRAD + METRICS + SCAN + VARIANTS + HAPLOTYPES + SHUFFLE + MOTIFS + MOTIFTREE + ACTNULL +
-         SPACING + ENRICH + CENTRAL + SITES + PWMSITES + PWMBEST + SITEQ + PWMVARIANTS)
+         SPACING + ENRICH + CENTRAL + SITES + PWMSITES + PWMBEST + SITEQ + PWMVARIANTS + WORDS)
 
 
 # Register cliffs measured in the pipeline: 1024-thread blocks of which TWO must
